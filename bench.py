@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — aligned Gbp/s of the seed -> non-linear chain -> extend path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads-per-step R] [--ref-mb M] [--cpu-sample S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads-per-step R] [--ref-mb M] [--cpu-sample S] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
 
 `--gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset) starts the N ranks ITSELF (launch_ranks below: one child of this same command
@@ -49,6 +49,67 @@ Random{eventset=["DEL:100:200,INV:300:600","INS:100:1000,NML:100:200","NML:100:2
 '''
 HBM_PEAK_GBS = 8000.0      # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 METRIC = 'aligned Gbp/s (whole node) + reads/s, 15 kb ONT-shape reads vs hg38-size ref, 1/2/4/8 MI355X'      # BASELINE.json
+DUMP_BYTES = 64 << 20      # --dump-outputs: all arrays together
+CIGAR_OPS = 'MIDNSHP=X'
+
+
+class KeepRecords:
+    """a job of the timed pass whose records stay in library memory (--dump-outputs): the same vm_align_resident call as ResidentReads.align
+    with want_records=False, which frees them at once; they are read after the timed pass, so nothing is converted inside it"""
+
+    def __init__(self, resident):
+        self.resident, self.bases, self.raw = resident, resident.bases, None
+
+    def align(self, index, prm, want_records=False, ctx=None):
+        self.raw = self.resident.align_raw(index, prm, ctx=ctx)
+        return self.raw.status, None, self.raw.stats
+
+
+def dump_outputs(path, kept, plan):
+    """what the last timed step computed — the per-read status and the records with their CIGARs that a caller of vm_align_resident receives — as
+    path/<name>.npy (float64; the CIGAR text as float32 byte codes). kept: {job: KeepRecords} of the step's jobs. Rows follow the schedule.
+      read_index [n]       pool index of each read of the step (the reads are a function of the command line: same arguments, same inputs)
+      status     [n]       per-read status
+      records    [m, 8]    read (pool index), contig, strand, mapq, q_st, q_en, r_st, r_en
+      cigar_ops  [m, 9]    bases per CIGAR operation, in the order of CIGAR_OPS
+      cigar_crc32 [m]      CRC-32 of each record's CIGAR string
+      cigar_text [t], cigar_text_off [s + 1], cigar_text_records [s]: the whole CIGAR strings of a fixed, seeded sample of s records (all that fit
+      into DUMP_BYTES)
+    Returns {name: shape}."""
+    import ctypes as C, re, zlib
+    reads, status, rows, cigars = [], [], [], []
+    for j in sorted(kept):
+        raw = kept[j].raw
+        idx = np.asarray(plan[j], dtype=np.int64)
+        reads.append(idx.astype(np.float64)); status.append(np.asarray(raw.status, dtype=np.float64))
+        base = raw.blob.value if raw.nrec else 0
+        for r_ in range(raw.nrec):
+            rc = raw.recs[r_]
+            rows.append((idx[rc.read_idx], rc.contig, rc.strand, rc.mapq, rc.q_st, rc.q_en, rc.r_st, rc.r_en))
+            cigars.append(C.string_at(base + rc.cigar_off, rc.cigar_len))
+        raw.close()
+    ops = np.zeros((len(cigars), len(CIGAR_OPS)), np.float64)
+    pat = re.compile(rb'(\d+)([%s])' % re.escape(CIGAR_OPS.encode()))
+    for r_, cg in enumerate(cigars):
+        for n_, op in pat.findall(cg):
+            ops[r_, CIGAR_OPS.index(op.decode())] += int(n_)
+    out = {'read_index': np.concatenate(reads), 'status': np.concatenate(status), 'records': np.asarray(rows, dtype=np.float64).reshape(-1, 8),
+           'cigar_ops': ops, 'cigar_crc32': np.asarray([zlib.crc32(cg) for cg in cigars], dtype=np.float64)}
+    left = DUMP_BYTES - sum(a.nbytes for a in out.values()) - 8 * 128          # (npy headers)
+    pick, used = [], 8
+    for r_ in np.random.default_rng(20240611).permutation(len(cigars)):
+        need = 4 * len(cigars[r_]) + 16
+        if used + need > left:
+            break
+        pick.append(int(r_)); used += need
+    pick.sort()
+    out['cigar_text_records'] = np.asarray(pick, dtype=np.float64)
+    out['cigar_text_off'] = np.concatenate([[0], np.cumsum([len(cigars[r_]) for r_ in pick])]).astype(np.float64)
+    out['cigar_text'] = np.frombuffer(b''.join(cigars[r_] for r_ in pick), dtype=np.uint8).astype(np.float32)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+    return {name: list(a.shape) for name, a in out.items()}
 
 
 def host_cores():
@@ -200,6 +261,8 @@ def main():
                     'reported under extra.configs next to the headline; "" disables')
     ap.add_argument('--extra-steps', type=int, default=24)
     ap.add_argument('--launch-dry-run', action='store_true', help='with --gpus N: print the N rank environments and the command the launcher would start, and exit')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write what the last one computed (per-read status, records, '
+                    'CIGARs; rank 0) as DIR/<name>.npy, at most 64 MB: two builds compared output for output (dump_outputs)')
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error('--gpus must be >= 1')
@@ -384,10 +447,19 @@ def main():
                 agg[kk] = agg.get(kk, 0) + v
         agg['ms_stage'] = [a + b for a, b in zip(agg.get('ms_stage', [0.0] * 16), stats['ms_stage'])]
 
+    timed, kept = resident, {}
+    if args.dump_outputs and rank == 0:
+        # the last step = the plan's trailing jobs that hold its reads_per_step reads; their records are kept for dump_outputs
+        n_ = 0
+        for j in range(njobs - 1, -1, -1):
+            kept[j] = KeepRecords(resident[j]); n_ += len(plan[j])
+            if n_ >= args.reads_per_step:
+                break
+        timed = [kept.get(j, r_) for j, r_ in enumerate(resident)]
     barrier()
     cpu0 = os.times()
     t1 = time.time()
-    pipe.run_resident(resident, want_records=False, on_result=on_result)      # the product's schedule (vacmap_amd/pipeline.py)
+    pipe.run_resident(timed, want_records=False, on_result=on_result)      # the product's schedule (vacmap_amd/pipeline.py)
     barrier()
     dt = time.time() - t1
     cpu1 = os.times()
@@ -395,6 +467,7 @@ def main():
     if getattr(pipe, 'timeline', None):                     # VMX_DBG_TIMELINE=1: when every batch of the timed pass started and ended, on which context
         for row in sorted(pipe.timeline, key=lambda r_: r_[3]):
             sys.stderr.write('[timeline] batch %2d ctx %d%s  %7.1f -> %7.1f ms  (%5.1f ms)  %6.1f Mbases\n' % (row[0], row[1], ' small' if row[2] else '      ', row[3] * 1e3, row[4] * 1e3, (row[4] - row[3]) * 1e3, row[5] / 1e6))
+    dumped = dump_outputs(args.dump_outputs, kept, plan) if kept else None
 
     host_rate = None
     if args.host_input and rank == 0 and world == 1:
@@ -557,6 +630,8 @@ def main():
             out['forced_dist_world_1'] = True
         if host_rate is not None:
             out['host_input'] = host_rate
+        if dumped is not None:
+            out['dumped_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
         print(json.dumps(out))
     if dist is not None:
         dist.barrier()

@@ -334,6 +334,45 @@ def test_bench_launcher_propagates_a_failing_rank():
     assert not [l for l in out.stdout.splitlines() if l.startswith('{')]
 
 
+def test_bench_dump_outputs_are_the_records_of_the_last_step(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs`: the jobs of the last step run through KeepRecords (the same vm_align_resident call, the records left in library
+    memory until the timed pass is over); dump_outputs writes them as float arrays that hold what ResidentReads.align returns for the same batch
+    (emulator build), and a small byte budget shrinks only the sample of whole CIGAR strings"""
+    import zlib
+    import emu_lib
+    import bench
+    from vacmap_amd import pipeline, synth
+    from vacmap_amd.lib import Index
+    ctx = emu_lib.context()
+    contigs = synth.make_reference([60000, 20000], seed=5)
+    cat, off, _ = synth.sample_reads_concat(contigs, 12, mean_len=2000, err=0.08, seed=7, min_len=500, max_len=5000)
+    plan = pipeline.plan_batches(np.diff(off), 4, 2)
+    res = pipeline.upload_batches(ctx, cat, off, plan)
+    gi = Index.from_seqs(ctx, ['a', 'b'], contigs, k=15, w=10)
+    prm = ctx.lib.params('H')
+    last = len(plan) - 1
+    st_r, recs, _ = res[last].align(gi, prm, want_records=True, ctx=ctx)
+    assert recs
+    for budget, whole in ((bench.DUMP_BYTES, True), (3000, False)):
+        monkeypatch.setattr(bench, 'DUMP_BYTES', budget)
+        kept = {last: bench.KeepRecords(res[last])}
+        st, none, sd = kept[last].align(gi, prm, ctx=ctx)
+        assert none is None and list(st) == list(st_r) and sd['n_records'] == len(recs)
+        d = tmp_path / str(budget)
+        shapes = bench.dump_outputs(str(d), kept, plan)
+        a = {n: np.load(str(d / (n + '.npy'))) for n in shapes}
+        assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+        assert sum(os.path.getsize(str(d / (n + '.npy'))) for n in shapes) <= budget
+        assert a['read_index'].tolist() == plan[last].tolist() and a['status'].tolist() == st_r.tolist()
+        assert [tuple(int(v) for v in row) for row in a['records']] == [(int(plan[last][r[0]]), r[1], 1 if r[2] == '+' else -1, r[7], r[3], r[4], r[5], r[6]) for r in recs]
+        assert a['cigar_crc32'].tolist() == [zlib.crc32(r[8].encode()) for r in recs]
+        assert a['cigar_ops'].sum(axis=1).tolist() == [sum(int(x) for x in re.findall(r'\d+', r[8])) for r in recs]
+        txt, o = a['cigar_text'].astype(np.uint8).tobytes(), a['cigar_text_off'].astype(np.int64)
+        sample = a['cigar_text_records'].astype(np.int64).tolist()
+        assert [txt[o[s]:o[s + 1]].decode() for s in range(len(sample))] == [recs[i][8] for i in sample]
+        assert (len(sample) == len(recs)) == whole
+
+
 def test_cross_rank_name_dedup_keeps_first_in_input_order(tmp_path):
     """range mode: a name that occurs in two ranks' byte ranges keeps its FIRST occurrence in input order — (file, then byte range = rank) — as the reference's
     single pass over the files does (/root/reference/src/vacmap/vacmap:457-487), not the lowest rank's; and the part filter drops exactly the
