@@ -146,6 +146,9 @@ typedef struct vm_chains_out {
     /* raw DP state of the LAST run of the exact DP (tests; null unless want_raw) : concatenated per read */
     double* S; int64_t* P; int64_t* S_arg; int64_t* gmax; int64_t* opcount;
 } vm_chains_out;
+/* Runs the global chain stage of vm_align_batch (S2 + G1-G3 + selection). A read of two anchors or fewer is not chained (unmapped, :23986):
+ * gmax -1, its S / P / S_arg undefined. -mode asm: a contig of 500 kb and more is not chained either (gmax -4, no path): vm_align_batch
+ * takes it through the linked DPs (vm_chain_linked). */
 int vm_chain_global_batch(vm_ctx*, const vm_params*, int kmersize, int64_t n, const int64_t* anchors,
                           const int64_t* anchor_off, const int64_t* readlens, int want_raw, vm_chains_out* out);
 void vm_chains_out_free(vm_chains_out*);
@@ -187,12 +190,12 @@ void vm_linked_out_free(vm_linked_out*);
 typedef struct vm_score { int32_t match, mismatch, o1, e1, o2, e2; } vm_score;
 int vm_k_cigar_batch(vm_ctx*, const vm_score*, int eqx, int64_t n, const char* t, const int64_t* t_off, const char* q,
                      const int64_t* q_off, char** cigars, int64_t** cigar_off, int32_t** scores);
-/* The same problems through the schedule vm_align_batch uses for its gap fill (mammap_clrnano.py:21554, :21598 call sites): longest-first
- * device queue, banded eight-per-wavefront fill first (anti-diagonal form on a fixed band of 32 * ns diagonals), the problems whose band
- * is not PROVEN optimal filled again in full by a second launch, per-problem layout flag for the traceback. CIGARs must equal
- * vm_k_cigar_batch's. band_flag[n]: 16 + ns = the band's result was proven and kept, 0 = full matrix. stats[4] = {small problems tried
- * in a band, proven, sent to the second launch (not proven, or small but never tried), problems outside the small class}. No scores
- * (that form never captures them). */
+/* The same problems through vm_align_batch's gap fill (mammap_clrnano.py:21554, :21598 call sites), as one chunk with the batch's traceback
+ * layout and queue order: longest-first device queue, banded eight-per-wavefront fill first (anti-diagonal form on a fixed band of 32 * ns
+ * diagonals, traceback slots as wide as each problem's own band needs), the problems whose band is not PROVEN optimal filled again in full
+ * by a second launch, per-problem layout flag for the traceback. CIGARs must equal vm_k_cigar_batch's. band_flag[n]: 16 + ns = the band's
+ * result was proven and kept, 0 = full matrix. stats[4] = {small problems tried in a band, proven, sent to the second launch (not proven,
+ * or small but never tried), problems outside the small class}. No scores (that form never captures them). */
 int vm_k_cigar_batch_banded(vm_ctx*, const vm_score*, int eqx, int64_t n, const char* t, const int64_t* t_off, const char* q,
                             const int64_t* q_off, char** cigars, int64_t** cigar_off, int32_t** band_flag, int64_t* stats);
 /* `mp.k_cigar(..., 4,4,4,4, bw=100, zdropvalue=50)` (:2381): banded x-drop extension from (0,0); out t_e[n], q_e[n], score[n] */

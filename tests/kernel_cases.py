@@ -328,8 +328,9 @@ def gapfill_banded_cases(rng, x4_max, dp16_max, base_len, big=True, pct=90, pct_
 
 
 def check_gapfill_banded(ctx, O, x4_max, dp16_max, base_len, seed=44, big=True, min_counts=(10, 10, 5), pct=90, pct_min=65, redo_pk_min=384):
-    """E5 through the schedule of the batched path (vm_k_cigar_batch_banded -> k_gapfill_fill_ns: anti-diagonal band fill of eight problems
-    per wave, optimality proof, redo queue, per-problem layout flag read by k_gapfill_trace) vs the oracle's full DP (mammap_clrnano.py:21554,
+    """E5 through the batched path's own gap-fill code (vm_k_cigar_batch_banded -> vmx_gapfill_chunk: queue order by the batch's keys,
+    k_gapfill_fill_ns: anti-diagonal band fill of eight problems per wave in traceback slots as wide as each problem's own band, optimality
+    proof, redo queue, per-problem layout flag read by k_gapfill_trace) vs the oracle's full DP (mammap_clrnano.py:21554,
     :21598 call sites): identical CIGARs with eqx on and off, in shuffled order (waves mix proven, unproven, never-tried and idle rows and
     band widths), and both branches provably taken. pct / pct_min: the band-width rule the library is running with (VMX_AD_PCT, VMX_AD_PCT_MIN)."""
     rng = np.random.default_rng(seed)

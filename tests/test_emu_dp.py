@@ -43,7 +43,7 @@ def test_emu_gapfill_tie_order(ctx, oracle):
 
 
 def test_emu_gapfill_banded(ctx, oracle, monkeypatch):
-    """the batched path's gap-fill schedule (anti-diagonal band + proof + redo queue + layout flag) with the emulator build's small
+    """the batched path's gap-fill chunk (vmx_gapfill_chunk: anti-diagonal band + proof + redo queue + layout flag) with the emulator build's small
     constants (small class up to tl + ql = 160, packed int16 up to 420). The band-width rule is pushed through all four widths with
     VMX_AD_PCT (at its default every problem this small gets the narrowest band)."""
     seen = set()

@@ -75,8 +75,8 @@ def test_gapfill_tie_order(ctx, oracle):
 
 
 def test_gapfill_banded_schedule(ctx, oracle):
-    """k_gapfill_fill_ns as vm_align_batch launches it (anti-diagonal band fill, eight problems per wave, optimality proof, redo queue, layout
-    flag): CIGARs vs the oracle on adversarial shapes — |tl - ql| from 0 to beyond the widest band, indels and opposite gap pairs just
+    """vm_align_batch's gap-fill chunk (vmx_gapfill_chunk: anti-diagonal band fill in slots as wide as each problem's band, eight problems per
+    wave, optimality proof, redo queue, layout flag): CIGARs vs the oracle on adversarial shapes — |tl - ql| from 0 to beyond the widest band, indels and opposite gap pairs just
     inside / on / beyond every band width's margin at the start, middle and end, second-piece gaps, tandem repeats, the sizes where the
     band-width rule switches, tl + ql in {1023..1025, 5999..6001}, N runs, mixed waves, eqx on and off"""
     seen = set()

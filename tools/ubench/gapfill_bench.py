@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Gap-fill schedule alone (vm_k_cigar_batch_banded = what vm_align_batch launches for E5) on ONT-shape problems:
+"""Gap-fill schedule alone (vm_k_cigar_batch_banded: vm_align_batch's E5 code, vmx_gapfill_chunk, on one chunk) on ONT-shape problems:
     python tools/ubench/gapfill_bench.py [--n 200000] [--len 268] [--err 0.10] [--reps 3]
 prints problems, wall ms per call (incl. upload / download), stats. Run under rocprofv3 --kernel-trace for the kernel times."""
 import argparse, os, sys, time

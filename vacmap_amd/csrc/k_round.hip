@@ -28,32 +28,14 @@
 
 template <bool DP> struct vmx_round_vals { static constexpr int NV = DP ? 6 : 2; };
 
-// slot width of a small-class problem's own band (0: no band is tried, the problem is filled in full by the second launch out of its pool)
-__device__ __forceinline__ int vmx_round_w(const vmx_round_args& A, long long tl, long long ql) {
-    return VMX_AD_W(vmx_ad_ns((int)tl, (int)ql, A.ad_match, A.ad_o1, A.ad_e1, A.ad_o2, A.ad_e2, A.ad_pct & 0xffff, (A.ad_pct >> 16) & 0xffff));
-}
 template <bool DP>
 __device__ __forceinline__ void vmx_round_values(const vmx_round_args& A, const vmx_pair_desc& d, long long* v) {
     const long long tl = d.t.len, ql = d.q.len;
     v[0] = tl; v[1] = ql;
     if constexpr (DP) {
-        const bool small = tl > 0 && ql > 0 && VMX_DP16X4_OK(tl, ql);
-        v[2] = (small && A.ad_on) ? VMX_AD_TB_BYTES_W(tl, ql, vmx_round_w(A, tl, ql)) : VMX_TB_BYTES_NS(tl, ql);
+        v[2] = vmx_round_tb_bytes(A, tl, ql);
         v[3] = 3 * (ql + 1); v[4] = tl + ql + 2; v[5] = 2 * (tl + ql) + 16;      // (k_dp_sizes of round 1-5)
     }
-}
-// the queue key of a gap-fill problem (vmx_round.h)
-__device__ __forceinline__ long long vmx_round_key(const vmx_round_args& A, long long tl, long long ql) {
-    if (tl <= 0 || ql <= 0) return 0;
-    if (!VMX_DP16X4_OK(tl, ql)) {
-        const long long b = VMX_TB_BYTES(tl, ql);
-        if (b > VMX_HEAD_THRESH) return (b < (1LL << 38) ? b : (1LL << 38)) << 24;
-        return b << 23;
-    }
-    const long long b64 = VMX_AD_TB_BYTES(tl, ql);                       // (tl + ql) * 64: 2^7 .. 2^16
-    if (!A.ad_on) return b64;
-    const int w = vmx_round_w(A, tl, ql);
-    return w == 4 ? b64 << 16 : (w == 2 ? b64 << 6 : (w == 1 ? b64 >> 4 : (b64 >> 14) + 1));
 }
 
 // the traceback chunk plan of a gap-fill round (k_tb_plan of rounds 2-5, unchanged): chunks of at most `limit` traceback bytes, found by bisection on tboff

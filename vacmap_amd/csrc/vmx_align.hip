@@ -59,16 +59,7 @@ __global__ void k_final_scalars(const int64_t* nr, const int64_t* nb, const int3
 
 struct vm_reads { vm_ctx* ctx; int64_t n; std::vector<int64_t> h_off; DevBuf raw, codes, off; };
 
-struct vmx_batch_bufs {
-    DevBuf seed[13];
-    DevBuf nanc64, aoff, rows, lens, keys, koff, sorted, flip, S, P, SA, cov, gmax, opc, rl, gap, scr, soff, res, plen, prow, ocodes;
-    // extend stage
-    DevBuf er, coff3, soff2, segA, st, en, segA_s, st_s, en_s, segprob, dup, desc[2], rcount, oflow, probread, tl, ql, toff, qoff, tpool, qpool;
-    DevBuf edout, carry, ext3, dpsz[4], dpoff[4], dptab, tb, tbredo, bnd, run, cig, ciglen, dpscore, rec, blob, bloboff, reccoff, recclen, dupd, totals;
-    DevBuf raw, codes, off, order, qrange, scanpart, scanoff, si, tg, cntp, fp, pp, chunkn, sellist, cigq, statblk, szh, side_codes, side_off, roundpart, gfctl, geotot;
-    void release() { DevBuf* p = (DevBuf*)this; for (size_t i = 0; i < sizeof(*this) / sizeof(DevBuf); ++i) p[i].release(); }
-};
-static vmx_batch_bufs* batch_bufs(vm_ctx* c) { if (!c->bbufs) c->bbufs = new vmx_batch_bufs(); return c->bbufs; }
+vmx_batch_bufs* vmx_ctx_batch_bufs(vm_ctx* c) { if (!c->bbufs) c->bbufs = new vmx_batch_bufs(); return c->bbufs; }
 void vmx_ctx_free_batch_bufs(vm_ctx* c) { if (c->bbufs) { c->bbufs->release(); delete c->bbufs; c->bbufs = nullptr; } }
 
 // k_chain_select by LDS size class: a read claims 17 B of LDS per anchor for its serial peel, so a launch whose reads have at most `cap`
@@ -103,6 +94,124 @@ int vmx_launch_chain_select(vm_ctx* c, int64_t n, const int64_t* h_aoff, DevBuf&
     return 0;
 }
 
+// S2 + G1/G2 global chain, G3 GC-fast and the selection (vmx_stage.h)
+int vmx_global_stage(vm_ctx* c, vmx_batch_bufs& B, const vm_params* prm, int k, int64_t n, const int64_t* d_roff, const std::vector<int64_t>& h_roff,
+                     const std::vector<int64_t>& h_aoff, int rmode, int32_t* d_ran) {
+    const int64_t tot = h_aoff[n], total_bases = h_roff[n];
+    std::vector<int64_t> koff((size_t)n + 1), soff((size_t)n + 1);
+    int64_t kt = 0, stt = 0;
+    for (int64_t r = 0; r < n; ++r) {
+        int64_t m = h_aoff[r + 1] - h_aoff[r]; int64_t N = 1; while (N < m) N <<= 1;
+        koff[r] = kt; kt += N; soff[r] = stt; stt += (vmx_select_scratch_bytes(m) + 15) & ~(int64_t)15;
+    }
+    koff[n] = kt; soff[n] = stt;
+    VMX_TRY(B.keys.reserve(8 * (size_t)(kt + 1))); VMX_TRY(vmx_push(c, B.koff, koff.data(), (size_t)n + 1));
+    VMX_TRY(B.sorted.reserve(sizeof(vmx_anchor) * (size_t)(tot + 1))); VMX_TRY(B.flip.reserve(4 * (size_t)(n + 1)));
+    hipLaunchKernelGGL(k_flip_sort, dim3((unsigned)std::min<int64_t>(n, (int64_t)c->num_cu * 8)), dim3(256), 0, c->stream, B.rows.as<int64_t>(), B.aoff.as<int64_t>(), B.lens.as<int64_t>(),
+                       (int)n, B.keys.as<uint64_t>(), B.koff.as<int64_t>(), B.sorted.as<vmx_anchor>(), B.flip.as<int32_t>());
+    VMX_TRY(B.S.reserve(8 * (size_t)(tot + 1))); VMX_TRY(B.P.reserve(4 * (size_t)(tot + 1))); VMX_TRY(B.SA.reserve(4 * (size_t)(tot + 1)));
+    VMX_TRY(B.cov.reserve((size_t)tot + 16)); VMX_TRY(B.gmax.reserve(8 * (size_t)(n + 1))); VMX_TRY(B.opc.reserve(8 * (size_t)(n + 1)));
+    const HostTables& T = host_tables();
+    {   // gapcost_list (:24843-24846): 0.01*k*g + 0.5*log2(g), evaluated in double exactly like the reference
+        if (prm->global_maxdiff > 62) { set_error("global_maxdiff > 62 unsupported"); return VM_ERR_UNSUPPORTED; }
+        std::vector<double> gap(64, 0.0);
+        for (int g = 1; g <= prm->global_maxdiff; ++g) gap[g] = (0.01 * k * g + 0.5 * T.log2int[g]);
+        VMX_TRY(vmx_push(c, B.gap, gap.data(), 64));
+    }
+    if (rmode == 1) { VMX_TRY(B.fp.reserve(8 * (size_t)(tot + 1))); VMX_TRY(B.pp.reserve(8 * (size_t)(tot + 1))); }   // fixed_penatly / pre_penatly of mode R's chain
+    // LDS buckets by anchor count (25 B per anchor), reads longest-first inside a bucket, one workgroup per read (see vmx_local_stage)
+    constexpr int NB = 10;
+    const int caps[NB] = {384, 512, 768, 1024, 1536, 2048, 3072, 4096, 8192, 13056};
+    std::vector<int32_t> lists[NB + 1];
+    std::vector<int64_t> asm_long;
+    static const int gc_lds_env = [] { const char* e = getenv("VMX_GC_LDS_MAX"); return e ? atoi(e) : -1; }();     // see vmx_stage_local.hip
+    const int gc_lds_max = gc_lds_env >= 0 ? gc_lds_env : VMX_CHAIN_LDS_MAX_SHARED;
+    const bool rows_kernel = vmx_chain_rows_on() && rmode != 2;          // four reads per wavefront (k_chain_rows.hip); -mode asm keeps the one-wave kernel
+    for (int64_t r = 0; r < n; ++r) {
+        int64_t m = h_aoff[r + 1] - h_aoff[r]; const int64_t L = h_roff[r + 1] - h_roff[r];
+        if (m <= 2) continue;                                             // :23986 unmapped
+        if (prm->mode == VM_MODE_ASM && L >= 500000) { asm_long.push_back(r); continue; }      // mammap_asm.py:23205: the linked path, not built on the device
+        if ((double)m / (double)L > 5.0) continue;                        // fast_enable (:23570): gmax stays -1 -> k_chain_global_fast below
+        int bk = NB; for (int q = 0; q < NB; ++q) if (m <= caps[q] && caps[q] <= gc_lds_max) { bk = q; break; }
+        if (rows_kernel) bk = NB;                                         // k_chain_global_rows: one list, nothing in LDS
+        lists[bk].push_back((int32_t)r);
+    }
+    {
+        std::vector<int32_t> rl; int64_t rl_off[NB + 2];
+        for (int q = 0; q <= NB; ++q) {
+            std::stable_sort(lists[q].begin(), lists[q].end(), [&](int32_t a, int32_t b) { return h_aoff[a + 1] - h_aoff[a] > h_aoff[b + 1] - h_aoff[b]; });
+            rl_off[q] = (int64_t)rl.size(); rl.insert(rl.end(), lists[q].begin(), lists[q].end());
+        }
+        VMX_TRY(vmx_push(c, B.rl, rl.data(), rl.size()));
+        VMX_HIP(hipMemsetAsync(B.gmax.p, 0xff, 8 * (size_t)n, c->stream));
+        { static const int64_t kUnsupported = -4; for (int64_t r : asm_long) VMX_HIP(hipMemcpyAsync(B.gmax.as<int64_t>() + r, &kUnsupported, 8, hipMemcpyHostToDevice, c->stream)); }
+#ifndef VMX_EMU
+        VMX_HIP(hipFuncSetAttribute((const void*)k_chain_global, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)caps[NB - 1] * VMX_GC_BYTES_PER_ANCHOR + 64)));
+#endif
+        vmx_fork fk(c);                                               // the LDS buckets are independent: run them side by side
+        for (int q = NB; q >= 0; --q) {                               // slowest (largest reads) first
+            int cnt = (int)lists[q].size(); if (!cnt) continue;
+            int cap = q < NB ? caps[q] : 0; size_t shmem = (size_t)cap * VMX_GC_BYTES_PER_ANCHOR + 64;
+            if (rows_kernel) {
+                hipLaunchKernelGGL((vmx_chain_rows_win3() ? k_chain_global_rows_w3 : k_chain_global_rows), dim3((unsigned)((cnt + 3) / 4)), dim3(64), 0, fk.next(), B.sorted.as<vmx_anchor>(), B.aoff.as<int64_t>(),
+                                   B.rl.as<int32_t>() + rl_off[q], cnt, c->tables, B.gap.as<double>(), prm->global_skipcost, prm->global_maxdiff, 1000, B.S.as<double>(),
+                                   B.P.as<int32_t>(), B.SA.as<int32_t>(), B.cov.as<uint8_t>(), B.gmax.as<int64_t>(), B.opc.as<int64_t>(), rmode, B.fp.as<double>(), B.pp.as<double>(),
+                                   vmx_chain_dbg());
+                continue;
+            }
+            hipLaunchKernelGGL(k_chain_global, dim3((unsigned)cnt), dim3(64), shmem, fk.next(), B.sorted.as<vmx_anchor>(), B.aoff.as<int64_t>(),
+                               B.rl.as<int32_t>() + rl_off[q], cnt, cap, c->tables, B.gap.as<double>(), prm->global_skipcost, prm->global_maxdiff, 1000, B.S.as<double>(),
+                               B.P.as<int32_t>(), B.SA.as<int32_t>(), B.cov.as<uint8_t>(), B.gmax.as<int64_t>(), B.opc.as<int64_t>(), rmode, B.fp.as<double>(), B.pp.as<double>());
+        }
+        fk.join();
+        vmx_chain_dbg_report(c->stream);
+        // G3: reads left at gmax = -1 (more than 5 anchors per base, :23570, or GC-exact's opcount bail-out, :24914) take GC-fast.
+        // One wave per read; reads that do not need it return at once.
+        VMX_TRY(B.si.reserve(4 * (size_t)(tot + 1))); VMX_TRY(B.tg.reserve(8 * (size_t)(tot + 1))); VMX_TRY(B.cntp.reserve(4 * (size_t)(total_bases + 50 * n + 64)));
+        hipLaunchKernelGGL(k_chain_global_fast, dim3((unsigned)n), dim3(64), 0, c->stream, B.sorted.as<vmx_anchor>(), B.aoff.as<int64_t>(), (int)n, d_roff, c->tables,
+                           B.gap.as<double>(), prm->global_skipcost, prm->global_maxdiff, 1000, B.S.as<double>(), B.P.as<int32_t>(), B.SA.as<int32_t>(), B.cov.as<uint8_t>(),
+                           B.si.as<int32_t>(), B.tg.as<int64_t>(), B.cntp.as<int32_t>(), B.gmax.as<int64_t>(), d_ran, rmode, B.fp.as<double>(), B.pp.as<double>());
+    }
+    VMX_TRY(B.scr.reserve((size_t)stt + 64)); VMX_TRY(vmx_push(c, B.soff, soff.data(), (size_t)n + 1));
+    VMX_TRY(B.res.reserve(16 * (size_t)(n + 2) + 64));
+    double* d_gscore; int32_t* d_mapq; int32_t* d_np; vmx_res_ptrs(B, n, &d_gscore, &d_mapq, &d_np);
+    VMX_TRY(B.plen.reserve(4 * (size_t)(tot + 1))); VMX_TRY(B.prow.reserve(sizeof(vmx_anchor) * (size_t)(tot + 1)));
+    return vmx_launch_chain_select(c, n, h_aoff.data(), B.sellist, B.sorted.as<vmx_anchor>(), B.aoff.as<int64_t>(), B.lens.as<int64_t>(), B.S.as<double>(), B.P.as<int32_t>(), B.SA.as<int32_t>(),
+                                   B.gmax.as<int64_t>(), B.flip.as<int32_t>(), prm->mode, B.scr.as<char>(), B.soff.as<int64_t>(), d_mapq, d_gscore, d_np, B.plen.as<int32_t>(), B.prow.as<vmx_anchor>());
+}
+
+// one gap-fill chunk (vmx_stage.h)
+void vmx_gapfill_chunk(vm_ctx* c, vmx_batch_bufs& B, const vm_score& sc, int ad_pct, int eqx, int p0, int64_t pn, const int32_t* n_ptr, int64_t tb_off0,
+                       int32_t* ctl, int32_t* redo_list, int64_t redo_cap, hipEvent_t* ke) {
+    int fill_waves = 16;                                              // waves per CU of the fill kernel (tuning knob: VMX_FILL_WAVES)
+    if (const char* e = getenv("VMX_FILL_WAVES")) { const int v = atoi(e); if (v >= 1 && v <= 32) fill_waves = v; }
+    static const int tr_spread = [] { const char* e = getenv("VMX_TRACE_SPREAD"); const int v = e ? atoi(e) : 1; return v >= 1 && v <= 64 ? v : 1; }();
+    int32_t* d_range = ctl; int32_t* d_cnt = ctl + 4; int32_t* d_redo_cnt = ctl + 12;
+    unsigned long long* d_redo_bytes = (unsigned long long*)(ctl + 16); int32_t* scratch = ctl + 32;
+    uint8_t* tb_base = B.tb.as<uint8_t>() - tb_off0;           // the problems' absolute traceback offsets index a buffer that holds this chunk only
+    vmx_dp_prob* probs = B.dptab.as<vmx_dp_prob>() + p0; int32_t* score = B.dpscore.as<int32_t>() + p0;
+    const unsigned Gs = (unsigned)std::max<int64_t>(1, std::min<int64_t>((pn + 1023) / 1024, (int64_t)c->num_cu * 2));
+    hipLaunchKernelGGL(k_size_hist, dim3(Gs), dim3(256), 0, c->stream, B.dpsz[0].as<int64_t>() + p0, n_ptr, (int64_t)((1LL << 42) - 1), scratch);        // (queue keys: vmx_round.h)
+    hipLaunchKernelGGL(k_size_scatter, dim3(Gs), dim3(256), 0, c->stream, B.dpsz[0].as<int64_t>() + p0, n_ptr, (const int32_t*)scratch, scratch + 257, B.order.as<int32_t>(), d_range, d_cnt);
+    if (ke) (void)hipEventRecord(ke[0], c->stream);
+    {
+        vmx_lowprio lp(c);                                    // the long launch at the lowest dispatch priority (vmx_host.h)
+        hipLaunchKernelGGL(k_gapfill_fill_ns, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(pn, (int64_t)c->num_cu * fill_waves))), dim3(64), 0, lp.stream(), B.tpool.as<uint8_t>(), B.qpool.as<uint8_t>(),
+                           probs, (int)pn, sc.match, sc.mismatch, sc.o1, sc.e1, sc.o2, sc.e2, tb_base, B.bnd.as<int32_t>(), score, B.order.as<int32_t>(), d_range, d_cnt,
+                           redo_list, d_redo_cnt, 0, ad_pct, (uint8_t*)nullptr, d_redo_bytes, n_ptr, (unsigned long long)redo_cap, 1);
+        lp.join();
+    }
+    // second launch: the problems whose band was not proven (a few per cent), in full: the larger ones on a whole wave, the others four per wave (its queue is the list the
+    // first launch left; any grid works)
+    hipLaunchKernelGGL(k_gapfill_fill_ns, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(pn, (int64_t)c->num_cu * 4))), dim3(64), 0, c->stream, B.tpool.as<uint8_t>(), B.qpool.as<uint8_t>(),
+                       probs, (int)pn, sc.match, sc.mismatch, sc.o1, sc.e1, sc.o2, sc.e2, tb_base, B.bnd.as<int32_t>(), score, B.order.as<int32_t>(), d_range, d_cnt,
+                       redo_list, d_redo_cnt, 1, ad_pct, B.tbredo.as<uint8_t>(), d_redo_bytes, n_ptr, (unsigned long long)redo_cap, 1);
+    if (ke) (void)hipEventRecord(ke[1], c->stream);
+    hipLaunchKernelGGL(k_gapfill_trace, dim3((unsigned)std::max<int64_t>(1, (pn * tr_spread + 63) / 64)), dim3(64), 0, c->stream, B.tpool.as<uint8_t>(), B.qpool.as<uint8_t>(), probs, (int)pn, eqx,
+                       tb_base, B.run.as<uint32_t>(), B.cig.as<char>(), B.ciglen.as<int32_t>() + p0, score, B.tbredo.as<uint8_t>(), tr_spread, B.cigq.as<int32_t>() + p0, n_ptr);
+    if (ke) (void)hipEventRecord(ke[2], c->stream);
+}
+
 #define LAUNCH1D(kernel, n, ...) hipLaunchKernelGGL(kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(((n) + 255) / 256, 4096))), dim3(256), 0, c->stream, __VA_ARGS__)
 
 __global__ void k_ext_geometry(const int32_t* la_cnt, const int64_t* roff, int n, int mul, int tmask, long long tdiv, long long capA, long long capS, long long capB, int64_t* coff3,
@@ -133,6 +242,8 @@ static int dev_scan_dev(vm_ctx* c, vmx_batch_bufs& B, const int64_t* in, int64_t
     return 0;
 }
 
+static const vm_score gf_score = {2, -4, 4, 2, 24, 1};           // the gap fill's scoring (E5: ext_gather_round's band-width rule, vmx_gapfill_chunk)
+
 // one DP round of the extend stage: descriptors (count on device) -> offsets -> gathered pools. The round's problem count stays on the
 // device (B.rcount; every consumer reads it there and launches a grid sized for the hardware, not for the count); it is copied into
 // slot `stat_slot` of the batch's counter block, which the host reads once at the end. want_cnt: also return a host copy (one wait) —
@@ -149,7 +260,7 @@ static int ext_gather_round(vm_ctx* c, vmx_batch_bufs& B, const vm_index_view& i
         for (int i = 0; i < 4; ++i) R.off[2 + i] = B.dpoff[i].as<int64_t>();
         R.tb_size = B.dpsz[0].as<int64_t>(); R.probs = B.dptab.as<vmx_dp_prob>(); R.plan_out = plan_out; R.tb_limit = tb_limit;
         if (caps) for (int i = 0; i < 4; ++i) R.cap[i] = caps[i];          // unplanned pass: every problem is checked against the pools (k_round.hip)
-        R.ad_on = 1; R.ad_match = 2; R.ad_o1 = 4; R.ad_e1 = 2; R.ad_o2 = 24; R.ad_e2 = 1; R.ad_pct = ad_pct;      // the fill's own scoring and band-width rule (gf_chunk)
+        R.ad_on = 1; R.ad_match = gf_score.match; R.ad_o1 = gf_score.o1; R.ad_e1 = gf_score.e1; R.ad_o2 = gf_score.o2; R.ad_e2 = gf_score.e2; R.ad_pct = ad_pct;      // the fill's own scoring and band-width rule
         hipLaunchKernelGGL(k_round_prep<true>, dim3(VMX_ROUND_WGS), dim3(256), 0, c->stream, R);
     } else
         hipLaunchKernelGGL(k_round_prep<false>, dim3(VMX_ROUND_WGS), dim3(256), 0, c->stream, R);
@@ -207,7 +318,7 @@ int align_device(vm_ctx* c, const vm_index* mi, const vm_params* prm, int64_t n,
     std::vector<int32_t> sub;                                    // reads of the batch that were short of an extend-stage pool
     for (int64_t r = 0; r < n; ++r) if (status[(size_t)r] == VMX_EXT_SHORT_INTERNAL || status[(size_t)r] == VMX_EXT_EXACT_INTERNAL) sub.push_back((int32_t)r);
     if (!sub.empty()) {
-        vmx_batch_bufs& B = *batch_bufs(c);
+        vmx_batch_bufs& B = *vmx_ctx_batch_bufs(c);
         std::vector<vm_record> all; all.reserve((size_t)*n_recs);
         {   // (a read that is run again delivers its records from there: the batch's own — none, for every real reason to run a read again — are dropped)
             std::vector<char> again((size_t)n + 1, 0); for (int32_t r : sub) again[(size_t)r] = 1;
@@ -268,14 +379,14 @@ int align_device(vm_ctx* c, const vm_index* mi, const vm_params* prm, int64_t n,
 static int align_device_once(vm_ctx* c, const vm_index* mi, const vm_params* prm, int64_t n, const uint8_t* d_codes, const int64_t* d_roff, const std::vector<int64_t>& h_roff,
                              vm_record** recs, int64_t* n_recs, char** cigar_blob, int32_t* status_per_read, vm_batch_stats* stats, vmx_seg_trace* trace, const vmx_preset* preset) {
     *recs = nullptr; *n_recs = 0; *cigar_blob = nullptr;
-    vmx_batch_bufs& B = *batch_bufs(c);
+    vmx_batch_bufs& B = *vmx_ctx_batch_bufs(c);
     vm_index_view ix; vmx_index_view(mi, &ix);
     const int64_t total_bases = h_roff[n];
     vm_batch_stats st; memset(&st, 0, sizeof st);
     st.n_reads = n; st.read_bases = total_bases;
     hipEvent_t* ev = c->ev; int nev = 0;
     c->n_syncs = 0; c->n_bandfall = 0; c->kev_set = 0; c->sync_wait_ns = 0; download_wait_ns() = 0;
-    c->mb.pend.clear(); c->mb.dn_used = 0; c->mb.big_used = 0;      // (fetches a failed call left behind must not be delivered into its dead buffers)
+    vmx_fetch_scope fetch_scope(c);
     c->call_t0_ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
     VMX_HIP(hipEventRecord(ev[nev++], c->stream));
     if (n == 0) { *recs = (vm_record*)malloc(sizeof(vm_record)); *cigar_blob = (char*)malloc(1); if (stats) *stats = st; return VM_OK; }
@@ -316,87 +427,9 @@ static int align_device_once(vm_ctx* c, const vm_index* mi, const vm_params* prm
     LAUNCH1D(k_readlens, n, d_roff, B.lens.as<int64_t>(), n);
     VMX_HIP(hipEventRecord(ev[nev++], c->stream));
 
-    // ---------------- S2 + G1/G2 global chain
-    std::vector<int64_t> koff((size_t)n + 1), soff((size_t)n + 1);
-    int64_t kt = 0, stt = 0;
-    for (int64_t r = 0; r < n; ++r) {
-        int64_t m = h_aoff[r + 1] - h_aoff[r]; int64_t N = 1; while (N < m) N <<= 1;
-        koff[r] = kt; kt += N; soff[r] = stt; stt += (vmx_select_scratch_bytes(m) + 15) & ~(int64_t)15;
-    }
-    koff[n] = kt; soff[n] = stt;
-    VMX_TRY(B.keys.reserve(8 * (size_t)(kt + 1))); VMX_TRY(vmx_push(c, B.koff, koff.data(), (size_t)n + 1));
-    VMX_TRY(B.sorted.reserve(sizeof(vmx_anchor) * (size_t)(tot + 1))); VMX_TRY(B.flip.reserve(4 * (size_t)(n + 1)));
-    hipLaunchKernelGGL(k_flip_sort, dim3((unsigned)std::min<int64_t>(n, (int64_t)c->num_cu * 8)), dim3(256), 0, c->stream, B.rows.as<int64_t>(), B.aoff.as<int64_t>(), B.lens.as<int64_t>(),
-                       (int)n, B.keys.as<uint64_t>(), B.koff.as<int64_t>(), B.sorted.as<vmx_anchor>(), B.flip.as<int32_t>());
-    VMX_TRY(B.S.reserve(8 * (size_t)(tot + 1))); VMX_TRY(B.P.reserve(4 * (size_t)(tot + 1))); VMX_TRY(B.SA.reserve(4 * (size_t)(tot + 1)));
-    VMX_TRY(B.cov.reserve((size_t)tot + 16)); VMX_TRY(B.gmax.reserve(8 * (size_t)(n + 1))); VMX_TRY(B.opc.reserve(8 * (size_t)(n + 1)));
-    const HostTables& T = host_tables();
-    {
-        if (prm->global_maxdiff > 62) { set_error("global_maxdiff > 62 unsupported"); return VM_ERR_UNSUPPORTED; }
-        std::vector<double> gap(64, 0.0);
-        for (int g = 1; g <= prm->global_maxdiff; ++g) gap[g] = (0.01 * ix.k * g + 0.5 * T.log2int[g]);
-        VMX_TRY(vmx_push(c, B.gap, gap.data(), 64));
-    }
-    if (rmode == 1) { VMX_TRY(B.fp.reserve(8 * (size_t)(tot + 1))); VMX_TRY(B.pp.reserve(8 * (size_t)(tot + 1))); }   // fixed_penatly / pre_penatly of mode R's chain
-    // LDS buckets by anchor count (25 B per anchor), reads longest-first inside a bucket, one workgroup per read (see vmx_local_stage)
-    constexpr int NB = 10;
-    const int caps[NB] = {384, 512, 768, 1024, 1536, 2048, 3072, 4096, 8192, 13056};
-    std::vector<int32_t> lists[NB + 1];
-    std::vector<int64_t> asm_long;
-    static const int gc_lds_env = [] { const char* e = getenv("VMX_GC_LDS_MAX"); return e ? atoi(e) : -1; }();     // see vmx_stage_local.hip
-    const int gc_lds_max = gc_lds_env >= 0 ? gc_lds_env : VMX_CHAIN_LDS_MAX_SHARED;
-    const bool rows_kernel = vmx_chain_rows_on() && rmode != 2;          // four reads per wavefront (k_chain_rows.hip); -mode asm keeps the one-wave kernel
-    for (int64_t r = 0; r < n; ++r) {
-        int64_t m = h_aoff[r + 1] - h_aoff[r]; const int64_t L = h_roff[r + 1] - h_roff[r];
-        if (m <= 2) continue;                                             // :23986 unmapped
-        if (prm->mode == VM_MODE_ASM && L >= 500000) { asm_long.push_back(r); continue; }      // mammap_asm.py:23205: the linked path, not built on the device
-        if ((double)m / (double)L > 5.0) continue;                        // fast_enable (:23570): gmax stays -1 -> k_chain_global_fast below
-        int bk = NB; for (int q = 0; q < NB; ++q) if (m <= caps[q] && caps[q] <= gc_lds_max) { bk = q; break; }
-        if (rows_kernel) bk = NB;                                         // k_chain_global_rows: one list, nothing in LDS
-        lists[bk].push_back((int32_t)r);
-    }
-    {
-        std::vector<int32_t> rl; int64_t rl_off[NB + 2];
-        for (int q = 0; q <= NB; ++q) {
-            std::stable_sort(lists[q].begin(), lists[q].end(), [&](int32_t a, int32_t b) { return h_aoff[a + 1] - h_aoff[a] > h_aoff[b + 1] - h_aoff[b]; });
-            rl_off[q] = (int64_t)rl.size(); rl.insert(rl.end(), lists[q].begin(), lists[q].end());
-        }
-        VMX_TRY(vmx_push(c, B.rl, rl.data(), rl.size()));
-        VMX_HIP(hipMemsetAsync(B.gmax.p, 0xff, 8 * (size_t)n, c->stream));
-        { static const int64_t kUnsupported = -4; for (int64_t r : asm_long) VMX_HIP(hipMemcpyAsync(B.gmax.as<int64_t>() + r, &kUnsupported, 8, hipMemcpyHostToDevice, c->stream)); }
-#ifndef VMX_EMU
-        VMX_HIP(hipFuncSetAttribute((const void*)k_chain_global, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)caps[NB - 1] * VMX_GC_BYTES_PER_ANCHOR + 64)));
-#endif
-        vmx_fork fk(c);                                               // the LDS buckets are independent: run them side by side
-        for (int q = NB; q >= 0; --q) {                               // slowest (largest reads) first
-            int cnt = (int)lists[q].size(); if (!cnt) continue;
-            int cap = q < NB ? caps[q] : 0; size_t shmem = (size_t)cap * VMX_GC_BYTES_PER_ANCHOR + 64;
-            if (rows_kernel) {
-                hipLaunchKernelGGL((vmx_chain_rows_win3() ? k_chain_global_rows_w3 : k_chain_global_rows), dim3((unsigned)((cnt + 3) / 4)), dim3(64), 0, fk.next(), B.sorted.as<vmx_anchor>(), B.aoff.as<int64_t>(),
-                                   B.rl.as<int32_t>() + rl_off[q], cnt, c->tables, B.gap.as<double>(), prm->global_skipcost, prm->global_maxdiff, 1000, B.S.as<double>(),
-                                   B.P.as<int32_t>(), B.SA.as<int32_t>(), B.cov.as<uint8_t>(), B.gmax.as<int64_t>(), B.opc.as<int64_t>(), rmode, B.fp.as<double>(), B.pp.as<double>(),
-                                   vmx_chain_dbg());
-                continue;
-            }
-            hipLaunchKernelGGL(k_chain_global, dim3((unsigned)cnt), dim3(64), shmem, fk.next(), B.sorted.as<vmx_anchor>(), B.aoff.as<int64_t>(),
-                               B.rl.as<int32_t>() + rl_off[q], cnt, cap, c->tables, B.gap.as<double>(), prm->global_skipcost, prm->global_maxdiff, 1000, B.S.as<double>(),
-                               B.P.as<int32_t>(), B.SA.as<int32_t>(), B.cov.as<uint8_t>(), B.gmax.as<int64_t>(), B.opc.as<int64_t>(), rmode, B.fp.as<double>(), B.pp.as<double>());
-        }
-        fk.join();
-        vmx_chain_dbg_report(c->stream);
-        // G3: reads left at gmax = -1 (more than 5 anchors per base, :23570, or GC-exact's opcount bail-out, :24914) take GC-fast.
-        // One wave per read; reads that do not need it return at once.
-        VMX_TRY(B.si.reserve(4 * (size_t)(tot + 1))); VMX_TRY(B.tg.reserve(8 * (size_t)(tot + 1))); VMX_TRY(B.cntp.reserve(4 * (size_t)(total_bases + 50 * n + 64)));
-        hipLaunchKernelGGL(k_chain_global_fast, dim3((unsigned)n), dim3(64), 0, c->stream, B.sorted.as<vmx_anchor>(), B.aoff.as<int64_t>(), (int)n, d_roff, c->tables,
-                           B.gap.as<double>(), prm->global_skipcost, prm->global_maxdiff, 1000, B.S.as<double>(), B.P.as<int32_t>(), B.SA.as<int32_t>(), B.cov.as<uint8_t>(),
-                           B.si.as<int32_t>(), B.tg.as<int64_t>(), B.cntp.as<int32_t>(), B.gmax.as<int64_t>(), (int32_t*)nullptr, rmode, B.fp.as<double>(), B.pp.as<double>());
-    }
-    VMX_TRY(B.scr.reserve((size_t)stt + 64)); VMX_TRY(vmx_push(c, B.soff, soff.data(), (size_t)n + 1));
-    VMX_TRY(B.res.reserve(16 * (size_t)(n + 2) + 64));
-    d_gscore = B.res.as<double>(); d_mapq = (int32_t*)(d_gscore + n + 1); d_np = d_mapq + n + 1;
-    VMX_TRY(B.plen.reserve(4 * (size_t)(tot + 1))); VMX_TRY(B.prow.reserve(sizeof(vmx_anchor) * (size_t)(tot + 1)));
-    VMX_TRY(vmx_launch_chain_select(c, n, h_aoff.data(), B.sellist, B.sorted.as<vmx_anchor>(), B.aoff.as<int64_t>(), B.lens.as<int64_t>(), B.S.as<double>(), B.P.as<int32_t>(), B.SA.as<int32_t>(),
-                                    B.gmax.as<int64_t>(), B.flip.as<int32_t>(), prm->mode, B.scr.as<char>(), B.soff.as<int64_t>(), d_mapq, d_gscore, d_np, B.plen.as<int32_t>(), B.prow.as<vmx_anchor>()));
+    // ---------------- S2 + G1/G2 global chain, G3, selection
+    VMX_TRY(vmx_global_stage(c, B, prm, ix.k, n, d_roff, h_roff, h_aoff, rmode, nullptr));
+    vmx_res_ptrs(B, n, &d_gscore, &d_mapq, &d_np);
     if (prm->mode == VM_MODE_ASM)        // decode_hit's edlib tie-break among equal chains (mammap_asm.py:21302-21326): marked contigs are settled here
         VMX_TRY(vmx_asm_resolve_ties(c, mi, n, h_roff, h_aoff, d_codes, B.sorted.as<vmx_anchor>(), B.S.as<double>(), B.P.as<int32_t>(), B.SA.as<int32_t>(), B.gmax.as<int64_t>(),
                                      B.flip.as<int32_t>(), d_mapq, d_gscore, d_np, B.plen.as<int32_t>(), B.prow.as<vmx_anchor>(), asm_override));
@@ -419,7 +452,7 @@ static int align_device_once(vm_ctx* c, const vm_index* mi, const vm_params* prm
         VMX_TRY(B.ocodes.reserve((size_t)total_bases + 64));
         VMX_HIP(hipMemcpyAsync(B.ocodes.p, d_codes, (size_t)total_bases, hipMemcpyDeviceToDevice, c->stream));
         VMX_TRY(B.res.reserve(16 * (size_t)(n + 2) + 64));
-        d_gscore = B.res.as<double>(); d_mapq = (int32_t*)(d_gscore + n + 1); d_np = d_mapq + n + 1;
+        vmx_res_ptrs(B, n, &d_gscore, &d_mapq, &d_np);
         std::vector<double> gs((size_t)n, 1.0); std::vector<int32_t> mq((size_t)n, 60), one((size_t)n, 1), zero((size_t)n, 0), len32((size_t)n);
         std::vector<vmx_anchor> chains; chains.reserve((size_t)tot_chain);
         L.h_la_off.assign((size_t)n + 1, 0); L.h_la_cnt.assign((size_t)n, 0);
@@ -490,7 +523,7 @@ static int align_device_once(vm_ctx* c, const vm_index* mi, const vm_params* prm
     VMX_TRY(B.recclen.reserve(4 * (size_t)(cS + 1))); VMX_TRY(B.dupd.reserve((size_t)cB + 64));
     VMX_HIP(hipMemsetAsync(B.oflow.p, 0, 4, c->stream));
     VMX_TRY(B.statblk.reserve(2048)); VMX_HIP(hipMemsetAsync(B.statblk.p, 0, 2048, c->stream));     // [0..7] i32 round counts | i64 [32..45] final scalars | i64 [64..121] chunk plan of pass 0 | i64 [128..185] of pass 1
-    const size_t gfctl_bytes = (size_t)2 * (VMX_MAX_CHUNKS + 1) * (32 + 544) * 4;
+    const size_t gfctl_bytes = (size_t)2 * (VMX_MAX_CHUNKS + 1) * VMX_GF_SLOT * 4;
     VMX_TRY(B.gfctl.reserve(gfctl_bytes)); VMX_HIP(hipMemsetAsync(B.gfctl.p, 0, gfctl_bytes, c->stream));      // the gap fill's per-chunk control blocks and size-order scratch (below), cleared once
     vmx_ext_args A; memset(&A, 0, sizeof A);
     A.n_reads = (int)n; A.nseq = ix.nseq; A.local_maxdiff = preset ? 50 : prm->local_maxdiff /* ass_extend_func: large_cost 50, mammap_asm.py:23426 */; A.asm_long = preset ? 1 : 0; A.nodiscard = prm->nodiscard; A.hardclip = prm->hardclip; A.redo_only = 0; A.mode = prm->mode; A.maxdivergence = prm->maxdivergence;
@@ -554,8 +587,6 @@ static int align_device_once(vm_ctx* c, const vm_index* mi, const vm_params* prm
     //  * pass 1 (the nofilter re-run of a read whose segment filter removed something and whose CIGARs carry paired indels, :24079-24080) is not part of a batch at all:
     //    hardly any read asks for it (none of the 150 golden reads, a handful per 100 k synthetic reads), and its eleven launches and one host wait were paid by every batch.
     //    A read that asks for it (E.redo) is run again alone by align_device with both passes (c->run_pass1), like the reads that need the later tiers of the divergence filter.
-    constexpr int GF_SLOT = 32 + 544;                                  // ints per chunk slot of B.gfctl: control block, then the size-order scratch (513 used)
-    auto gf_slot = [&](int pass, int q) -> int32_t* { return B.gfctl.as<int32_t>() + (size_t)(pass * (VMX_MAX_CHUNKS + 1) + q) * GF_SLOT; };
     // The band-width rule (vmx_ad_ns: the narrowest band whose margin covers pct % of the problem) only decides which problems are TRIED in a band and how wide — the
     // proof decides what is kept, so the records do not depend on it. Round 6: pct follows the reads instead of the mode alone. Each context starts at the mode's
     // default (90; mode L 40) and steps down (to 20 at the least) by 20 / 10 while fewer than 1 / 2.5 % of a batch's problems are tried in a band and not proven (they are
@@ -567,40 +598,15 @@ static int align_device_once(vm_ctx* c, const vm_index* mi, const vm_params* prm
     int ad_cur; { std::lock_guard<std::mutex> g(ad_m); if (adr.pct == 0) adr.pct = vmx_ad_pct_env(prm->mode) & 0xffff; ad_cur = adr.pct; }
     const bool ad_pinned = getenv("VMX_AD_PCT") != nullptr || getenv("VMX_AD_PCT_MIN") != nullptr;
     const int ad_pct = ad_pinned ? vmx_ad_pct_env(prm->mode) : (ad_cur | (std::max(20, ad_cur - 25) << 16));
-    int fill_waves = 16;                                              // waves per CU of the fill kernel (tuning knob: VMX_FILL_WAVES)
-    if (const char* e = getenv("VMX_FILL_WAVES")) { const int v = atoi(e); if (v >= 1 && v <= 32) fill_waves = v; }
-    static const int tr_spread = [] { const char* e = getenv("VMX_TRACE_SPREAD"); const int v = e ? atoi(e) : 1; return v >= 1 && v <= 64 ? v : 1; }();
     static const int64_t tb_chunk = [] { const char* e = getenv("VMX_TB_CHUNK_GB"); const double v = e ? atof(e) : 0.0; return v > 0.5 ? (int64_t)(v * (double)(1 << 30)) : (int64_t)VMX_TB_CHUNK; }();     // tuning knob
     int gf_chunks[2] = {0, 0}; int64_t gf_redo_cap = 0;
-    // one chunk: problems [p0, p0 + pn) — pn an upper bound when n_ptr names the count on the device
-    auto gf_chunk = [&](int pass, int q, int p0, int64_t pn, const int32_t* n_ptr, int64_t tb_off0) -> int {
-        int32_t* ctl = gf_slot(pass, q); int32_t* d_range = ctl; int32_t* d_cnt = ctl + 4; int32_t* d_redo_cnt = ctl + 12;
-        unsigned long long* d_redo_bytes = (unsigned long long*)(ctl + 16); int32_t* scratch = ctl + 32;
-        int32_t* d_redo_list = B.order.as<int32_t>() + round_cap + 32;
-        uint8_t* tb_base = B.tb.as<uint8_t>() - tb_off0;           // the problems' absolute traceback offsets index a buffer that holds this chunk only
+    // one chunk: problems [p0, p0 + pn) — pn an upper bound when n_ptr names the count on the device; control block q of the pass's in B.gfctl
+    auto gf_chunk = [&](int pass, int q, int p0, int64_t pn, const int32_t* n_ptr, int64_t tb_off0) {
+        int32_t* ctl = B.gfctl.as<int32_t>() + (size_t)(pass * (VMX_MAX_CHUNKS + 1) + q) * VMX_GF_SLOT;
         hipEvent_t* ke = q < 8 ? c->gev + (pass ? 24 : 0) + 3 * q : nullptr;      // HIP events around the dominant kernel, on the stream it runs on
-        const unsigned Gs = (unsigned)std::max<int64_t>(1, std::min<int64_t>((pn + 1023) / 1024, (int64_t)c->num_cu * 2));
-        hipLaunchKernelGGL(k_size_hist, dim3(Gs), dim3(256), 0, c->stream, B.dpsz[0].as<int64_t>() + p0, n_ptr, (int64_t)((1LL << 42) - 1), scratch);        // (queue keys: k_round.hip)
-        hipLaunchKernelGGL(k_size_scatter, dim3(Gs), dim3(256), 0, c->stream, B.dpsz[0].as<int64_t>() + p0, n_ptr, (const int32_t*)scratch, scratch + 257, B.order.as<int32_t>(), d_range, d_cnt);
-        if (ke) (void)hipEventRecord(ke[0], c->stream);
-        {
-            vmx_lowprio lp(c);                                    // the long launch at the lowest dispatch priority (vmx_host.h)
-            hipLaunchKernelGGL(k_gapfill_fill_ns, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(pn, (int64_t)c->num_cu * fill_waves))), dim3(64), 0, lp.stream(), B.tpool.as<uint8_t>(), B.qpool.as<uint8_t>(),
-                               B.dptab.as<vmx_dp_prob>() + p0, (int)pn, 2, -4, 4, 2, 24, 1, tb_base, B.bnd.as<int32_t>(), B.dpscore.as<int32_t>() + p0, B.order.as<int32_t>(), d_range, d_cnt,
-                               d_redo_list, d_redo_cnt, 0, ad_pct, (uint8_t*)nullptr, d_redo_bytes, n_ptr, (unsigned long long)gf_redo_cap, 1);
-            lp.join();
-        }
-        // second launch: the problems whose band was not proven (a few per cent), in full: the larger ones on a whole wave, the others four per wave (its queue is the list the
-        // first launch left; any grid works)
-        hipLaunchKernelGGL(k_gapfill_fill_ns, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(pn, (int64_t)c->num_cu * 4))), dim3(64), 0, c->stream, B.tpool.as<uint8_t>(), B.qpool.as<uint8_t>(),
-                           B.dptab.as<vmx_dp_prob>() + p0, (int)pn, 2, -4, 4, 2, 24, 1, tb_base, B.bnd.as<int32_t>(), B.dpscore.as<int32_t>() + p0, B.order.as<int32_t>(), d_range, d_cnt,
-                           d_redo_list, d_redo_cnt, 1, ad_pct, B.tbredo.as<uint8_t>(), d_redo_bytes, n_ptr, (unsigned long long)gf_redo_cap, 1);
-        if (ke) (void)hipEventRecord(ke[1], c->stream);
-        hipLaunchKernelGGL(k_gapfill_trace, dim3((unsigned)std::max<int64_t>(1, (pn * tr_spread + 63) / 64)), dim3(64), 0, c->stream, B.tpool.as<uint8_t>(), B.qpool.as<uint8_t>(), B.dptab.as<vmx_dp_prob>() + p0, (int)pn, prm->eqx,
-                           tb_base, B.run.as<uint32_t>(), B.cig.as<char>(), B.ciglen.as<int32_t>() + p0, B.dpscore.as<int32_t>() + p0, B.tbredo.as<uint8_t>(), tr_spread, B.cigq.as<int32_t>() + p0, n_ptr);
-        if (ke) { (void)hipEventRecord(ke[2], c->stream); c->n_gev[pass] = q + 1; }
+        vmx_gapfill_chunk(c, B, gf_score, ad_pct, prm->eqx, p0, pn, n_ptr, tb_off0, ctl, B.order.as<int32_t>() + round_cap + 32, gf_redo_cap, ke);
+        if (ke) c->n_gev[pass] = q + 1;
         gf_chunks[pass] = q + 1;
-        return 0;
     };
     auto gapfill = [&](int redo_only) -> int {
         // per-problem tables are sized for the round's capacity
@@ -636,7 +642,7 @@ static int align_device_once(vm_ctx* c, const vm_index* mi, const vm_params* prm
             if (cnt) {
                 std::vector<int32_t> csz; for (size_t q = 0; q + 1 < cuts.size(); ++q) csz.push_back(cuts[q + 1] - cuts[q]);
                 VMX_TRY(vmx_push(c, B.chunkn, csz.data(), csz.size()));
-                for (size_t q = 0; q + 1 < cuts.size(); ++q) VMX_TRY(gf_chunk(redo_only, (int)q, cuts[q], cuts[q + 1] - cuts[q], B.chunkn.as<int32_t>() + q, h_tboff_at[q]));
+                for (size_t q = 0; q + 1 < cuts.size(); ++q) gf_chunk(redo_only, (int)q, cuts[q], cuts[q + 1] - cuts[q], B.chunkn.as<int32_t>() + q, h_tboff_at[q]);
             }
         }
         A.redo_only = redo_only;
@@ -757,7 +763,7 @@ static int align_device_once(vm_ctx* c, const vm_index* mi, const vm_params* prm
         bool again = false; int64_t need_max = 0, ad_failed = 0;
         for (int pass = 0; pass < 2; ++pass)
             for (int q = 0; q < gf_chunks[pass]; ++q) {
-                const int32_t* ctl = h_ctl.data() + (size_t)(pass * (VMX_MAX_CHUNKS + 1) + q) * GF_SLOT;
+                const int32_t* ctl = h_ctl.data() + (size_t)(pass * (VMX_MAX_CHUNKS + 1) + q) * VMX_GF_SLOT;
                 unsigned long long rb = 0; memcpy(&rb, ctl + 16, 8);
                 st.n_dp_redo += ctl[12]; st.dp_redo_tb_bytes += (int64_t)rb; st.dp_cells += (int64_t)rb; ad_failed += ctl[15];
                 need_max = std::max<int64_t>(need_max, (int64_t)rb);
@@ -933,7 +939,7 @@ int vm_align_resident(vm_ctx* c, const vm_index* mi, const vm_params* prm, const
     if (R->n <= VMX_MAX_BATCH_READS && R->h_off[(size_t)R->n] <= vmx_pass_bases())
         return align_device(c, mi, prm, R->n, R->codes.as<uint8_t>(), R->off.as<int64_t>(), R->h_off, recs, n_recs, cigar_blob, status_per_read, stats);
     // more bases than one pass takes: consecutive ranges of the resident reads (their codes stay where they are; a range's offsets are rebased and uploaded)
-    vmx_batch_bufs& B = *batch_bufs(c);
+    vmx_batch_bufs& B = *vmx_ctx_batch_bufs(c);
     auto run_one = [&](int64_t a, int64_t b, vm_record** r, int64_t* nr, char** cb, vm_batch_stats* st) -> int {
         std::vector<int64_t> h((size_t)(b - a) + 1);
         for (int64_t i = a; i <= b; ++i) h[(size_t)(i - a)] = R->h_off[(size_t)i] - R->h_off[(size_t)a];
@@ -948,7 +954,7 @@ int vm_align_trace(vm_ctx* c, const vm_index* mi, const vm_params* prm, int64_t 
     if (!c) { set_error("no context"); return VM_ERR_NO_CTX; }
     if (stage != 0 && stage != 3 && stage != 5) { set_error("vm_align_trace: stage must be 0, 3 or 5"); return VM_ERR_ARG; }
     VMX_HIP(hipSetDevice(c->device));
-    vmx_batch_bufs& B = *batch_bufs(c);
+    vmx_batch_bufs& B = *vmx_ctx_batch_bufs(c);
     const int64_t tot = offsets[n];
     VMX_TRY(upload(B.raw, seqs, (size_t)tot, c->stream)); VMX_TRY(B.codes.reserve((size_t)tot + 64)); VMX_TRY(upload(B.off, offsets, (size_t)n + 1, c->stream));
     if (tot) LAUNCH1D(k_encode, tot, B.raw.as<char>(), B.codes.as<uint8_t>(), tot);
@@ -967,7 +973,7 @@ int vm_align_trace(vm_ctx* c, const vm_index* mi, const vm_params* prm, int64_t 
 
 static int align_batch_one(vm_ctx* c, const vm_index* mi, const vm_params* prm, int64_t n, const char* seqs, const int64_t* offsets, vm_record** recs, int64_t* n_recs,
                            char** cigar_blob, int32_t* status_per_read, vm_batch_stats* stats) {
-    vmx_batch_bufs& B = *batch_bufs(c);
+    vmx_batch_bufs& B = *vmx_ctx_batch_bufs(c);
     const int64_t base = offsets[0], tot = offsets[n] - base;
     std::vector<int64_t> h_off((size_t)n + 1);
     for (int64_t i = 0; i <= n; ++i) h_off[(size_t)i] = offsets[i] - base;

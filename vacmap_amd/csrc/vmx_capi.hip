@@ -4,6 +4,7 @@
 #include <time.h>
 #include "vmx_select.h"
 #include "vmx_stage.h"
+#include "vmx_round.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -467,27 +468,31 @@ int vm_k_extend_batch(vm_ctx* c, int match, int mismatch, int o, int e, int bw, 
     return VM_OK;
 }
 
-// schedule = 0: k_gapfill_fill (full matrix, scores captured). schedule = 1: exactly what vm_align_batch launches for its gap-fill
-// problems (vmx_align.hip): longest-first device queue, k_gapfill_fill_ns with the anti-diagonal BAND form first (eight small problems per
-// wave), the problems whose band is not proven (or that are not worth a band) queued and filled in full by the second launch, the
-// per-problem layout flag handed to k_gapfill_trace. stats: small problems tried in a band, kept (proven), queued for the second launch
-// (incl. the small ones never tried), problems outside the small class.
-static int k_cigar_batch_impl(vm_ctx* c, const vm_score* sc, int eqx, int schedule, int64_t n, const char* t, const int64_t* t_off, const char* q,
-                              const int64_t* q_off, char** cigars, int64_t** cigar_off, int32_t** scores, int32_t** band_flag, int64_t* stats) {
+// the CIGARs of n problems (problem i's at probs[i].cig_off of the pool, len[i] bytes) as NUL-terminated strings one after the other
+static void cigar_strings(int64_t n, const vmx_dp_prob* probs, const char* pool, const int32_t* len, char** cigars, int64_t** cigar_off) {
+    *cigar_off = host_alloc<int64_t>((size_t)n + 1);
+    int64_t tot = 0;
+    for (int64_t i = 0; i < n; ++i) { (*cigar_off)[i] = tot; tot += len[i] + 1; }
+    (*cigar_off)[n] = tot;
+    *cigars = host_alloc<char>((size_t)tot + 1);
+    for (int64_t i = 0; i < n; ++i) { memcpy(*cigars + (*cigar_off)[i], pool + probs[i].cig_off, (size_t)len[i]); (*cigars)[(*cigar_off)[i] + len[i]] = 0; }
+}
+
+// k_gapfill_fill: the full matrix, scores captured (the reference's k_cigar call shape)
+int vm_k_cigar_batch(vm_ctx* c, const vm_score* sc, int eqx, int64_t n, const char* t, const int64_t* t_off, const char* q,
+                     const int64_t* q_off, char** cigars, int64_t** cigar_off, int32_t** scores) {
     if (!c) { set_error("no context"); return VM_ERR_NO_CTX; }
     if (n > 0x7fffffff) { set_error("too many problems"); return VM_ERR_ARG; }
     VMX_HIP(hipSetDevice(c->device));
     VMX_TRY(upload_encode(c, t, t_off, n, c->b[0], c->b[1], c->b[2]));
     VMX_TRY(upload_encode(c, q, q_off, n, c->b[3], c->b[4], c->b[5]));
     std::vector<vmx_dp_prob> probs((size_t)n);
-    std::vector<int64_t> tbsz((size_t)n);
     int64_t tb = 0, bnd = 0, run = 0, cig = 0;
     for (int64_t i = 0; i < n; ++i) {
         vmx_dp_prob& p = probs[i];
         p.t_off = t_off[i]; p.q_off = q_off[i]; p.tl = (int32_t)(t_off[i + 1] - t_off[i]); p.ql = (int32_t)(q_off[i + 1] - q_off[i]);
         p.tb_off = tb; p.bnd_off = bnd; p.run_off = run; p.cig_off = cig;
-        tbsz[i] = schedule == 0 ? VMX_TB_BYTES((int64_t)p.tl, (int64_t)p.ql) : VMX_TB_BYTES_NS((int64_t)p.tl, (int64_t)p.ql);
-        tb += tbsz[i];
+        tb += VMX_TB_BYTES((int64_t)p.tl, (int64_t)p.ql);
         bnd += 3 * (int64_t)(p.ql + 1); run += (int64_t)p.tl + p.ql + 2; cig += 2 * ((int64_t)p.tl + p.ql) + 16;
     }
     VMX_TRY(upload(c->b[6], probs.data(), (size_t)n, c->stream));
@@ -495,36 +500,12 @@ static int k_cigar_batch_impl(vm_ctx* c, const vm_score* sc, int eqx, int schedu
     VMX_TRY(c->b[9].reserve(sizeof(uint32_t) * (size_t)(run + 4))); VMX_TRY(c->b[10].reserve((size_t)cig + 16));
     VMX_TRY(c->b[11].reserve(sizeof(int32_t) * 2 * (size_t)(n + 1)));
     int32_t* d_score = c->b[11].as<int32_t>(); int32_t* d_len = d_score + n;
-    int32_t redo[2] = {0, 0};
-    const int ad_pct = vmx_ad_pct_env();
-    if (n && schedule == 0) {
+    if (n) {
         hipLaunchKernelGGL(k_gapfill_fill, dim3(grid_for(c, n, 16)), dim3(64), 0, c->stream, c->b[1].as<uint8_t>(), c->b[4].as<uint8_t>(),
                            c->b[6].as<vmx_dp_prob>(), (int)n, sc->match, sc->mismatch, sc->o1, sc->e1, sc->o2, sc->e2, c->b[7].as<uint8_t>(),
                            c->b[8].as<int32_t>(), d_score, (const int32_t*)nullptr, (int32_t*)nullptr);
         hipLaunchKernelGGL(k_gapfill_trace, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, c->b[1].as<uint8_t>(), c->b[4].as<uint8_t>(),
                            c->b[6].as<vmx_dp_prob>(), (int)n, eqx, c->b[7].as<uint8_t>(), c->b[9].as<uint32_t>(), c->b[10].as<char>(), d_len, (const int32_t*)nullptr, (const uint8_t*)nullptr, 1, (int32_t*)nullptr);
-    } else if (n) {
-        const int32_t nn = (int32_t)n;
-        VMX_TRY(upload(c->b[12], tbsz.data(), (size_t)n, c->stream)); VMX_TRY(upload(c->b[13], &nn, 1, c->stream));
-        VMX_TRY(c->b[14].reserve(4 * (size_t)(2 * n + 64))); VMX_TRY(c->b[15].reserve(128));
-        int32_t* d_range = c->b[15].as<int32_t>(); int32_t* d_cnt = d_range + 4; int32_t* d_redo_cnt = d_range + 12;
-        unsigned long long* d_redo_bytes = (unsigned long long*)(d_range + 16);
-        int32_t* d_order = c->b[14].as<int32_t>(); int32_t* d_redo_list = d_order + n + 32;
-        hipLaunchKernelGGL(k_size_order, dim3(1), dim3(1024), 0, c->stream, c->b[12].as<int64_t>(), c->b[13].as<int32_t>(), (int64_t)VMX_HEAD_THRESH, d_order, d_range, d_cnt);
-        VMX_HIP(hipMemsetAsync(d_redo_cnt, 0, 16, c->stream)); VMX_HIP(hipMemsetAsync(d_redo_bytes, 0, 8, c->stream));
-        hipLaunchKernelGGL(k_gapfill_fill_ns, dim3(grid_for(c, n, 16)), dim3(64), 0, c->stream, c->b[1].as<uint8_t>(), c->b[4].as<uint8_t>(), c->b[6].as<vmx_dp_prob>(), (int)n,
-                           sc->match, sc->mismatch, sc->o1, sc->e1, sc->o2, sc->e2, c->b[7].as<uint8_t>(), c->b[8].as<int32_t>(), d_score, d_order, d_range, d_cnt, d_redo_list, d_redo_cnt, 0, ad_pct,
-                           (uint8_t*)nullptr, d_redo_bytes);
-        unsigned long long redo_bytes = 0;
-        VMX_TRY(download(redo, d_redo_cnt, 1, c->stream));          // entries queued by the first launch and the full-matrix traceback space they need
-        VMX_TRY(download(&redo_bytes, d_redo_bytes, 1, c->stream));
-        VMX_HIP(hipStreamSynchronize(c->stream));
-        VMX_TRY(c->b[16].reserve((size_t)redo_bytes + 64));
-        hipLaunchKernelGGL(k_gapfill_fill_ns, dim3(grid_for(c, (n + 3) / 4, 4)), dim3(64), 0, c->stream, c->b[1].as<uint8_t>(), c->b[4].as<uint8_t>(), c->b[6].as<vmx_dp_prob>(), (int)n,
-                           sc->match, sc->mismatch, sc->o1, sc->e1, sc->o2, sc->e2, c->b[7].as<uint8_t>(), c->b[8].as<int32_t>(), d_score, d_order, d_range, d_cnt, d_redo_list, d_redo_cnt, 1, ad_pct,
-                           c->b[16].as<uint8_t>(), d_redo_bytes);
-        hipLaunchKernelGGL(k_gapfill_trace, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, c->b[1].as<uint8_t>(), c->b[4].as<uint8_t>(),
-                           c->b[6].as<vmx_dp_prob>(), (int)n, eqx, c->b[7].as<uint8_t>(), c->b[9].as<uint32_t>(), c->b[10].as<char>(), d_len, d_score, c->b[16].as<uint8_t>(), 1, (int32_t*)nullptr);
     }
     std::vector<char> hc((size_t)cig + 16); std::vector<int32_t> hl((size_t)n);
     *scores = host_alloc<int32_t>((size_t)n);
@@ -533,43 +514,62 @@ static int k_cigar_batch_impl(vm_ctx* c, const vm_score* sc, int eqx, int schedu
     VMX_TRY(download(*scores, d_score, (size_t)n, c->stream));
     VMX_HIP(hipStreamSynchronize(c->stream));
     VMX_HIP(hipGetLastError());
-    if (schedule != 0) {            // the _ns form leaves the layout flag where the score would be (it never captures scores)
-        if (band_flag) { *band_flag = host_alloc<int32_t>((size_t)n); memcpy(*band_flag, *scores, sizeof(int32_t) * (size_t)n); }
-        int64_t nb = 0, eligible = 0;
-        for (int64_t i = 0; i < n; ++i) {
-            const bool small = probs[i].tl > 0 && probs[i].ql > 0 && VMX_DP16X4_OK(probs[i].tl, probs[i].ql);
-            if (!small && band_flag) (*band_flag)[i] = 0;         // (the larger forms leave their score there)
-            nb += small && (*scores)[i] > VMX_AD_FLAG;
-            eligible += probs[i].tl > 0 && probs[i].ql > 0 && VMX_DP16X4_OK(probs[i].tl, probs[i].ql) &&
-                        vmx_ad_ns(probs[i].tl, probs[i].ql, sc->match, sc->o1, sc->e1, sc->o2, sc->e2, ad_pct & 0xffff, (ad_pct >> 16) & 0xffff) > 0;
-            (*scores)[i] = 0;
-        }
-        if (stats) {
-            int64_t small = 0;
-            for (int64_t i = 0; i < n; ++i) small += probs[i].tl > 0 && probs[i].ql > 0 && VMX_DP16X4_OK(probs[i].tl, probs[i].ql);
-            stats[0] = eligible; stats[1] = nb; stats[2] = redo[0]; stats[3] = n - small;
-        }
-    } else if (band_flag) *band_flag = nullptr;
-    *cigar_off = host_alloc<int64_t>((size_t)n + 1);
-    int64_t tot = 0;
-    for (int64_t i = 0; i < n; ++i) { (*cigar_off)[i] = tot; tot += hl[i] + 1; }
-    (*cigar_off)[n] = tot;
-    *cigars = host_alloc<char>((size_t)tot + 1);
-    for (int64_t i = 0; i < n; ++i) { memcpy(*cigars + (*cigar_off)[i], hc.data() + probs[i].cig_off, (size_t)hl[i]); (*cigars)[(*cigar_off)[i] + hl[i]] = 0; }
+    cigar_strings(n, probs.data(), hc.data(), hl.data(), cigars, cigar_off);
     return VM_OK;
 }
 
-int vm_k_cigar_batch(vm_ctx* c, const vm_score* sc, int eqx, int64_t n, const char* t, const int64_t* t_off, const char* q,
-                     const int64_t* q_off, char** cigars, int64_t** cigar_off, int32_t** scores) {
-    return k_cigar_batch_impl(c, sc, eqx, 0, n, t, t_off, q, q_off, cigars, cigar_off, scores, nullptr, nullptr);
-}
-
+// the gap fill of vm_align_batch (vmx_gapfill_chunk) on n problems as one chunk: the problem table is built here with the batch's traceback sizes and queue keys
+// (vmx_round.h), the second launch's pool is sized for its worst case (every small problem filled again in full). stats: small problems tried in a band, kept
+// (proven), queued for the second launch (incl. the small ones never tried), problems outside the small class.
 int vm_k_cigar_batch_banded(vm_ctx* c, const vm_score* sc, int eqx, int64_t n, const char* t, const int64_t* t_off, const char* q,
                             const int64_t* q_off, char** cigars, int64_t** cigar_off, int32_t** band_flag, int64_t* stats) {
-    int32_t* dummy = nullptr;
-    const int rc = k_cigar_batch_impl(c, sc, eqx, 1, n, t, t_off, q, q_off, cigars, cigar_off, &dummy, band_flag, stats);
-    free(dummy);
-    return rc;
+    if (!c) { set_error("no context"); return VM_ERR_NO_CTX; }
+    if (n > 0x7fffffff) { set_error("too many problems"); return VM_ERR_ARG; }
+    VMX_HIP(hipSetDevice(c->device));
+    vmx_fetch_scope fetch_scope(c);
+    vmx_batch_bufs& B = *vmx_ctx_batch_bufs(c);
+    VMX_TRY(upload_encode(c, t, t_off, n, c->b[0], B.tpool, c->b[2]));
+    VMX_TRY(upload_encode(c, q, q_off, n, c->b[3], B.qpool, c->b[5]));
+    const int ad_pct = vmx_ad_pct_env();
+    vmx_round_args R; memset(&R, 0, sizeof R);
+    R.ad_on = 1; R.ad_match = sc->match; R.ad_o1 = sc->o1; R.ad_e1 = sc->e1; R.ad_o2 = sc->o2; R.ad_e2 = sc->e2; R.ad_pct = ad_pct;
+    std::vector<vmx_dp_prob> probs((size_t)n);
+    std::vector<int64_t> keys((size_t)n);
+    int64_t tb = 0, bnd = 0, run = 0, cig = 0, redo = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        vmx_dp_prob& p = probs[i];
+        p.t_off = t_off[i]; p.q_off = q_off[i]; p.tl = (int32_t)(t_off[i + 1] - t_off[i]); p.ql = (int32_t)(q_off[i + 1] - q_off[i]);
+        p.tb_off = tb; p.bnd_off = bnd; p.run_off = run; p.cig_off = cig;
+        tb += vmx_round_tb_bytes(R, p.tl, p.ql); keys[i] = vmx_round_key(R, p.tl, p.ql);
+        if (p.tl > 0 && p.ql > 0 && VMX_DP16X4_OK(p.tl, p.ql)) redo += VMX_REDO_TB_BYTES((int64_t)p.tl, (int64_t)p.ql);
+        bnd += 3 * (int64_t)(p.ql + 1); run += (int64_t)p.tl + p.ql + 2; cig += 2 * ((int64_t)p.tl + p.ql) + 16;
+    }
+    const int32_t nn = (int32_t)n;
+    VMX_TRY(upload(B.dptab, probs.data(), (size_t)n, c->stream)); VMX_TRY(upload(B.dpsz[0], keys.data(), (size_t)n, c->stream)); VMX_TRY(upload(B.chunkn, &nn, 1, c->stream));
+    VMX_TRY(B.tb.reserve((size_t)tb + 64)); VMX_TRY(B.tbredo.reserve((size_t)redo + 64)); VMX_TRY(B.bnd.reserve(sizeof(int32_t) * (size_t)(bnd + 4)));
+    VMX_TRY(B.run.reserve(sizeof(uint32_t) * (size_t)(run + 4))); VMX_TRY(B.cig.reserve((size_t)cig + 16));
+    VMX_TRY(B.ciglen.reserve(4 * (size_t)(n + 1))); VMX_TRY(B.cigq.reserve(4 * (size_t)(n + 1))); VMX_TRY(B.dpscore.reserve(4 * (size_t)(n + 1)));
+    VMX_TRY(B.order.reserve(4 * (size_t)(2 * n + 64)));
+    VMX_TRY(B.gfctl.reserve(4 * VMX_GF_SLOT)); VMX_HIP(hipMemsetAsync(B.gfctl.p, 0, 4 * VMX_GF_SLOT, c->stream));
+    if (n) vmx_gapfill_chunk(c, B, *sc, ad_pct, eqx, 0, n, B.chunkn.as<int32_t>(), 0, B.gfctl.as<int32_t>(), B.order.as<int32_t>() + n + 32, redo, nullptr);
+    std::vector<char> hc((size_t)cig + 16); std::vector<int32_t> hl((size_t)n), flag((size_t)n), ctl(32);
+    VMX_TRY(download(hc.data(), B.cig.p, (size_t)cig, c->stream));
+    VMX_TRY(download(hl.data(), B.ciglen.p, (size_t)n, c->stream));
+    VMX_TRY(download(flag.data(), B.dpscore.p, (size_t)n, c->stream));          // the _ns form leaves the layout flag where the score would be (it never captures scores)
+    VMX_TRY(download(ctl.data(), B.gfctl.p, ctl.size(), c->stream));
+    VMX_HIP(vmx_stream_sync(c));
+    VMX_HIP(hipGetLastError());
+    int64_t nb = 0, eligible = 0, small = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const bool sm = probs[i].tl > 0 && probs[i].ql > 0 && VMX_DP16X4_OK(probs[i].tl, probs[i].ql);
+        if (!sm) flag[i] = 0;                                     // (the larger forms leave their score there)
+        small += sm; nb += sm && flag[i] > VMX_AD_FLAG;
+        eligible += sm && vmx_ad_ns(probs[i].tl, probs[i].ql, sc->match, sc->o1, sc->e1, sc->o2, sc->e2, ad_pct & 0xffff, (ad_pct >> 16) & 0xffff) > 0;
+    }
+    if (stats) { stats[0] = eligible; stats[1] = nb; stats[2] = ctl[12]; stats[3] = n - small; }
+    if (band_flag) { *band_flag = host_alloc<int32_t>((size_t)n); memcpy(*band_flag, flag.data(), sizeof(int32_t) * (size_t)n); }
+    cigar_strings(n, probs.data(), hc.data(), hl.data(), cigars, cigar_off);
+    return VM_OK;
 }
 
 int vm_k_cigar(vm_ctx* c, const char* t, int64_t tl, const char* q, int64_t ql, const vm_score* sc, int bw, int zdrop, int eqx, vm_cigar_out* out) {
@@ -605,120 +605,45 @@ int vm_chain_global_batch(vm_ctx* c, const vm_params* prm, int kmersize, int64_t
     if (!c) { set_error("no context"); return VM_ERR_NO_CTX; }
     if (prm->global_maxdiff > 62) { set_error("global_maxdiff > 62 unsupported"); return VM_ERR_UNSUPPORTED; }
     VMX_HIP(hipSetDevice(c->device));
+    vmx_fetch_scope fetch_scope(c);
+    vmx_batch_bufs& B = *vmx_ctx_batch_bufs(c);
     const int64_t tot = aoff[n];
-    DevBuf &d_rows = c->b[0], &d_aoff = c->b[1], &d_len = c->b[2], &d_keys = c->b[3], &d_koff = c->b[4], &d_sorted = c->b[5], &d_flip = c->b[6];
-    DevBuf &d_S = c->b[7], &d_P = c->b[8], &d_SA = c->b[9], &d_cov = c->b[10], &d_gmax = c->b[11], &d_opc = c->b[12], &d_rl = c->b[13];
-    DevBuf &d_gap = c->b[14], &d_scr = c->b[15], &d_soff = c->b[16], &d_res = c->b[17], &d_plen = c->b[18], &d_prow = c->b[19];
-    VMX_TRY(upload(d_rows, anchors, (size_t)tot * 4, c->stream));
-    VMX_TRY(upload(d_aoff, aoff, (size_t)n + 1, c->stream));
-    VMX_TRY(upload(d_len, readlens, (size_t)n, c->stream));
-    std::vector<int64_t> koff((size_t)n + 1), soff((size_t)n + 1);
-    int64_t kt = 0, st = 0;
-    for (int64_t r = 0; r < n; ++r) {
-        int64_t m = aoff[r + 1] - aoff[r]; int64_t N = 1; while (N < m) N <<= 1;
-        koff[r] = kt; kt += N;
-        soff[r] = st; st += (vmx_select_scratch_bytes(m) + 15) & ~(int64_t)15;
-    }
-    koff[n] = kt; soff[n] = st;
-    VMX_TRY(d_keys.reserve(sizeof(uint64_t) * (size_t)(kt + 1)));
-    VMX_TRY(upload(d_koff, koff.data(), (size_t)n + 1, c->stream));
-    VMX_TRY(d_sorted.reserve(sizeof(vmx_anchor) * (size_t)(tot + 1)));
-    VMX_TRY(d_flip.reserve(sizeof(int32_t) * (size_t)(n + 1)));
-    if (n) hipLaunchKernelGGL(k_flip_sort, dim3(grid_for(c, n, 8)), dim3(256), 0, c->stream, d_rows.as<int64_t>(), d_aoff.as<int64_t>(),
-                              d_len.as<int64_t>(), (int)n, d_keys.as<uint64_t>(), d_koff.as<int64_t>(), d_sorted.as<vmx_anchor>(), d_flip.as<int32_t>());
-    VMX_TRY(d_S.reserve(sizeof(double) * (size_t)(tot + 1))); VMX_TRY(d_P.reserve(sizeof(int32_t) * (size_t)(tot + 1)));
-    VMX_TRY(d_SA.reserve(sizeof(int32_t) * (size_t)(tot + 1))); VMX_TRY(d_cov.reserve((size_t)tot + 16));
-    VMX_TRY(d_gmax.reserve(sizeof(int64_t) * (size_t)(n + 1))); VMX_TRY(d_opc.reserve(sizeof(int64_t) * (size_t)(n + 1)));
-    // gapcost_list (:24843-24846): 0.01*k*g + 0.5*log2(g), evaluated in double exactly like the reference
-    const HostTables& T = host_tables();
-    std::vector<double> gap(64, 0.0);
-    for (int g = 1; g <= prm->global_maxdiff; ++g) gap[g] = (0.01 * kmersize * g + 0.5 * T.log2int[g]);
-    VMX_TRY(upload(d_gap, gap.data(), 64, c->stream));
+    const std::vector<int64_t> h_aoff(aoff, aoff + n + 1);
+    std::vector<int64_t> h_roff((size_t)n + 1, 0);
+    for (int64_t r = 0; r < n; ++r) h_roff[(size_t)r + 1] = h_roff[(size_t)r] + readlens[r];
+    VMX_TRY(upload(B.rows, anchors, (size_t)tot * 4, c->stream)); VMX_TRY(upload(B.aoff, aoff, (size_t)n + 1, c->stream));
+    VMX_TRY(upload(B.lens, readlens, (size_t)n, c->stream)); VMX_TRY(upload(B.off, h_roff.data(), (size_t)n + 1, c->stream));
+    DevBuf& d_ran = c->b[0];                                          // GC-fast's flags: fast_used
+    VMX_TRY(d_ran.reserve(4 * (size_t)(n + 1))); VMX_HIP(hipMemsetAsync(d_ran.p, 0, 4 * (size_t)n, c->stream));
     const int rmode = prm->mode == VM_MODE_R ? 1 : (prm->mode == VM_MODE_ASM ? 2 : 0);
-    if (rmode == 1) { VMX_TRY(c->b[25].reserve(8 * (size_t)(tot + 1))); VMX_TRY(c->b[26].reserve(8 * (size_t)(tot + 1))); }   // mode R: fixed_penatly / pre_penatly
-    // bucket the reads by anchor count so that each launch asks for no more LDS than it needs (160 KiB per CU on gfx950)
-    const int caps[4] = {768, 1536, 3072, 13056};
-    std::vector<int32_t> lists[5];
-    std::vector<char> fastflag((size_t)n, 0);
-    for (int64_t r = 0; r < n; ++r) {
-        int64_t m = aoff[r + 1] - aoff[r];
-        if ((double)m / (double)readlens[r] > 5.0) { fastflag[r] = 1; continue; }   // fast_enable (:23570)
-        int bk = 4; for (int k = 0; k < 4; ++k) if (m <= caps[k]) { bk = k; break; }
-        lists[bk].push_back((int32_t)r);
-    }
-    std::vector<int32_t> rl; std::vector<int64_t> rl_off(6, 0);
-    for (int k = 0; k < 5; ++k) { rl_off[k] = (int64_t)rl.size(); rl.insert(rl.end(), lists[k].begin(), lists[k].end()); }
-    rl_off[5] = (int64_t)rl.size();
-    VMX_TRY(upload(d_rl, rl.data(), rl.size(), c->stream));
-    VMX_HIP(hipMemsetAsync(d_gmax.p, 0xff, sizeof(int64_t) * (size_t)n, c->stream));   // -1 = needs GC-fast
-    if (vmx_chain_rows_on() && rmode != 2 && !rl.empty()) {            // four reads per wavefront (k_chain_rows.hip), most anchors first
-        std::vector<int32_t> all(rl);
-        std::stable_sort(all.begin(), all.end(), [&](int32_t a, int32_t b) { return aoff[a + 1] - aoff[a] > aoff[b + 1] - aoff[b]; });
-        VMX_TRY(upload(d_rl, all.data(), all.size(), c->stream));
-        const int cnt = (int)all.size();
-        hipLaunchKernelGGL((vmx_chain_rows_win3() ? k_chain_global_rows_w3 : k_chain_global_rows), dim3((unsigned)((cnt + 3) / 4)), dim3(64), 0, c->stream, d_sorted.as<vmx_anchor>(), d_aoff.as<int64_t>(),
-                           d_rl.as<int32_t>(), cnt, c->tables, d_gap.as<double>(), prm->global_skipcost, prm->global_maxdiff,
-                           1000, d_S.as<double>(), d_P.as<int32_t>(), d_SA.as<int32_t>(), d_cov.as<uint8_t>(), d_gmax.as<int64_t>(), d_opc.as<int64_t>(), rmode,
-                           c->b[25].as<double>(), c->b[26].as<double>(), vmx_chain_dbg());
-        for (auto& l : lists) l.clear();
-    }
-    for (int k = 0; k < 5; ++k) {
-        int cnt = (int)lists[k].size();
-        if (!cnt) continue;
-        int cap = k < 4 ? caps[k] : 0;
-        size_t shmem = (size_t)cap * VMX_GC_BYTES_PER_ANCHOR + 64;
-#ifndef VMX_EMU
-        if (shmem > 48 * 1024) VMX_HIP(hipFuncSetAttribute((const void*)k_chain_global, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-#endif
-        hipLaunchKernelGGL(k_chain_global, dim3(grid_for(c, cnt, 8)), dim3(64), shmem, c->stream, d_sorted.as<vmx_anchor>(), d_aoff.as<int64_t>(),
-                           d_rl.as<int32_t>() + rl_off[k], cnt, cap, c->tables, d_gap.as<double>(), prm->global_skipcost, prm->global_maxdiff,
-                           1000, d_S.as<double>(), d_P.as<int32_t>(), d_SA.as<int32_t>(), d_cov.as<uint8_t>(), d_gmax.as<int64_t>(), d_opc.as<int64_t>(), rmode,
-                           c->b[25].as<double>(), c->b[26].as<double>());
-    }
-    // G3: reads left at gmax = -1 (fast_enable or the opcount bail-out) go through GC-fast (k_chain_fast.hip)
+    double* d_score = nullptr; int32_t* d_mapq = nullptr; int32_t* d_np = nullptr;
     if (n) {
-        DevBuf &d_si = c->b[20], &d_tg = c->b[21], &d_cnt = c->b[22], &d_roff = c->b[23], &d_ran = c->b[24];
-        VMX_TRY(d_ran.reserve(4 * (size_t)(n + 1))); VMX_HIP(hipMemsetAsync(d_ran.p, 0, 4 * (size_t)n, c->stream));
-        std::vector<int64_t> roff((size_t)n + 1, 0);
-        for (int64_t r = 0; r < n; ++r) roff[(size_t)r + 1] = roff[(size_t)r] + readlens[r];
-        VMX_TRY(upload(d_roff, roff.data(), (size_t)n + 1, c->stream));
-        VMX_TRY(d_si.reserve(4 * (size_t)(tot + 1))); VMX_TRY(d_tg.reserve(8 * (size_t)(tot + 1))); VMX_TRY(d_cnt.reserve(4 * (size_t)(roff[(size_t)n] + 50 * n + 64)));
-        hipLaunchKernelGGL(k_chain_global_fast, dim3((unsigned)n), dim3(64), 0, c->stream, d_sorted.as<vmx_anchor>(), d_aoff.as<int64_t>(), (int)n, d_roff.as<int64_t>(),
-                           c->tables, d_gap.as<double>(), prm->global_skipcost, prm->global_maxdiff, 1000, d_S.as<double>(), d_P.as<int32_t>(), d_SA.as<int32_t>(),
-                           d_cov.as<uint8_t>(), d_si.as<int32_t>(), d_tg.as<int64_t>(), d_cnt.as<int32_t>(), d_gmax.as<int64_t>(), d_ran.as<int32_t>(), rmode,
-                           c->b[25].as<double>(), c->b[26].as<double>());
+        VMX_TRY(vmx_global_stage(c, B, prm, kmersize, n, B.off.as<int64_t>(), h_roff, h_aoff, rmode, d_ran.as<int32_t>()));
+        vmx_res_ptrs(B, n, &d_score, &d_mapq, &d_np);
     }
-    VMX_TRY(d_scr.reserve((size_t)st + 64));
-    VMX_TRY(upload(d_soff, soff.data(), (size_t)n + 1, c->stream));
-    VMX_TRY(d_res.reserve((sizeof(double) + 2 * sizeof(int32_t)) * (size_t)(n + 1) + 64));
-    double* d_score = d_res.as<double>(); int32_t* d_mapq = (int32_t*)(d_score + n + 1); int32_t* d_np = d_mapq + n + 1;
-    VMX_TRY(d_plen.reserve(sizeof(int32_t) * (size_t)(tot + 1))); VMX_TRY(d_prow.reserve(sizeof(vmx_anchor) * (size_t)(tot + 1)));
-    std::vector<int64_t> h_ao(aoff, aoff + n + 1);
-    VMX_TRY(vmx_launch_chain_select(c, n, h_ao.data(), c->b[27], d_sorted.as<vmx_anchor>(), d_aoff.as<int64_t>(), d_len.as<int64_t>(), d_S.as<double>(), d_P.as<int32_t>(), d_SA.as<int32_t>(),
-                                    d_gmax.as<int64_t>(), d_flip.as<int32_t>(), prm->mode, d_scr.as<char>(), d_soff.as<int64_t>(), d_mapq, d_score, d_np, d_plen.as<int32_t>(), d_prow.as<vmx_anchor>()));
     // download
     std::vector<int32_t> h_np((size_t)n), h_plen((size_t)tot);
     std::vector<vmx_anchor> h_prow((size_t)tot);
     out->need_reverse = host_alloc<int32_t>((size_t)n); out->mapq = host_alloc<int32_t>((size_t)n); out->score = host_alloc<double>((size_t)n);
     out->fast_used = host_alloc<int32_t>((size_t)n); out->gmax = host_alloc<int64_t>((size_t)n); out->opcount = host_alloc<int64_t>((size_t)n);
-    VMX_TRY(download(out->need_reverse, d_flip.p, (size_t)n, c->stream)); VMX_TRY(download(out->mapq, d_mapq, (size_t)n, c->stream));
+    VMX_TRY(download(out->need_reverse, B.flip.p, (size_t)n, c->stream)); VMX_TRY(download(out->mapq, d_mapq, (size_t)n, c->stream));
     VMX_TRY(download(out->score, d_score, (size_t)n, c->stream)); VMX_TRY(download(h_np.data(), d_np, (size_t)n, c->stream));
-    VMX_TRY(download(h_plen.data(), d_plen.p, (size_t)tot, c->stream)); VMX_TRY(download(h_prow.data(), d_prow.p, (size_t)tot, c->stream));
-    VMX_TRY(download(out->gmax, d_gmax.p, (size_t)n, c->stream)); VMX_TRY(download(out->opcount, d_opc.p, (size_t)n, c->stream));
+    VMX_TRY(download(h_plen.data(), B.plen.p, (size_t)tot, c->stream)); VMX_TRY(download(h_prow.data(), B.prow.p, (size_t)tot, c->stream));
+    VMX_TRY(download(out->gmax, B.gmax.p, (size_t)n, c->stream)); VMX_TRY(download(out->opcount, B.opc.p, (size_t)n, c->stream));
+    VMX_TRY(download(out->fast_used, d_ran.p, (size_t)n, c->stream));
     std::vector<int32_t> hP, hSA;
     if (want_raw) {
         out->S = host_alloc<double>((size_t)tot); out->P = host_alloc<int64_t>((size_t)tot); out->S_arg = host_alloc<int64_t>((size_t)tot);
         hP.resize((size_t)tot); hSA.resize((size_t)tot);
-        VMX_TRY(download(out->S, d_S.p, (size_t)tot, c->stream)); VMX_TRY(download(hP.data(), d_P.p, (size_t)tot, c->stream));
-        VMX_TRY(download(hSA.data(), d_SA.p, (size_t)tot, c->stream));
+        VMX_TRY(download(out->S, B.S.p, (size_t)tot, c->stream)); VMX_TRY(download(hP.data(), B.P.p, (size_t)tot, c->stream));
+        VMX_TRY(download(hSA.data(), B.SA.p, (size_t)tot, c->stream));
     }
-    VMX_HIP(hipStreamSynchronize(c->stream));
+    VMX_HIP(vmx_stream_sync(c));
     VMX_HIP(hipGetLastError());
     if (want_raw) for (int64_t i = 0; i < tot; ++i) { out->P[i] = hP[i]; out->S_arg[i] = hSA[i]; }
     for (int64_t r = 0; r < n; ++r) if (h_np[r] < 0) h_np[r] = 0;      // -mode asm: a contig waiting for decode_hit's edlib tie-break (made inside vm_align_batch) has no path at this stage entry
     int64_t npaths = 0, nrows = 0;
     for (int64_t r = 0; r < n; ++r) { npaths += h_np[r]; for (int p = 0; p < h_np[r]; ++p) nrows += h_plen[aoff[r] + p]; }
-    if (n) { VMX_TRY(download(out->fast_used, c->b[24].p, (size_t)n, c->stream)); VMX_HIP(hipStreamSynchronize(c->stream)); }
     out->read_path_off = host_alloc<int64_t>((size_t)n + 1); out->path_off = host_alloc<int64_t>((size_t)npaths + 1);
     out->path_anchors = host_alloc<int64_t>((size_t)nrows * 4);
     int64_t pi = 0, ro = 0;

@@ -256,6 +256,14 @@ template <class T> int vmx_fetch(vm_ctx* c, T* host, const void* dev, size_t n, 
     vmx::copy_census().add(file, -line, sizeof(T) * n);
     return vmx_fetch_bytes(c, (void*)host, dev, sizeof(T) * n);
 }
+// held by every call that fetches: drops the fetch notes (and their landing space) that a failed call left behind when the call starts, and its own when it
+// returns with an error (they point into buffers the caller frees). A call that returns normally has waited for all of its fetches: nothing is left to drop.
+struct vmx_fetch_scope {
+    vm_ctx* c;
+    explicit vmx_fetch_scope(vm_ctx* ctx) : c(ctx) { drop(); }
+    ~vmx_fetch_scope() { drop(); }
+    void drop() { c->mb.pend.clear(); c->mb.dn_used = 0; c->mb.big_used = 0; }
+};
 
 // fork/join of independent launches over the context's side streams (all ordered after / before the main stream)
 struct vmx_fork {

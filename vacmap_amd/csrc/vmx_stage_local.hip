@@ -322,6 +322,7 @@ int vm_local_chain_batch(vm_ctx* c, const vm_index* mi, const vm_params* prm, in
     memset(out, 0, sizeof(*out));
     if (!c) { set_error("no context"); return VM_ERR_NO_CTX; }
     VMX_HIP(hipSetDevice(c->device));
+    vmx_fetch_scope fetch_scope(c);
     vm_index_view ix; vmx_index_view(mi, &ix);
     // reads
     DevBuf &raw = c->b[0], &codes = c->b[1], &roff = c->b[2];
