@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — aligned Gbp/s of the seed -> non-linear chain -> extend path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads-per-step R] [--ref-mb M] [--cpu-sample S] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads-per-step R] [--ref-mb M] [--full] [--cpu-sample S] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
+
+A plain run does only what the headline needs: it sets up (reference, reads, index, contexts), warms up, times the K steps, writes
+--dump-outputs if asked, and prints the line. `--full` adds what the headline does not need: the other single-GPU configs in runs of their
+own (extra.configs), the oracle cross-check of the first warm-up batch (oracle_crosscheck), the second timed pass with the reads in host
+memory (host_input) and the CPU baseline (cpu_baseline). It only changes the defaults of --extra-configs, --verify, --host-input and
+--cpu-sample, so each of these can also be asked for on its own.
 
 `--gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset) starts the N ranks ITSELF (launch_ranks below: one child of this same command
 line per GPU with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT set, rank 0's JSON line relayed, any rank's non-zero exit code
@@ -50,6 +56,8 @@ Random{eventset=["DEL:100:200,INV:300:600","INS:100:1000,NML:100:200","NML:100:2
 HBM_PEAK_GBS = 8000.0      # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 METRIC = 'aligned Gbp/s (whole node) + reads/s, 15 kb ONT-shape reads vs hg38-size ref, 1/2/4/8 MI355X'      # BASELINE.json
 DUMP_BYTES = 64 << 20      # --dump-outputs: all arrays together
+# what --full turns on: the defaults of these options with it (without it: "", 0, False, 0)
+FULL_DEFAULTS = {'extra_configs': 'ont_100mb,hifi_hg38,vacsim_r', 'verify': 64, 'host_input': True, 'cpu_sample': 96}
 CIGAR_OPS = 'MIDNSHP=X'
 
 
@@ -233,9 +241,7 @@ def launch_ranks(n, argv, dry_run=False):
     return rc
 
 
-def main():
-    from vacmap_amd.driver import _keep_heap_pages
-    _keep_heap_pages()                          # the driver's allocator setting (freed result buffers are reused, not unmapped): VMX_DRIVER_MALLOPT=0 disables
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=25, help='timed batches (default 25 x 4096 = the 100k reads of configs[1]/[2])')
@@ -245,27 +251,40 @@ def main():
     ap.add_argument('--mean-len', type=int, default=0, help='0: the config\'s (15000 ONT, 18000 HiFi)')
     ap.add_argument('--max-len', type=int, default=100000, help='longest read drawn (ONT shape: the Gamma tail is clipped here; 200000 with --mean-len 30000 = the ultra-long robustness run)')
     ap.add_argument('--err', type=float, default=None, help='default: the config\'s (0.10 ONT, 0.005 HiFi)')
-    ap.add_argument('--cpu-sample', type=int, default=96, help='minimum reads for the CPU baseline leg (rank 0, N=1 only); 0 disables')
+    ap.add_argument('--full', action='store_true', help='also what the headline does not need: the side configs, the oracle cross-check, the host-input pass and the CPU '
+                    'baseline (the defaults of --extra-configs, --verify, --host-input and --cpu-sample become FULL_DEFAULTS\'s; without --full they are off)')
+    ap.add_argument('--cpu-sample', type=int, default=None, help='minimum reads for the CPU baseline leg (rank 0, N=1 only); 0 disables')
     ap.add_argument('--cpu-seconds', type=float, default=15.0, help='target wall time of the CPU baseline leg (the sample is sized by a pilot)')
     ap.add_argument('--streams', type=int, default=0, help='batches in flight per GPU (vacmap_amd.pipeline); 0 (default): five, then as many more (up to eight) as the HBM has room '
                     'for after the sizing run — the scheduler\'s own rule (Pipeline.grow_to_memory)')
     ap.add_argument('--window-batches', type=int, default=16, help='length binning window of the scheduler, in batches')
     ap.add_argument('--arrival-order', action='store_true', help='no length binning: batches in arrival order (measured once for comparison)')
-    ap.add_argument('--no-host-input', dest='host_input', action='store_false', help='skip the second timed pass, in which the same batches are handed over as HOST buffers (page-locked, as the '
-                    'product\'s driver holds them) and uploaded inside vm_align_batch: the PCIe-inclusive rate, reported as `host_input` next to `value`, never as it')
-    ap.add_argument('--verify', type=int, default=64, help='reads of the first batch cross-checked against the oracle (0 disables)')
+    ap.add_argument('--host-input', dest='host_input', action='store_true', default=None, help='a second timed pass, in which the same batches are handed over as HOST buffers '
+                    '(page-locked, as the product\'s driver holds them) and uploaded inside vm_align_batch: the PCIe-inclusive rate, reported as `host_input` next to `value`, never as it')
+    ap.add_argument('--no-host-input', dest='host_input', action='store_false', help='no host-input pass (for --full runs)')
+    ap.add_argument('--verify', type=int, default=None, help='reads of the first batch cross-checked against the oracle (0 disables)')
     ap.add_argument('--config', choices=sorted(CONFIGS), default='ont_hg38', help='BASELINE.json workload: ont_hg38 = the metric\'s configuration (default), '
                     'ont_100mb = configs[1], hifi_hg38 = configs[2] (HiFi 18 kb, 0.5 %% error, -mode L -k 19), vacsim_r = configs[4] (vacsim-grammar donor, HiFi-shape reads across the SVs, -mode R)')
     ap.add_argument('--vacsim-svs', type=int, default=1000, help='vacsim_r: complex SVs per grammar line (six lines)')
-    ap.add_argument('--extra-configs', default='ont_100mb,hifi_hg38,vacsim_r', help='other single-GPU BASELINE configs timed in their own short runs of this script (N = 1 only) and '
+    ap.add_argument('--extra-configs', default=None, help='other single-GPU BASELINE configs timed in their own short runs of this script (N = 1 only) and '
                     'reported under extra.configs next to the headline; "" disables')
     ap.add_argument('--extra-steps', type=int, default=24)
     ap.add_argument('--launch-dry-run', action='store_true', help='with --gpus N: print the N rank environments and the command the launcher would start, and exit')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write what the last one computed (per-read status, records, '
                     'CIGARs; rank 0) as DIR/<name>.npy, at most 64 MB: two builds compared output for output (dump_outputs)')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    for name, full_value in FULL_DEFAULTS.items():
+        if getattr(args, name) is None:
+            setattr(args, name, full_value if args.full else type(full_value)())
     if args.gpus < 1:
         ap.error('--gpus must be >= 1')
+    return args
+
+
+def main():
+    from vacmap_amd.driver import _keep_heap_pages
+    _keep_heap_pages()                          # the driver's allocator setting (freed result buffers are reused, not unmapped): VMX_DRIVER_MALLOPT=0 disables
+    args = parse_args()
     if 'WORLD_SIZE' in os.environ:
         if int(os.environ['WORLD_SIZE']) != args.gpus:       # under a launcher (torchrun): one rank per GPU asked for, nothing else
             sys.stderr.write('bench: --gpus %d does not agree with WORLD_SIZE=%s of the launcher\n' % (args.gpus, os.environ['WORLD_SIZE']))
@@ -281,7 +300,7 @@ def main():
 
     rank = int(os.environ.get('RANK', '0')); world = int(os.environ.get('WORLD_SIZE', '1')); local_rank = int(os.environ.get('LOCAL_RANK', '0'))
     if world == 1 and args.extra_configs and os.environ.get('VMX_BENCH_CHILD') != '1' and os.environ.get('VMX_FORCE_DIST') != '1':
-        # One GPU, side configs asked for (the default command): this process only orchestrates and never touches the GPU. The headline config runs FIRST in a process of
+        # One GPU, side configs asked for (--full): this process only orchestrates and never touches the GPU. The headline config runs FIRST in a process of
         # its own (this command line with --extra-configs ""), then every side config in its own; each finds the device as a fresh process does and has it to itself.
         # (Until late in round 5 the side configs ran in front of the headline run inside this process; run after it, with this process still holding its HIP queues,
         # they lost 6 - 23 %: ont_100mb 3.90 / 3.93 against 4.23, vacsim_r 2.40 / 2.34 against 3.03 Gbp/s — two processes' queues on one device are time-sliced.)
@@ -345,10 +364,15 @@ def main():
         for ev in events:
             types[ev['type']] = types.get(ev['type'], 0) + 1
         vacsim_info = {'complex_svs': 6 * args.vacsim_svs, 'events': len(events), 'events_by_type': types, 'events_reads_are_drawn_around': len(ev_c), 'implant_s': time.time() - tq}
-    for s in range(nsteps):
+
+    def draw(s):            # the reads of step s are a function of (step, rank) alone, so the steps are drawn side by side on the host's cores
         seed = 1000 + 7919 * (s * world + rank)
-        cat, off, truth = synth.sample_reads_concat(source, args.reads_per_step, mean_len=mean_len, err=err, seed=seed, shape=cfg['shape'], min_len=cfg['min_len'], max_len=args.max_len, around=around)
-        pool_cat.append(cat); pool_off.extend((off[1:] + pool_off[-1]).tolist())
+        cat, off, _truth = synth.sample_reads_concat(source, args.reads_per_step, mean_len=mean_len, err=err, seed=seed, shape=cfg['shape'], min_len=cfg['min_len'], max_len=args.max_len, around=around)
+        return cat, off
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max_workers=max(1, min(nsteps, cores // int(os.environ.get('LOCAL_WORLD_SIZE', world))))) as ex:
+        for cat, off in ex.map(draw, range(nsteps)):
+            pool_cat.append(cat); pool_off.extend((off[1:] + pool_off[-1]).tolist())
     pool_cat = np.concatenate(pool_cat); pool_off = np.asarray(pool_off, dtype=np.int64)
     lens = np.diff(pool_off)
     plan = pipeline.plan_batches(lens, args.reads_per_step, args.window_batches, sort=not args.arrival_order)

@@ -334,6 +334,17 @@ def test_bench_launcher_propagates_a_failing_rank():
     assert not [l for l in out.stdout.splitlines() if l.startswith('{')]
 
 
+def test_bench_plain_run_leaves_the_extras_to_full():
+    """a plain `bench.py --gpus 1 --steps N --warmup W` runs the headline alone; --full turns on the side configs, the oracle cross-check, the
+    host-input pass and the CPU baseline; an explicit option wins either way"""
+    import bench
+    extras = lambda a: (a.extra_configs, a.verify, a.host_input, a.cpu_sample)
+    assert extras(bench.parse_args(['--gpus', '1', '--steps', '20', '--warmup', '5'])) == ('', 0, False, 0)
+    assert extras(bench.parse_args(['--gpus', '1', '--steps', '20', '--warmup', '5', '--full'])) == ('ont_100mb,hifi_hg38,vacsim_r', 64, True, 96)
+    assert extras(bench.parse_args(['--full', '--extra-configs', '', '--verify', '16', '--no-host-input'])) == ('', 16, False, 96)
+    assert extras(bench.parse_args(['--verify', '8', '--host-input'])) == ('', 8, True, 0)
+
+
 def test_bench_dump_outputs_are_the_records_of_the_last_step(tmp_path, monkeypatch):
     """`bench.py --dump-outputs`: the jobs of the last step run through KeepRecords (the same vm_align_resident call, the records left in library
     memory until the timed pass is over); dump_outputs writes them as float arrays that hold what ResidentReads.align returns for the same batch

@@ -5,7 +5,7 @@
 set -u
 TAG=${1:-r03}; OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 tail -c 400 $OUT/bench.err
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace -d $OUT/prof3 -o p3 -- python $GRAFT_REPO_ROOT/bench.py --cpu-sample 0 --verify 0 --extra-configs "" > $OUT/bench_prof3.json 2>/dev/null
