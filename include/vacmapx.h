@@ -332,6 +332,26 @@ void vm_fastx_close(vm_fastx*);
 int64_t vm_fastx_read(vm_fastx*, int64_t max_reads, int64_t max_bases, char** names, int64_t** name_off, char** seqs, int64_t** seq_off, char** quals,
                       int64_t** qual_off, char** comments, int64_t** com_off);
 
+/* ------------------------------------------------------------------ BAM output (SAMv1 §4.2, BGZF §4.1) on the device
+ * A writer holds the header's @SQ names (device hash table) and grow-only device / page-locked buffers; use it from one thread at a time.
+ * SAM text is split at its newlines, every line becomes one BAM record (refID from the @SQ order, '*' = -1, RNEXT '=' = RNAME's; bin =
+ * reg2bin(pos, pos + reference span, 1 for CIGAR '*'); above 65 535 CIGAR operations <qlen>S<span>N plus a CG:B,I tag; 'i' tags in the
+ * smallest of c C s S i I; 'f' as strtod + a cast to float). A malformed line makes the call return VM_ERR_ARG and vm_last_error() names
+ * its 1-based line number in the call's text. Results are malloc'ed (vm_free). BGZF members hold <= 65 280 input bytes each, carry no EOF
+ * marker, and depend on the input bytes only. */
+typedef struct vm_bam_writer vm_bam_writer;
+int vm_bam_writer_create(vm_ctx*, const char* sam_header, int64_t len, vm_bam_writer** out);
+void vm_bam_writer_free(vm_bam_writer*);
+/* the BAM header (magic, l_text, text, n_ref, references) as BGZF members */
+int vm_bam_header(vm_bam_writer*, char** out, int64_t* n);
+/* uncompressed BAM records of the lines of sam[0, len) */
+int vm_bam_encode(vm_bam_writer*, const char* sam, int64_t len, char** out, int64_t* n);
+/* the lines of entries idx[j] of blob part[j] (the arguments of vm_blob_gather_parts), encoded and compressed into BGZF members */
+int vm_bam_compress_parts(vm_bam_writer*, const char* const* blobs, const int64_t* const* offs, const int32_t* part, const int64_t* idx, int64_t n,
+                          char** out, int64_t* n_out);
+/* n arbitrary bytes as BGZF members */
+int vm_bgzf_compress(vm_ctx*, const void* in, int64_t n, char** out, int64_t* n_out);
+
 /* cost tables C0 as uploaded to the device (tests): which = 0 extra,1 readgap_h,2 readgap_r,3 large_readgap (f32),
  * 4 log2cache, 5 log2int (f64). returns length, *data = host copy read back FROM THE DEVICE (vm_free) */
 int64_t vm_table(vm_ctx*, int which, void** data);

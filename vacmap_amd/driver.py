@@ -284,6 +284,9 @@ def build_parser():
     p.add_argument('--shard', choices=['auto', 'range', 'batch'], default='auto'); p.add_argument('--parts', action='store_true')
     p.add_argument('--parse-threads', type=int, default=0, help='parser threads per rank over record-aligned slices of a plain input (0: max(1, min(4, t / 4)))')
     p.add_argument('--debug', action='store_true', help='log every read the aligner skipped with its status (vacmap:127; mammap_clrnano.py:24120-24123)')
+    p.add_argument('--bam-writer', choices=['samtools', 'native'], default='samtools',
+                   help='how -o x.bam is written: a `samtools view -b` pipe (default) or the GPU encoder and BGZF compressor (vacmap_amd.bamout); '
+                        'native does not sort: .sorted.bam needs samtools')
     return p
 
 
@@ -318,6 +321,7 @@ def _run_asm(args, lib, ctx, index, prm, rg, mark, out, proc, world, rank, text_
     prm.eqx = 1; prm.check_num = -1; prm.maxdivergence = 1.0
     opts = SamOpts(int(bool(args.MD)), int(args.cs != 'long'), int(bool(args.L)), int(bool(mark)), int(bool(args.H)), int(bool(args.fakecigar)), rg['ID'].encode(), 1)
     seen = set(); n_contigs = n_lines = n_skipped = 0
+    native_bam = args.bam_writer == 'native' and args.o.endswith('.bam')
 
     def blob(parts):
         off = np.zeros(len(parts) + 1, np.int64)
@@ -350,12 +354,18 @@ def _run_asm(args, lib, ctx, index, prm, rg, mark, out, proc, world, rank, text_
             done = {}
             for d in parts:
                 done.update(d)
+        text = []                                                                           # --bam-writer native: the group's lines in one BAM call
         for gi in sorted(done):
             if done[gi] is None:
                 n_skipped += 1
                 continue
-            out.write(done[gi])
+            if native_bam:
+                text.append(done[gi])
+            else:
+                out.write(done[gi])
             n_lines += done[gi].count(b'\n')
+        if text:
+            out.write(b''.join(text))
 
     group, gbases = [], 0
     for grp in args.read:
@@ -417,6 +427,9 @@ def main(argv=None, comm=None):
         _keep_heap_pages()
     if args.o != '-' and not (args.o.endswith('.sam') or args.o.endswith('.bam')):
         sys.exit("Output path must end with .sam, .bam, .sorted.bam, or be '-' for stdout.")
+    native_bam = args.bam_writer == 'native' and args.o.endswith('.bam')
+    if native_bam and args.o.endswith('sorted.bam'):
+        sys.exit('--bam-writer native writes unsorted BAM only: write %s with --bam-writer samtools, or name the output .bam' % args.o)
     world, rank, local_rank = 1, 0, 0
     own_group = False
     # VMX_FORCE_DIST=1: the N-rank start-up at world 1 too (process group over nccl = RCCL, gloo text group, index through a replica built from the
@@ -503,9 +516,14 @@ def main(argv=None, comm=None):
     if range_mode and rank != 0:
         out = open(part_path, 'w+b')
     if rank == 0:
-        out, proc = (open(part_path, 'w+b'), None) if range_mode else _open_output(args.o)
-        for ln in sam.header_lines([(n, ln_) for n, ln_ in zip(names, index.lens)], ' '.join(sys.argv if argv is None else ['vacmapx'] + list(argv)), rg):
-            out.write(ln.encode() + b'\n')
+        head = sam.header_lines([(n, ln_) for n, ln_ in zip(names, index.lens)], ' '.join(sys.argv if argv is None else ['vacmapx'] + list(argv)), rg)
+        if native_bam:
+            from .bamout import BamWriter
+            out, proc = BamWriter(args.o, head, device=device), None          # the header goes in as the BAM header
+        else:
+            out, proc = (open(part_path, 'w+b'), None) if range_mode else _open_output(args.o)
+            for ln in head:
+                out.write(ln.encode() + b'\n')
     if args.mode == 'asm':
         rc = _run_asm(args, lib, ctx, index, prm, rg, mark, out, proc, world, rank, text_group, t_start)
         ctx.close()
@@ -762,6 +780,7 @@ def main(argv=None, comm=None):
 
     def writer():
         """a window's lines in input order (one more gather over the concatenated batch texts) while later windows align and emit"""
+        t_cpu0 = time.thread_time()
         try:
             while True:
                 w = oq.get()
@@ -783,7 +802,9 @@ def main(argv=None, comm=None):
                         parts = []
                 counts['lines'] += nl; counts['skipped'] += ns
                 if parts:
-                    if out_fd is not None:           # straight from the batches' texts to the file, no assembled copy of the window: into the file's own pages
+                    if native_bam:                       # BAM records and BGZF members on the GPU, straight from the batches' texts
+                        out.write_parts([p[1] for p in parts], [p[2] for p in parts], [p[0] for p in parts])
+                    elif out_fd is not None:           # straight from the batches' texts to the file, no assembled copy of the window: into the file's own pages
                         out.flush()                  # by a few threads when it is a regular file (mmap), else one writev stream
                         pos = None
                         if mmap_out:
@@ -802,6 +823,8 @@ def main(argv=None, comm=None):
         except BaseException as e:
             errs.append(e)
         finally:
+            with tml:
+                tm['writer_cpu'] = time.thread_time() - t_cpu0
             for _ in range(n_slots):                    # whatever ended the writer, nobody stays parked on a window slot
                 slots.release()
 

@@ -177,6 +177,12 @@ class VmxLib:
         L.vm_reads_free.argtypes = [vp]
         L.vm_reads_reupload.argtypes = [vp, vp, i64, vp, vp]
         L.vm_align_resident.argtypes = [vp, vp, P(Params), vp, P(P(Record)), P(i64), P(vp), vp, P(BatchStats)]
+        L.vm_bam_writer_create.argtypes = [vp, cp, i64, P(vp)]
+        L.vm_bam_writer_free.argtypes = [vp]; L.vm_bam_writer_free.restype = None
+        L.vm_bam_header.argtypes = [vp, P(vp), P(i64)]
+        L.vm_bam_encode.argtypes = [vp, cp, i64, P(vp), P(i64)]
+        L.vm_bam_compress_parts.argtypes = [vp, vp, vp, vp, vp, i64, P(vp), P(i64)]
+        L.vm_bgzf_compress.argtypes = [vp, vp, i64, P(vp), P(i64)]
 
     def err(self):
         return self.L.vm_last_error().decode()
@@ -622,6 +628,64 @@ def blob_write_parts(lib, fd, blobs, offs, order_keys, file_off=None, nthreads=4
     if w < 0:
         raise VmxError(-1, lib.err())
     return int(w)
+
+
+def _take_bytes(lib, p, n):
+    b = C.string_at(p, n.value) if n.value else b''
+    lib.L.vm_free(p)
+    return b
+
+
+def bgzf_compress(ctx, data):
+    """bytes -> BGZF members (no EOF marker), deflated on the device (vm_bgzf_compress)"""
+    data = bytes(data)
+    p = C.c_void_p(); n = C.c_int64()
+    ctx.lib.check(ctx.lib.L.vm_bgzf_compress(ctx.h, data, len(data), C.byref(p), C.byref(n)))
+    return _take_bytes(ctx.lib, p, n)
+
+
+class BamCodec:
+    """vm_bam_writer: SAM header text -> reference table on the device; SAM lines -> BAM records -> BGZF members"""
+
+    def __init__(self, ctx, header_text):
+        self.ctx, self.lib = ctx, ctx.lib
+        t = _b(header_text)
+        h = C.c_void_p()
+        self.lib.check(self.lib.L.vm_bam_writer_create(ctx.h, t, len(t), C.byref(h)))
+        self.h = h
+
+    def header(self):
+        """BAM magic, header text and references as BGZF members"""
+        p = C.c_void_p(); n = C.c_int64()
+        self.lib.check(self.lib.L.vm_bam_header(self.h, C.byref(p), C.byref(n)))
+        return _take_bytes(self.lib, p, n)
+
+    def encode(self, sam_text):
+        """uncompressed BAM records of SAM lines"""
+        t = _b(sam_text)
+        p = C.c_void_p(); n = C.c_int64()
+        self.lib.check(self.lib.L.vm_bam_encode(self.h, t, len(t), C.byref(p), C.byref(n)))
+        return _take_bytes(self.lib, p, n)
+
+    def compress_parts(self, blobs, offs, order_keys):
+        """the entries of several (blob, off) pairs in ascending order_keys (as blob_gather_parts), as BGZF members of their BAM records"""
+        blobs = [_u8(b) for b in blobs]; offs = [np.ascontiguousarray(o, dtype=np.int64) for o in offs]
+        part, local = _parts_order(blobs, offs, order_keys)
+        bp = (C.c_void_p * max(len(blobs), 1))(*[b.ctypes.data for b in blobs]); op = (C.c_void_p * max(len(offs), 1))(*[o.ctypes.data for o in offs])
+        p = C.c_void_p(); n = C.c_int64()
+        self.lib.check(self.lib.L.vm_bam_compress_parts(self.h, bp, op, part.ctypes.data, local.ctypes.data, len(local), C.byref(p), C.byref(n)))
+        return _take_bytes(self.lib, p, n)
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.L.vm_bam_writer_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Fastx:
