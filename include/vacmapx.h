@@ -198,7 +198,10 @@ int vm_k_cigar_batch(vm_ctx*, const vm_score*, int eqx, int64_t n, const char* t
  * or small but never tried), problems outside the small class}. No scores (that form never captures them). */
 int vm_k_cigar_batch_banded(vm_ctx*, const vm_score*, int eqx, int64_t n, const char* t, const int64_t* t_off, const char* q,
                             const int64_t* q_off, char** cigars, int64_t** cigar_off, int32_t** band_flag, int64_t* stats);
-/* `mp.k_cigar(..., 4,4,4,4, bw=100, zdropvalue=50)` (:2381): banded x-drop extension from (0,0); out t_e[n], q_e[n], score[n] */
+/* `mp.k_cigar(..., 4,4,4,4, bw=100, zdropvalue=50)` (:2381): banded x-drop extension from (0,0) (spec VMX-DP-X); out t_e[n], q_e[n],
+ * score[n]. bw: the band |i - j| <= bw, 0 <= bw <= 496; bw < 0 = no band, accepted when every problem has a side of at most 496 bases.
+ * Anything else returns VM_ERR_UNSUPPORTED and computes nothing: the kernel's LDS ring holds a diagonal of at most 497 cells.
+ * vm_k_cigar with zdrop >= 0 takes this path with its bw. */
 int vm_k_extend_batch(vm_ctx*, int match, int mismatch, int o, int e, int bw, int zdrop, int64_t n, const char* t,
                       const int64_t* t_off, const char* q, const int64_t* q_off, int32_t** t_e, int32_t** q_e, int32_t** score);
 /* single-problem form with the reference's argument list; out mirrors the returned tuple (cigar, q_e, t_e) */

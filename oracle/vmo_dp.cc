@@ -20,7 +20,8 @@
 //   same recurrences (one gap piece) on in-band cells, anchored at (0,0), processed by anti-diagonal
 //   d = i + j = 1,2,...  Best M = 0 at (0,0); a cell replaces the best iff H > M strictly, cells visited
 //   in (d ascending, i ascending) order. After diagonal d: stop if max(m_d, m_{d-1}) < M - zdrop, where m_d is
-//   the max H on diagonal d (m_0 = 0). Returns (t_e, q_e) = (i, j) of the best cell.
+//   the max H on diagonal d (m_0 = 0; -inf on a diagonal without in-band cells: every odd one when bw = 0).
+//   bw < 0: no band. Returns (t_e, q_e) = (i, j) of the best cell.
 // VMX-ED: global unit-cost Levenshtein distance over the 5-letter code alphabet.
 #include "vmo_internal.h"
 #include <algorithm>
@@ -138,7 +139,8 @@ int k_extend(const char* t, int64_t tl, const char* q, int64_t ql, int match, in
         // band |i - j| <= bw with j = d - i  <=>  (d - bw)/2 <= i <= (d + bw)/2
         if (d - bw > 0) ilo = std::max<int64_t>(ilo, (d - bw + 1) / 2);
         ihi = std::min<int64_t>(ihi, (d + bw) / 2);
-        if (ilo > ihi) break;
+        // no cell on d: the end of the band, except for bw = 0, whose odd diagonals are empty up to the last cell (mn, mn)
+        if (ilo > ihi && (bw > 0 || d > 2 * std::min(tl, ql))) break;
         int32_t m_d = NEG;
         for (int64_t i = ilo; i <= ihi; ++i) {
             int64_t j = d - i;

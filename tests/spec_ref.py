@@ -1,0 +1,298 @@
+"""TEST-ONLY: plain NumPy references of the primitive specs, written from the spec text (DESIGN.md §2 and the header comments of
+oracle/vmo_dp.cc and oracle/vmo_seed.cc), not from any implementation of them. Neither the oracle nor the product is imported here:
+these functions judge both. Scores and hashes are int64 / uint64; every DP is the full (or whole banded) matrix, one row at a time.
+
+  levenshtein   VMX-ED     unit-cost edit distance over the 5-letter code alphabet (A C G T, every other byte one code; case ignored)
+  dpg_score     VMX-DP-G   optimal global dual-affine score; cigar_score rescores a CIGAR under the same scoring
+  dpx           VMX-DP-X   banded anti-diagonal x-drop extension: (score, t_e, q_e)
+  sketch        VMX-S1     (w, k) window minimizers with minimap2's published hash64, all ties kept
+  ksw2_order_cigar         VMX-DP-G with ksw2's published tie order, cell by cell (small problems only)
+"""
+import re
+import numpy as np
+
+NEG = -(1 << 50)                 # minus infinity of the DPs: far below any reachable score, far above int64 overflow
+
+_CODE = np.full(256, 4, np.uint8)
+for _i, _c in enumerate('ACGT'):
+    _CODE[ord(_c)] = _CODE[ord(_c.lower())] = _i
+
+
+def codes(s):
+    """A C G T (either case) -> 0 1 2 3, any other byte -> 4"""
+    b = s.encode() if isinstance(s, str) else bytes(s)
+    return _CODE[np.frombuffer(b, np.uint8)] if b else np.zeros(0, np.uint8)
+
+
+# ------------------------------------------------------------------------------------------------ VMX-ED
+def levenshtein(a, b):
+    """D(i, j) = min(D(i-1, j) + 1, D(i, j-1) + 1, D(i-1, j-1) + [a_i != b_j]) over codes. The row's left-to-right dependency is a
+    prefix minimum: D(i, j) = min_{l <= j} (T(l) + j - l) with T(0) = i and T(l) = min(D(i-1, l) + 1, D(i-1, l-1) + [a_i != b_l])."""
+    x, y = codes(a).astype(np.int64), codes(b).astype(np.int64)
+    n = len(y)
+    J = np.arange(n + 1, dtype=np.int64)
+    prev = J.copy()
+    for i in range(1, len(x) + 1):
+        t = np.empty(n + 1, np.int64)
+        t[0] = i
+        t[1:] = np.minimum(prev[1:] + 1, prev[:-1] + (y != x[i - 1]))
+        prev = np.minimum.accumulate(t - J) + J
+    return int(prev[n])
+
+
+# ------------------------------------------------------------------------------------------------ VMX-DP-G
+def _subst(x_i, y, match, mismatch):
+    """s(a, b) = match if a == b and a is A/C/G/T, else mismatch (an N never matches, not even an N)"""
+    return np.where((y == x_i) & (x_i < 4), match, mismatch).astype(np.int64)
+
+
+def _row_gap(H, o, e):
+    """F(j) = max(H(j-1) - o, F(j-1)) - e along a row, F(0) = -inf: max_{l < j} (H(l) - o - (j - l) e)"""
+    J = np.arange(len(H), dtype=np.int64)
+    F = np.full(len(H), NEG, np.int64)
+    if len(H) > 1:
+        F[1:] = np.maximum.accumulate((H + J * e)[:-1]) - o - J[1:] * e
+    return np.maximum(F, NEG)
+
+
+def _close_row(Hv, pieces):
+    """H = max(Hv, F_k) where F_k opens from H itself (an insertion run may follow one of the other piece): iterate to the fixed point"""
+    H = Hv
+    while True:
+        Hn = Hv
+        for o, e in pieces:
+            Hn = np.maximum(Hn, _row_gap(H, o, e))
+        if np.array_equal(Hn, H):
+            return H
+        H = Hn
+
+
+def dpg_score(t, q, match=2, mismatch=-4, o1=4, e1=2, o2=24, e2=1):
+    """VMX-DP-G: max over all global alignments of t (rows, consumed by D) and q (columns, consumed by I) of
+    sum s(a, b) - sum over gap runs of the better piece min_k (o_k + L e_k) (E_k / F_k recurrences, H(0,0) = 0)"""
+    x, y = codes(t), codes(q)
+    pieces = ((o1, e1), (o2, e2))
+    Hv = np.full(len(y) + 1, NEG, np.int64)
+    Hv[0] = 0
+    H = _close_row(Hv, pieces)
+    E = [np.full(len(y) + 1, NEG, np.int64) for _ in pieces]
+    for i in range(1, len(x) + 1):
+        E = [np.maximum(np.maximum(H - o, Ek) - e, NEG) for (o, e), Ek in zip(pieces, E)]
+        Hv = np.maximum(E[0], E[1])
+        Hv[1:] = np.maximum(Hv[1:], H[:-1] + _subst(x[i - 1], y, match, mismatch))
+        H = _close_row(Hv, pieces)
+    return int(H[len(y)])
+
+
+def parse_cigar(cigar):
+    ops = re.findall(r'(\d+)([MIDX=])', cigar)
+    assert ''.join(n + o for n, o in ops) == cigar, 'malformed CIGAR %r' % cigar
+    return [(int(n), o) for n, o in ops]
+
+
+def cigar_score(cigar, t, q, match=2, mismatch=-4, o1=4, e1=2, o2=24, e2=1):
+    """score of the alignment a CIGAR spells, under VMX-DP-G's scoring. It must consume t (M = X D) and q (M = X I) exactly, '=' must
+    be a match and 'X' a mismatch; each gap run of L bases costs min(o1 + e1 L, o2 + e2 L). Raises AssertionError otherwise."""
+    x, y = codes(t), codes(q)
+    i = j = 0
+    sc = 0
+    for L, op in parse_cigar(cigar):
+        assert L > 0, cigar
+        if op in 'M=X':
+            assert i + L <= len(x) and j + L <= len(y), 'CIGAR runs past a side: %s' % cigar
+            eq = (x[i:i + L] == y[j:j + L]) & (x[i:i + L] < 4)
+            assert op != '=' or eq.all(), "'=' over a mismatch at t %d" % i
+            assert op != 'X' or not eq.any(), "'X' over a match at t %d" % i
+            sc += int(eq.sum()) * match + int(L - eq.sum()) * mismatch
+            i += L; j += L
+        else:
+            if op == 'D':
+                i += L
+            else:
+                j += L
+            sc -= min(o1 + e1 * L, o2 + e2 * L)
+    assert i == len(x) and j == len(y), 'CIGAR consumes (%d, %d) of (%d, %d)' % (i, j, len(x), len(y))
+    return sc
+
+
+def ksw2_order_cigar(t, q, match=2, mis=-4, o1=4, e1=2, o2=24, e2=1):
+    """independent pure-Python restatement of VMX-DP-G with the PUBLISHED ksw2 (ksw_extd2, left-aligned) priorities: the source of H is
+    the first of diagonal > E1 (deletion, short piece) > F1 (insertion, short piece) > E2 > F2 that is strictly larger than the ones
+    before it; a gap state continues iff its extension is strictly better than a new opening. Small inputs only."""
+    NEG = -10 ** 9
+    tl, ql = len(t), len(q)
+    mk = lambda: [[NEG] * (ql + 1) for _ in range(tl + 1)]
+    H, E1, E2, F1, F2 = mk(), mk(), mk(), mk(), mk()
+    src, x1, x2, y1, y2 = mk(), mk(), mk(), mk(), mk()
+    H[0][0] = 0
+    for i in range(tl + 1):
+        for j in range(ql + 1):
+            if i == 0 and j == 0:
+                continue
+            if i > 0:
+                a1, a2 = H[i - 1][j] - o1, H[i - 1][j] - o2
+                x1[i][j] = E1[i - 1][j] > a1; x2[i][j] = E2[i - 1][j] > a2
+                E1[i][j] = max(a1, E1[i - 1][j]) - e1; E2[i][j] = max(a2, E2[i - 1][j]) - e2
+            if j > 0:
+                c1, c2 = H[i][j - 1] - o1, H[i][j - 1] - o2
+                y1[i][j] = F1[i][j - 1] > c1; y2[i][j] = F2[i][j - 1] > c2
+                F1[i][j] = max(c1, F1[i][j - 1]) - e1; F2[i][j] = max(c2, F2[i][j - 1]) - e2
+            d = NEG
+            if i > 0 and j > 0:
+                d = H[i - 1][j - 1] + (match if (t[i - 1] == q[j - 1] and t[i - 1] in 'ACGT') else mis)
+            h, sr = d, 0
+            for kk, v in ((1, E1[i][j]), (3, F1[i][j]), (2, E2[i][j]), (4, F2[i][j])):       # state codes: 1 E1, 2 E2, 3 F1, 4 F2
+                if v > h:
+                    h, sr = v, kk
+            H[i][j] = h; src[i][j] = sr
+    ops = []; i, j, st = tl, ql, 0
+    while i > 0 or j > 0:
+        if st == 0:
+            sr = src[i][j]
+            if sr == 0:
+                ops.append('M'); i -= 1; j -= 1
+            else:
+                st = sr
+        elif st in (1, 2):
+            ext = x1[i][j] if st == 1 else x2[i][j]
+            ops.append('D'); i -= 1
+            if not ext:
+                st = 0
+        else:
+            ext = y1[i][j] if st == 3 else y2[i][j]
+            ops.append('I'); j -= 1
+            if not ext:
+                st = 0
+    ops.reverse()
+    out = []; a = 0
+    while a < len(ops):
+        b = a
+        while b < len(ops) and ops[b] == ops[a]:
+            b += 1
+        out.append('%d%s' % (b - a, ops[a])); a = b
+    return ''.join(out), H[tl][ql]
+
+
+# ------------------------------------------------------------------------------------------------ VMX-DP-X
+def dpx(t, q, match=2, mismatch=-4, o=4, e=4, bw=100, zdrop=50):
+    """VMX-DP-X on the whole banded matrix: single affine (o, e), cells with |i - j| <= bw (bw < 0: every cell), anchored at H(0,0) = 0,
+    cells outside the band are -inf. Then the diagonals d = i + j = 1, 2, ... in order: a cell replaces the best M (start: 0 at (0,0)) iff
+    its H > M strictly, cells of a diagonal by ascending i; after diagonal d stop if max(m_d, m_{d-1}) < M - zdrop, m_d the max H on d
+    (-inf for a diagonal without in-band cells, m_0 = 0). Returns (M, t_e, q_e)."""
+    x, y = codes(t), codes(q)
+    tl, ql = len(x), len(y)
+    if bw < 0:
+        bw = max(tl, ql)
+    J = np.arange(ql + 1, dtype=np.int64)
+    mdiag = np.full(tl + ql + 1, NEG, np.int64)          # per diagonal: max H and the smallest i that reaches it
+    adiag = np.zeros(tl + ql + 1, np.int64)
+
+    def finish_row(i, Hv):
+        band = np.abs(J - i) <= bw
+        H = np.where(band, _close_row(np.where(band, Hv, NEG), ((o, e),)), NEG)
+        upd = band & (H > mdiag[i + J])                  # rows by ascending i: strict '>' keeps the smallest i of a diagonal's max
+        mdiag[(i + J)[upd]] = H[upd]; adiag[(i + J)[upd]] = i
+        return H
+
+    Hv = np.full(ql + 1, NEG, np.int64)
+    Hv[0] = 0
+    H = finish_row(0, Hv)
+    E = np.full(ql + 1, NEG, np.int64)
+    for i in range(1, tl + 1):
+        E = np.where(np.abs(J - i) <= bw, np.maximum(np.maximum(H - o, E) - e, NEG), NEG)
+        Hv = E.copy()
+        Hv[1:] = np.maximum(Hv[1:], H[:-1] + _subst(x[i - 1], y, match, mismatch))
+        H = finish_row(i, Hv)
+    M, bi, bj, m_prev = 0, 0, 0, 0
+    for d in range(1, tl + ql + 1):
+        m_d = int(mdiag[d])
+        if m_d > M:
+            M, bi = m_d, int(adiag[d]); bj = d - bi
+        if max(m_d, m_prev) < M - zdrop:
+            break
+        m_prev = m_d
+    return M, bi, bj
+
+
+# ------------------------------------------------------------------------------------------------ VMX-S1
+def hash64(key, mask):
+    """minimap2's published hash64 (Thomas Wang's invertible integer mix), every step modulo 2^(2k)"""
+    key = np.asarray(key, dtype=np.uint64)
+    mask = np.uint64(mask)
+    with np.errstate(over='ignore'):
+        key = (~key + (key << np.uint64(21))) & mask
+        key = key ^ (key >> np.uint64(24))
+        key = ((key + (key << np.uint64(3))) + (key << np.uint64(8))) & mask
+        key = key ^ (key >> np.uint64(14))
+        key = ((key + (key << np.uint64(2))) + (key << np.uint64(4))) & mask
+        key = key ^ (key >> np.uint64(28))
+        key = (key + (key << np.uint64(31))) & mask
+    return key
+
+
+INF64 = np.uint64(0xFFFFFFFFFFFFFFFF)
+
+
+def kmer_hashes(seq, k):
+    """per k-mer start p in [0, L - k]: (hash of the canonical k-mer, strand = rc < fwd); hash INF64 for a k-mer that holds a non-ACGT
+    base or equals its own reverse complement"""
+    c = codes(seq)
+    P = len(c) - k + 1
+    if P <= 0:
+        return np.zeros(0, np.uint64), np.zeros(0, np.int8)
+    mask = (1 << (2 * k)) - 1
+    fwd = np.zeros(P, np.uint64); rc = np.zeros(P, np.uint64)
+    c64 = (c & 3).astype(np.uint64)
+    for a in range(k):
+        fwd = (fwd << np.uint64(2)) | c64[a:a + P]
+        rc = rc | ((np.uint64(3) - c64[a:a + P]) << np.uint64(2 * a))
+    amb = np.concatenate([[0], np.cumsum(c > 3)])
+    valid = (amb[k:k + P] - amb[:P] == 0) & (fwd != rc)
+    h = np.where(valid, hash64(np.minimum(fwd, rc), mask), INF64)
+    z = np.where(valid & (rc < fwd), 1, 0).astype(np.int8)
+    return h, z
+
+
+def sketch(seq, k, w):
+    """VMX-S1: the k-mer start p is a minimizer iff it is valid and some window of w consecutive k-mer starts inside [0, L - k] that
+    contains p (one short window of all starts when there are fewer than w) has its minimum hash equal to p's (ties: all kept).
+    Returns (hash uint64, pos int32, strand int8) by ascending pos."""
+    h, z = kmer_hashes(seq, k)
+    P = len(h)
+    if P == 0:
+        return h, np.zeros(0, np.int32), z
+    wl = min(w, P)
+    wmin = np.lib.stride_tricks.sliding_window_view(h, wl).min(axis=1)
+    # every window holding p has a minimum <= h[p]; p is selected iff the largest of those minima equals h[p]
+    pad = np.concatenate([np.zeros(wl - 1, np.uint64), wmin, np.zeros(P - len(wmin), np.uint64)])
+    best = np.lib.stride_tricks.sliding_window_view(pad, wl).max(axis=1)
+    sel = (h != INF64) & (best == h)
+    pos = np.nonzero(sel)[0]
+    return h[pos], pos.astype(np.int32), z[pos]
+
+
+def sketch_brute(seq, k, w):
+    """sketch() by enumerating every window (tiny inputs)"""
+    h, z = kmer_hashes(seq, k)
+    P = len(h)
+    wins = [range(a, a + w) for a in range(P - w + 1)] if P >= w else ([range(P)] if P else [])
+    keep = set()
+    for win in wins:
+        m = min(int(h[p]) for p in win)
+        keep.update(p for p in win if int(h[p]) == m and h[p] != INF64)
+    pos = sorted(keep)
+    return h[pos].astype(np.uint64), np.array(pos, np.int32), z[pos].astype(np.int8)
+
+
+def index_minimizers(seqs, k, w):
+    """the index of VMX-S1: every contig's sketch (windows never cross contigs) as (hash, gpos << 1 | strand) pairs, gpos = the contig's
+    start in the concatenation of all contigs + p, in ascending (hash, position) order"""
+    hs, ps = [np.zeros(0, np.uint64)], [np.zeros(0, np.uint64)]
+    off = 0
+    for s in seqs:
+        h, p, z = sketch(s, k, w)
+        hs.append(h); ps.append(((p.astype(np.uint64) + np.uint64(off)) << np.uint64(1)) | z.astype(np.uint64))
+        off += len(s)
+    H, Pp = np.concatenate(hs), np.concatenate(ps)
+    o = np.lexsort((Pp, H))
+    return H[o], Pp[o]

@@ -43,7 +43,10 @@ __global__ void __launch_bounds__(64) k_extend(const uint8_t* __restrict__ tcode
         const uint8_t* Q = qcodes + q_off[p];
         const int tl = (int)(t_off[p + 1] - t_off[p]);
         const int ql = (int)(q_off[p + 1] - q_off[p]);
-        int bw = bw_in; if (bw < 0 || bw > VMX_EXT_RING - 16) bw = VMX_EXT_RING - 16;   // host rejects wider bands
+        // bw < 0: no band, i.e. a band as wide as the matrix. A diagonal then holds up to min(tl, ql) + 1 cells; the host refuses the problems
+        // whose diagonals the ring cannot hold (bw > VMX_EXT_RING - 16, or no band and both sides longer than that)
+        const int mn = tl < ql ? tl : ql, mx = tl < ql ? ql : tl;
+        int bw = bw_in; if (bw < 0 || bw > mx) bw = mx;
         for (int x = lane; x < VMX_EXT_RING; x += 64) {
             sH[0][x] = VMX_NEG; sH[1][x] = VMX_NEG; sH[2][x] = VMX_NEG;
             sE[0][x] = VMX_NEG; sE[1][x] = VMX_NEG; sF[0][x] = VMX_NEG; sF[1][x] = VMX_NEG;
@@ -57,7 +60,7 @@ __global__ void __launch_bounds__(64) k_extend(const uint8_t* __restrict__ tcode
             int ihi = d < tl ? d : tl;
             if (d - bw > 0) { int b2 = (d - bw + 1) >> 1; if (b2 > ilo) ilo = b2; }
             { int b3 = (d + bw) >> 1; if (b3 < ihi) ihi = b3; }
-            if (ilo > ihi) break;
+            if (ilo > ihi && (bw > 0 || d > 2 * mn)) break;      // bw = 0: the odd diagonals are empty (m_d = -inf) up to the last cell (mn, mn)
             int* Hc = sH[d % 3]; const int* H1 = sH[(d + 2) % 3]; const int* H2 = sH[(d + 1) % 3];
             int* Ec = sE[d & 1]; const int* E1 = sE[(d + 1) & 1];
             int* Fc = sF[d & 1]; const int* F1 = sF[(d + 1) & 1];

@@ -453,6 +453,11 @@ int vm_k_extend_batch(vm_ctx* c, int match, int mismatch, int o, int e, int bw, 
                       const char* q, const int64_t* q_off, int32_t** t_e, int32_t** q_e, int32_t** score) {
     if (!c) { set_error("no context"); return VM_ERR_NO_CTX; }
     if (bw > 496) { set_error("vm_k_extend_batch: band wider than 496 unsupported"); return VM_ERR_UNSUPPORTED; }
+    if (bw < 0)      // no band: k_extend's LDS ring holds diagonals of up to 497 cells, min(tl, ql) + 1 without a band
+        for (int64_t p = 0; p < n; ++p)
+            if (std::min(t_off[p + 1] - t_off[p], q_off[p + 1] - q_off[p]) > 496) {
+                set_error("vm_k_extend_batch: no band (bw < 0) with both sides longer than 496 unsupported"); return VM_ERR_UNSUPPORTED;
+            }
     VMX_HIP(hipSetDevice(c->device));
     VMX_TRY(upload_encode(c, t, t_off, n, c->b[0], c->b[1], c->b[2]));
     VMX_TRY(upload_encode(c, q, q_off, n, c->b[3], c->b[4], c->b[5]));
