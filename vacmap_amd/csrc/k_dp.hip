@@ -506,6 +506,7 @@ __device__ __forceinline__ void vmx_gapfill_ad_pass(const uint8_t* __restrict__ 
                                                    unsigned long long redo_cap, int tb_by_ns) {
     const int lane = vmx_lane();
     const int pct = ad_pct & 0xffff, pct_min = (ad_pct >> 16) & 0xffff;
+    const bool ad_ok = vmx_ad_scores_ok(match, mismatch, o1, e1, o2, e2);
     // the head of the longest-first queue (range[0] entries: the size classes above the small one) goes one problem per task: eight of them in
     // a row on one wave would be a multi-millisecond serial chain at the start of the launch; then eight at a time
     const int n_head = range[0] < n_prob ? range[0] : n_prob;
@@ -528,7 +529,8 @@ __device__ __forceinline__ void vmx_gapfill_ad_pass(const uint8_t* __restrict__ 
         if (pX >= 0) prX = probs[pX];
         if (pY >= 0) prY = probs[pY];
         const bool x4X = pX >= 0 && prX.tl > 0 && prX.ql > 0 && VMX_DP16X4_OK(prX.tl, prX.ql), x4Y = pY >= 0 && prY.tl > 0 && prY.ql > 0 && VMX_DP16X4_OK(prY.tl, prY.ql);
-        const int nsX = x4X ? vmx_ad_ns(prX.tl, prX.ql, match, o1, e1, o2, e2, pct, pct_min) : 0, nsY = x4Y ? vmx_ad_ns(prY.tl, prY.ql, match, o1, e1, o2, e2, pct, pct_min) : 0;
+        // scores whose values do not fit the band's tagged 16-bit halves (vmx_ad_scores_ok: never the gap fill's own) send every problem to the second launch
+        const int nsX = x4X && ad_ok ? vmx_ad_ns(prX.tl, prX.ql, match, o1, e1, o2, e2, pct, pct_min) : 0, nsY = x4Y && ad_ok ? vmx_ad_ns(prY.tl, prY.ql, match, o1, e1, o2, e2, pct, pct_min) : 0;
         const int ns = vmx_uniform_i32(vmx_wave_max_i32(nsX > nsY ? nsX : nsY));
         bool keepX = false, keepY = false, triedX = false, triedY = false;
         if (ns > 0) {

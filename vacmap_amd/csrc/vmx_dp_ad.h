@@ -35,39 +35,88 @@ __device__ __forceinline__ int vmx_r16_shl1_in(int v, int in) { return __builtin
 __device__ __forceinline__ unsigned vmx_perm(unsigned s0, unsigned s1, unsigned sel) { return __builtin_amdgcn_perm(s0, s1, sel); }
 #endif
 
-// Scores are kept BIASED: a register half holds score + VMX_AD_BIAS, always in [0, 32767]. Every wave-instruction of the two-operand 32-bit
-// class (v_add_u32, v_sub_u32, v_and / or / xor, v_ashrrev_i32) issues in 2.3 cycles on gfx950, everything in the VOP3 / VOP3P / DPP class —
-// all packed-int16 arithmetic — in 4.2 (profiles/r04_q_valu_calibration.md). With non-negative halves that can neither borrow nor carry
-// into each other, subtracting a gap cost or adding the match score is a plain 32-bit subtract / add of the two halves at once, and a
-// half's sign bit becomes a traceback flag with one 32-bit arithmetic shift and a mask; only what compares two scores (v_pk_max_i16, the
-// sign of a v_pk_sub_i16) still needs the packed forms. 26 four-cycle + 22 two-cycle instructions per cell pair (was 40 + 9).
-//   Range: real cells of a problem with tl + ql <= 1024 score in [-1100, 1024]; "-infinity" is -4096 and loses at most 2 per step
-// (1024 steps) plus one gap opening, so with the bias 8192 every half stays in [2000, 9300].
-#define VMX_AD_BIAS 8192
+// TAGGED scores: a register half holds 8 * (score + bias) + tag, an unsigned 16-bit value. Every wave-instruction of the two-operand
+// 32-bit class (v_add_u32, v_sub_u32, v_and / or / xor) issues in 2.3 cycles on gfx950, everything in the VOP3 / VOP3P / DPP class — all
+// packed-int16 arithmetic, v_bfi, v_perm, v_alignbit — in 4.2 (profiles/r04_q_valu_calibration.md). Gap costs and match scores are scaled by
+// 8, so subtracting or adding them is a plain 32-bit subtract / add of both halves at once that never touches the tags (and, with every half
+// of every result inside [0, 65535], never borrows or carries between the halves: the 32-bit sum of the halves' sums is exact whatever the
+// order of the terms). A max is one v_pk_max_u16, and on equal scores the larger tag wins, so the tags encode ksw2's tie order and the
+// winner carries its own traceback code:
+//   - stored H and every gap-opening candidate H - O carry tag 7; stored E1 / F1 / E2 / F2 carry 6 / 3 / 1 / 0 (VMX_AD_T*). An E or F max of
+//     (H - O, E) therefore gives the opening on a tie (as the strict "E > H - O" of the flags always did) and leaves tag 7 when it opened,
+//     the E's own tag when it extended: the extension flag is one bit of the result (E1: bit 0, E2: bit 1, F1: bit 2, F2: bit 0 clear).
+//   - the h max of (H_diag + score [tag 7], E1, F1, E2, F2) takes the first of diagonal > E1 > F1 > E2 > F2 on a tie, and its tag names
+//     the source. One v_and per E / F puts the stored tag back after the max, one v_or per cell the 7 on H.
+// The byte is built per pair of cells (vmx_ad_bytes): the low bytes of the halves are gathered with v_perm into the [k.X, k+1.X, k.Y, k+1.Y]
+// order the stores want, the source comes out of a v_perm lookup on the h tags, the four flags out of three v_bfi. The match score is
+// min(tc ^ qc, PEN) with the codes held << VMX_AD_CSH: 0 on a match, PEN = 8 (match - mismatch) on any mismatch.
+// Compiled (gfx950, NS = 4), one step of four cell pairs with its DPP hand-offs and store: 137 VALU = 62 two-cycle + 75 four-cycle,
+// ~458 cycles by the table, where the int16 form took 203 = 56 + 147, ~746 (profiles/r07_tagged_fill_ab.md).
+//   Range (vmx_ad_bias, vmx_ad_scores_ok): every value a step computes is at most match * (VMX_DP16X4_MAX / 2 + 1) (one match more than the
+// best a problem with tl + ql <= VMX_DP16X4_MAX reaches); "-infinity" is VMX_AD_NEGINF and every value, -infinity included, loses at most
+// max(e1, e2) per step (E = max(..., E_prev) - e), plus one gap opening or mismatch for the candidates fed to a max. The bias lifts that
+// lowest value to 0; the scores fit when the highest one then stays <= 8191. For the gap fill's scoring (2, -4, 4, 2, 24, 1) the values lie
+// in [-6170, 1026]: bias 6170, halves in [0, 57575] of the 65535 an unsigned half allows. The same integers as the former int16 form
+// (score + 8192) are compared, with the same tie rules, so every traceback byte is the same.
 #define VMX_AD_NEGINF (-4096)
-struct vmx_ad_consts { unsigned O1, O2, E1, E2, MATCH, NMIS, ONE, NEGP; };
+#define VMX_AD_CSH 12                                              // codes are held << 12: tc ^ qc is 0 or >= 4096 >= PEN
+#define VMX_AD_TE1 6u
+#define VMX_AD_TF1 3u
+#define VMX_AD_TE2 1u
+#define VMX_AD_TF2 0u
+__host__ __device__ constexpr long long vmx_ad_imax(long long a, long long b) { return a > b ? a : b; }
+__host__ __device__ constexpr long long vmx_ad_imin(long long a, long long b) { return a < b ? a : b; }
+__host__ __device__ constexpr long long vmx_ad_bias(int mismatch, int o1, int e1, int o2, int e2) {
+    return -((long long)VMX_AD_NEGINF - (long long)(VMX_DP16X4_MAX + 1) * vmx_ad_imax(e1, e2) - vmx_ad_imax(vmx_ad_imax(o1, o2), -(long long)mismatch));
+}
+// can the anti-diagonal fill run a problem of the small class (tl + ql <= VMX_DP16X4_MAX) with these scores? Besides the range, -infinity
+// must stay below every real value of the band (a path along diagonal 0, then one gap), gap costs included.
+__host__ __device__ constexpr bool vmx_ad_scores_ok(int match, int mismatch, int o1, int e1, int o2, int e2) {
+    return match >= 0 && mismatch <= match && 8LL * (match - mismatch) <= (1 << VMX_AD_CSH) && o1 >= 0 && e1 >= 0 && o2 >= 0 && e2 >= 0 &&
+           (long long)match * (VMX_DP16X4_MAX / 2 + 1) + vmx_ad_bias(mismatch, o1, e1, o2, e2) <= 8191 &&
+           vmx_ad_imin(mismatch, 0) * (VMX_DP16X4_MAX / 2) - vmx_ad_imin(o1 + (long long)e1 * VMX_DP16X4_MAX, o2 + (long long)e2 * VMX_DP16X4_MAX)
+               - vmx_ad_imax(o1, o2) - vmx_ad_imax(e1, e2) > (long long)VMX_AD_NEGINF + vmx_ad_imax(o1, o2);
+}
+static_assert(vmx_ad_scores_ok(2, -4, 4, 2, 24, 1), "the gap fill's own scoring (vmx_align.hip: gf_score) must fit the tagged 16-bit domain");
+struct vmx_ad_consts { unsigned O1, O2, E1, E2, MATCH, PEN, NH, NE1, NE2, NF1, NF2; };
 
 // one cell (both halves): up = (H, E1, E2) of the cell above, left = (H, F1, F2) of the cell to the left, H = the diagonal predecessor on
-// entry and the cell's H on return; tc / qc = target / query codes. Returns the traceback byte (bits 0-6 of each half).
-__device__ __forceinline__ unsigned vmx_ad_cell(const vmx_ad_consts& K, unsigned upH, unsigned upE1, unsigned upE2, unsigned leftH, unsigned leftF1,
-                                                unsigned leftF2, unsigned tc, unsigned qc, unsigned& H, unsigned& E1, unsigned& E2, unsigned& F1, unsigned& F2) {
-    const unsigned a1 = upH - K.O1, a2 = upH - K.O2;                                   // (32-bit subtract: no half borrows)
-    unsigned b = (unsigned)((int)vmx_pk_sub(a1, upE1) >> 12) & 0x00080008u;             // upE1 > a1: E1 extends (the halves' sign bits land on bits 3 and 19)
-    b |= (unsigned)((int)vmx_pk_sub(a2, upE2) >> 11) & 0x00100010u;
-    const unsigned e1v = vmx_pk_max(a1, upE1) - K.E1, e2v = vmx_pk_max(a2, upE2) - K.E2;
-    const unsigned c1 = leftH - K.O1, c2 = leftH - K.O2;
-    b |= (unsigned)((int)vmx_pk_sub(c1, leftF1) >> 10) & 0x00200020u;                   // F1 > c1
-    b |= (unsigned)((int)vmx_pk_sub(c2, leftF2) >> 9) & 0x00400040u;
-    const unsigned f1v = vmx_pk_max(c1, leftF1) - K.E1, f2v = vmx_pk_max(c2, leftF2) - K.E2;
-    // codes are 0..6: min(tc ^ qc, 1) = 1 on a mismatch; h = H + match - (match - mismatch) * that
-    unsigned h = vmx_pk_mad(vmx_pk_min_u16(tc ^ qc, K.ONE), K.NMIS, H) + K.MATCH;
-    unsigned src = 0, m;
-    m = vmx_pk_neg(vmx_pk_sub(h, e1v)); src = vmx_bfi(m, 0x00010001u, src); h = vmx_pk_max(h, e1v);
-    m = vmx_pk_neg(vmx_pk_sub(h, f1v)); src = vmx_bfi(m, 0x00030003u, src); h = vmx_pk_max(h, f1v);     // ksw2's order: diagonal > E1 > F1 > E2 > F2
-    m = vmx_pk_neg(vmx_pk_sub(h, e2v)); src = vmx_bfi(m, 0x00020002u, src); h = vmx_pk_max(h, e2v);
-    m = vmx_pk_neg(vmx_pk_sub(h, f2v)); src = vmx_bfi(m, 0x00040004u, src); h = vmx_pk_max(h, f2v);
-    H = h; E1 = e1v; E2 = e2v; F1 = f1v; F2 = f2v;
-    return b | src;
+// entry and the cell's H on return; tc / qc = target / query codes (<< VMX_AD_CSH). w = {h, e1, e2, f1, f2} before the tags are put back:
+// what vmx_ad_bytes reads the traceback byte from.
+__device__ __forceinline__ void vmx_ad_cell(const vmx_ad_consts& K, unsigned upH, unsigned upE1, unsigned upE2, unsigned leftH, unsigned leftF1,
+                                            unsigned leftF2, unsigned tc, unsigned qc, unsigned& H, unsigned& E1, unsigned& E2, unsigned& F1, unsigned& F2,
+                                            unsigned (&w)[5]) {
+    const unsigned e1v = vmx_pk_max_u16(upH - K.O1, upE1) - K.E1, e2v = vmx_pk_max_u16(upH - K.O2, upE2) - K.E2;        // tag 7: opened
+    const unsigned f1v = vmx_pk_max_u16(leftH - K.O1, leftF1) - K.E1, f2v = vmx_pk_max_u16(leftH - K.O2, leftF2) - K.E2;
+    E1 = e1v & ~((7u ^ VMX_AD_TE1) * 0x00010001u); E2 = e2v & ~((7u ^ VMX_AD_TE2) * 0x00010001u);                       // 7 -> the stored tag
+    F1 = f1v & ~((7u ^ VMX_AD_TF1) * 0x00010001u); F2 = f2v & ~((7u ^ VMX_AD_TF2) * 0x00010001u);
+    const unsigned hd = H + K.MATCH - vmx_pk_min_u16(tc ^ qc, K.PEN);                                                  // tag 7
+    const unsigned h = vmx_pk_max_u16(vmx_pk_max_u16(hd, E1), vmx_pk_max_u16(vmx_pk_max_u16(F1, E2), F2));
+    H = h | 0x00070007u;
+    w[0] = h; w[1] = e1v; w[2] = e2v; w[3] = f1v; w[4] = f2v;
+}
+
+// the traceback bytes of cells a and b, [a.X, b.X, a.Y, b.Y] (the order the stores take): bits 0-2 the source (0 diagonal, 1 E1, 2 E2, 3 F1,
+// 4 F2), bits 3-6 the extension flags of E1, E2, F1, F2 — the byte the striped forms of k_dp.hip write
+__device__ __forceinline__ unsigned vmx_ad_bytes(const unsigned (&a)[5], const unsigned (&b)[5]) {
+    constexpr unsigned SEL = 0x06020400u;                                   // low bytes of the halves of a and b
+    const unsigned gh = vmx_perm(b[0], a[0], SEL), ge1 = vmx_perm(b[1], a[1], SEL), ge2 = vmx_perm(b[2], a[2], SEL);
+    const unsigned gf1 = vmx_perm(b[3], a[3], SEL), gf2 = vmx_perm(b[4], a[4], SEL);
+    // source by the h tag: 7 -> 0, 6 (E1) -> 1, 1 (E2) -> 2, 3 (F1) -> 3, 0 (F2) -> 4
+    const unsigned src = vmx_perm(0x00010000u, 0x03000204u, gh & 0x07070707u);
+    unsigned op = vmx_bfi(0x01010101u, ge1, ge2);                           // "opened" bits: 0 E1, 1 E2 (tag 7, not 6 / 1)
+    op = vmx_bfi(0x04040404u, gf1, op);                                     // 2 F1 (7, not 3)
+    op = vmx_bfi(0x08080808u, (gf2 << 3) | (gf2 >> 29), op);                // 3 F2 (7, not 0; bit 0 of each byte rotated to bit 3)
+    return src | (((op & 0x0f0f0f0fu) ^ 0x0f0f0f0fu) << 3);
+}
+
+// the step's stores: w01 = [0.X, 1.X, 0.Y, 1.Y], w23 = [2.X, 3.X, 2.Y, 3.Y]; the byte of a cell the band does not have (k >= NS) is 0
+template <int NS>
+__device__ __forceinline__ void vmx_ad_pack(const unsigned (&w)[NS][5], unsigned& w01, unsigned& w23) {
+    w01 = vmx_ad_bytes(w[0], w[NS > 1 ? 1 : 0]);
+    w23 = 0;
+    if (NS > 2) w23 = vmx_ad_bytes(w[NS > 2 ? 2 : 0], w[NS > 3 ? 3 : 0]);
+    if (NS == 3) w23 &= 0x00ff00ffu;
 }
 
 // v[k] by masks, not by a select of array elements (which the compiler turns into a dynamically indexed load and the arrays into memory)
@@ -87,16 +136,20 @@ __device__ __forceinline__ void vmx_gapfill_fill_ad(const uint8_t* __restrict__ 
                                                    int match, int mismatch, int o1, int e1, int o2, int e2, int lane, int& scoreX, int& scoreY) {
     const int l = lane & 15;
     vmx_ad_consts K;
-    K.O1 = vmx_pk(o1, o1); K.O2 = vmx_pk(o2, o2); K.E1 = vmx_pk(e1, e1); K.E2 = vmx_pk(e2, e2);
-    K.MATCH = vmx_pk(match, match); K.NMIS = vmx_pk(mismatch - match, mismatch - match); K.ONE = vmx_pk(1, 1); K.NEGP = vmx_pk(VMX_AD_NEGINF + VMX_AD_BIAS, VMX_AD_NEGINF + VMX_AD_BIAS);
+    K.O1 = vmx_pk(8 * o1, 8 * o1); K.O2 = vmx_pk(8 * o2, 8 * o2); K.E1 = vmx_pk(8 * e1, 8 * e1); K.E2 = vmx_pk(8 * e2, 8 * e2);
+    K.MATCH = vmx_pk(8 * match, 8 * match); K.PEN = vmx_pk(8 * (match - mismatch), 8 * (match - mismatch));
+    const int bias = (int)vmx_ad_bias(mismatch, o1, e1, o2, e2);         // (the caller checked vmx_ad_scores_ok)
+    const unsigned neg = 8u * (unsigned)(VMX_AD_NEGINF + bias);
+    K.NH = (neg + 7u) * 0x00010001u; K.NE1 = (neg + VMX_AD_TE1) * 0x00010001u; K.NE2 = (neg + VMX_AD_TE2) * 0x00010001u;
+    K.NF1 = (neg + VMX_AD_TF1) * 0x00010001u; K.NF2 = (neg + VMX_AD_TF2) * 0x00010001u;
     const int afX = (tlX > 0 && qlX > 0) ? tlX + qlX : 0, afY = (tlY > 0 && qlY > 0) ? tlY + qlY : 0;     // the last anti-diagonal: cell (tl, ql)
     const int total = vmx_uniform_i32(vmx_wave_max_i32(afX > afY ? afX : afY));
     const int npairs = (total + 1) >> 1;                        // pair p = 1 ..: the odd step a = 2p - 1 (C sets), then the even step a = 2p (A sets)
     const int poX = (afX + 1) >> 1, peX = afX >> 1, poY = (afY + 1) >> 1, peY = afY >> 1;     // last pair whose odd / even step stores
     const int hX = dloX >> 1, hY = dloY >> 1;                   // dlo is even
     // set k of lane l in pair p: target row p - 1 - h - NS l - k on the odd step and one more on the even step, query column p + h + NS l + k on both
-    auto tcf = [&](const uint8_t* T, int tl, int i) -> int { return (i >= 1 && i <= tl) ? vmx_tcode(T[i - 1]) : 5; };
-    auto qcf = [&](const uint8_t* Q, int ql, int j) -> int { return (j >= 1 && j <= ql) ? (int)Q[j - 1] : 4; };
+    auto tcf = [&](const uint8_t* T, int tl, int i) -> int { return ((i >= 1 && i <= tl) ? vmx_tcode(T[i - 1]) : 5) << VMX_AD_CSH; };
+    auto qcf = [&](const uint8_t* Q, int ql, int j) -> int { return ((j >= 1 && j <= ql) ? (int)Q[j - 1] : 4) << VMX_AD_CSH; };
     unsigned tcode[NS], qcode[NS];
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
@@ -110,9 +163,9 @@ __device__ __forceinline__ void vmx_gapfill_fill_ad(const uint8_t* __restrict__ 
 #pragma unroll
         for (int k = 0; k < NS; ++k) {
             const unsigned m = ((l == l0X && k == k0X) ? 0xffffu : 0u) | ((l == l0Y && k == k0Y) ? 0xffff0000u : 0u);
-            HA[k] = vmx_bfi(m, vmx_pk(VMX_AD_BIAS, VMX_AD_BIAS), K.NEGP);
-            E1A[k] = K.NEGP; E2A[k] = K.NEGP; F1A[k] = K.NEGP; F2A[k] = K.NEGP;
-            HC[k] = K.NEGP; E1C[k] = K.NEGP; E2C[k] = K.NEGP; F1C[k] = K.NEGP; F2C[k] = K.NEGP;
+            HA[k] = vmx_bfi(m, (8u * (unsigned)bias + 7u) * 0x00010001u, K.NH);
+            E1A[k] = K.NE1; E2A[k] = K.NE2; F1A[k] = K.NF1; F2A[k] = K.NF2;
+            HC[k] = K.NH; E1C[k] = K.NE1; E2C[k] = K.NE2; F1C[k] = K.NF1; F2C[k] = K.NF2;
         }
     }
     // where H(tl, ql) lives: diagonal x = (ql - tl) - dlo
@@ -150,21 +203,19 @@ __device__ __forceinline__ void vmx_gapfill_fill_ad(const uint8_t* __restrict__ 
                 qch = (unsigned)vmx_r16_ror1((int)qch);
             }
             // odd step a = 2p - 1: C_k takes the cell above from A_{k+1} (the last one from the next lane) and the cell to its left from A_k
-            unsigned bb[NS];
+            unsigned w[NS][5];
             {
-                const unsigned nH = (unsigned)vmx_r16_shl1_in((int)HA[0], (int)K.NEGP), nE1 = (unsigned)vmx_r16_shl1_in((int)E1A[0], (int)K.NEGP),
-                               nE2 = (unsigned)vmx_r16_shl1_in((int)E2A[0], (int)K.NEGP);
+                const unsigned nH = (unsigned)vmx_r16_shl1_in((int)HA[0], (int)K.NH), nE1 = (unsigned)vmx_r16_shl1_in((int)E1A[0], (int)K.NE1),
+                               nE2 = (unsigned)vmx_r16_shl1_in((int)E2A[0], (int)K.NE2);
 #pragma unroll
                 for (int k = 0; k < NS; ++k) {
                     const unsigned uH = k + 1 < NS ? HA[k + 1 < NS ? k + 1 : 0] : nH, uE1 = k + 1 < NS ? E1A[k + 1 < NS ? k + 1 : 0] : nE1, uE2 = k + 1 < NS ? E2A[k + 1 < NS ? k + 1 : 0] : nE2;
-                    bb[k] = vmx_ad_cell(K, uH, uE1, uE2, HA[k], F1A[k], F2A[k], tcode[k], qcode[k], HC[k], E1C[k], E2C[k], F1C[k], F2C[k]);
+                    vmx_ad_cell(K, uH, uE1, uE2, HA[k], F1A[k], F2A[k], tcode[k], qcode[k], HC[k], E1C[k], E2C[k], F1C[k], F2C[k], w[k]);
                 }
             }
             {
-                unsigned w01 = bb[0], w23 = 0;
-                if (NS > 1) w01 |= bb[NS > 1 ? 1 : 0] << 8;
-                if (NS > 2) w23 = bb[NS > 2 ? 2 : 0];
-                if (NS > 3) w23 |= bb[NS > 3 ? 3 : 0] << 8;
+                unsigned w01, w23;
+                vmx_ad_pack<NS>(w, w01, w23);
                 const size_t so = VMX_AD_TB_OFF_W(2 * p - 2, 0, W);   // anti-diagonal a = 2p - 1 is step s = a - 1
                 if (p <= poX) put(pX + so, w01, w23, false);
                 if (p <= poY) put(pY + so, w01, w23, true);
@@ -179,19 +230,17 @@ __device__ __forceinline__ void vmx_gapfill_fill_ad(const uint8_t* __restrict__ 
             }
             // even step a = 2p: A_k takes the cell above from C_k and the cell to its left from C_{k-1} (the first one from the previous lane)
             {
-                const unsigned nH = (unsigned)vmx_r16_shr1_in((int)HC[NS - 1], (int)K.NEGP), nF1 = (unsigned)vmx_r16_shr1_in((int)F1C[NS - 1], (int)K.NEGP),
-                               nF2 = (unsigned)vmx_r16_shr1_in((int)F2C[NS - 1], (int)K.NEGP);
+                const unsigned nH = (unsigned)vmx_r16_shr1_in((int)HC[NS - 1], (int)K.NH), nF1 = (unsigned)vmx_r16_shr1_in((int)F1C[NS - 1], (int)K.NF1),
+                               nF2 = (unsigned)vmx_r16_shr1_in((int)F2C[NS - 1], (int)K.NF2);
 #pragma unroll
                 for (int k = 0; k < NS; ++k) {
                     const unsigned lH = k > 0 ? HC[k > 0 ? k - 1 : 0] : nH, lF1 = k > 0 ? F1C[k > 0 ? k - 1 : 0] : nF1, lF2 = k > 0 ? F2C[k > 0 ? k - 1 : 0] : nF2;
-                    bb[k] = vmx_ad_cell(K, HC[k], E1C[k], E2C[k], lH, lF1, lF2, tcode[k], qcode[k], HA[k], E1A[k], E2A[k], F1A[k], F2A[k]);
+                    vmx_ad_cell(K, HC[k], E1C[k], E2C[k], lH, lF1, lF2, tcode[k], qcode[k], HA[k], E1A[k], E2A[k], F1A[k], F2A[k], w[k]);
                 }
             }
             {
-                unsigned w01 = bb[0], w23 = 0;
-                if (NS > 1) w01 |= bb[NS > 1 ? 1 : 0] << 8;
-                if (NS > 2) w23 = bb[NS > 2 ? 2 : 0];
-                if (NS > 3) w23 |= bb[NS > 3 ? 3 : 0] << 8;
+                unsigned w01, w23;
+                vmx_ad_pack<NS>(w, w01, w23);
                 const size_t so = VMX_AD_TB_OFF_W(2 * p - 1, 0, W);
                 if (p <= peX) put(pX + so, w01, w23, false);
                 if (p <= peY) put(pY + so, w01, w23, true);
@@ -200,8 +249,8 @@ __device__ __forceinline__ void vmx_gapfill_fill_ad(const uint8_t* __restrict__ 
             if (__any(p == poX || p == poY)) {
                 const unsigned aX = vmx_ad_pick<NS>(HA, kfX), cX = vmx_ad_pick<NS>(HC, kfX), aY = vmx_ad_pick<NS>(HA, kfY), cY = vmx_ad_pick<NS>(HC, kfY);
                 const unsigned vX = (afX & 1) ? cX : aX, vY = (afY & 1) ? cY : aY;
-                if (p == poX && l == lfX) finX = vmx_pk_lo(vX) - VMX_AD_BIAS;
-                if (p == poY && l == lfY) finY = vmx_pk_hi(vY) - VMX_AD_BIAS;
+                if (p == poX && l == lfX) finX = (int)((vX & 0xffffu) >> 3) - bias;
+                if (p == poY && l == lfY) finY = (int)(vY >> 19) - bias;
             }
         }
     }
