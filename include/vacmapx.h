@@ -355,6 +355,22 @@ int vm_bam_compress_parts(vm_bam_writer*, const char* const* blobs, const int64_
 /* n arbitrary bytes as BGZF members */
 int vm_bgzf_compress(vm_ctx*, const void* in, int64_t n, char** out, int64_t* n_out);
 
+/* Coordinate-sorted BAM and its CSI index (driver: --bam-writer native-sort). Order: ascending uint32(refID) << 32 | uint32(pos + 1) << 1 | reverse
+ * strand, ties in the order the lines arrived; refID -1 last. An external sort: every vm_bam_sorter_add_parts call encodes its lines and returns
+ * their records in sorted order, uncompressed (a run; the caller writes it to a file of its own, an empty call leaves no run); the sorter keeps
+ * the run's keys and record sizes. vm_bam_sorter_plan takes the run files' paths in call order and file_base = the bytes the output file holds
+ * already (the header's members), sorts all keys once and cuts the output into *n_chunks chunks of about chunk_bytes record bytes;
+ * vm_bam_sorter_chunk(k), called for k = 0, 1, ... in order, returns chunk k's BGZF members (possibly none) and records its index entries;
+ * vm_bam_sorter_index returns the complete .csi file (min_shift 14, depth 5, BGZF with the EOF member). The sorter borrows the writer: free it first. */
+typedef struct vm_bam_sorter vm_bam_sorter;
+int vm_bam_sorter_create(vm_bam_writer*, int64_t chunk_bytes, vm_bam_sorter** out);
+void vm_bam_sorter_free(vm_bam_sorter*);
+int vm_bam_sorter_add_parts(vm_bam_sorter*, const char* const* blobs, const int64_t* const* offs, const int32_t* part, const int64_t* idx, int64_t n,
+                            char** out, int64_t* n_out);
+int vm_bam_sorter_plan(vm_bam_sorter*, const char* const* run_paths, int64_t n_paths, int64_t file_base, int64_t* n_chunks);
+int vm_bam_sorter_chunk(vm_bam_sorter*, int64_t k, char** out, int64_t* n_out);
+int vm_bam_sorter_index(vm_bam_sorter*, char** out, int64_t* n_out);
+
 /* cost tables C0 as uploaded to the device (tests): which = 0 extra,1 readgap_h,2 readgap_r,3 large_readgap (f32),
  * 4 log2cache, 5 log2int (f64). returns length, *data = host copy read back FROM THE DEVICE (vm_free) */
 int64_t vm_table(vm_ctx*, int which, void** data);

@@ -9,6 +9,9 @@
         tools/driver_bench.py's input shape (one 100 Mb contig, ONT reads of mean 15 kb) with seeded qualities, the generated reads written
         --replicate times under new names; `-o out.sam` and `-o out.bam --bam-writer native` alternated in fresh processes on the full and a
         quarter-length input: marginal (steady-state) reads/s, output sizes, the writer thread's CPU seconds.
+    python tools/bam_bench.py sorted [same options] [--out profiles/bam_sorted_driver.json]
+        the same runs with `-o out.bam --bam-writer native` (the baseline: unsorted) and `-o out.sorted.bam --bam-writer native-sort` alternated:
+        what sorting and indexing cost. Per sorted run also the wall time of the merge in close(), its GB/s of record bytes and the run files' bytes.
 """
 import argparse, json, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -64,7 +67,7 @@ def kernels(args):
     codec.close(); ctx.close()
 
 
-def driver(args):
+def driver(args, kinds=('sam', 'bam')):
     """Steady-state reads/s, as tools/driver_bench.py measures it: a run's read loop includes the start-up of its contexts (several seconds
     of pool allocation whatever the input's length, and it varies from process to process), so the rate is the MARGINAL one between a full
     and a quarter-length input, (reads_full - reads_quarter) / (loop_full - loop_quarter). SAM and BAM runs alternate, each in a fresh
@@ -99,8 +102,8 @@ def driver(args):
     n_full, n_q = len(reads) * rep, len(reads) * qrep
 
     def run(kind, path):
-        out = os.path.join(args.tmp, 'out.' + kind)
-        extra = ['--bam-writer', 'native'] if kind == 'bam' else []
+        out = os.path.join(args.tmp, 'out.' + {'sorted': 'sorted.bam'}.get(kind, kind))
+        extra = {'bam': ['--bam-writer', 'native'], 'sorted': ['--bam-writer', 'native-sort', '-workdir', os.path.join(args.tmp, 'wd')]}.get(kind, [])
         env = dict(os.environ, VMX_DRIVER_TIMING='1', PYTHONPATH=ROOT + os.pathsep + os.environ.get('PYTHONPATH', ''))
         t0 = time.time()
         pr = subprocess.run([sys.executable, '-m', 'vacmap_amd.driver', '-ref', fa, '-read', path, '-mode', 'H', '-o', out, '-t', str(args.t), '--nowriteindex',
@@ -115,30 +118,49 @@ def driver(args):
             raise SystemExit('driver run failed (%s)' % kind)
         size = os.path.getsize(out)
         os.remove(out)
-        return {'wall_s': dt, 'loop_s': tm.get('loop'), 'writer_cpu_s': tm.get('writer_cpu'), 'assemble_write_s': tm.get('assemble_write'), 'bytes': size}
+        res = {'wall_s': dt, 'loop_s': tm.get('loop'), 'writer_cpu_s': tm.get('writer_cpu'), 'assemble_write_s': tm.get('assemble_write'), 'bytes': size}
+        if kind == 'sorted':                               # the driver's last line: "... index X.csi (merge of N runs, M MB of records: S s)"
+            import re
+            m = re.search(r'merge of (\d+) runs, ([0-9.]+) MB of records: ([0-9.]+) s', pr.stderr)
+            res.update({'runs': int(m.group(1)), 'run_file_bytes': float(m.group(2)) * 1e6, 'merge_s': float(m.group(3)),
+                        'merge_GBps_of_records': float(m.group(2)) / 1e3 / max(float(m.group(3)), 1e-9), 'index_bytes': os.path.getsize(out + '.csi')})
+            os.remove(out + '.csi')
+        return res
+
+    def med(v):
+        """median of the rounds that gave a figure (a quarter run's loop can come out longer than the full run's: no marginal rate then)"""
+        v = [x for x in v if x is not None]
+        return float(np.median(v)) if v else None
 
     rounds = []
     for rd in range(args.rounds):
         r = {}
-        order = ('sam', 'bam') if rd % 2 == 0 else ('bam', 'sam')
+        order = kinds if rd % 2 == 0 else kinds[::-1]
         for length, path in (('full', fq), ('quarter', fq4)):
             for kind in order:
                 r['%s_%s' % (kind, length)] = run(kind, path)
                 print(json.dumps({'round': rd, 'run': '%s_%s' % (kind, length), **r['%s_%s' % (kind, length)]}), flush=True)
-        for kind in ('sam', 'bam'):
+        for kind in kinds:
             d = r[kind + '_full']['loop_s'] - r[kind + '_quarter']['loop_s']
             r[kind + '_marginal_reads_per_s'] = (n_full - n_q) / d if d > 0 else None
-        r['bam_over_sam'] = r['bam_marginal_reads_per_s'] / r['sam_marginal_reads_per_s']
+        base, new = kinds
+        ratio = '%s_over_%s' % (new, base)
+        r[ratio] = r[new + '_marginal_reads_per_s'] / r[base + '_marginal_reads_per_s'] if r[new + '_marginal_reads_per_s'] and r[base + '_marginal_reads_per_s'] else None
         rounds.append(r)
-        print(json.dumps({'round': rd, 'sam_marginal_reads_per_s': r['sam_marginal_reads_per_s'], 'bam_marginal_reads_per_s': r['bam_marginal_reads_per_s'],
-                          'bam_over_sam': r['bam_over_sam']}), flush=True)
+        print(json.dumps({'round': rd, base + '_marginal_reads_per_s': r[base + '_marginal_reads_per_s'], new + '_marginal_reads_per_s': r[new + '_marginal_reads_per_s'],
+                          ratio: r[ratio]}), flush=True)
     res = {'reads_full': n_full, 'reads_quarter': n_q, 'rounds': rounds,
-           'sam_marginal_reads_per_s_median': float(np.median([r['sam_marginal_reads_per_s'] for r in rounds])),
-           'bam_marginal_reads_per_s_median': float(np.median([r['bam_marginal_reads_per_s'] for r in rounds])),
-           'bam_over_sam_per_round': [r['bam_over_sam'] for r in rounds]}
-    res['bam_over_sam_of_medians'] = res['bam_marginal_reads_per_s_median'] / res['sam_marginal_reads_per_s_median']
+           base + '_marginal_reads_per_s_median': med([r[base + '_marginal_reads_per_s'] for r in rounds]),
+           new + '_marginal_reads_per_s_median': med([r[new + '_marginal_reads_per_s'] for r in rounds]),
+           ratio + '_per_round': [r[ratio] for r in rounds]}
+    res[ratio + '_of_medians'] = (res[new + '_marginal_reads_per_s_median'] / res[base + '_marginal_reads_per_s_median']
+                                  if res[new + '_marginal_reads_per_s_median'] and res[base + '_marginal_reads_per_s_median'] else None)
+    if new == 'sorted':
+        for k in ('merge_s', 'merge_GBps_of_records', 'run_file_bytes', 'runs'):
+            res['sorted_full_%s_median' % k] = float(np.median([r['sorted_full'][k] for r in rounds]))
+        res['sorted_full_loop_over_bam_full_loop_per_round'] = [r['sorted_full']['loop_s'] / r['bam_full']['loop_s'] for r in rounds]
     # the start-up share of a run varies by seconds between processes: the full runs' loops and the writer thread's busy time say more
-    for kind in ('sam', 'bam'):
+    for kind in kinds:
         res[kind + '_full_loop_s_median'] = float(np.median([r[kind + '_full']['loop_s'] for r in rounds]))
         res[kind + '_full_writer_busy_s_median'] = float(np.median([r[kind + '_full']['assemble_write_s'] for r in rounds]))
     print(json.dumps({k: v for k, v in res.items() if k != 'rounds'}))
@@ -151,9 +173,9 @@ def driver(args):
 
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
-    ap.add_argument('what', choices=['kernels', 'driver'])
+    ap.add_argument('what', choices=['kernels', 'driver', 'sorted'])
     ap.add_argument('--gb', type=float, default=2.0); ap.add_argument('--reads', type=int, default=40960); ap.add_argument('--replicate', type=int, default=8); ap.add_argument('--ref-mb', type=float, default=100.0)
     ap.add_argument('--rounds', type=int, default=3); ap.add_argument('--t', type=int, default=16); ap.add_argument('--tmp', default='/tmp/vmx_bam_bench')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
-    kernels(a) if a.what == 'kernels' else driver(a)
+    kernels(a) if a.what == 'kernels' else driver(a, ('bam', 'sorted')) if a.what == 'sorted' else driver(a)

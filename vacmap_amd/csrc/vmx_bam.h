@@ -49,4 +49,27 @@ __global__ void k_bam_patch(uint8_t* out, const int64_t* off, const uint32_t* va
 __global__ void k_bgzf_deflate(const uint8_t* in, int64_t n_in, int64_t first_member, uint8_t* slots, int64_t* msize, uint32_t* g_match, uint16_t* g_prev);
 __global__ void k_bgzf_compact(const uint8_t* slots, const int64_t* moff, uint8_t* out);
 
+// coordinate sort, merge and CSI (k_bam_sort.hip)
+#define VMX_BAM_RUN_SHIFT 40            // value of the merge sort: run << 40 | index in run
+#define VMX_BAM_RUN_MASK ((1ULL << VMX_BAM_RUN_SHIFT) - 1)
+__global__ void k_bam_sort_keys(const uint8_t* rec, const int64_t* roff, int64_t n, uint64_t* key, uint64_t* val);
+__global__ void k_bam_sort_sizes(const int64_t* roff, const uint64_t* perm, int64_t n, int64_t* ssz, int64_t* so);
+__global__ void k_bam_gather(const uint8_t* src, const int64_t* so, const int64_t* doff, int64_t dbase, uint8_t* dst, int64_t n);
+__global__ void k_bam_merge_vals(const int64_t* rstart, int32_t n_runs, int64_t n, uint64_t* val);
+__global__ void k_bam_merge_sizes(const uint64_t* gval, const int64_t* roff_all, const int64_t* rstart, int64_t n, int64_t* gsz);
+__global__ void k_bam_merge_cuts(const int64_t* goff, int64_t n, int64_t chunk_bytes, int64_t n_chunks, int64_t* cut, int64_t* cutoff);
+__global__ void k_bam_merge_runmax(const uint64_t* gval, const int64_t* cut, int64_t n_chunks, int32_t n_runs, int64_t n, unsigned long long* rmax);
+__global__ void k_bam_merge_src(const uint64_t* gval, int64_t m, const int64_t* roff_all, const int64_t* rstart, const int64_t* sbase, int64_t* so);
+__global__ void k_bam_index_entries(const uint8_t* rec, const int64_t* doff, int64_t dbase, int64_t m, const int64_t* moff, int64_t file_base,
+                                    uint64_t* e_key, uint64_t* e_vbeg, uint64_t* e_vend, int32_t* e_beg, uint32_t* e_end, uint32_t* e_unm);
+__global__ void k_csi_iota(uint64_t* v, int64_t n);
+__global__ void k_csi_flags(const uint64_t* skey, const uint64_t* sidx, const uint64_t* vbeg, const uint64_t* vend, int64_t n, int64_t* flag);
+__global__ void k_csi_chunks(const uint64_t* skey, const uint64_t* sidx, const uint64_t* vbeg, const uint64_t* vend, const int64_t* flag, const int64_t* cpos, int64_t n,
+                             uint64_t* ckey, uint64_t* cbeg, uint64_t* cend);
+__global__ void k_csi_linear(const uint64_t* e_key, const uint64_t* vbeg, const int32_t* e_beg, const uint32_t* e_end, int64_t n, int32_t n_ref, const int64_t* wbase,
+                             unsigned long long* lin);
+__global__ void k_csi_loffset(const uint64_t* ckey, int64_t nc, int32_t n_ref, const int64_t* wbase, const unsigned long long* lin, uint64_t* cloff);
+__global__ void k_csi_refstats(const uint64_t* e_key, const uint64_t* vbeg, const uint64_t* vend, const uint32_t* e_unm, int64_t n, int32_t n_ref, uint64_t* rbeg,
+                               uint64_t* rend, unsigned long long* cnt);
+
 #endif

@@ -15,7 +15,7 @@ records produces no line.
 With N ranks, rank 0 builds the index and broadcasts it over RCCL (vacmap_amd/dist.py), batch i of a window goes to rank i mod N, and
 rank 0 gathers and writes the lines. `-mode asm` (assembly contigs; contig c -> rank c mod N): the contigs go through vm_align_batch with VM_MODE_ASM in
 groups, in input order, and their lines come from the native emitter in its asm form (vm_sam_opts.asm_mode = iterator_get_bam_dict_str,
-mammap_asm.py:22757; vacmap_amd/sam.py holds the same emitter in Python); `-workdir` is accepted and created like the reference's, but nothing is spilled into it.
+mammap_asm.py:22757; vacmap_amd/sam.py holds the same emitter in Python); `-workdir` is accepted and created like the reference's; only `--bam-writer native-sort` spills into it (its run files, removed at the end).
 """
 import argparse, gzip, os, shutil, struct, subprocess, sys, threading, time, queue
 
@@ -284,9 +284,10 @@ def build_parser():
     p.add_argument('--shard', choices=['auto', 'range', 'batch'], default='auto'); p.add_argument('--parts', action='store_true')
     p.add_argument('--parse-threads', type=int, default=0, help='parser threads per rank over record-aligned slices of a plain input (0: max(1, min(4, t / 4)))')
     p.add_argument('--debug', action='store_true', help='log every read the aligner skipped with its status (vacmap:127; mammap_clrnano.py:24120-24123)')
-    p.add_argument('--bam-writer', choices=['samtools', 'native'], default='samtools',
+    p.add_argument('--bam-writer', choices=['samtools', 'native', 'native-sort'], default='samtools',
                    help='how -o x.bam is written: a `samtools view -b` pipe (default) or the GPU encoder and BGZF compressor (vacmap_amd.bamout); '
-                        'native does not sort: .sorted.bam needs samtools')
+                        'native does not sort: .sorted.bam needs samtools or native-sort, which sorts by coordinate on the GPU and writes x.sorted.bam.csi '
+                        '(run files go to a fresh directory under -workdir, else next to the output, and are removed)')
     return p
 
 
@@ -321,7 +322,7 @@ def _run_asm(args, lib, ctx, index, prm, rg, mark, out, proc, world, rank, text_
     prm.eqx = 1; prm.check_num = -1; prm.maxdivergence = 1.0
     opts = SamOpts(int(bool(args.MD)), int(args.cs != 'long'), int(bool(args.L)), int(bool(mark)), int(bool(args.H)), int(bool(args.fakecigar)), rg['ID'].encode(), 1)
     seen = set(); n_contigs = n_lines = n_skipped = 0
-    native_bam = args.bam_writer == 'native' and args.o.endswith('.bam')
+    native_bam = args.bam_writer in ('native', 'native-sort') and args.o.endswith('.bam')
 
     def blob(parts):
         off = np.zeros(len(parts) + 1, np.int64)
@@ -397,8 +398,15 @@ def _run_asm(args, lib, ctx, index, prm, rg, mark, out, proc, world, rank, text_
         else:
             out.flush()
         tt = max(time.time() - t_start, 0.001)
-        sys.stderr.write('vacmapx: %d contigs, %d SAM lines, %d contigs skipped, %.1f s\n' % (n_contigs, n_lines, n_skipped, tt))
+        sys.stderr.write('vacmapx: %d contigs, %d SAM lines, %d contigs skipped, %.1f s%s\n' % (n_contigs, n_lines, n_skipped, tt, _index_note(out)))
     return 0
+
+
+def _index_note(out):
+    """the tail of the final stderr line after --bam-writer native-sort: the index file and what the merge in close() cost"""
+    if not hasattr(out, 'merge_seconds'):
+        return ''
+    return '; sorted by coordinate, index %s.csi (merge of %d runs, %.1f MB of records: %.2f s)' % (out.path, len(out.runs), out.run_bytes / 1e6, out.merge_seconds)
 
 
 def _keep_heap_pages():
@@ -427,9 +435,10 @@ def main(argv=None, comm=None):
         _keep_heap_pages()
     if args.o != '-' and not (args.o.endswith('.sam') or args.o.endswith('.bam')):
         sys.exit("Output path must end with .sam, .bam, .sorted.bam, or be '-' for stdout.")
-    native_bam = args.bam_writer == 'native' and args.o.endswith('.bam')
-    if native_bam and args.o.endswith('sorted.bam'):
-        sys.exit('--bam-writer native writes unsorted BAM only: write %s with --bam-writer samtools, or name the output .bam' % args.o)
+    native_bam = args.bam_writer in ('native', 'native-sort') and args.o.endswith('.bam')
+    native_sort = args.bam_writer == 'native-sort' and args.o.endswith('sorted.bam')
+    if native_bam and args.o.endswith('sorted.bam') and not native_sort:
+        sys.exit('--bam-writer native writes unsorted BAM only: write %s with --bam-writer native-sort or samtools, or name the output .bam' % args.o)
     world, rank, local_rank = 1, 0, 0
     own_group = False
     # VMX_FORCE_DIST=1: the N-rank start-up at world 1 too (process group over nccl = RCCL, gloo text group, index through a replica built from the
@@ -518,8 +527,13 @@ def main(argv=None, comm=None):
     if rank == 0:
         head = sam.header_lines([(n, ln_) for n, ln_ in zip(names, index.lens)], ' '.join(sys.argv if argv is None else ['vacmapx'] + list(argv)), rg)
         if native_bam:
-            from .bamout import BamWriter
-            out, proc = BamWriter(args.o, head, device=device), None          # the header goes in as the BAM header
+            from .bamout import BamWriter, SortedBamWriter
+            if native_sort:                                                   # sorted runs now, merge + index in out.close()
+                if args.workdir:
+                    os.makedirs(args.workdir, exist_ok=True)
+                out, proc = SortedBamWriter(args.o, head, device=device, workdir=args.workdir), None
+            else:
+                out, proc = BamWriter(args.o, head, device=device), None      # the header goes in as the BAM header
         else:
             out, proc = (open(part_path, 'w+b'), None) if range_mode else _open_output(args.o)
             for ln in head:
@@ -969,7 +983,7 @@ def main(argv=None, comm=None):
             out.flush()
         tt = max(time.time() - prog['t0'], 0.001)     # vacmap:535-541
         sys.stderr.write('User time (h:m:s): %d:%d:%d %d / sec AVG. %d sequences processed.\n' % (tt // 3600, (tt % 3600) // 60, tt % 60, round(counts['reads'] / tt), counts['reads']))
-        sys.stderr.write('vacmapx: %d reads, %d SAM lines, %d reads skipped\n' % (counts['reads'], counts['lines'], counts['skipped']))
+        sys.stderr.write('vacmapx: %d reads, %d SAM lines, %d reads skipped%s\n' % (counts['reads'], counts['lines'], counts['skipped'], _index_note(out)))
     if own_group:
         comm.barrier(); comm.destroy_process_group()
     return 0

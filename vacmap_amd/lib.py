@@ -182,6 +182,12 @@ class VmxLib:
         L.vm_bam_header.argtypes = [vp, P(vp), P(i64)]
         L.vm_bam_encode.argtypes = [vp, cp, i64, P(vp), P(i64)]
         L.vm_bam_compress_parts.argtypes = [vp, vp, vp, vp, vp, i64, P(vp), P(i64)]
+        L.vm_bam_sorter_create.argtypes = [vp, i64, P(vp)]
+        L.vm_bam_sorter_free.argtypes = [vp]; L.vm_bam_sorter_free.restype = None
+        L.vm_bam_sorter_add_parts.argtypes = [vp, vp, vp, vp, vp, i64, P(vp), P(i64)]
+        L.vm_bam_sorter_plan.argtypes = [vp, vp, i64, i64, P(i64)]
+        L.vm_bam_sorter_chunk.argtypes = [vp, i64, P(vp), P(i64)]
+        L.vm_bam_sorter_index.argtypes = [vp, P(vp), P(i64)]
         L.vm_bgzf_compress.argtypes = [vp, vp, i64, P(vp), P(i64)]
 
     def err(self):
@@ -679,6 +685,54 @@ class BamCodec:
     def close(self):
         if getattr(self, 'h', None):
             self.lib.L.vm_bam_writer_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BamSorter:
+    """vm_bam_sorter on a BamCodec: sorted runs per call, then the merge in chunks and the CSI index (include/vacmapx.h)"""
+
+    def __init__(self, codec, chunk_bytes):
+        self.codec, self.lib = codec, codec.lib
+        h = C.c_void_p()
+        self.lib.check(self.lib.L.vm_bam_sorter_create(codec.h, int(chunk_bytes), C.byref(h)))
+        self.h = h
+
+    def add_parts(self, blobs, offs, order_keys):
+        """the lines (as BamCodec.compress_parts takes them) -> their BAM records in coordinate order, uncompressed: one run (b'' when there is no line)"""
+        blobs = [_u8(b) for b in blobs]; offs = [np.ascontiguousarray(o, dtype=np.int64) for o in offs]
+        part, local = _parts_order(blobs, offs, order_keys)
+        bp = (C.c_void_p * max(len(blobs), 1))(*[b.ctypes.data for b in blobs]); op = (C.c_void_p * max(len(offs), 1))(*[o.ctypes.data for o in offs])
+        p = C.c_void_p(); n = C.c_int64()
+        self.lib.check(self.lib.L.vm_bam_sorter_add_parts(self.h, bp, op, part.ctypes.data, local.ctypes.data, len(local), C.byref(p), C.byref(n)))
+        return _take_bytes(self.lib, p, n)
+
+    def plan(self, run_paths, file_base):
+        """run_paths: the files of the non-empty runs in call order; file_base: bytes already in the output file. Returns the number of chunks"""
+        raw = [os.fsencode(x) for x in run_paths]
+        arr = (C.c_char_p * max(len(raw), 1))(*raw)
+        n = C.c_int64()
+        self.lib.check(self.lib.L.vm_bam_sorter_plan(self.h, arr, len(raw), int(file_base), C.byref(n)))
+        return n.value
+
+    def chunk(self, k):
+        p = C.c_void_p(); n = C.c_int64()
+        self.lib.check(self.lib.L.vm_bam_sorter_chunk(self.h, int(k), C.byref(p), C.byref(n)))
+        return _take_bytes(self.lib, p, n)
+
+    def index(self):
+        p = C.c_void_p(); n = C.c_int64()
+        self.lib.check(self.lib.L.vm_bam_sorter_index(self.h, C.byref(p), C.byref(n)))
+        return _take_bytes(self.lib, p, n)
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.L.vm_bam_sorter_free(self.h)
             self.h = None
 
     def __del__(self):
