@@ -148,7 +148,9 @@ typedef struct vm_chains_out {
 } vm_chains_out;
 /* Runs the global chain stage of vm_align_batch (S2 + G1-G3 + selection). A read of two anchors or fewer is not chained (unmapped, :23986):
  * gmax -1, its S / P / S_arg undefined. -mode asm: a contig of 500 kb and more is not chained either (gmax -4, no path): vm_align_batch
- * takes it through the linked DPs (vm_chain_linked). */
+ * takes it through the linked DPs (vm_chain_linked). The device keeps an anchor's q in 32 bits and its l, s in 16: a batch with a row whose l is outside
+ * 0 ... 65535, whose q or q + l is outside int32 or whose s is outside int16 is refused as a whole (VM_ERR_UNSUPPORTED, the message names the row); map() never
+ * returns such a row. */
 int vm_chain_global_batch(vm_ctx*, const vm_params*, int kmersize, int64_t n, const int64_t* anchors,
                           const int64_t* anchor_off, const int64_t* readlens, int want_raw, vm_chains_out* out);
 void vm_chains_out_free(vm_chains_out*);
@@ -174,7 +176,8 @@ void vm_local_out_free(vm_local_out*);
  * out: S[n], P[n]; the HOT part of the score-sorted index S_arg (its last n_hot entries in the reference's order — the n_cold entries below can
  * never be visited, k_chain_linked.hip); gmax (-1: GC-exact's bail-out); and what :23250-23272 carries into the next batch: carry_status 0
  * with saved = 0 (`continue`: best chain ends in a carried or fresh anchor) or saved = 1 and carry_S / carry_P / carry_rows [n_carry], or
- * a negative status when the device refuses (slice reaches the cold entries, bail-out) or the reference raises. */
+ * a negative status when the device refuses (slice reaches the cold entries, bail-out) or the reference raises. Rows that the device's fields cannot carry
+ * (l outside 0 ... 65535, q or q + l outside int32, s outside int16) are refused with VM_ERR_UNSUPPORTED, as by vm_chain_global_batch. */
 typedef struct vm_linked_out {
     int64_t gmax, n_hot, n_cold, opcount; double cold_max;
     double* S; int64_t* P; int64_t* S_arg_hot;

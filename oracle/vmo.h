@@ -87,6 +87,8 @@ int vmo_strand_flip(int64_t* anchors, int64_t n, int64_t readlen);
  * returns g_max_index (or -1 when exact bails out, :24914) */
 int64_t vmo_chain_global_raw(const int64_t* anchors, int64_t n, int mode, int kmersize, double skipcost,
                              int maxdiff, int maxgap, int which, double* S, int64_t* P, int64_t* S_arg);
+/* opcount of the exact DP (:24896, :24951) when it returns — at its end, or at the bail-out of :24914 */
+int64_t vmo_chain_global_opcount(const int64_t* anchors, int64_t n, int mode, int kmersize, double skipcost, int maxdiff, int maxgap);
 
 typedef struct vmo_chains {      /* result of hit2work_1 + decode_hit (:23491, :23981) */
     int32_t need_reverse;

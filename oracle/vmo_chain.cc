@@ -390,6 +390,15 @@ int64_t vmo_chain_global_raw(const int64_t* a, int64_t n, int mode, int kmersize
     return g;
 }
 
+int64_t vmo_chain_global_opcount(const int64_t* a, int64_t n, int mode, int kmersize, double skipcost, int maxdiff, int maxgap) {
+    std::vector<Anchor> v(n);
+    for (int64_t i = 0; i < n; ++i) v[i] = Anchor{a[4 * i], a[4 * i + 1], a[4 * i + 2], a[4 * i + 3]};
+    std::vector<double> s; std::vector<int64_t> p, sa;
+    int64_t opcount = 0;
+    chain_global_exact(v, kmersize, skipcost, maxdiff, maxgap, s, p, sa, &opcount, mode == VMO_MODE_R);
+    return opcount;
+}
+
 int vmo_decode_hit(const int64_t* a, int64_t n, int64_t readlen, int kmersize, const vmo_params* prm, vmo_chains* out) {
     std::vector<Anchor> v(n);
     for (int64_t i = 0; i < n; ++i) v[i] = Anchor{a[4 * i], a[4 * i + 1], a[4 * i + 2], a[4 * i + 3]};

@@ -73,6 +73,8 @@ def lib():
     L.vmo_strand_flip.argtypes = [vp, i64, i64]
     L.vmo_chain_global_raw.argtypes = [vp, i64, C.c_int, C.c_int, dbl, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.vmo_chain_global_raw.restype = i64
+    L.vmo_chain_global_opcount.argtypes = [vp, i64, C.c_int, C.c_int, dbl, C.c_int, C.c_int]
+    L.vmo_chain_global_opcount.restype = i64
     L.vmo_decode_hit.argtypes = [vp, i64, i64, C.c_int, P(Params), P(Chains)]
     L.vmo_chains_free.argtypes = [P(Chains)]
     L.vmo_local_chain.argtypes = [vp, cp, i64, C.c_int, vp, vp, P(Params), P(dbl), P(P(i64)), P(i64), P(P(i64)), P(i64), P(i32)]
@@ -216,6 +218,12 @@ def chain_global_raw(anchors_sorted, kmersize, skipcost=40., maxdiff=50, maxgap=
     g = lib().vmo_chain_global_raw(a.ctypes.data, n, MODES[mode], kmersize, skipcost, maxdiff, maxgap, which,
                                    S.ctypes.data, P.ctypes.data, SA.ctypes.data)
     return g, S, P, SA
+
+
+def chain_global_opcount(anchors_sorted, kmersize, skipcost=40., maxdiff=50, maxgap=1000, mode='H'):
+    """opcount of the exact DP on q-sorted anchors (at its end or at its bail-out)"""
+    a = np.ascontiguousarray(anchors_sorted, dtype=np.int64)
+    return lib().vmo_chain_global_opcount(a.ctypes.data, len(a), MODES[mode], kmersize, skipcost, maxdiff, maxgap)
 
 
 def decode_hit(anchors, readlen, kmersize, prm):

@@ -34,6 +34,10 @@ extern "C" int vm_chain_linked(vm_ctx* c, int which, int kmersize, double skipco
     if (!c) { set_error("no context"); return VM_ERR_NO_CTX; }
     if (!out || n <= 0 || n_pre < 0 || n_pre >= n || which < 0 || which > 2 || maxdiff > 62) { set_error("vm_chain_linked: bad arguments"); return VM_ERR_ARG; }
     memset(out, 0, sizeof(*out));
+    if (const int64_t bad = vmx_rows_misfit(rows, n); bad >= 0) {
+        char msg[192]; snprintf(msg, sizeof msg, "vm_chain_linked: anchor row %lld does not fit the device row (l in 0 ... 65535, q and q + l in int32, s in int16)", (long long)bad);
+        set_error(msg); return VM_ERR_UNSUPPORTED;
+    }
     VMX_HIP(hipSetDevice(c->device));
     const int lc = which == 2;
     const int cap_pre = (int)std::max<int64_t>(4096, n_pre);

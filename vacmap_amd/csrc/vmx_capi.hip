@@ -609,10 +609,14 @@ int vm_chain_global_batch(vm_ctx* c, const vm_params* prm, int kmersize, int64_t
     memset(out, 0, sizeof(*out));
     if (!c) { set_error("no context"); return VM_ERR_NO_CTX; }
     if (prm->global_maxdiff > 62) { set_error("global_maxdiff > 62 unsupported"); return VM_ERR_UNSUPPORTED; }
+    const int64_t tot = aoff[n];
+    if (const int64_t bad = vmx_rows_misfit(anchors, tot); bad >= 0) {
+        char msg[192]; snprintf(msg, sizeof msg, "vm_chain_global_batch: anchor row %lld does not fit the device row (l in 0 ... 65535, q and q + l in int32, s in int16)", (long long)bad);
+        set_error(msg); return VM_ERR_UNSUPPORTED;
+    }
     VMX_HIP(hipSetDevice(c->device));
     vmx_fetch_scope fetch_scope(c);
     vmx_batch_bufs& B = *vmx_ctx_batch_bufs(c);
-    const int64_t tot = aoff[n];
     const std::vector<int64_t> h_aoff(aoff, aoff + n + 1);
     std::vector<int64_t> h_roff((size_t)n + 1, 0);
     for (int64_t r = 0; r < n; ++r) h_roff[(size_t)r + 1] = h_roff[(size_t)r] + readlens[r];
@@ -660,7 +664,7 @@ int vm_chain_global_batch(vm_ctx* c, const vm_params* prm, int kmersize, int64_t
             for (int x = 0; x < h_plen[aoff[r] + p]; ++x) {
                 const vmx_anchor& a = h_prow[src++];
                 int64_t* o = out->path_anchors + 4 * ro++;
-                o[0] = a.q; o[1] = a.r; o[2] = a.s; o[3] = a.l;
+                o[0] = a.q; o[1] = a.r; o[2] = a.s; o[3] = (uint16_t)a.l;      // (the length is an unsigned 16-bit field: 32768 ... 65535 read back as such)
             }
         }
     }

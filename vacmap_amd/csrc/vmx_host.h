@@ -333,6 +333,15 @@ __global__ void k_chain_global(const vmx_anchor* anchors, const int64_t* aoff, c
                                vmx_tables tab, const double* gapcost_list, double oskipcost, int omaxdiff, int maxgap,
                                double* S_out, int32_t* P_out, int32_t* SA_out, uint8_t* cov_pool, int64_t* gmax_out, int64_t* opcount_out, int rmode,
                                double* FP_pool, double* PP_pool);
+// The stage entries take anchor rows (q, r, s, l) as int64; the device row (vmx_anchor) keeps q in 32 bits and s, l in 16, and the kernels read l as an
+// unsigned 16-bit length. Index of the first row that does not fit (l outside 0 ... 65535, q or q + l outside int32, s outside int16), or -1.
+static inline int64_t vmx_rows_misfit(const int64_t* rows, int64_t n) {
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t q = rows[4 * i], s = rows[4 * i + 2], l = rows[4 * i + 3];
+        if (l < 0 || l > 65535 || q < INT32_MIN || q > INT32_MAX || q + l > INT32_MAX || s < INT16_MIN || s > INT16_MAX) return i;
+    }
+    return -1;
+}
 // k_chain_rows.hip: four reads per wavefront (one per 16-lane row); VMX_CHAIN_ROWS=0 keeps the one-wavefront-per-read kernels for A/B
 __global__ void k_chain_global_rows(const vmx_anchor* anchors, const int64_t* aoff, const int32_t* rlist, int nlist, vmx_tables tab, const double* gapcost_list,
                                     double oskipcost, int omaxdiff, int maxgap, double* S_out, int32_t* P_out, int32_t* SA_out, uint8_t* cov_pool,
