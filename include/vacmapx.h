@@ -358,6 +358,25 @@ int vm_bam_compress_parts(vm_bam_writer*, const char* const* blobs, const int64_
 /* n arbitrary bytes as BGZF members */
 int vm_bgzf_compress(vm_ctx*, const void* in, int64_t n, char** out, int64_t* n_out);
 
+/* BAM input on the GPU (driver: --bam-reader native). vm_bgzf_decompress is the counterpart of vm_bgzf_compress: any series of complete BGZF
+ * members (any writer's: stored, fixed and dynamic blocks, empty members, with or without the EOF block) -> their bytes (vm_free). A member
+ * that does not inflate to its ISIZE and CRC32 makes the call fail with VM_ERR_IO; vm_last_error() names the member's offset.
+ * vm_bam_reader_open: VM_ERR_UNSUPPORTED when the file is gzip without the BGZF BC subfield, VM_ERR_ARG when the inflated stream does not begin
+ * with BAM\1, VM_ERR_IO for everything else that is wrong with the file. vm_bam_reader_read has vm_fastx_read's signature and return
+ * convention: names, bases (a reverse-strand record turned back to the read's orientation: reversed, ACGTN complemented) and qualities + 33
+ * (empty when the record has none); comments are always empty; records without bases are dropped. The reader reads the file ahead on a thread
+ * of its own. vm_bam_reader_stats: seconds of I/O thread work, waiting for it, upload + inflate, record walk, sizes + scans + decode, download,
+ * handing out; then windows, file bytes, inflated bytes, records handed to the caller's windows, records dropped (12 numbers), as of the
+ * latest window the caller has begun to take (the window decoded ahead is not in them yet).
+ * An open reader owns its context (it decodes ahead on a thread of its own): close it before other calls use the context or destroy it. */
+int vm_bgzf_decompress(vm_ctx*, const void* in, int64_t n, char** out, int64_t* n_out);
+typedef struct vm_bam_reader vm_bam_reader;
+int vm_bam_reader_open(vm_ctx*, const char* path, vm_bam_reader** out);
+int64_t vm_bam_reader_read(vm_bam_reader*, int64_t max_reads, int64_t max_bases, char** names, int64_t** name_off, char** seqs, int64_t** seq_off, char** quals,
+                           int64_t** qual_off, char** comments, int64_t** com_off);
+int vm_bam_reader_stats(const vm_bam_reader*, double* out, int n);
+void vm_bam_reader_close(vm_bam_reader*);
+
 /* Coordinate-sorted BAM and its CSI index (driver: --bam-writer native-sort). Order: ascending uint32(refID) << 32 | uint32(pos + 1) << 1 | reverse
  * strand, ties in the order the lines arrived; refID -1 last. An external sort: every vm_bam_sorter_add_parts call encodes its lines and returns
  * their records in sorted order, uncompressed (a run; the caller writes it to a file of its own, an empty call leaves no run); the sorter keeps

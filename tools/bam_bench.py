@@ -12,6 +12,15 @@
     python tools/bam_bench.py sorted [same options] [--out profiles/bam_sorted_driver.json]
         the same runs with `-o out.bam --bam-writer native` (the baseline: unsorted) and `-o out.sorted.bam --bam-writer native-sort` alternated:
         what sorting and indexing cost. Per sorted run also the wall time of the merge in close(), its GB/s of record bytes and the run files' bytes.
+    python tools/bam_bench.py input [--gb 2] [--only reader] [--tmp DIR] [--out profiles/bam_input_reader.json]
+        native BAM input (lib.BamReader): >= --gb GB of unaligned BAM (15 kb ONT-shape reads, tests/bam_input_cases.scale_records) written once
+        as zlib level 6 members and once through the device deflate; the reader alone on both (reads/s, GB/s of file and of inflated bytes,
+        the reader's own phase times), a bench.py line of the same session (what the reader must feed), driver._bam_chunks on the first
+        2 000 records (the parent's reader) and one host thread of gzip.decompress on the same file. --only reader: the first part alone,
+        for a run under `rocprofv3 --kernel-trace --stats`.
+    python tools/bam_bench.py input-driver [--reads 40960] [--replicate 8] [--rounds 3] [--out profiles/bam_input_driver.json]
+        the driver on the same reads as plain FASTQ and as unaligned BAM with --bam-reader native, alternated in fresh processes: the
+        driver's own wait_input seconds and loop time per run.
 """
 import argparse, json, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -171,11 +180,153 @@ def driver(args, kinds=('sam', 'bam')):
         os.remove(pth)
 
 
+def _save(res, out):
+    print(json.dumps(res))
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        json.dump(res, open(out, 'w'), indent=1)
+
+
+def input_bench(args):
+    import gzip, itertools
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import bam_input_cases as K
+    from vacmap_amd import driver as D
+    from vacmap_amd.lib import Context, BamReader
+    os.makedirs(args.tmp, exist_ok=True)
+    ctx = Context(0)
+    t0 = time.time()
+    head, recs, _ = K.scale_records(int(args.gb * (1 << 30)))
+    total = len(head) + sum(len(r) for r in recs)
+    res = {'reads': len(recs), 'inflated_bytes': total, 'generate_s': time.time() - t0, 'files': {}}
+    paths = {k: os.path.join(args.tmp, 'in_%s.bam' % k) for k in ('zlib6', 'device')}
+    K.write_bgzf_zlib(paths['zlib6'], [head] + recs)
+    K.write_bgzf_device(paths['device'], [head] + recs, ctx)
+    del recs
+    for kind, p in paths.items():
+        runs = []
+        for rep in range(3):                                            # the first pass grows the reader's pools and warms the page cache; the third hands out with one memcpy
+            os.environ['VMX_BAM_IN_COPY_THREADS'] = '1' if rep == 2 else '4'
+            t0 = time.time()
+            rd = BamReader(ctx, p)
+            n = 0
+            for ch in iter(lambda: rd.read(4096), None):
+                n += len(ch['seqs_off']) - 1
+            dt = time.time() - t0
+            st = rd.stats(); rd.close()
+            runs.append({'reads': n, 'wall_s': dt, 'reads_per_s': n / dt, 'file_GBps': os.path.getsize(p) / dt / 1e9, 'inflated_GBps': total / dt / 1e9, 'phases': st})
+        res['files'][kind] = {'file_bytes': os.path.getsize(p), 'first_pass': runs[0], 'second_pass': runs[1], 'one_copy_thread_pass': runs[2]}
+        print(json.dumps({kind: runs[1]}), flush=True)
+    if args.only != 'reader':
+        z = paths['zlib6']
+        t0 = time.time()
+        n = sum(len(c['seqs_off']) - 1 for c in itertools.islice(D._bam_chunks(z, 100), 20))
+        res['python_reader'] = {'reads': n, 'wall_s': time.time() - t0}
+        res['python_reader']['reads_per_s'] = n / res['python_reader']['wall_s']
+        raw = open(z, 'rb').read(64 << 20)
+        cut = 0
+        for off, m in K.split_members(raw):                # whole members only
+            cut = off + len(m)
+        t0 = time.time(); inf = gzip.decompress(raw[:cut]); dt = time.time() - t0
+        res['host_zlib_one_thread'] = {'inflated_bytes': len(inf), 'wall_s': dt, 'inflated_GBps': len(inf) / dt / 1e9}
+        ctx.close()
+        pr = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', str(args.bench_steps), '--warmup', '1'], stdout=subprocess.PIPE, text=True, timeout=600)
+        line = [ln for ln in pr.stdout.splitlines() if ln.startswith('{')]
+        if pr.returncode == 0 and line:
+            b = json.loads(line[-1])
+            rps = b.get('reads_per_s') or (b.get('extra') or {}).get('reads_per_s') or b.get('value')
+            res['bench_line'] = {'reads_per_s': rps, 'unit': b.get('unit'), 'value': b.get('value')}
+            res['reader_over_bench_reads_per_s'] = res['files']['zlib6']['second_pass']['reads_per_s'] / rps if rps else None
+        else:
+            raise SystemExit('bench.py failed with status %d: nothing more is started' % pr.returncode)
+        r2 = res['files']['zlib6']['second_pass']
+        res['reader_over_python_reader'] = r2['reads_per_s'] / res['python_reader']['reads_per_s']
+        res['inflate_in_host_zlib_threads'] = (total / max(r2['phases']['inflate_s'], 1e-9) / 1e9) / res['host_zlib_one_thread']['inflated_GBps']
+    for p in paths.values():
+        os.remove(p)
+    _save(res, args.out)
+
+
+def input_driver(args):
+    """wait_input and loop seconds of the driver on FASTQ and on unaligned BAM (--bam-reader native) of the same reads, alternated"""
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import bam_input_cases as K
+    from vacmap_amd import synth
+    os.makedirs(args.tmp, exist_ok=True)
+    ref = synth.make_reference([int(args.ref_mb * 1e6)], seed=1)[0]
+    fa = os.path.join(args.tmp, 'ref.fa')
+    with open(fa, 'wb') as f:
+        f.write(b'>chr1\n'); f.write(ref.tobytes()); f.write(b'\n')
+    rng = np.random.default_rng(9)
+    reads = []
+    for s in range(0, args.reads, 4096):
+        c, o, _ = synth.sample_reads_concat([ref], min(4096, args.reads - s), mean_len=15000, err=0.10, seed=1000 + 7919 * (s // 4096))
+        for i in range(len(o) - 1):
+            sq = c[o[i]:o[i + 1]].tobytes()
+            reads.append((sq, quals(len(sq), rng).tobytes()))
+    fq, bam = os.path.join(args.tmp, 'reads.fq'), os.path.join(args.tmp, 'reads.bam')
+    code = np.zeros(256, np.uint8); code[[65, 67, 71, 84, 78]] = [1, 2, 4, 8, 15]
+
+    def records():
+        yield K.bam_header('@HD\tVN:1.6\tSO:unsorted\n')
+        import struct
+        for rp in range(args.replicate):
+            for i, (sq, q) in enumerate(reads):
+                name = b'r%d_%d' % (rp, i)
+                c = code[np.frombuffer(sq, np.uint8)]
+                c = np.concatenate([c, np.zeros(len(c) & 1, np.uint8)])
+                body = struct.pack('<iiBBHHHiiii', -1, -1, len(name) + 1, 0, 4680, 0, 4, len(sq), -1, -1, 0) + name + b'\0' + ((c[0::2] << 4) | c[1::2]).tobytes() + \
+                    (np.frombuffer(q, np.uint8) - 33).tobytes()
+                yield struct.pack('<i', len(body)) + body
+    with open(fq, 'wb', buffering=1 << 24) as f:
+        for rp in range(args.replicate):
+            for i, (sq, q) in enumerate(reads):
+                f.write(b'@r%d_%d\n' % (rp, i)); f.write(sq); f.write(b'\n+\n'); f.write(q); f.write(b'\n')
+    K.write_bgzf_zlib(bam, records())
+    n_reads = len(reads) * args.replicate
+
+    def run(kind):
+        out = os.path.join(args.tmp, 'out.sam')
+        env = dict(os.environ, VMX_DRIVER_TIMING='1', PYTHONPATH=ROOT + os.pathsep + os.environ.get('PYTHONPATH', ''))
+        cmd = [sys.executable, '-m', 'vacmap_amd.driver', '-ref', fa, '-read', fq if kind == 'fastq' else bam, '-mode', 'H', '-o', out, '-t', str(args.t), '--nowriteindex', '--force']
+        pr = subprocess.run(cmd + (['--bam-reader', 'native'] if kind == 'ubam' else []), env=env, stderr=subprocess.PIPE, text=True, timeout=args.run_timeout)   # (a run that hangs or faults ends the bench: nothing more is started)
+        tm = {}
+        for ln in pr.stderr.splitlines():
+            if ln.startswith('vacmapx timing (s):'):
+                tm = {kv.split('=')[0]: float(kv.split('=')[1]) for kv in ln.split(':', 1)[1].split()}
+        if pr.returncode != 0:
+            sys.stderr.write(pr.stderr[-3000:])
+            raise SystemExit('driver run failed (%s)' % kind)
+        lines = sum(1 for _ in open(out, 'rb'))
+        os.remove(out)
+        return {'wait_input_s': tm.get('wait_input'), 'loop_s': tm.get('loop'), 'sam_lines': lines}
+    rounds = []
+    for rd in range(args.rounds):
+        r = {}
+        for kind in (('fastq', 'ubam') if rd % 2 == 0 else ('ubam', 'fastq')):
+            r[kind] = run(kind)
+            print(json.dumps({'round': rd, 'kind': kind, **r[kind]}), flush=True)
+        rounds.append(r)
+    fw = [r['fastq']['wait_input_s'] for r in rounds]; uw = [r['ubam']['wait_input_s'] for r in rounds]
+    res = {'reads': n_reads, 'fastq_bytes': os.path.getsize(fq), 'ubam_bytes': os.path.getsize(bam), 'rounds': rounds, 'fastq_wait_input_s': fw, 'ubam_wait_input_s': uw,
+           'fastq_wait_input_spread_s': max(fw) - min(fw), 'ubam_wait_input_median_s': float(np.median(uw)), 'fastq_wait_input_median_s': float(np.median(fw)),
+           'same_sam_lines': len({r[k]['sam_lines'] for r in rounds for k in r}) == 1}
+    for pth in (fq, bam, fa):
+        os.remove(pth)
+    _save(res, args.out)
+
+
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
-    ap.add_argument('what', choices=['kernels', 'driver', 'sorted'])
+    ap.add_argument('what', choices=['kernels', 'driver', 'sorted', 'input', 'input-driver'])
+    ap.add_argument('--only', default=None); ap.add_argument('--run-timeout', type=float, default=600.0); ap.add_argument('--bench-steps', type=int, default=12)
     ap.add_argument('--gb', type=float, default=2.0); ap.add_argument('--reads', type=int, default=40960); ap.add_argument('--replicate', type=int, default=8); ap.add_argument('--ref-mb', type=float, default=100.0)
     ap.add_argument('--rounds', type=int, default=3); ap.add_argument('--t', type=int, default=16); ap.add_argument('--tmp', default='/tmp/vmx_bam_bench')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
-    kernels(a) if a.what == 'kernels' else driver(a, ('bam', 'sorted')) if a.what == 'sorted' else driver(a)
+    if a.what == 'input':
+        input_bench(a)
+    elif a.what == 'input-driver':
+        input_driver(a)
+    else:
+        kernels(a) if a.what == 'kernels' else driver(a, ('bam', 'sorted')) if a.what == 'sorted' else driver(a)

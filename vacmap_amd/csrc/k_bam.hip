@@ -413,18 +413,7 @@ __global__ void __launch_bounds__(256) k_bam_patch(uint8_t* out, const int64_t* 
 
 // ------------------------------------------------------------------------------------------------ BGZF deflate
 
-#define CRC_POLY 0xedb88320u
-
-// a(x) * b(x) modulo the CRC polynomial (reflected; zlib's multmodp). a must not be 0
-__device__ static uint32_t crc_multmodp(uint32_t a, uint32_t b) {
-    uint32_t m = 1u << 31, p = 0;
-    for (;;) {
-        if (a & m) { p ^= b; if ((a & (m - 1)) == 0) break; }
-        m >>= 1;
-        b = b & 1 ? (b >> 1) ^ CRC_POLY : b >> 1;
-    }
-    return p;
-}
+// (CRC_POLY, crc_multmodp and crc_x8n: vmx_bam.h, shared with the inflate kernel)
 
 // LSB-first bits into the LDS bit buffer; v < 2^nb, nb <= 16
 __device__ __forceinline__ void bz_put(uint32_t* buf, uint32_t off, uint32_t v, int nb) {
@@ -566,10 +555,7 @@ __global__ void __launch_bounds__(VMX_BGZF_THREADS) k_bgzf_deflate(const uint8_t
             uint32_t c = 0xffffffffu;
             for (int i = b; i < e; ++i) c = s_crctab[(c ^ s_in[i]) & 0xff] ^ (c >> 8);
             c = ~c;
-            uint32_t mul = 1u << 31;
-            uint32_t k = 3;
-            for (uint32_t r = (uint32_t)(n - e); r; r >>= 1, ++k) if (r & 1) mul = crc_multmodp(s_x2n[k & 31], mul);
-            part = crc_multmodp(mul, c);
+            part = crc_multmodp(crc_x8n(s_x2n, (uint32_t)(n - e)), c);
         }
         for (int o = 32; o; o >>= 1) part ^= __shfl_xor(part, o);
         if ((t & 63) == 0) s_red[t >> 6] = part;

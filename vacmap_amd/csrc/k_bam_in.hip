@@ -1,0 +1,392 @@
+// k_bam_in.hip — BAM input on the device (SAMv1 §4.1 BGZF, §4.2 records; RFC 1951).
+//
+// Inflate: one BGZF member per wavefront (workgroups of one wave). The host has walked the member headers (vmx_bam.hip) and hands over a
+// table of (deflate data, its size, ISIZE, CRC32, output offset): members inflate independently into one contiguous buffer, and a member's
+// window is its own output, so there is no LDS window. The decoder's state (bit buffer, cursors, the symbol in hand) is the same in every
+// lane and is read back through vmx_uniform_i32, so it lives in scalar registers; the lanes differ only in what they load and store:
+//   * compressed input: 512 bytes at a time into an LDS ring (one coalesced load), words from there into a 64-bit bit buffer;
+//   * Huffman tables (per wave in LDS; the kernel uses 4 960 B in all): code-length counts by LDS atomics, every symbol's rank among the symbols of its
+//     length by 15 ballots per 64 symbols, canonical codes from there; a primary table of 10 (literal / length) or 9 (distance) bits is
+//     filled by all lanes, longer codes (rare: the primary table covers every code of probability above 2^-10) are decoded canonically,
+//     bit by bit, from the per-length counts and the symbols sorted by (length, symbol);
+//   * literals are staged one per lane in a register and stored 64 at a time; a match is copied by all lanes, 64 bytes per step.
+// THE ORDERING RULE OF THE MATCH COPY: a back-reference reads bytes this wave stored a moment ago, mostly from other lanes. The compiler
+// orders a work-item's own store -> load, not lane 3's store -> lane 7's load. bzi_store_fence() (release fence, s_waitcnt vmcnt(0): every
+// store of the wave has been acknowledged; acquire fence) stands between the stores and the copy's loads whenever the source range reaches
+// beyond `safe`, the output position of the latest fence; sources below it were complete before the loads were issued. dist < len copies
+// read src[i mod dist]: every source byte lies below the match's first byte, none is written by the copy itself.
+// Every input read is bounded by the member's deflate size, every output write by its ISIZE, every distance by the bytes produced so far.
+// Code-length sets are accepted exactly where zlib's inflate_table accepts them. The first bad member wins (atomicMin on member << 8 | code).
+//
+// Records: k_bam_in_walk follows the block_size chain (serial by nature: one dependent load per record), k_bam_in_sizes sizes every
+// record's name, bases and qualities, and after four scans (names, bases, qualities, kept records) k_bam_in_decode writes them, one wave per record, 64 bases per step.
+#include "vmx_bam.h"
+
+#ifdef VMX_EMU
+#define VMX_BAM_CONST static const
+#else
+#define VMX_BAM_CONST __constant__
+#endif
+
+#define BZI_LIT_BITS 10
+#define BZI_DIST_BITS 9
+#define BZI_RING 128                    // words of compressed input held in LDS
+
+// every store of this wave is complete and visible to every lane's later loads
+__device__ __forceinline__ void bzi_store_fence() {
+#ifdef VMX_EMU
+    __syncthreads();
+#else
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+#endif
+}
+
+__device__ __forceinline__ uint32_t bzi_u(uint32_t v) { return (uint32_t)vmx_uniform_i32((int)v); }
+
+struct BziIn {
+    const uint32_t* w;      // aligned words that cover the deflate data
+    uint32_t n_words;
+    uint32_t* ring;         // LDS: words [loaded - BZI_RING, loaded)
+    uint64_t bb;
+    uint32_t nb, wi, loaded;
+};
+
+__device__ static void bzi_load(BziIn& s, int lane) {
+    vmx_wave_lds_fence();                                               // (every lane has read what it wanted of the old ring)
+    for (uint32_t k = (uint32_t)lane; k < BZI_RING; k += 64) { const uint32_t i = s.loaded + k; s.ring[i & (BZI_RING - 1)] = i < s.n_words ? s.w[i] : 0u; }
+    s.loaded += BZI_RING;
+    vmx_wave_lds_fence();
+}
+
+// more than 32 bits in the bit buffer afterwards (zeros beyond the input: the callers compare bzi_bitpos with the data's end)
+__device__ __forceinline__ void bzi_ensure(BziIn& s, int lane) {
+    if (s.nb <= 32) {
+        if (s.wi >= s.loaded) bzi_load(s, lane);
+        s.bb |= (uint64_t)bzi_u(s.ring[s.wi & (BZI_RING - 1)]) << s.nb;
+        s.nb += 32; ++s.wi;
+    }
+}
+__device__ __forceinline__ uint32_t bzi_take(BziIn& s, uint32_t n) { const uint32_t v = (uint32_t)s.bb & ((1u << n) - 1u); s.bb >>= n; s.nb -= n; return v; }
+__device__ __forceinline__ uint32_t bzi_bitpos(const BziIn& s) { return s.wi * 32u - s.nb; }
+__device__ static void bzi_seek(BziIn& s, uint32_t byte, int lane) {
+    s.wi = byte >> 2; s.loaded = s.wi; s.bb = 0; s.nb = 0;
+    bzi_ensure(s, lane);
+    (void)bzi_take(s, 8 * (byte & 3));
+}
+
+// one Huffman code: per-length counts, first code and first slot per length, the symbols by (length, symbol), the primary table
+struct BziCode { int* cnt; int* nc; int* of; uint16_t* sym; uint16_t* tab; int pb; };
+
+__device__ __forceinline__ uint32_t bzi_rev(uint32_t c, int len) { uint32_t r = 0; for (int i = 0; i < len; ++i) { r = r << 1 | (c & 1); c >>= 1; } return r; }
+
+// kind 0: the code-length code, 1: literal / length, 2: distance (zlib's CODES, LENS, DISTS), 3: a fixed code (complete by construction).
+// 0 or a VMX_BGZF_E_* code, the same in every lane
+__device__ static int bzi_build(const uint8_t* lens, int n, const BziCode& C, int kind, int lane) {
+    if (lane < 16) C.cnt[lane] = 0;
+    for (int k = lane; k < (1 << C.pb); k += 64) C.tab[k] = 0;
+    vmx_wave_lds_fence();
+    for (int s = lane; s < n; s += 64) atomicAdd(&C.cnt[lens[s]], 1);
+    vmx_wave_lds_fence();
+    int left = 1, maxl = 0;
+    for (int l = 1; l <= 15; ++l) {
+        const int c = vmx_uniform_i32(C.cnt[l]);
+        left = (left << 1) - c;
+        if (left < 0) return VMX_BGZF_E_LENS;                           // over-subscribed
+        if (c) maxl = l;
+    }
+    vmx_wave_lds_fence();
+    if (lane == 0) C.cnt[0] = 0;
+    if (maxl == 0) { vmx_wave_lds_fence(); return 0; }                  // no code at all: every use of it is an invalid code
+    if (left > 0 && kind != 3 && (kind == 0 || maxl != 1)) return VMX_BGZF_E_LENS;      // incomplete where RFC 1951 (and zlib) forbid it
+    if (lane >= 1 && lane < 16) {
+        int code = 0, o = 0;
+        for (int b = 1; b < lane; ++b) { code = (code + C.cnt[b]) << 1; o += C.cnt[b]; }
+        C.nc[lane] = code; C.of[lane] = o;
+    }
+    vmx_wave_lds_fence();
+    int base[16];
+#pragma unroll
+    for (int l = 0; l < 16; ++l) base[l] = 0;
+    for (int c0 = 0; c0 < n; c0 += 64) {
+        const int s = c0 + lane;
+        const int l = s < n ? (int)lens[s] : 0;
+        int rank = 0;
+#pragma unroll
+        for (int L = 1; L <= 15; ++L) {
+            const unsigned long long m = __ballot(l == L);
+            if (l == L) rank = base[L] + __popcll(m & ((1ull << lane) - 1ull));
+            base[L] += __popcll(m);
+        }
+        if (l) {
+            C.sym[C.of[l] + rank] = (uint16_t)s;
+            if (l <= C.pb) {
+                const uint32_t r = bzi_rev((uint32_t)(C.nc[l] + rank), l);
+                for (uint32_t k = r; k < (1u << C.pb); k += 1u << l) C.tab[k] = (uint16_t)(s | l << 9);
+            }
+        }
+    }
+    vmx_wave_lds_fence();
+    return 0;
+}
+
+// the next symbol of code C, or -1 (no such code). More than 32 bits are in the bit buffer
+__device__ __forceinline__ int bzi_decode(BziIn& s, const BziCode& C) {
+    const uint32_t e = bzi_u(C.tab[(uint32_t)s.bb & ((1u << C.pb) - 1u)]);
+    if (e) { (void)bzi_take(s, e >> 9); return (int)(e & 511u); }
+    int code = 0, first = 0, index = 0;
+    for (int len = 1; len <= 15; ++len) {
+        code |= (int)(s.bb >> (len - 1)) & 1;
+        const int count = vmx_uniform_i32(C.cnt[len]);
+        if (code - count < first) { (void)bzi_take(s, (uint32_t)len); return (int)bzi_u(C.sym[index + (code - first)]); }
+        index += count; first += count; first <<= 1; code <<= 1;
+    }
+    return -1;
+}
+
+VMX_BAM_CONST uint8_t bzi_cl_order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+
+__global__ void __launch_bounds__(64) k_bgzf_inflate(const uint8_t* comp, const vmx_bgzf_member* tab, int64_t n_members, uint8_t* out_all, vmx_crc_x2n x2n,
+                                                     unsigned long long* err_key) {
+    __shared__ uint16_t s_ltab[1 << BZI_LIT_BITS];                      // (the CRC table and x^(2^k) lie over it once the last block is decoded)
+    __shared__ uint16_t s_dtab[1 << BZI_DIST_BITS];                     // (the code-length code's table while a dynamic header is read)
+    __shared__ uint16_t s_lsym[288], s_dsym[32];
+    __shared__ uint8_t s_lens[320 + 32];                                // literal / length and distance lengths; [320, 339): the code-length code's
+    __shared__ int s_cnt[2][16], s_nc[2][16], s_of[2][16];
+    __shared__ uint32_t s_ring[BZI_RING];
+    const int lane = (int)threadIdx.x;
+    const int64_t mb = blockIdx.x;
+    if (mb >= n_members) return;
+    const vmx_bgzf_member M = tab[mb];
+    uint8_t* out = out_all + M.ooff;
+    const uint32_t isize = M.isize;
+    const uint8_t* cdata = comp + M.coff;
+    const uint32_t a = (uint32_t)((uintptr_t)cdata & 3);
+    const uint32_t end_byte = a + (uint32_t)M.csize;                    // the deflate data: bytes [a, end_byte) of the words
+    BziIn in;
+    in.w = (const uint32_t*)(cdata - a); in.n_words = (end_byte + 3) >> 2; in.ring = s_ring;
+    const BziCode CL{s_cnt[0], s_nc[0], s_of[0], s_lsym, s_ltab, BZI_LIT_BITS};
+    const BziCode CD{s_cnt[1], s_nc[1], s_of[1], s_dsym, s_dtab, BZI_DIST_BITS};
+    const BziCode CC{s_cnt[1], s_nc[1], s_of[1], s_dsym, s_dtab, 7};
+    bzi_seek(in, a, lane);
+    uint32_t opos = 0, safe = 0, nl = 0, lit = 0;
+    int err = 0;
+#define BZI_FAIL(code) do { err = (code); goto done; } while (0)
+#define BZI_FLUSH() do { if ((uint32_t)lane < nl) out[opos + lane] = (uint8_t)lit; opos += nl; nl = 0; } while (0)
+    for (;;) {
+        bzi_ensure(in, lane);
+        if (bzi_bitpos(in) + 3 > 8 * end_byte) BZI_FAIL(VMX_BGZF_E_INPUT);
+        const uint32_t bfinal = bzi_take(in, 1), btype = bzi_take(in, 2);
+        if (btype == 3) BZI_FAIL(VMX_BGZF_E_BTYPE);
+        if (btype == 0) {
+            BZI_FLUSH();
+            (void)bzi_take(in, in.nb & 7);
+            bzi_ensure(in, lane);
+            const uint32_t len = bzi_take(in, 16);
+            bzi_ensure(in, lane);
+            const uint32_t nlen = bzi_take(in, 16);
+            const uint32_t p = bzi_bitpos(in) >> 3;
+            if (p > end_byte) BZI_FAIL(VMX_BGZF_E_INPUT);
+            if (len != (nlen ^ 0xffffu)) BZI_FAIL(VMX_BGZF_E_STORED);
+            if (p + len > end_byte) BZI_FAIL(VMX_BGZF_E_INPUT);
+            if (opos + len > isize) BZI_FAIL(VMX_BGZF_E_LONG);
+            const uint8_t* src = (const uint8_t*)in.w + p;
+            for (uint32_t i = (uint32_t)lane; i < len; i += 64) out[opos + i] = src[i];
+            opos += len;
+            bzi_seek(in, p + len, lane);
+        } else {
+            if (btype == 1) {
+                for (int i = lane; i < 288; i += 64) s_lens[i] = (uint8_t)(i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : 8);
+                if (lane < 32) s_lens[288 + lane] = 5;
+                vmx_wave_lds_fence();
+                (void)bzi_build(s_lens, 288, CL, 3, lane);
+                (void)bzi_build(s_lens + 288, 32, CD, 3, lane);
+            } else {
+                bzi_ensure(in, lane);
+                const int hlit = (int)bzi_take(in, 5) + 257, hdist = (int)bzi_take(in, 5) + 1, hclen = (int)bzi_take(in, 4) + 4;
+                if (hlit > 286 || hdist > 30) BZI_FAIL(VMX_BGZF_E_HEADER);
+                if (lane < 19) s_lens[320 + lane] = 0;
+                vmx_wave_lds_fence();
+                for (int i = 0; i < hclen; ++i) {
+                    bzi_ensure(in, lane);
+                    const uint32_t v = bzi_take(in, 3);
+                    if (lane == 0) s_lens[320 + bzi_cl_order[i]] = (uint8_t)v;
+                }
+                vmx_wave_lds_fence();
+                if (bzi_bitpos(in) > 8 * end_byte) BZI_FAIL(VMX_BGZF_E_INPUT);
+                if ((err = bzi_build(s_lens + 320, 19, CC, 0, lane)) != 0) goto done;
+                int have = 0, prev = 0;
+                const int want = hlit + hdist;
+                while (have < want) {
+                    bzi_ensure(in, lane);
+                    const int sy = bzi_decode(in, CC);
+                    if (sy < 0) BZI_FAIL(VMX_BGZF_E_HEADER);
+                    int rep = 1, val = sy;
+                    if (sy == 16) { if (have == 0) BZI_FAIL(VMX_BGZF_E_HEADER); val = prev; rep = 3 + (int)bzi_take(in, 2); }
+                    else if (sy == 17) { val = 0; rep = 3 + (int)bzi_take(in, 3); }
+                    else if (sy == 18) { val = 0; rep = 11 + (int)bzi_take(in, 7); }
+                    if (have + rep > want) BZI_FAIL(VMX_BGZF_E_HEADER);
+                    if (lane < rep) s_lens[have + lane] = (uint8_t)val;
+                    if (lane + 64 < rep) s_lens[have + lane + 64] = (uint8_t)val;
+                    if (lane + 128 < rep) s_lens[have + lane + 128] = (uint8_t)val;
+                    have += rep; prev = val;
+                    if (bzi_bitpos(in) > 8 * end_byte) BZI_FAIL(VMX_BGZF_E_INPUT);
+                }
+                vmx_wave_lds_fence();
+                if (vmx_uniform_i32(s_lens[256]) == 0) BZI_FAIL(VMX_BGZF_E_HEADER);        // no end-of-block code
+                // the distance lengths move behind slot 288 so that both builds read from a fixed place
+                uint8_t dl = 0;
+                if (lane < hdist) dl = s_lens[hlit + lane];
+                vmx_wave_lds_fence();
+                if (lane < 32) s_lens[288 + lane] = lane < hdist ? dl : (uint8_t)0;
+                vmx_wave_lds_fence();
+                if ((err = bzi_build(s_lens, hlit, CL, 1, lane)) != 0) goto done;
+                if ((err = bzi_build(s_lens + 288, hdist, CD, 2, lane)) != 0) goto done;
+            }
+            for (;;) {
+                bzi_ensure(in, lane);
+                if (bzi_bitpos(in) > 8 * end_byte) BZI_FAIL(VMX_BGZF_E_INPUT);
+                const int sy = bzi_decode(in, CL);
+                if (sy < 0) BZI_FAIL(VMX_BGZF_E_CODE);
+                if (sy < 256) {
+                    if (opos + nl >= isize) BZI_FAIL(VMX_BGZF_E_LONG);
+                    if ((uint32_t)lane == nl) lit = (uint32_t)sy;
+                    if (++nl == 64) BZI_FLUSH();
+                    continue;
+                }
+                if (sy == 256) break;
+                if (sy > 285) BZI_FAIL(VMX_BGZF_E_CODE);
+                const int ls = sy - 257;
+                uint32_t len;
+                if (ls < 8) len = 3u + (uint32_t)ls;
+                else if (ls == 28) len = 258;
+                else { const uint32_t eb = (uint32_t)(ls >> 2) - 1u; len = 3u + ((4u + (uint32_t)(ls & 3)) << eb) + bzi_take(in, eb); }
+                bzi_ensure(in, lane);
+                const int ds = bzi_decode(in, CD);
+                if (ds < 0 || ds > 29) BZI_FAIL(VMX_BGZF_E_CODE);
+                uint32_t dist;
+                if (ds < 4) dist = 1u + (uint32_t)ds;
+                else { const uint32_t eb = (uint32_t)(ds >> 1) - 1u; dist = 1u + ((2u + (uint32_t)(ds & 1)) << eb) + bzi_take(in, eb); }
+                if (bzi_bitpos(in) > 8 * end_byte) BZI_FAIL(VMX_BGZF_E_INPUT);
+                BZI_FLUSH();
+                if (dist > opos) BZI_FAIL(VMX_BGZF_E_DIST);
+                if (opos + len > isize) BZI_FAIL(VMX_BGZF_E_LONG);
+                const uint32_t s0 = opos - dist;
+                if (s0 + (len < dist ? len : dist) > safe) { bzi_store_fence(); safe = opos; }
+                if (dist >= len) {
+                    for (uint32_t i = (uint32_t)lane; i < len; i += 64) out[opos + i] = out[s0 + i];
+                } else {
+                    for (uint32_t i = (uint32_t)lane; i < len; i += 64) out[opos + i] = out[s0 + i % dist];
+                }
+                opos += len;
+            }
+        }
+        if (bfinal) break;
+    }
+    BZI_FLUSH();
+    if (bzi_bitpos(in) > 8 * end_byte) BZI_FAIL(VMX_BGZF_E_INPUT);
+    if (((bzi_bitpos(in) + 7) >> 3) != end_byte) BZI_FAIL(VMX_BGZF_E_TAIL);
+    if (opos != isize) BZI_FAIL(VMX_BGZF_E_SHORT);
+    {
+        // CRC32 of the output: 64 chunks, combined as the deflate kernel combines its own (vmx_bam.h)
+        uint32_t* crctab = (uint32_t*)s_ltab;
+        uint32_t* s_x2n = crctab + 256;
+        vmx_wave_lds_fence();
+        for (int k = lane; k < 256; k += 64) { uint32_t c = (uint32_t)k; for (int j = 0; j < 8; ++j) c = c & 1 ? (c >> 1) ^ CRC_POLY : c >> 1; crctab[k] = c; }
+        if (lane < 32) s_x2n[lane] = x2n.v[lane];
+        bzi_store_fence();                                              // (the LDS stores too: __syncthreads in the emulator, program order on the device)
+        vmx_wave_lds_fence();
+        const uint32_t chunk = (isize + 63) / 64;
+        const uint32_t b = (uint32_t)lane * chunk < isize ? (uint32_t)lane * chunk : isize, e = b + chunk < isize ? b + chunk : isize;
+        uint32_t part = 0;
+        if (b < e) {
+            uint32_t c = 0xffffffffu;
+            uint32_t i = b;
+            for (; i + 8 <= e; i += 8) {                                    // eight loads in flight, then the dependent table look-ups
+                uint8_t v[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] = out[i + k];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) c = crctab[(c ^ v[k]) & 0xff] ^ (c >> 8);
+            }
+            for (; i < e; ++i) c = crctab[(c ^ out[i]) & 0xff] ^ (c >> 8);
+            part = crc_multmodp(crc_x8n(s_x2n, isize - e), ~c);
+        }
+        for (int o = 32; o; o >>= 1) part ^= __shfl_xor(part, o);
+        if (part != M.crc) err = VMX_BGZF_E_CRC;
+    }
+done:
+    if (err && lane == 0) atomicMin(err_key, (unsigned long long)mb << 8 | (unsigned long long)err);
+#undef BZI_FAIL
+#undef BZI_FLUSH
+}
+
+// ------------------------------------------------------------------------------------------------ records
+
+__device__ __forceinline__ uint32_t bin_u32(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+
+// records [begin, ...) of buf: roff[i] = offset of record i, until the next one is not complete below `end`. A block_size below 32 or
+// smaller than what l_read_name, n_cigar_op and l_seq need, or above VMX_BAM_IN_MAX_RECORD, ends the walk with an error (record << 8 | code). One work-item: the chain
+// block_size -> next record is serial; the loads of one record's fields are independent of each other.
+__global__ void k_bam_in_walk(const uint8_t* buf, int64_t begin, int64_t end, int64_t max_rec, int64_t* roff, vmx_bam_in_walk* res) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    VMX_SETPRIO(3);
+    int64_t p = begin, n = 0;
+    uint64_t bad = ~0ull;
+    while (p + 36 <= end && n < max_rec) {
+        const uint8_t* r = buf + p;
+        const int64_t bs = (int64_t)bin_u32(r);
+        const int64_t l_name = r[12], n_cig = (int64_t)r[16] | (int64_t)r[17] << 8, l_seq = (int64_t)bin_u32(r + 20);
+        if (bs < 32 || bs > VMX_BAM_IN_MAX_RECORD || l_name < 1 || l_seq > 0x7fffffff || 32 + l_name + 4 * n_cig + (l_seq + 1) / 2 + l_seq > bs) { bad = (uint64_t)n << 8 | VMX_BAM_IN_E_SIZE; break; }
+        if (p + 4 + bs > end) break;
+        roff[n++] = p;
+        p += 4 + bs;
+    }
+    roff[n] = p;
+    res->n_rec = n; res->end = p; res->err_key = bad;
+}
+
+// per record: bytes of its name, bases and qualities; keep = 0 for a record without bases (dropped, as the reference skips it)
+__global__ void __launch_bounds__(256) k_bam_in_sizes(const uint8_t* buf, const int64_t* roff, int64_t n, int64_t* nsz, int64_t* ssz, int64_t* qsz, int64_t* keep) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n) return;
+    if (i == n) { nsz[i] = 0; ssz[i] = 0; qsz[i] = 0; keep[i] = 0; return; }        // (the scans' totals land here)
+    const uint8_t* r = buf + roff[i];
+    const int64_t l_name = r[12], n_cig = (int64_t)r[16] | (int64_t)r[17] << 8, l_seq = (int64_t)bin_u32(r + 20);
+    const bool k = l_seq > 0;
+    const uint8_t* q = r + 36 + l_name + 4 * n_cig + (l_seq + 1) / 2;
+    nsz[i] = k ? l_name - 1 : 0; ssz[i] = k ? l_seq : 0; qsz[i] = k && q[0] != 0xff ? l_seq : 0; keep[i] = k ? 1 : 0;
+}
+
+// one wave per record. noff / soff / qoff / kidx: exclusive scans of k_bam_in_sizes' columns (n + 1 entries); the kept records' offsets go to
+// out_*off[kidx], the totals to out_*off[kidx[n]]. A reverse-strand record (flag & 16) is turned back to the read's own orientation:
+// bases reversed with A <-> T, C <-> G and every other letter kept, qualities reversed.
+__global__ void __launch_bounds__(256) k_bam_in_decode(const uint8_t* buf, const int64_t* roff, int64_t n, const int64_t* noff, const int64_t* soff, const int64_t* qoff,
+                                                       const int64_t* kidx, char* names, char* seqs, char* quals, int64_t* out_noff, int64_t* out_soff, int64_t* out_qoff) {
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = (int)(threadIdx.x & 63);
+    if (i > n) return;
+    const int64_t k = kidx[i];
+    if (i == n) { if (lane == 0) { out_noff[k] = noff[n]; out_soff[k] = soff[n]; out_qoff[k] = qoff[n]; } return; }
+    if (kidx[i + 1] == k) return;                                       // dropped
+    const uint8_t* r = buf + roff[i];
+    const int64_t l_name = r[12], n_cig = (int64_t)r[16] | (int64_t)r[17] << 8, l_seq = (int64_t)bin_u32(r + 20);
+    const bool rev = (r[18] & 16) != 0;
+    const int64_t no = noff[i], so = soff[i], qo = qoff[i];
+    if (lane == 0) { out_noff[k] = no; out_soff[k] = so; out_qoff[k] = qo; }
+    for (int64_t j = lane; j < l_name - 1; j += 64) names[no + j] = (char)r[36 + j];
+    const uint8_t* sq = r + 36 + l_name + 4 * n_cig;
+    const uint8_t* qu = sq + (l_seq + 1) / 2;
+    const bool hasq = qoff[i + 1] != qo;
+    const uint64_t fwd_lo = 0x565352474d43413dull, fwd_hi = 0x4e42444b48595754ull;      // "=ACMGRSV" "TWYHKDBN", first letter in the low byte
+    const uint64_t rc_lo = 0x565352434d47543dull, rc_hi = 0x4e42444b48595741ull;       // "=TGMCRSV" "AWYHKDBN"
+    const uint64_t lo = rev ? rc_lo : fwd_lo, hi = rev ? rc_hi : fwd_hi;
+    for (int64_t j = lane; j < l_seq; j += 64) {
+        const uint32_t b = sq[j >> 1];
+        const uint32_t c = j & 1 ? b & 15u : b >> 4;
+        const int64_t at = rev ? l_seq - 1 - j : j;
+        seqs[so + at] = (char)((c < 8 ? lo >> (8 * c) : hi >> (8 * (c - 8))) & 0xff);
+        if (hasq) quals[qo + at] = (char)(qu[j] + 33);
+    }
+}

@@ -1,4 +1,5 @@
-// vmx_bam.h — BAM output on the device: SAM text -> BAM records (k_bam_*), BGZF deflate (k_bgzf_*). Kernels in k_bam.hip, the C-ABI in vmx_bam.hip.
+// vmx_bam.h — BAM on the device. Output: SAM text -> BAM records (k_bam_*), BGZF deflate (k_bgzf_deflate), kernels in k_bam.hip. Input: BGZF inflate
+// (k_bgzf_inflate), record walk and decode (k_bam_in_*), kernels in k_bam_in.hip. The C-ABI of both is in vmx_bam.hip.
 #ifndef VMX_BAM_H
 #define VMX_BAM_H
 #include "vmx_device.h"
@@ -48,6 +49,49 @@ __global__ void k_bam_encode(const char* text, const int64_t* nl, int64_t n_line
 __global__ void k_bam_patch(uint8_t* out, const int64_t* off, const uint32_t* val, int64_t n);
 __global__ void k_bgzf_deflate(const uint8_t* in, int64_t n_in, int64_t first_member, uint8_t* slots, int64_t* msize, uint32_t* g_match, uint16_t* g_prev);
 __global__ void k_bgzf_compact(const uint8_t* slots, const int64_t* moff, uint8_t* out);
+
+// CRC32 pieces shared by the deflate and the inflate kernel: crc(A B) = crc(A) * x^(8|B|) + crc(B), all modulo the (reflected) CRC polynomial
+#define CRC_POLY 0xedb88320u
+
+// a(x) * b(x) modulo the CRC polynomial (reflected; zlib's multmodp). a must not be 0
+__host__ __device__ static inline uint32_t crc_multmodp(uint32_t a, uint32_t b) {
+    uint32_t m = 1u << 31, p = 0;
+    for (;;) {
+        if (a & m) { p ^= b; if ((a & (m - 1)) == 0) break; }
+        m >>= 1;
+        b = b & 1 ? (b >> 1) ^ CRC_POLY : b >> 1;
+    }
+    return p;
+}
+
+// x^(8 n) modulo the polynomial; x2n[k] = x^(2^k)
+__device__ static inline uint32_t crc_x8n(const uint32_t* x2n, uint32_t n) {
+    uint32_t mul = 1u << 31;
+    uint32_t k = 3;
+    for (uint32_t r = n; r; r >>= 1, ++k) if (r & 1) mul = crc_multmodp(x2n[k & 31], mul);
+    return mul;
+}
+
+// BAM input on the device (k_bam_in.hip): BGZF inflate, record walk, record decode
+struct vmx_bgzf_member {
+    int64_t coff;           // the member's deflate data in the compressed buffer
+    int64_t ooff;           // where its ISIZE bytes go in the inflated buffer (exclusive scan of ISIZE)
+    int32_t csize;          // deflate bytes (BSIZE + 1 - header - trailer)
+    uint32_t isize, crc;    // the trailer
+    int32_t pad;
+};
+struct vmx_crc_x2n { uint32_t v[32]; };
+enum { VMX_BGZF_E_BTYPE = 1, VMX_BGZF_E_STORED = 2, VMX_BGZF_E_INPUT = 3, VMX_BGZF_E_LONG = 4, VMX_BGZF_E_SHORT = 5, VMX_BGZF_E_CRC = 6, VMX_BGZF_E_LENS = 7,
+       VMX_BGZF_E_CODE = 8, VMX_BGZF_E_DIST = 9, VMX_BGZF_E_TAIL = 10, VMX_BGZF_E_HEADER = 11 };
+enum { VMX_BAM_IN_E_SIZE = 1 };
+#define VMX_BAM_IN_MAX_RECORD (1 << 29)      // a larger block_size is taken for corrupt at once (a 300 Mb read is 450 MB), not carried window after window to the end of the file
+// what the record walk leaves: records found, where the incomplete tail begins, the first bad record (all ones: none)
+struct vmx_bam_in_walk { int64_t n_rec, end; uint64_t err_key; };
+__global__ void k_bgzf_inflate(const uint8_t* comp, const vmx_bgzf_member* tab, int64_t n_members, uint8_t* out, vmx_crc_x2n x2n, unsigned long long* err_key);
+__global__ void k_bam_in_walk(const uint8_t* buf, int64_t begin, int64_t end, int64_t max_rec, int64_t* roff, vmx_bam_in_walk* res);
+__global__ void k_bam_in_sizes(const uint8_t* buf, const int64_t* roff, int64_t n, int64_t* nsz, int64_t* ssz, int64_t* qsz, int64_t* keep);
+__global__ void k_bam_in_decode(const uint8_t* buf, const int64_t* roff, int64_t n, const int64_t* noff, const int64_t* soff, const int64_t* qoff, const int64_t* kidx,
+                                char* names, char* seqs, char* quals, int64_t* out_noff, int64_t* out_soff, int64_t* out_qoff);
 
 // coordinate sort, merge and CSI (k_bam_sort.hip)
 #define VMX_BAM_RUN_SHIFT 40            // value of the merge sort: run << 40 | index in run

@@ -1,4 +1,5 @@
-// vmx_bam.hip — C-ABI of the BAM writer (include/vacmapx.h): SAM text -> BAM records -> BGZF members, on the device (kernels: k_bam.hip).
+// vmx_bam.hip — C-ABI of the BAM writer (include/vacmapx.h): SAM text -> BAM records -> BGZF members, on the device (kernels: k_bam.hip), and, at the
+// end of the file, of the BAM reader (BGZF members -> records -> read blobs; kernels: k_bam_in.hip).
 // A writer owns grow-only device buffers and one page-locked staging buffer: after the first windows, a call allocates nothing but its
 // malloc'ed result. Host work per call: gathering the text into the staging buffer, three small waits (line count, record sizes and
 // errors, compressed size) and the few float tokens the device cannot convert exactly (vmx_bam_patch).
@@ -649,6 +650,439 @@ int vm_bam_sorter_index(vm_bam_sorter* s, char** out, int64_t* n_out) {
     if (!full) { free(z); set_error("out of host memory"); return VM_ERR_OOM; }
     memcpy(full + nz, kBgzfEof, sizeof kBgzfEof);
     *out = full; *n_out = nz + (int64_t)sizeof kBgzfEof;
+    return 0;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ BAM input
+// The host walks the BGZF member headers of a compressed chunk (magic, FLG.FEXTRA, the BC subfield among the extra subfields, BSIZE, the
+// trailer's CRC32 and ISIZE) and sums ISIZE into output offsets; the device inflates every member (k_bgzf_inflate), walks the records,
+// sizes and decodes them (k_bam_in_*). A reader reads the file ahead on an I/O thread into two page-locked staging buffers; the tail of a
+// window that holds no complete record is carried to the front of the next window's inflate buffer with a device copy.
+
+namespace {
+
+struct MemberTab {
+    std::vector<vmx_bgzf_member> m;
+    std::vector<int64_t> foff;                          // every member's offset in the file (messages)
+    int64_t consumed = 0, inflated = 0;
+};
+
+inline uint32_t le32(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+
+// the complete members of p[0, n) (file offset of p[0]: base), until their ISIZE sum would pass max_inf (one member is always taken).
+// *not_bgzf: a gzip member without the BC subfield was met
+int walk_members(const uint8_t* p, int64_t n, int64_t base, int64_t max_inf, MemberTab& T, std::string* err, bool* not_bgzf) {
+    T.m.clear(); T.foff.clear(); T.consumed = 0; T.inflated = 0;
+    *not_bgzf = false;
+    int64_t at = 0;
+    while (n - at >= 18) {
+        const uint8_t* h = p + at;
+        const std::string where = " at file offset " + std::to_string((long long)(base + at));
+        if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8) { *err = "not a gzip member" + where; return VM_ERR_IO; }
+        if (h[3] != 4) { *not_bgzf = true; *err = "gzip member without the BGZF extra field (FLG " + std::to_string((int)h[3]) + ")" + where; return VM_ERR_UNSUPPORTED; }
+        const int64_t xlen = (int64_t)h[10] | (int64_t)h[11] << 8;
+        if (n - at < 12 + xlen) break;
+        int64_t bsize = -1;
+        for (int64_t q = 12; q + 4 <= 12 + xlen;) {
+            const int64_t slen = (int64_t)h[q + 2] | (int64_t)h[q + 3] << 8;
+            if (q + 4 + slen > 12 + xlen) { *err = "malformed gzip extra field" + where; return VM_ERR_IO; }
+            if (h[q] == 'B' && h[q + 1] == 'C' && slen == 2) bsize = (int64_t)h[q + 4] | (int64_t)h[q + 5] << 8;
+            q += 4 + slen;
+        }
+        if (bsize < 0) { *not_bgzf = true; *err = "gzip member without the BGZF BC subfield" + where; return VM_ERR_UNSUPPORTED; }
+        const int64_t total = bsize + 1;
+        if (total < 12 + xlen + 8) { *err = "BGZF member with a BSIZE smaller than its header and trailer" + where; return VM_ERR_IO; }
+        if (n - at < total) break;
+        const uint32_t isize = le32(h + total - 4);
+        if (isize > (1u << 28)) { *err = "BGZF member with an ISIZE beyond what its size can hold" + where; return VM_ERR_IO; }
+        if (!T.m.empty() && T.inflated + (int64_t)isize > max_inf) break;
+        T.m.push_back(vmx_bgzf_member{at + 12 + xlen, T.inflated, (int32_t)(total - 12 - xlen - 8), isize, le32(h + total - 8), 0});
+        T.foff.push_back(base + at);
+        T.inflated += isize; at += total;
+    }
+    T.consumed = at;
+    return 0;
+}
+
+const char* bgzf_reason(int code) {
+    switch (code) {
+        case VMX_BGZF_E_BTYPE: return "reserved block type 3";
+        case VMX_BGZF_E_STORED: return "stored block whose LEN is not the complement of NLEN";
+        case VMX_BGZF_E_INPUT: return "deflate data runs past the member's end (truncated member)";
+        case VMX_BGZF_E_LONG: return "deflate data holds more bytes than ISIZE";
+        case VMX_BGZF_E_SHORT: return "deflate data holds fewer bytes than ISIZE";
+        case VMX_BGZF_E_CRC: return "CRC32 mismatch";
+        case VMX_BGZF_E_LENS: return "over-subscribed or incomplete set of code lengths";
+        case VMX_BGZF_E_CODE: return "invalid literal / length or distance code";
+        case VMX_BGZF_E_DIST: return "distance reaches before the member's start";
+        case VMX_BGZF_E_TAIL: return "deflate data ends before the member's trailer";
+        default: return "malformed dynamic block header";
+    }
+}
+
+const vmx_crc_x2n& crc_x2n_table() {
+    static const vmx_crc_x2n t = [] { vmx_crc_x2n x; uint32_t p = 1u << 30; for (int k = 0; k < 32; ++k) { x.v[k] = p; p = crc_multmodp(p, p); } return x; }();
+    return t;
+}
+
+struct InflateBufs { DevBuf comp, tab, key; };
+
+// the members T of the n_comp compressed bytes at `comp` (host) -> d_out[0, T.inflated); waits for the result
+int inflate_run(vm_ctx* c, InflateBufs& z, HostPinned& pin, const uint8_t* comp, int64_t n_comp, const MemberTab& T, uint8_t* d_out) {
+    const int64_t nm = (int64_t)T.m.size();
+    if (nm == 0) return 0;
+    VMX_TRY(z.comp.reserve((size_t)n_comp + 16));
+    VMX_TRY(z.tab.reserve((size_t)nm * sizeof(vmx_bgzf_member)));
+    VMX_TRY(z.key.reserve(8));
+    VMX_TRY(pin.reserve(64));
+    VMX_HIP(hipMemcpyAsync(z.comp.p, comp, (size_t)n_comp, hipMemcpyHostToDevice, c->stream));
+    VMX_HIP(hipMemcpyAsync(z.tab.p, T.m.data(), (size_t)nm * sizeof(vmx_bgzf_member), hipMemcpyHostToDevice, c->stream));
+    VMX_HIP(hipMemsetAsync(z.key.p, 0xff, 8, c->stream));
+    hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)nm), dim3(64), 0, c->stream, z.comp.as<const uint8_t>(), z.tab.as<const vmx_bgzf_member>(), nm, d_out,
+                       crc_x2n_table(), z.key.as<unsigned long long>());
+    VMX_HIP(hipMemcpyAsync(pin.p, z.key.p, 8, hipMemcpyDeviceToHost, c->stream));
+    VMX_TRY(sync(c));
+    uint64_t key; memcpy(&key, pin.p, 8);
+    if (key != ~0ull) {
+        const int64_t mb = (int64_t)(key >> 8);
+        set_error("BGZF member at file offset " + std::to_string((long long)(mb < nm ? T.foff[mb] : -1)) + ": " + bgzf_reason((int)(key & 0xff)));
+        return VM_ERR_IO;
+    }
+    return 0;
+}
+
+struct Grow {
+    char* p = nullptr; size_t n = 0, cap = 0;
+    bool append(const char* s, size_t k) {
+        if (n + k > cap) { const size_t want = (n + k) + (n + k) / 2 + 64; char* q = (char*)realloc(p, want); if (!q) return false; p = q; cap = want; }
+        // a window's bases are hundreds of MB: the copy (into fresh pages) is split over VMX_BAM_IN_COPY_THREADS threads (default 4; 1: one memcpy);
+        // measured against one memcpy by `tools/bam_bench.py input`
+        int nt = 1;
+        if (k >= ((size_t)8 << 20)) { const char* e = getenv("VMX_BAM_IN_COPY_THREADS"); const int v = e ? atoi(e) : 4; nt = v < 1 ? 1 : v > 16 ? 16 : v; }
+        if (nt == 1) { if (k) memcpy(p + n, s, k); }
+        else {
+            std::vector<std::thread> th;
+            for (int t = 0; t < nt; ++t) th.emplace_back([=] { const size_t a = k * t / nt, b = k * (t + 1) / nt; memcpy(p + n + a, s + a, b - a); });
+            for (auto& t : th) t.join();
+        }
+        n += k;
+        return true;
+    }
+    char* release() { char* q = p ? p : (char*)malloc(1); p = nullptr; n = cap = 0; return q; }
+    ~Grow() { free(p); }
+};
+
+double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+struct DecodedWin { HostPinned names, seqs, quals, off; int64_t n = 0; };     // a window's reads on the host: blobs and 3 x (n + 1) offsets
+
+struct BamInChunk { HostPinned stage; MemberTab T; int64_t fpos = 0, got = 0; int rc = 0; std::string err; bool not_bgzf = false; double busy = 0; };
+
+}  // namespace
+
+struct vm_bam_reader {
+    vm_ctx* c = nullptr;
+    int fd = -1;
+    int64_t fsize = 0, chunk_bytes = 0, max_inf = 0;
+    BamInChunk ch[2];
+    int slot = 0;                                       // the chunk the next window takes
+    std::future<void> pre; bool pre_on = false; bool file_done = false; int64_t next_fpos = 0;
+    InflateBufs z;
+    DevBuf d_inf[2]; int which = 0; int64_t tail_off = 0, carry = 0;     // the bytes of d_inf[which] from tail_off on go in front of the next window
+    bool hdr_done = false;
+    DevBuf d_roff, d_walk, d_sz, d_off, d_tmp, d_names, d_seqs, d_quals, d_ooff;
+    HostPinned pin;
+    DecodedWin win[2]; int cur = 0; int64_t at = 0;     // records [at, win[cur].n) are not handed out yet; the other slot is being produced
+    std::future<int> prod; bool prod_on = false; std::string prod_err;      // the next window, decoded ahead on a thread of its own
+    int64_t n_seen = 0, n_dropped = 0;                  // records walked / without bases
+    double st[12] = {0};                                // written by whoever produces a window
+    double pub[12] = {0}; double handout_s = 0;         // what vm_bam_reader_stats reads: st as of the latest window the caller's thread has taken over
+};
+
+namespace {
+
+void read_chunk_in(vm_bam_reader* r, int slot, int64_t fpos) {
+    BamInChunk& k = r->ch[slot];
+    const double t0 = now_s();
+    k.fpos = fpos; k.got = 0; k.rc = 0; k.err.clear(); k.T.m.clear(); k.T.foff.clear(); k.T.consumed = 0; k.T.inflated = 0;
+    const int64_t want = std::min<int64_t>(r->chunk_bytes, r->fsize - fpos);
+    while (k.got < want) {
+        const ssize_t q = pread(r->fd, k.stage.p + k.got, (size_t)(want - k.got), (off_t)(fpos + k.got));
+        if (q < 0) { k.rc = VM_ERR_IO; k.err = "read error at file offset " + std::to_string((long long)(fpos + k.got)); return; }
+        if (q == 0) break;
+        k.got += q;
+    }
+    if (k.got > 0) {
+        k.rc = walk_members((const uint8_t*)k.stage.p, k.got, fpos, r->max_inf, k.T, &k.err, &k.not_bgzf);
+        if (k.rc == 0 && k.T.m.empty()) {
+            k.rc = VM_ERR_IO;
+            k.err = fpos + k.got >= r->fsize ? "truncated file: the BGZF member at file offset " + std::to_string((long long)fpos) + " is not complete"
+                                             : "BGZF member at file offset " + std::to_string((long long)fpos) + " is larger than the reader's chunk";
+        }
+    }
+    k.busy = now_s() - t0;
+}
+
+// 1: the BAM header ends at *end; 0: more bytes are needed; -1: not BAM
+int parse_bam_header(const uint8_t* h, int64_t n, int64_t* end) {
+    if (n < 4) return 0;
+    if (memcmp(h, "BAM\1", 4) != 0) return -1;
+    if (n < 8) return 0;
+    int64_t p = 8 + (int64_t)le32(h + 4);
+    if (n < p + 4) return 0;
+    const int64_t n_ref = le32(h + p); p += 4;
+    for (int64_t i = 0; i < n_ref; ++i) {
+        if (n < p + 4) return 0;
+        p += 4 + (int64_t)le32(h + p) + 4;
+    }
+    if (n < p) return 0;
+    *end = p;
+    return 1;
+}
+
+int prim_scan64_in(vm_ctx* c, DevBuf& tmp, const int64_t* in, int64_t* out, size_t n) {
+    size_t tb = 0;
+    int e = vmx_prim_excl_scan_i64(nullptr, &tb, in, out, n, c->stream);
+    if (e != 0) return vmx::hip_fail((hipError_t)e, "scan", __FILE__, __LINE__);
+    VMX_TRY(tmp.reserve(tb ? tb : 8));
+    e = vmx_prim_excl_scan_i64(tmp.p, &tb, in, out, n, c->stream);
+    if (e != 0) return vmx::hip_fail((hipError_t)e, "scan", __FILE__, __LINE__);
+    return 0;
+}
+
+// the next window into win[slot]: 1 (its records decoded, possibly none), 0 at the end of the file, or a negative status
+int bam_in_window(vm_bam_reader* r, int slot) {
+    vm_ctx* c = r->c;
+    DecodedWin& D = r->win[slot];
+    D.n = 0;
+    if (r->file_done) {
+        if (r->carry > 0) { set_error(r->hdr_done ? "truncated file: BAM record " + std::to_string((long long)r->n_seen + 1) + " is not complete" : "truncated file: the BAM header is not complete"); return VM_ERR_IO; }
+        return 0;
+    }
+    double t0 = now_s();
+    if (r->pre_on) { r->pre.get(); r->pre_on = false; }
+    else read_chunk_in(r, r->slot, r->next_fpos);
+    r->st[1] += now_s() - t0;
+    BamInChunk& k = r->ch[r->slot];
+    r->st[0] += k.busy;
+    if (k.rc < 0) { set_error(k.err); return k.rc; }
+    r->next_fpos = k.fpos + k.T.consumed;
+    if (k.T.m.empty() || r->next_fpos >= r->fsize) r->file_done = true;
+    else { r->pre_on = true; r->pre = std::async(std::launch::async, read_chunk_in, r, r->slot ^ 1, r->next_fpos); }
+    r->slot ^= 1;
+    if (k.T.m.empty()) return bam_in_window(r, slot);                         // (an empty file tail: the end-of-file checks above)
+    // inflate behind the carried tail
+    t0 = now_s();
+    DevBuf& dst = r->d_inf[r->which ^ 1];
+    const int64_t avail = r->carry + k.T.inflated;
+    VMX_TRY(dst.reserve((size_t)avail + 64));
+    if (r->carry) VMX_HIP(hipMemcpyAsync(dst.p, r->d_inf[r->which].as<uint8_t>() + r->tail_off, (size_t)r->carry, hipMemcpyDeviceToDevice, c->stream));
+    VMX_TRY(inflate_run(c, r->z, r->pin, (const uint8_t*)k.stage.p, k.T.consumed, k.T, dst.as<uint8_t>() + r->carry));
+    r->which ^= 1;
+    r->st[2] += now_s() - t0; r->st[7] += 1; r->st[8] += (double)k.T.consumed; r->st[9] += (double)k.T.inflated;
+    int64_t begin = 0;
+    if (!r->hdr_done) {
+        std::vector<uint8_t> H;
+        for (int64_t have = 0;;) {
+            const int64_t want = std::min<int64_t>(avail, std::max<int64_t>(have * 4, 1 << 16));
+            H.resize((size_t)want);
+            if (want) VMX_HIP(hipMemcpy(H.data(), dst.p, (size_t)want, hipMemcpyDeviceToHost));
+            have = want;
+            const int pr = parse_bam_header(H.data(), have, &begin);
+            if (pr < 0) { set_error("not a BAM file: the inflated stream does not begin with BAM\\1"); return VM_ERR_ARG; }
+            if (pr > 0) break;
+            if (have == avail) {
+                if (r->file_done && avail < 4) { set_error("not a BAM file: the inflated stream does not begin with BAM\\1"); return VM_ERR_ARG; }
+                r->tail_off = 0; r->carry = avail; return 1;
+            }
+        }
+        r->hdr_done = true;
+    }
+    // records
+    t0 = now_s();
+    const int64_t max_rec = (avail - begin) / 36 + 1;
+    VMX_TRY(r->d_roff.reserve((size_t)(max_rec + 1) * 8));
+    VMX_TRY(r->d_walk.reserve(sizeof(vmx_bam_in_walk)));
+    hipLaunchKernelGGL(k_bam_in_walk, dim3(1), dim3(64), 0, c->stream, dst.as<const uint8_t>(), begin, avail, max_rec, r->d_roff.as<int64_t>(), r->d_walk.as<vmx_bam_in_walk>());
+    VMX_HIP(hipMemcpyAsync(r->pin.p, r->d_walk.p, sizeof(vmx_bam_in_walk), hipMemcpyDeviceToHost, c->stream));
+    VMX_TRY(sync(c));
+    vmx_bam_in_walk W; memcpy(&W, r->pin.p, sizeof W);
+    r->st[3] += now_s() - t0;
+    if (W.err_key != ~0ull) {
+        set_error("BAM record " + std::to_string((long long)(r->n_seen + (int64_t)(W.err_key >> 8)) + 1) + ": block_size is below 32, smaller than its name, CIGAR and bases, or above 512 MB");
+        return VM_ERR_IO;
+    }
+    const int64_t n = W.n_rec;
+    r->n_seen += n;
+    r->tail_off = W.end; r->carry = avail - W.end;
+    if (n == 0) return 1;
+    t0 = now_s();
+    const size_t col = (size_t)(n + 1);
+    VMX_TRY(r->d_sz.reserve(col * 8 * 4)); VMX_TRY(r->d_off.reserve(col * 8 * 4)); VMX_TRY(r->d_ooff.reserve(col * 8 * 3));
+    int64_t* sz = r->d_sz.as<int64_t>(); int64_t* off = r->d_off.as<int64_t>(); int64_t* oo = r->d_ooff.as<int64_t>();
+    hipLaunchKernelGGL(k_bam_in_sizes, dim3(grid256(n + 1)), dim3(256), 0, c->stream, dst.as<const uint8_t>(), r->d_roff.as<const int64_t>(), n, sz, sz + col, sz + 2 * col, sz + 3 * col);
+    for (int j = 0; j < 4; ++j) VMX_TRY(prim_scan64_in(c, r->d_tmp, sz + j * col, off + j * col, col));
+    int64_t* tot = (int64_t*)r->pin.p;
+    for (int j = 0; j < 4; ++j) VMX_HIP(hipMemcpyAsync(tot + j, off + j * col + n, 8, hipMemcpyDeviceToHost, c->stream));
+    VMX_TRY(sync(c));
+    const int64_t tn = tot[0], ts = tot[1], tq = tot[2], nk = tot[3];
+    r->n_dropped += n - nk;
+    VMX_TRY(r->d_names.reserve((size_t)tn + 8)); VMX_TRY(r->d_seqs.reserve((size_t)ts + 8)); VMX_TRY(r->d_quals.reserve((size_t)tq + 8));
+    hipLaunchKernelGGL(k_bam_in_decode, dim3((unsigned)((n + 1 + 3) / 4)), dim3(256), 0, c->stream, dst.as<const uint8_t>(), r->d_roff.as<const int64_t>(), n, off, off + col,
+                       off + 2 * col, off + 3 * col, r->d_names.as<char>(), r->d_seqs.as<char>(), r->d_quals.as<char>(), oo, oo + col, oo + 2 * col);
+    VMX_TRY(sync(c));
+    r->st[4] += now_s() - t0;
+    t0 = now_s();
+    VMX_TRY(D.names.reserve((size_t)tn + 8)); VMX_TRY(D.seqs.reserve((size_t)ts + 8)); VMX_TRY(D.quals.reserve((size_t)tq + 8)); VMX_TRY(D.off.reserve((size_t)(nk + 1) * 8 * 3));
+    if (tn) VMX_HIP(hipMemcpyAsync(D.names.p, r->d_names.p, (size_t)tn, hipMemcpyDeviceToHost, c->stream));
+    if (ts) VMX_HIP(hipMemcpyAsync(D.seqs.p, r->d_seqs.p, (size_t)ts, hipMemcpyDeviceToHost, c->stream));
+    if (tq) VMX_HIP(hipMemcpyAsync(D.quals.p, r->d_quals.p, (size_t)tq, hipMemcpyDeviceToHost, c->stream));
+    for (int j = 0; j < 3; ++j) VMX_HIP(hipMemcpyAsync((int64_t*)D.off.p + j * (nk + 1), oo + j * col, (size_t)(nk + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    VMX_TRY(sync(c));
+    r->st[5] += now_s() - t0;
+    D.n = nk; r->st[10] += (double)nk; r->st[11] = (double)r->n_dropped;
+    return 1;
+}
+
+// the producer thread: the device belongs to the reader's context, the message to the thread that asks for it
+int bam_in_produce(vm_bam_reader* r, int slot) {
+    (void)hipSetDevice(r->c->device);
+    const int rc = bam_in_window(r, slot);
+    if (rc < 0) r->prod_err = vm_last_error();
+    return rc;
+}
+
+// win[cur] is drained: the window produced ahead becomes the current one and the next is started in the drained slot
+int bam_in_next(vm_bam_reader* r) {
+    const int nxt = r->cur ^ 1;
+    int rc;
+    if (r->prod_on) { rc = r->prod.get(); r->prod_on = false; if (rc < 0) set_error(r->prod_err); }
+    else rc = bam_in_window(r, nxt);
+    memcpy(r->pub, r->st, sizeof r->pub);                               // (no window is in production here)
+    if (rc < 0) return rc;
+    r->cur = nxt; r->at = 0;
+    if (rc == 0) { r->win[nxt].n = 0; return 0; }
+    r->prod_on = true; r->prod_err.clear();
+    r->prod = std::async(std::launch::async, bam_in_produce, r, nxt ^ 1);
+    return 1;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vm_bgzf_decompress(vm_ctx* c, const void* in, int64_t n, char** out, int64_t* n_out) {
+    if (out) *out = nullptr;
+    if (n_out) *n_out = 0;
+    if (!c) return VM_ERR_NO_CTX;
+    if (!out || !n_out || n < 0 || (n > 0 && !in)) return VM_ERR_ARG;
+    MemberTab T; std::string err; bool nb = false;
+    const int wrc = walk_members((const uint8_t*)in, n, 0, INT64_MAX, T, &err, &nb);
+    if (wrc < 0) { set_error(err); return wrc; }
+    if (T.consumed != n) { set_error("truncated input: the BGZF member at file offset " + std::to_string((long long)T.consumed) + " is not complete"); return VM_ERR_IO; }
+    InflateBufs z; HostPinned pin; DevBuf d_out;
+    int rc = d_out.reserve((size_t)T.inflated + 64);
+    if (rc == 0) rc = inflate_run(c, z, pin, (const uint8_t*)in, n, T, d_out.as<uint8_t>());
+    char* res = nullptr;
+    if (rc == 0 && !(res = (char*)malloc((size_t)T.inflated + 1))) { set_error("out of host memory"); rc = VM_ERR_OOM; }
+    if (rc == 0 && T.inflated && hipMemcpy(res, d_out.p, (size_t)T.inflated, hipMemcpyDeviceToHost) != hipSuccess) { set_error("vm_bgzf_decompress: download failed"); rc = VM_ERR_HIP; }
+    (void)hipStreamSynchronize(c->stream);
+    DevBuf* bufs[] = {&d_out, &z.comp, &z.tab, &z.key};
+    for (DevBuf* b : bufs) b->release();
+    if (rc < 0) { free(res); return rc; }
+    *out = res; *n_out = T.inflated;
+    return 0;
+}
+
+void vm_bam_reader_close(vm_bam_reader* r) {
+    if (!r) return;
+    if (r->prod_on) (void)r->prod.get();
+    if (r->pre_on) r->pre.get();
+    (void)hipStreamSynchronize(r->c->stream);
+    if (r->fd >= 0) close(r->fd);
+    DevBuf* bufs[] = {&r->z.comp, &r->z.tab, &r->z.key, &r->d_inf[0], &r->d_inf[1], &r->d_roff, &r->d_walk, &r->d_sz, &r->d_off, &r->d_tmp, &r->d_names, &r->d_seqs, &r->d_quals, &r->d_ooff};
+    for (DevBuf* b : bufs) b->release();
+    delete r;
+}
+
+int vm_bam_reader_open(vm_ctx* c, const char* path, vm_bam_reader** out) {
+    if (out) *out = nullptr;
+    if (!c) return VM_ERR_NO_CTX;
+    if (!out || !path) return VM_ERR_ARG;
+    const int fd = open(path, O_RDONLY);
+    if (fd < 0) { set_error(std::string("cannot open ") + path); return VM_ERR_IO; }
+    vm_bam_reader* r = new vm_bam_reader();
+    r->c = c; r->fd = fd;
+    r->fsize = (int64_t)lseek(fd, 0, SEEK_END);
+    // VMX_BAM_IN_CHUNK / VMX_BAM_IN_MAXINF: compressed bytes per read and inflated bytes per window (tests cross many windows with small files)
+    r->chunk_bytes = 64 << 20; r->max_inf = (int64_t)512 << 20;
+    if (const char* e = getenv("VMX_BAM_IN_CHUNK")) r->chunk_bytes = std::max<int64_t>(atoll(e), 1 << 17);
+    if (const char* e = getenv("VMX_BAM_IN_MAXINF")) r->max_inf = std::max<int64_t>(atoll(e), 1 << 16);
+    int rc = r->fsize < 0 ? (int)VM_ERR_IO : 0;
+    if (rc < 0) set_error(std::string("cannot seek in ") + path);
+    const size_t stage = (size_t)std::min<int64_t>(r->chunk_bytes, std::max<int64_t>(r->fsize, 1));
+    if (rc == 0) rc = r->ch[0].stage.reserve(stage);
+    if (rc == 0) rc = r->ch[1].stage.reserve(stage);
+    if (rc == 0) rc = r->pin.reserve(256);
+    if (rc == 0 && r->fsize == 0) { set_error(std::string("empty file: ") + path); rc = VM_ERR_IO; }
+    while (rc == 0 && !r->hdr_done) {
+        rc = bam_in_window(r, 0);
+        if (rc == 0) { set_error("truncated file: the BAM header is not complete"); rc = VM_ERR_IO; }
+        else if (rc > 0) rc = 0;
+    }
+    if (rc < 0) { vm_bam_reader_close(r); return rc; }
+    r->cur = 0; r->at = 0;
+    memcpy(r->pub, r->st, sizeof r->pub);
+    r->prod_on = true;                                                  // the second window is decoded while the caller takes the first
+    r->prod = std::async(std::launch::async, bam_in_produce, r, 1);
+    *out = r;
+    return 0;
+}
+
+int64_t vm_bam_reader_read(vm_bam_reader* r, int64_t max_reads, int64_t max_bases, char** names, int64_t** name_off, char** seqs, int64_t** seq_off, char** quals,
+                           int64_t** qual_off, char** comments, int64_t** com_off) {
+    if (!r || !r->c) return VM_ERR_NO_CTX;
+    if (!names || !name_off || !seqs || !seq_off || !quals || !qual_off || !comments || !com_off) return VM_ERR_ARG;
+    try {
+        Grow nb, sb, qb;
+        std::vector<int64_t> no(1, 0), so(1, 0), qo(1, 0);
+        int64_t n = 0;
+        bool end = false;
+        while (n < max_reads && (int64_t)sb.n < max_bases && !end) {
+            if (r->at >= r->win[r->cur].n) {
+                const int rc = bam_in_next(r);
+                if (rc < 0) return rc;
+                if (rc == 0) end = true;
+                continue;
+            }
+            const double t0 = now_s();
+            const DecodedWin& D = r->win[r->cur];
+            const int64_t nk = D.n;
+            const int64_t* hn = (const int64_t*)D.off.p; const int64_t* hs = hn + (nk + 1); const int64_t* hq = hs + (nk + 1);
+            const int64_t a = r->at;
+            int64_t m = 0;
+            while (a + m < nk && n + m < max_reads && (int64_t)sb.n + (hs[a + m] - hs[a]) < max_bases) ++m;
+            if (!nb.append(D.names.p + hn[a], (size_t)(hn[a + m] - hn[a])) || !sb.append(D.seqs.p + hs[a], (size_t)(hs[a + m] - hs[a])) ||
+                !qb.append(D.quals.p + hq[a], (size_t)(hq[a + m] - hq[a]))) { set_error("vm_bam_reader_read: out of host memory"); return VM_ERR_OOM; }
+            const int64_t n0 = no.back() - hn[a], s0 = so.back() - hs[a], q0 = qo.back() - hq[a];
+            for (int64_t j = 1; j <= m; ++j) { no.push_back(n0 + hn[a + j]); so.push_back(s0 + hs[a + j]); qo.push_back(q0 + hq[a + j]); }
+            r->at += m; n += m;
+            r->handout_s += now_s() - t0;
+        }
+        auto giveo = [](const std::vector<int64_t>& v, int64_t** p) { *p = (int64_t*)malloc(8 * v.size()); memcpy(*p, v.data(), 8 * v.size()); };
+        *names = nb.release(); *seqs = sb.release(); *quals = qb.release(); *comments = (char*)malloc(1);
+        giveo(no, name_off); giveo(so, seq_off); giveo(qo, qual_off);
+        giveo(std::vector<int64_t>((size_t)n + 1, 0), com_off);
+        return n;
+    }
+    catch (const std::bad_alloc&) { set_error("vm_bam_reader_read: out of host memory"); return VM_ERR_OOM; }
+}
+
+int vm_bam_reader_stats(const vm_bam_reader* r, double* out, int n) {
+    if (!r || !out) return VM_ERR_ARG;
+    for (int i = 0; i < n; ++i) out[i] = i == 6 ? r->handout_s : i < 12 ? r->pub[i] : 0.0;         // (both written by the caller's own thread)
     return 0;
 }
 

@@ -112,6 +112,28 @@ def _bam_chunks(path, n_max):
         yield pack(cur)
 
 
+def _native_bam_chunks(path, n_max, lib, device):
+    """--bam-reader native: the chunks of _bam_chunks from lib.BamReader (BGZF inflate and record decoding on the GPU) on a context of its own.
+    A .bam that is gzip but not BGZF (no member boundaries to inflate side by side) goes to the Python reader, with one line on stderr."""
+    from .lib import BamReader, Context, VmxError
+    ctx = Context(device, lib=lib)
+    try:
+        try:
+            rd = BamReader(ctx, path)
+        except VmxError as e:
+            if e.code != -7:                               # VM_ERR_UNSUPPORTED
+                raise
+            sys.stderr.write('[vacmap_amd] --bam-reader native: %s is gzip but not BGZF, reading it with the Python BAM reader\n' % path)
+            yield from _bam_chunks(path, n_max)
+            return
+        try:
+            yield from iter(lambda: rd.read(n_max), None)
+        finally:
+            rd.close()
+    finally:
+        ctx.close()
+
+
 def _is_plain_fastx(path):
     """an uncompressed FASTA / FASTQ file (byte ranges of it can be parsed independently)"""
     if path.endswith('.bam') or not os.path.isfile(path):
@@ -288,6 +310,9 @@ def build_parser():
                    help='how -o x.bam is written: a `samtools view -b` pipe (default) or the GPU encoder and BGZF compressor (vacmap_amd.bamout); '
                         'native does not sort: .sorted.bam needs samtools or native-sort, which sorts by coordinate on the GPU and writes x.sorted.bam.csi '
                         '(run files go to a fresh directory under -workdir, else next to the output, and are removed)')
+    p.add_argument('--bam-reader', choices=['python', 'native'], default='python',
+                   help='how -read x.bam is read: the Python reader on one host thread (default) or BGZF inflate and record decoding on the GPU '
+                        '(lib.BamReader, on a context of its own); a .bam that is gzip but not BGZF falls back to the Python reader')
     return p
 
 
@@ -307,7 +332,7 @@ def _open_output(path):
 last_timing = {}          # wall seconds of the last main() call by phase (tools/driver_bench.py reads it)
 
 
-def _run_asm(args, lib, ctx, index, prm, rg, mark, out, proc, world, rank, text_group, t_start):
+def _run_asm(args, lib, ctx, index, prm, rg, mark, out, proc, world, rank, text_group, t_start, device=0):
     """-mode asm (src/vacmap/vacmap:245-255, :394-411; worker mammap_asm.py:23462-23511): every input sequence is an assembly contig. --eqx is
     forced and maxdivergence set to 1 by vm_params_default(VM_MODE_ASM); contigs are aligned in groups (the long ones of a group side by side on
     the GPU) and their SAM lines written in input order. A contig the reference would skip (raised) is logged and skipped.
@@ -372,7 +397,10 @@ def _run_asm(args, lib, ctx, index, prm, rg, mark, out, proc, world, rank, text_
     for grp in args.read:
         for path in grp:
             # (.bam input like every other mode: vacmap:452-470)
-            chunks = _bam_chunks(path, 64) if path.endswith('.bam') else iter(lambda rd=Fastx(path, lib=lib): rd.read(64), None)
+            if path.endswith('.bam'):
+                chunks = _native_bam_chunks(path, 64, lib, device) if args.bam_reader == 'native' else _bam_chunks(path, 64)
+            else:
+                chunks = iter(lambda rd=Fastx(path, lib=lib): rd.read(64), None)
             for ch in chunks:
                 nb, no, sb, so = ch['names'].tobytes(), ch['names_off'], ch['seqs'].tobytes(), ch['seqs_off']
                 qb, qo, cb, co = ch['quals'].tobytes(), ch['quals_off'], ch['comments'].tobytes(), ch['comments_off']
@@ -539,7 +567,7 @@ def main(argv=None, comm=None):
             for ln in head:
                 out.write(ln.encode() + b'\n')
     if args.mode == 'asm':
-        rc = _run_asm(args, lib, ctx, index, prm, rg, mark, out, proc, world, rank, text_group, t_start)
+        rc = _run_asm(args, lib, ctx, index, prm, rg, mark, out, proc, world, rank, text_group, t_start, device=device)
         ctx.close()
         if own_group:                                   # no rank leaves while rank 0 still gathers and writes
             comm.barrier(); comm.destroy_process_group()
@@ -571,7 +599,7 @@ def main(argv=None, comm=None):
         mode the rank takes its own byte range of the file, and `parse_threads` threads parse slices ahead of the consumer (one thread
         parses ~3 GB/s: a third of what one GPU aligns)"""
         if path.endswith('.bam'):
-            yield from _bam_chunks(path, win_reads)
+            yield from (_native_bam_chunks(path, win_reads, lib, device) if args.bam_reader == 'native' else _bam_chunks(path, win_reads))
             return
         if not _is_plain_fastx(path):
             rd = Fastx(path, lib=lib)

@@ -189,6 +189,10 @@ class VmxLib:
         L.vm_bam_sorter_chunk.argtypes = [vp, i64, P(vp), P(i64)]
         L.vm_bam_sorter_index.argtypes = [vp, P(vp), P(i64)]
         L.vm_bgzf_compress.argtypes = [vp, vp, i64, P(vp), P(i64)]
+        L.vm_bgzf_decompress.argtypes = [vp, vp, i64, P(vp), P(i64)]
+        L.vm_bam_reader_open.argtypes = [vp, cp, P(vp)]; L.vm_bam_reader_close.argtypes = [vp]; L.vm_bam_reader_close.restype = None
+        L.vm_bam_reader_read.argtypes = [vp, i64, i64] + [P(vp), P(P(i64))] * 4; L.vm_bam_reader_read.restype = i64
+        L.vm_bam_reader_stats.argtypes = [vp, P(C.c_double), C.c_int]
 
     def err(self):
         return self.L.vm_last_error().decode()
@@ -648,6 +652,59 @@ def bgzf_compress(ctx, data):
     p = C.c_void_p(); n = C.c_int64()
     ctx.lib.check(ctx.lib.L.vm_bgzf_compress(ctx.h, data, len(data), C.byref(p), C.byref(n)))
     return _take_bytes(ctx.lib, p, n)
+
+
+def bgzf_decompress(ctx, data):
+    """BGZF members (any writer's, with or without the EOF block) -> their bytes, inflated on the device (vm_bgzf_decompress)"""
+    data = bytes(data)
+    p = C.c_void_p(); n = C.c_int64()
+    ctx.lib.check(ctx.lib.L.vm_bgzf_decompress(ctx.h, data, len(data), C.byref(p), C.byref(n)))
+    return _take_bytes(ctx.lib, p, n)
+
+
+class BamReader:
+    """BAM reader into blobs (vm_bam_reader_*): BGZF inflate and record decoding on the device; read() as Fastx.read()"""
+    STATS = ('io_busy_s', 'io_wait_s', 'inflate_s', 'walk_s', 'decode_s', 'download_s', 'handout_s', 'windows', 'file_bytes', 'inflated_bytes', 'records', 'dropped')
+
+    def __init__(self, ctx, path):
+        self.ctx, self.lib = ctx, ctx.lib
+        h = C.c_void_p()
+        self.lib.check(self.lib.L.vm_bam_reader_open(ctx.h, _b(path), C.byref(h)))
+        self.h = h
+
+    def read(self, max_reads, max_bases=1 << 62):
+        """next chunk: dict of uint8 blobs and int64 offsets (names, seqs, quals, comments), or None at the end of the input"""
+        ptrs = [C.c_void_p() for _ in range(4)]; offs = [C.POINTER(C.c_int64)() for _ in range(4)]
+        args = []
+        for p, o in zip(ptrs, offs):
+            args += [C.byref(p), C.byref(o)]
+        n = self.lib.L.vm_bam_reader_read(self.h, int(max_reads), int(max_bases), *args)
+        if n < 0:
+            raise VmxError(int(n), self.lib.err())
+        out = {}
+        for key, p, o in zip(('names', 'seqs', 'quals', 'comments'), ptrs, offs):
+            oo = np.ctypeslib.as_array(o, shape=(n + 1,)).copy(); self.lib.L.vm_free(o)
+            tot = int(oo[-1])
+            out[key] = _OwnedText(self.lib, p, tot).array
+            out[key + '_off'] = oo
+        return out if n > 0 else None
+
+    def stats(self):
+        v = (C.c_double * 12)()
+        self.lib.check(self.lib.L.vm_bam_reader_stats(self.h, v, 12))
+        return dict(zip(self.STATS, list(v)))
+
+    def close(self):
+        if getattr(self, 'h', None):
+            if self.ctx.h:                                   # (a reader outlives its context only by mistake: then its memory is left to the process)
+                self.lib.L.vm_bam_reader_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class BamCodec:
