@@ -67,6 +67,18 @@ class BamWriter:
         if self.ctx is not None:
             self.ctx.close(); self.ctx = None
 
+    def _abort(self):
+        """an error: nothing more is written; the device is released (and the run files of a sorting writer go)"""
+        try:
+            self._drain()
+        except BaseException:
+            pass
+        if self.f is not None:
+            self.f.close()
+            self.f = None
+        self._io.shutdown()
+        self._release()
+
     def _finish(self):
         """what is still to be written before the EOF member"""
 
@@ -149,18 +161,6 @@ class SortedBamWriter(BamWriter):
         if self._dir is not None:
             self._rm()
             self._dir = None
-
-    def _abort(self):
-        """an error: nothing more is written; the run files go and the device is released"""
-        try:
-            self._drain()
-        except BaseException:
-            pass
-        if self.f is not None:
-            self.f.close()
-            self.f = None
-        self._io.shutdown()
-        self._release()
 
     def _finish(self):
         t0 = time.time()

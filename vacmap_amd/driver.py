@@ -16,10 +16,47 @@ With N ranks, rank 0 builds the index and broadcasts it over RCCL (vacmap_amd/di
 rank 0 gathers and writes the lines. `-mode asm` (assembly contigs; contig c -> rank c mod N): the contigs go through vm_align_batch with VM_MODE_ASM in
 groups, in input order, and their lines come from the native emitter in its asm form (vm_sam_opts.asm_mode = iterator_get_bam_dict_str,
 mammap_asm.py:22757; vacmap_amd/sam.py holds the same emitter in Python); `-workdir` is accepted and created like the reference's; only `--bam-writer native-sort` spills into it (its run files, removed at the end).
+main() lists the stages of a run; the stage that opens something (process groups, context and index, output, the read stream's contexts and
+page-locked buffers) releases it however the run ends. The environment variables the driver reads are the table SWITCHES.
 """
-import argparse, gzip, os, shutil, struct, subprocess, sys, threading, time, queue
+import argparse, concurrent.futures, contextlib, gzip, os, queue, shutil, struct, subprocess, sys, threading, time, types
 
 from . import sam
+# numpy is imported inside the functions that use it: a command-line run sets the allocator up (_keep_heap_pages) before numpy's first import
+
+
+# Every environment variable the driver reads: (name, default, how its text is read, what it does). main() reads them once, when it starts
+# (_switches); nothing below this table looks at the environment. INTEGRATION.md shows the same table to users.
+_is1, _not0 = (lambda v: v == '1'), (lambda v: v != '0')
+SWITCHES = (
+    ('WORLD_SIZE', '1', int, 'torchrun: number of ranks; above 1 the process groups are created (nccl = RCCL for the index, gloo for SAM text)'),
+    ('RANK', '0', int, 'torchrun: this process\'s rank'),
+    ('LOCAL_RANK', '0', int, 'torchrun: this process\'s GPU unless --device names one'),
+    ('VMX_FORCE_DIST', '0', _is1, '1: the N-rank start-up at world 1 too (process groups, index through a replica built from the broadcast metadata): '
+                            'what an 8-GPU run executes, testable on one GPU'),
+    ('VMX_GATHER_TIMEOUT', '1800', int, 'seconds after which the gloo group gives up on a rank that died (an error instead of a hang)'),
+    ('VMX_DRIVER_MALLOPT', '1', _not0, '0: leave glibc\'s allocator alone (default: one arena, no mmap, no trimming, so that freed windows are reused)'),
+    ('VMX_DRIVER_RAMP', '0', _is1, '1: the stream starts on one sized context and the others are sized in the background and join one by one '
+                             '(measured: the first batch starts 1.6 s instead of 5.9 s after the loop begins, the loop takes the same 12.8 s '
+                             'because hipMalloc under load slows the running batches, profiles/r05_zz_driver_long_ramped_start.json)'),
+    ('VMX_NO_WARM', '0', _is1, '1: no sizing run before the stream (every context then grows its pools when it meets its first long batch); also turns the ramp and the feeders off'),
+    ('VMX_MIN_FREE_GB', '10', float, 'HBM head-room after the sizing run: contexts are given up until this much is free'),
+    ('VMX_SPIN_SYNC', '0', _is1, '1: threads that wait for the GPU spin instead of sleeping (default: sleep, the emitters need the cores)'),
+    ('VMX_EMIT_THREADS', '0', int, 'host threads that produce SAM text, in all (0: -t)'),
+    ('VMX_PARSE_THREADS', '0', int, 'parser threads when --parse-threads is 0 (0: max(1, min(4, t / 4)))'),
+    ('VMX_SLICE_MB', '1024', float, 'size of the record-aligned slices a plain FASTA / FASTQ input is parsed in'),
+    ('VMX_DRIVER_WINDOWS', '10', int, 'windows in memory at a time, input blobs and SAM text (at least 2)'),
+    ('VMX_DRIVER_PINNED', '1', _not0, '0: gather a batch\'s reads into pageable instead of page-locked memory (the upload is then staged on the aligner thread); also turns the feeders off'),
+    ('VMX_DRIVER_FEEDERS', '2', int, 'threads with a context of their own that gather and upload batches ahead of the aligners (0: the aligner thread does both)'),
+    ('VMX_DRIVER_WRITEV', '1', _not0, '0: assemble a window\'s text and write() it instead of writing the batches\' texts straight to the descriptor'),
+    ('VMX_SKIP_EMIT', '0', _is1, '1: diagnostic, no SAM text is produced: the aligners alone'),
+    ('VMX_DRIVER_TIMING', '', str, 'set: one stderr line of seconds by phase at the end; 2: also one line per batch'),
+)
+
+
+def _switches():
+    """{name: value} of SWITCHES as the environment has them now"""
+    return {name: read(os.environ.get(name, default)) for name, default, read, _ in SWITCHES}
 
 
 def read_fastx(path, want_comment=False):
@@ -140,6 +177,66 @@ def _is_plain_fastx(path):
         return False
     with open(path, 'rb') as f:
         return f.read(2) != b'\x1f\x8b'
+
+
+def _parse_slice(path, lib, a, b, n_max):
+    from .lib import Fastx
+    rd = Fastx(path, lib=lib, byte_range=(a, b))
+    try:
+        return list(iter(lambda: rd.read(n_max), None))
+    finally:
+        rd.close()
+
+
+def _input_chunks(path, n_max, lib, device=0, bam_reader='python', parse_threads=0, share=(0, 1), slice_bytes=1 << 30):
+    """blob chunks (names, upper-cased sequences, qualities, comments; at most n_max records each) of one input in file order: a .bam through
+    the native or the Python reader, a compressed FASTA / FASTQ file through one library reader. parse_threads > 0: a plain file is cut into
+    record-aligned slices of about slice_bytes (vm_fastx_open_range) which that many threads parse ahead of the consumer, and share = (i, n)
+    takes the i-th of n equal byte ranges of it (range mode: the rank's own). parse_threads = 0: one reader over the whole file.
+    Closing the generator early releases the reader, its threads and the native BAM reader's context."""
+    from .lib import Fastx
+    if path.endswith('.bam'):
+        yield from (_native_bam_chunks(path, n_max, lib, device) if bam_reader == 'native' else _bam_chunks(path, n_max))
+        return
+    if not parse_threads or not _is_plain_fastx(path):
+        rd = Fastx(path, lib=lib)
+        try:
+            yield from iter(lambda: rd.read(n_max), None)
+        finally:
+            rd.close()
+        return
+    size = os.path.getsize(path)
+    lo, hi = size * share[0] // share[1], size * (share[0] + 1) // share[1]
+    ns = max(1, -(-(hi - lo) // slice_bytes))
+    cuts = [lo + (hi - lo) * i // ns for i in range(ns + 1)]
+    pool = concurrent.futures.ThreadPoolExecutor(max_workers=parse_threads)
+    try:
+        futs, nxt = [], 0
+        while nxt < ns or futs:
+            while nxt < ns and len(futs) < parse_threads + 1:
+                futs.append(pool.submit(_parse_slice, path, lib, cuts[nxt], cuts[nxt + 1], n_max)); nxt += 1
+            yield from futs.pop(0).result()
+    finally:
+        pool.shutdown(wait=True, cancel_futures=True)
+
+
+def _first_of_each_name(chunks, seen, lib):
+    """the chunks without the reads whose name came before (vacmap:457,475,487); `seen`: the set of names so far, added to as they pass"""
+    import numpy as np
+    from .lib import blob_gather
+    for ch in chunks:
+        n = len(ch['seqs_off']) - 1
+        nb, no = ch['names'].tobytes(), ch['names_off']
+        keep = []
+        for i in range(n):
+            nm = nb[no[i]:no[i + 1]]
+            if nm not in seen:
+                seen.add(nm); keep.append(i)
+        if len(keep) < n:
+            ix = np.asarray(keep, dtype=np.int64)
+            for key in ('names', 'seqs', 'quals', 'comments'):
+                ch[key], ch[key + '_off'] = blob_gather(lib, ch[key], ch[key + '_off'], ix)
+        yield ch
 
 
 _HASH_POW = None
@@ -316,133 +413,15 @@ def build_parser():
     return p
 
 
-def _open_output(path):
-    """'-' / .sam: text; .bam / .sorted.bam: a `samtools view -b` / `samtools sort --write-index` pipe (output_functions.py:200-208)"""
-    if path == '-':
-        return sys.stdout.buffer, None
-    if path.endswith('.sam'):
-        return open(path, 'w+b'), None            # (read + write: the writer maps the file's end to copy a window's lines in by several threads)
-    if not shutil.which('samtools'):
-        sys.exit('writing %s needs the samtools binary on PATH (the reference pipes SAM text into it too); write .sam instead' % path)
-    cmd = ['samtools', 'sort', '-@', '8', '--write-index', '-o', path, '-'] if path.endswith('sorted.bam') else ['samtools', 'view', '-b', '-@', '8', '-o', path, '-']
-    proc = subprocess.Popen(cmd, stdin=subprocess.PIPE, bufsize=1 << 20)
-    return proc.stdin, proc
-
-
 last_timing = {}          # wall seconds of the last main() call by phase (tools/driver_bench.py reads it)
 
 
-def _run_asm(args, lib, ctx, index, prm, rg, mark, out, proc, world, rank, text_group, t_start, device=0):
-    """-mode asm (src/vacmap/vacmap:245-255, :394-411; worker mammap_asm.py:23462-23511): every input sequence is an assembly contig. --eqx is
-    forced and maxdivergence set to 1 by vm_params_default(VM_MODE_ASM); contigs are aligned in groups (the long ones of a group side by side on
-    the GPU) and their SAM lines written in input order. A contig the reference would skip (raised) is logged and skipped.
-    With N ranks every rank parses the input, contig c of it goes to rank c mod N (contigs are independent: no data-path collective), and
-    rank 0 gathers each group's lines and writes them in input order."""
-    import numpy as np
-    from .lib import Fastx, SamOpts, align_batch_raw, sam_emit
-    if not args.workdir:
-        sys.exit('workdir not provided! -workdir /path/to/workdir')                      # vacmap:247-249
-    os.makedirs(args.workdir, exist_ok=True)
-    # the fork hard-codes these, whatever -c / -maxdivergence say: check_num = -1 (mammap_asm.py:23206), maxdivergence = 1.0 (:23483), --eqx
-    prm.eqx = 1; prm.check_num = -1; prm.maxdivergence = 1.0
-    opts = SamOpts(int(bool(args.MD)), int(args.cs != 'long'), int(bool(args.L)), int(bool(mark)), int(bool(args.H)), int(bool(args.fakecigar)), rg['ID'].encode(), 1)
-    seen = set(); n_contigs = n_lines = n_skipped = 0
-    native_bam = args.bam_writer in ('native', 'native-sort') and args.o.endswith('.bam')
-
-    def blob(parts):
-        off = np.zeros(len(parts) + 1, np.int64)
-        np.cumsum([len(x) for x in parts], out=off[1:])
-        return np.frombuffer(b''.join(parts) or b'\0', np.uint8), off
-
-    def flush(group):
-        """group: (input index, name, sequence, quality, comment — bytes) of consecutive input contigs, the same list on every rank"""
-        nonlocal n_lines, n_skipped
-        share = [g for g in group if g[0] % world == rank]
-        done = {}                                                                           # input index -> text of its lines, None = skipped
-        if share:
-            nb, no = blob([g[1] for g in share]); sb, so = blob([g[2] for g in share])
-            qb, qo = blob([g[3] for g in share]); cb, co = blob([g[4] for g in share])
-            raw = align_batch_raw(ctx, index, prm, sb, so)
-            # the asm emitter (iterator_get_bam_dict_str, mammap_asm.py:22757) in the native emitter: vm_sam_opts.asm_mode
-            text, toff, _, ns = sam_emit(lib, index, opts, nb, no, sb, so, raw, quals=qb, qual_off=qo, comments=cb if args.copycomments else None,
-                                         com_off=co if args.copycomments else None, nthreads=max(1, args.t))
-            for x, g in enumerate(share):
-                if raw.status[x] != 0:                                                      # the worker's except (:23493-23498)
-                    sys.stderr.write('%s is not aligned.\n' % g[1].decode()); done[g[0]] = None
-                else:
-                    done[g[0]] = text[int(toff[x]):int(toff[x + 1])].tobytes()
-            raw.close()
-        if world > 1:
-            from .dist import gather_lines
-            parts = gather_lines(done, dst=0, group=text_group)
-            if rank != 0:
-                return
-            done = {}
-            for d in parts:
-                done.update(d)
-        text = []                                                                           # --bam-writer native: the group's lines in one BAM call
-        for gi in sorted(done):
-            if done[gi] is None:
-                n_skipped += 1
-                continue
-            if native_bam:
-                text.append(done[gi])
-            else:
-                out.write(done[gi])
-            n_lines += done[gi].count(b'\n')
-        if text:
-            out.write(b''.join(text))
-
-    group, gbases = [], 0
-    for grp in args.read:
-        for path in grp:
-            # (.bam input like every other mode: vacmap:452-470)
-            if path.endswith('.bam'):
-                chunks = _native_bam_chunks(path, 64, lib, device) if args.bam_reader == 'native' else _bam_chunks(path, 64)
-            else:
-                chunks = iter(lambda rd=Fastx(path, lib=lib): rd.read(64), None)
-            for ch in chunks:
-                nb, no, sb, so = ch['names'].tobytes(), ch['names_off'], ch['seqs'].tobytes(), ch['seqs_off']
-                qb, qo, cb, co = ch['quals'].tobytes(), ch['quals_off'], ch['comments'].tobytes(), ch['comments_off']
-                for i in range(len(so) - 1):
-                    nm = nb[no[i]:no[i + 1]]
-                    if nm in seen:
-                        continue
-                    seen.add(nm)
-                    keep = n_contigs % world == rank                                       # the other ranks' contigs only hold their place
-                    group.append((n_contigs, nm, sb[so[i]:so[i + 1]] if keep else b'', (b'' if args.Q or not keep else qb[qo[i]:qo[i + 1]]),
-                                  cb[co[i]:co[i + 1]] if keep else b''))
-                    n_contigs += 1
-                    gbases += so[i + 1] - so[i]
-                    if len(group) >= 64 * world or gbases >= 400_000_000 * world:
-                        flush(group); group, gbases = [], 0
-    if group:
-        flush(group)
-    if rank == 0:
-        if proc is not None:
-            out.close(); proc.wait()
-        elif args.o != '-':
-            out.close()
-        else:
-            out.flush()
-        tt = max(time.time() - t_start, 0.001)
-        sys.stderr.write('vacmapx: %d contigs, %d SAM lines, %d contigs skipped, %.1f s%s\n' % (n_contigs, n_lines, n_skipped, tt, _index_note(out)))
-    return 0
-
-
-def _index_note(out):
-    """the tail of the final stderr line after --bam-writer native-sort: the index file and what the merge in close() cost"""
-    if not hasattr(out, 'merge_seconds'):
-        return ''
-    return '; sorted by coordinate, index %s.csi (merge of %d runs, %.1f MB of records: %.2f s)' % (out.path, len(out.runs), out.run_bytes / 1e6, out.merge_seconds)
-
-
-def _keep_heap_pages():
+def _keep_heap_pages(sw=None):
     """A window of input is ~1 GB of blobs, a batch's SAM text ~125 MB, all short-lived: glibc serves blocks that large from fresh mmap()s and
     unmaps them on free, so every byte the host pipeline writes lands on a page that is faulted in and zeroed first — measured on the FASTQ
     parser alone: 1.25 -> 2.85 GB/s once the pages are reused. One arena, no mmap for malloc, no trimming: freed blocks stay in the heap and
     the next window / batch reuses them. (VMX_DRIVER_MALLOPT=0 leaves the allocator alone.)"""
-    if os.environ.get('VMX_DRIVER_MALLOPT', '1') == '0':
+    if not (sw or _switches())['VMX_DRIVER_MALLOPT']:
         return
     try:
         import ctypes
@@ -455,60 +434,81 @@ def _keep_heap_pages():
         pass
 
 
-def main(argv=None, comm=None):
-    """comm: an initialised torch.distributed module (tests); under torchrun (WORLD_SIZE > 1) the process group is created here"""
-    t_start = time.time()
+# ---------------------------------------------------------------- the stages of main(), in the order it runs them
+
+def _parse_args(argv, comm, sw):
+    """stage 1: the options, checked as far as they can be before anything is opened"""
     args, _unknown = build_parser().parse_known_args(argv)          # unknown flags are ignored like the reference's parse_known_args (vacmap:152)
     if comm is None:                            # (a process of its own, not a test harness that shares the interpreter)
-        _keep_heap_pages()
+        _keep_heap_pages(sw)
     if args.o != '-' and not (args.o.endswith('.sam') or args.o.endswith('.bam')):
         sys.exit("Output path must end with .sam, .bam, .sorted.bam, or be '-' for stdout.")
-    native_bam = args.bam_writer in ('native', 'native-sort') and args.o.endswith('.bam')
-    native_sort = args.bam_writer == 'native-sort' and args.o.endswith('sorted.bam')
-    if native_bam and args.o.endswith('sorted.bam') and not native_sort:
+    args.native_bam = args.bam_writer in ('native', 'native-sort') and args.o.endswith('.bam')
+    args.native_sort = args.bam_writer == 'native-sort' and args.o.endswith('sorted.bam')
+    if args.native_bam and args.o.endswith('sorted.bam') and not args.native_sort:
         sys.exit('--bam-writer native writes unsorted BAM only: write %s with --bam-writer native-sort or samtools, or name the output .bam' % args.o)
-    world, rank, local_rank = 1, 0, 0
-    own_group = False
-    # VMX_FORCE_DIST=1: the N-rank start-up at world 1 too (process group over nccl = RCCL, gloo text group, index through a replica built from the
-    # broadcast metadata): what an 8-GPU run executes, testable on one GPU (tests/test_gpu_dist.py)
-    force_dist = comm is None and os.environ.get('VMX_FORCE_DIST') == '1'
-    if comm is None and (int(os.environ.get('WORLD_SIZE', '1')) > 1 or force_dist):
-        import torch, torch.distributed as comm
-        local_rank = int(os.environ.get('LOCAL_RANK', '0'))
+    return args
+
+
+@contextlib.contextmanager
+def _process_groups(comm, sw):
+    """stage 2: who this process is among the ranks (comm, world, rank, local_rank, text_group, force). Under torchrun, or with VMX_FORCE_DIST=1,
+    the groups are created here and destroyed on the way out — after a barrier when the run succeeded: no rank leaves while rank 0 still
+    gathers and writes."""
+    net = types.SimpleNamespace(comm=comm, world=1, rank=0, local_rank=0, text_group=None, force=comm is None and sw['VMX_FORCE_DIST'])
+    own = comm is None and (sw['WORLD_SIZE'] > 1 or net.force)
+    if own:
+        import torch, torch.distributed as dist
+        net.comm, net.local_rank = dist, sw['LOCAL_RANK']
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1'); os.environ.setdefault('MASTER_PORT', '29541')
-        torch.cuda.set_device(local_rank)
-        comm.init_process_group(backend='nccl', device_id=torch.device('cuda', local_rank), rank=int(os.environ.get('RANK', '0')), world_size=int(os.environ.get('WORLD_SIZE', '1')))
-        own_group = True
-    text_group = None
-    if own_group:
-        # SAM text is host data gathered from a writer THREAD: a gloo (CPU) group suits it — an object gather over the nccl group would
-        # stage its byte tensors on the calling thread's current device (cuda:0 in a new thread), not the rank's — and its timeout turns
-        # a peer that died into an error instead of a hang
-        import datetime
-        text_group = comm.new_group(backend='gloo', timeout=datetime.timedelta(seconds=int(os.environ.get('VMX_GATHER_TIMEOUT', '1800'))))
-    if comm is not None:
-        world, rank = comm.get_world_size(), comm.get_rank()
-    if rank == 0 and args.o != '-' and os.path.exists(args.o) and not args.force:
-        sys.exit('%s exists (use --force)' % args.o)
-    if comm is None and world == 1 and __name__ == '__main__':
-        os.environ.setdefault('VACMAPX_SKIP_TORCH', '1')        # one GPU from the command line: nothing here needs torch (its import is 1.5-2 s)
-    from .lib import Context, Index, load
-    from . import pipeline
-    lib = load()
-    device = args.device if args.device is not None else local_rank
-    ctx = Context(device)
-    k, w = int(args.k), int(args.w)
-    index = None
-    if rank == 0:
-        from .indexfile import find_index
-        index = find_index(ctx, args.ref, k, w, write=not args.nowriteindex)
-    if world > 1 or force_dist:
-        import torch
-        from .dist import broadcast_index
-        dev = torch.device('cuda', device) if torch.cuda.is_available() else torch.device('cpu')
-        index, t_bc = broadcast_index(ctx, index, src=0, device=dev, self_replica=(world == 1))
-        if force_dist and rank == 0:
-            sys.stderr.write('vacmapx: VMX_FORCE_DIST: process group %s, world %d, index through broadcast_index in %.2f s\n' % (comm.get_backend(), world, t_bc))
+        torch.cuda.set_device(net.local_rank)
+        dist.init_process_group(backend='nccl', device_id=torch.device('cuda', net.local_rank), rank=sw['RANK'], world_size=sw['WORLD_SIZE'])
+    try:
+        if own:
+            # SAM text is host data gathered from a writer THREAD: a gloo (CPU) group suits it — an object gather over the nccl group would
+            # stage its byte tensors on the calling thread's current device (cuda:0 in a new thread), not the rank's — and its timeout turns
+            # a peer that died into an error instead of a hang
+            import datetime
+            net.text_group = net.comm.new_group(backend='gloo', timeout=datetime.timedelta(seconds=sw['VMX_GATHER_TIMEOUT']))
+        if net.comm is not None:
+            net.world, net.rank = net.comm.get_world_size(), net.comm.get_rank()
+        yield net
+        if own:
+            net.comm.barrier()
+    finally:
+        if own:
+            net.comm.destroy_process_group()
+
+
+@contextlib.contextmanager
+def _context_and_index(args, net, device):
+    """stage 3: the first context and the index in its HBM: found or built by rank 0 (indexfile.find_index), broadcast to the others"""
+    from .lib import Context
+    ctx, index = Context(device), None
+    try:
+        if net.rank == 0:
+            from .indexfile import find_index
+            index = find_index(ctx, args.ref, int(args.k), int(args.w), write=not args.nowriteindex)
+        if net.world > 1 or net.force:
+            import torch
+            from .dist import broadcast_index
+            dev = torch.device('cuda', device) if torch.cuda.is_available() else torch.device('cpu')
+            built = index
+            index, t_bc = broadcast_index(ctx, built, src=0, device=dev, self_replica=(net.world == 1))
+            if built is not None and built is not index:
+                built.close()
+            if net.force and net.rank == 0:
+                sys.stderr.write('vacmapx: VMX_FORCE_DIST: process group %s, world %d, index through broadcast_index in %.2f s\n' % (net.comm.get_backend(), net.world, t_bc))
+        yield ctx, index
+    finally:
+        if index is not None:
+            index.close()
+        ctx.close()
+
+
+def _alignment_options(args, lib):
+    """stage 4: (aligner parameters, read group, emitter options), the same for the read modes and asm"""
+    from .lib import SamOpts
     prm = lib.params(args.mode)                     # mode defaults (vacmap:257-296), then the explicit options
     prm.check_num = args.c; prm.global_maxdiff = args.globalmaxdiff; prm.local_maxdiff = args.localmaxdiff
     prm.eqx = 1 if args.eqx else 0; prm.hardclip = 1 if args.H else 0
@@ -516,7 +516,6 @@ def main(argv=None, comm=None):
     if args.maxdivergence is not None: prm.maxdivergence = args.maxdivergence
     if args.globalpenalty is not None: prm.global_skipcost = args.globalpenalty
     if args.localpenalty is not None: prm.local_skipcost = args.localpenalty
-    names = index.names
     # read group: always present, like the reference (vacmap:186-218) — {'ID': '1', 'SM': 'sample'} unless --rg-* options are given
     rg = {}
     for a, tag in RG_ARGS:
@@ -528,492 +527,693 @@ def main(argv=None, comm=None):
     if not rg:
         rg = {'ID': '1', 'SM': 'sample'}
     mark = args.markunbalancetra or args.mode in ('H', 'L')          # mode defaults of vacmap:286-296 (False for asm unless asked)
-    from .lib import SamOpts, Fastx, PinnedPool, align_batch_raw, sam_emit, blob_gather, blob_gather_parts, blob_write_parts
-    opts = SamOpts(int(bool(args.MD)), int(args.cs != 'long'), int(bool(args.L)), int(bool(mark)), int(bool(args.H)), int(bool(args.fakecigar)), rg['ID'].encode())
+    opts = SamOpts(int(bool(args.MD)), int(args.cs != 'long'), int(bool(args.L)), int(bool(mark)), int(bool(args.H)), int(bool(args.fakecigar)), rg['ID'].encode(),
+                   int(args.mode == 'asm'))
+    return prm, rg, opts
+
+
+def _sharding(args, net):
+    """stage 5: True for range mode (every rank parses its own byte range of each input and writes its own part of the SAM file), False for
+    the batch scheme (every rank parses everything and keeps every N-th batch, rank 0 gathers the text)"""
     plain = all(_is_plain_fastx(pth) for grp in args.read for pth in grp)
-    range_mode = world > 1 and args.mode != 'asm' and args.shard != 'batch' and plain and args.o.endswith('.sam')
-    if world > 1 and args.shard == 'range' and not range_mode:
+    range_mode = net.world > 1 and args.mode != 'asm' and args.shard != 'batch' and plain and args.o.endswith('.sam')
+    if net.world > 1 and args.shard == 'range' and not range_mode:
         sys.exit('--shard range needs uncompressed FASTA / FASTQ input and a .sam output path')
     if range_mode:
         # every rank writes <out>.partNNN and rank 0 joins them: they must land in one directory. Ranks on several hosts only see each other's
         # parts on a shared file system — nothing here can check that, so `auto` falls back to the batch scheme (text gathered over gloo) and an
-        # explicit `--shard range` goes on with a warning (ADVICE r4)
+        # explicit `--shard range` goes on with a warning
         import socket
-        hosts = [None] * world
-        comm.all_gather_object(hosts, socket.gethostname(), group=text_group)
+        hosts = [None] * net.world
+        net.comm.all_gather_object(hosts, socket.gethostname(), group=net.text_group)
         if len(set(hosts)) > 1:
             if args.shard == 'auto':
                 range_mode = False
-                if rank == 0:
+                if net.rank == 0:
                     sys.stderr.write('vacmapx: ranks on %d hosts: --shard auto uses the batch scheme (SAM text gathered by rank 0); --shard range needs %s.partNNN on a shared file system\n' % (len(set(hosts)), args.o))
-            elif rank == 0:
+            elif net.rank == 0:
                 sys.stderr.write('vacmapx: ranks on %d hosts with --shard range: %s.partNNN of every rank must be visible to rank 0 (shared file system)\n' % (len(set(hosts)), args.o))
-    part_path = '%s.part%03d' % (args.o, rank) if range_mode else None
-    out, proc = (None, None)
-    if range_mode and rank != 0:
-        out = open(part_path, 'w+b')
-    if rank == 0:
-        head = sam.header_lines([(n, ln_) for n, ln_ in zip(names, index.lens)], ' '.join(sys.argv if argv is None else ['vacmapx'] + list(argv)), rg)
-        if native_bam:
-            from .bamout import BamWriter, SortedBamWriter
-            if native_sort:                                                   # sorted runs now, merge + index in out.close()
-                if args.workdir:
-                    os.makedirs(args.workdir, exist_ok=True)
-                out, proc = SortedBamWriter(args.o, head, device=device, workdir=args.workdir), None
-            else:
-                out, proc = BamWriter(args.o, head, device=device), None      # the header goes in as the BAM header
+    return range_mode
+
+
+class Output:
+    """What -o names on this rank, behind one interface: stdout, a text file, a rank's part file, a samtools pipe, a BamWriter or a
+    SortedBamWriter (`native`: it takes a window as parts, bamout.BamWriter.write_parts). `sink` stays None on a rank that writes nothing."""
+
+    def __init__(self, stdout=False, native=False):
+        self.sink, self.proc, self.stdout, self.native, self.closed = None, None, stdout, native, False
+
+    def write(self, data):
+        self.sink.write(data)
+
+    def write_parts(self, blobs, offs, order_keys):
+        self.sink.write_parts(blobs, offs, order_keys)
+
+    def flush(self):
+        self.sink.flush()
+
+    def fd(self):
+        """the descriptor the batches' texts can be written to directly, or None"""
+        try:
+            return self.sink.fileno()
+        except Exception:
+            return None
+
+    def finish(self):
+        """the end of a run that succeeded: the output is closed (stdout: flushed); returns samtools' exit code after a pipe, else None"""
+        if self.sink is None or self.closed:
+            return None
+        if self.stdout:
+            self.sink.flush()
         else:
-            out, proc = (open(part_path, 'w+b'), None) if range_mode else _open_output(args.o)
-            for ln in head:
-                out.write(ln.encode() + b'\n')
-    if args.mode == 'asm':
-        rc = _run_asm(args, lib, ctx, index, prm, rg, mark, out, proc, world, rank, text_group, t_start, device=device)
-        ctx.close()
-        if own_group:                                   # no rank leaves while rank 0 still gathers and writes
-            comm.barrier(); comm.destroy_process_group()
-        return rc
-    # Ramped start (VMX_DRIVER_RAMP=1; off by default): the stream starts on ONE context as soon as its pools are sized, the others are sized in the background and
-    # join one by one (Pipeline.run_stream, ramp). Measured on the 1.64 M-read input: the first batch starts 1.6 s after the loop begins instead of 5.9 s, but
-    # hipMalloc under load is slower than on an idle device and slows the running batches down — the seventh context joins after ~1 M reads, and the loop
-    # takes the same 12.8 s (`profiles/r05_zz_driver_long_ramped_start.json`). Default: every context is sized before the first batch runs.
-    ramp_on = os.environ.get('VMX_DRIVER_RAMP', '0') == '1' and os.environ.get('VMX_NO_WARM') != '1'
-    pipe = pipeline.Pipeline(index, prm, device=device, inflight=1 if ramp_on else (args.inflight or 5), first_ctx=ctx)
-    if os.environ.get('VMX_SPIN_SYNC') != '1':
-        for cx in pipe.ctxs:
-            cx.set_blocking_sync(True)                    # the emitters need the cores the waiting aligner threads would spin on
-    # host threads (-t in all): `inflight` of them feed the GPU (gather a batch's reads, vm_align_batch) and mostly wait for it; the SAM
-    # text of finished batches is produced by a pool of emit_jobs concurrent vm_sam_emit calls of emit_threads threads each, so that the
-    # GPU never waits for text and the text never waits for the GPU
-    emit_total = int(os.environ.get('VMX_EMIT_THREADS', '0')) or args.t
-    emit_jobs = max(1, min(4, emit_total // 4))
-    emit_threads = max(1, emit_total // emit_jobs)
-    counts = {'reads': 0, 'lines': 0, 'skipped': 0}
-    win_reads = max(1, args.batch_reads * args.window_batches)
+            self.sink.close()
+        self.closed = True                               # (a close that raised leaves the rest to abort())
+        return self.proc.wait() if self.proc is not None else None
+
+    def abort(self):
+        """the end of a run that failed: nothing more is written, the file is closed as it is, samtools is waited for, a native writer gives
+        up its device memory and its run files"""
+        if self.sink is None or self.closed:
+            return
+        self.closed = True
+        with contextlib.suppress(Exception):
+            if self.native:
+                self.sink._abort()
+            elif not self.stdout:
+                self.sink.close()
+        if self.proc is not None:
+            self.proc.wait()
+
+    def note(self):
+        """the tail of the final stderr line after --bam-writer native-sort: the index file and what the merge in close() cost"""
+        s = self.sink
+        if not hasattr(s, 'merge_seconds'):
+            return ''
+        return '; sorted by coordinate, index %s.csi (merge of %d runs, %.1f MB of records: %.2f s)' % (s.path, len(s.runs), s.run_bytes / 1e6, s.merge_seconds)
+
+
+def _text_sink(path):
+    """'-' / .sam: text; .bam / .sorted.bam: a `samtools view -b` / `samtools sort --write-index` pipe (output_functions.py:200-208)"""
+    if path == '-':
+        return sys.stdout.buffer, None
+    if path.endswith('.sam'):
+        return open(path, 'w+b'), None
+    if not shutil.which('samtools'):
+        sys.exit('writing %s needs the samtools binary on PATH (the reference pipes SAM text into it too); write .sam instead' % path)
+    cmd = ['samtools', 'sort', '-@', '8', '--write-index', '-o', path, '-'] if path.endswith('sorted.bam') else ['samtools', 'view', '-b', '-@', '8', '-o', path, '-']
+    proc = subprocess.Popen(cmd, stdin=subprocess.PIPE, bufsize=1 << 20)
+    return proc.stdin, proc
+
+
+@contextlib.contextmanager
+def _open_output(args, net, range_mode, index, rg, argv, device):
+    """stage 6: the Output of this rank with the header in it (rank 0 writes it; in range mode into its part). A run that fails from here on
+    aborts the output on its way out; a run that succeeds ends it in _finish."""
+    out = Output(stdout=args.o == '-', native=args.native_bam)
+    try:
+        if range_mode:
+            out.sink = open('%s.part%03d' % (args.o, net.rank), 'w+b')
+        if net.rank == 0:
+            head = sam.header_lines(list(zip(index.names, index.lens)), ' '.join(sys.argv if argv is None else ['vacmapx'] + list(argv)), rg)
+            if args.native_bam:                                 # the header goes in as the BAM header
+                from .bamout import BamWriter, SortedBamWriter
+                if args.native_sort and args.workdir:           # sorted runs now, merge + index in close()
+                    os.makedirs(args.workdir, exist_ok=True)
+                out.sink = SortedBamWriter(args.o, head, device=device, workdir=args.workdir) if args.native_sort else BamWriter(args.o, head, device=device)
+            else:
+                if not range_mode:
+                    out.sink, out.proc = _text_sink(args.o)
+                for ln in head:
+                    out.write(ln.encode() + b'\n')
+        yield out
+    except BaseException:
+        out.abort()
+        raise
+
+
+def _finish(out, rank, report):
+    """stage 8: the output is closed, samtools waited for, and rank 0 writes the final stderr lines: report(tail) gives their text"""
+    rc = out.finish()
+    if rank != 0:
+        return
+    if rc:
+        sys.stderr.write('Error: samtools exited with code %d\n' % rc)
+    sys.stderr.write(report(out.note()))
+
+
+def _blob(parts):
     import numpy as np
-    from concurrent.futures import ThreadPoolExecutor
+    off = np.zeros(len(parts) + 1, np.int64)
+    np.cumsum([len(x) for x in parts], out=off[1:])
+    return np.frombuffer(b''.join(parts) or b'\0', np.uint8), off
 
-    parse_threads = args.parse_threads or int(os.environ.get('VMX_PARSE_THREADS', '0')) or max(1, min(4, args.t // 4))
 
-    def chunks_of(path):
-        """blob chunks of one input in file order. A plain FASTA / FASTQ file is cut into record-aligned slices (vm_fastx_open_range): in range
-        mode the rank takes its own byte range of the file, and `parse_threads` threads parse slices ahead of the consumer (one thread
-        parses ~3 GB/s: a third of what one GPU aligns)"""
-        if path.endswith('.bam'):
-            yield from (_native_bam_chunks(path, win_reads, lib, device) if args.bam_reader == 'native' else _bam_chunks(path, win_reads))
-            return
-        if not _is_plain_fastx(path):
-            rd = Fastx(path, lib=lib)
-            yield from iter(lambda: rd.read(win_reads), None)
-            return
-        size = os.path.getsize(path)
-        lo, hi = (size * rank // world, size * (rank + 1) // world) if range_mode else (0, size)
-        target = max(1 << 20, int(float(os.environ.get('VMX_SLICE_MB', '1024')) * (1 << 20)))
-        ns = max(1, -(-(hi - lo) // target))
-        cuts = [lo + (hi - lo) * i // ns for i in range(ns + 1)]
+def _run_asm(args, net, lib, ctx, index, prm, opts, out, device, t_start):
+    """-mode asm (src/vacmap/vacmap:245-255, :394-411; worker mammap_asm.py:23462-23511): every input sequence is an assembly contig. --eqx is
+    forced and maxdivergence set to 1 by vm_params_default(VM_MODE_ASM); contigs are aligned in groups (the long ones of a group side by side on
+    the GPU) and their SAM lines written in input order. A contig the reference would skip (raised) is logged and skipped.
+    With N ranks every rank parses the input, contig c of it goes to rank c mod N (contigs are independent: no data-path collective), and
+    rank 0 gathers each group's lines and writes them in input order. Returns the final stderr line as _finish takes it."""
+    from .lib import align_batch_raw, sam_emit
+    world, rank = net.world, net.rank
+    if not args.workdir:
+        sys.exit('workdir not provided! -workdir /path/to/workdir')                      # vacmap:247-249
+    os.makedirs(args.workdir, exist_ok=True)
+    # the fork hard-codes these, whatever -c / -maxdivergence say: check_num = -1 (mammap_asm.py:23206), maxdivergence = 1.0 (:23483), --eqx
+    prm.eqx = 1; prm.check_num = -1; prm.maxdivergence = 1.0
+    seen = set(); n_contigs = n_lines = n_skipped = 0
 
-        def parse(a, b):
-            rd = Fastx(path, lib=lib, byte_range=(a, b))
-            try:
-                return list(iter(lambda: rd.read(win_reads), None))
-            finally:
-                rd.close()
-        with ThreadPoolExecutor(max_workers=parse_threads) as pool:
-            futs, nxt = [], 0
-            while nxt < ns or futs:
-                while nxt < ns and len(futs) < parse_threads + 1:
-                    futs.append(pool.submit(parse, cuts[nxt], cuts[nxt + 1])); nxt += 1
-                yield from futs.pop(0).result()
+    def flush(group):
+        """group: (input index, name, sequence, quality, comment — bytes) of consecutive input contigs, the same list on every rank"""
+        nonlocal n_lines, n_skipped
+        share = [g for g in group if g[0] % world == rank]
+        done = {}                                                                           # input index -> text of its lines, None = skipped
+        if share:
+            nb, no = _blob([g[1] for g in share]); sb, so = _blob([g[2] for g in share])
+            qb, qo = _blob([g[3] for g in share]); cb, co = _blob([g[4] for g in share])
+            raw = align_batch_raw(ctx, index, prm, sb, so)
+            # the asm emitter (iterator_get_bam_dict_str, mammap_asm.py:22757) in the native emitter: vm_sam_opts.asm_mode
+            text, toff, _, ns = sam_emit(lib, index, opts, nb, no, sb, so, raw, quals=qb, qual_off=qo, comments=cb if args.copycomments else None,
+                                         com_off=co if args.copycomments else None, nthreads=max(1, args.t))
+            for x, g in enumerate(share):
+                if raw.status[x] != 0:                                                      # the worker's except (:23493-23498)
+                    sys.stderr.write('%s is not aligned.\n' % g[1].decode()); done[g[0]] = None
+                else:
+                    done[g[0]] = text[int(toff[x]):int(toff[x + 1])].tobytes()
+            raw.close()
+        if world > 1:
+            from .dist import gather_lines
+            parts = gather_lines(done, dst=0, group=net.text_group)
+            if rank != 0:
+                return
+            done = {}
+            for d in parts:
+                done.update(d)
+        text = [done[gi] for gi in sorted(done) if done[gi] is not None]
+        n_skipped += len(done) - len(text)
+        n_lines += sum(t.count(b'\n') for t in text)
+        if args.native_bam and text:                                                        # --bam-writer native: the group's lines in one BAM call
+            text = [b''.join(text)]
+        for t in text:
+            out.write(t)
 
-    def windows():
-        """input records in arrival order as blobs (names, upper-cased sequences, qualities, comments), de-duplicated by name
-        (vacmap:457,475,487; in range mode inside the rank's own part of the input), one window of at most win_reads reads at a time"""
-        seen = set()
-        file_no = -1
-        for group in args.read:
-            for path in group:
-                file_no += 1
-                for ch in chunks_of(path):
-                    n = len(ch['seqs_off']) - 1
-                    nb, no = ch['names'].tobytes(), ch['names_off']
-                    keep = []
-                    for i in range(n):
-                        nm = nb[no[i]:no[i + 1]]
-                        if nm in seen:
-                            continue
-                        seen.add(nm); keep.append(i)
-                    if len(keep) < n:
-                        ix = np.asarray(keep, dtype=np.int64)
-                        for key in ('names', 'seqs', 'quals', 'comments'):
-                            ch[key], ch[key + '_off'] = blob_gather(lib, ch[key], ch[key + '_off'], ix)
-                    if range_mode and len(ch['names_off']) > 1:
-                        rank_hashes.append(name_hashes(ch['names'], ch['names_off']))      # compared across the ranks at the end of the run
-                        rank_hash_file.append(np.full(len(ch['names_off']) - 1, file_no, np.int32))  # ... in INPUT order: (file, byte range = rank)
-                    if args.Q:
-                        ch['quals_off'] = np.zeros(len(ch['seqs_off']), np.int64)
-                    if not args.copycomments:
-                        ch['comments_off'] = np.zeros(len(ch['seqs_off']), np.int64)
-                    if len(ch['seqs_off']) > 1:
-                        yield ch
+    group, gbases = [], 0
+    for path in (p for grp in args.read for p in grp):
+        # (.bam input like every other mode: vacmap:452-470)
+        with contextlib.closing(_input_chunks(path, 64, lib, device, args.bam_reader)) as chunks:
+            for ch in _first_of_each_name(chunks, seen, lib):
+                nb, no, sb, so = ch['names'].tobytes(), ch['names_off'], ch['seqs'].tobytes(), ch['seqs_off']
+                qb, qo, cb, co = ch['quals'].tobytes(), ch['quals_off'], ch['comments'].tobytes(), ch['comments_off']
+                for i in range(len(so) - 1):
+                    keep = n_contigs % world == rank                                       # the other ranks' contigs only hold their place
+                    group.append((n_contigs, nb[no[i]:no[i + 1]], sb[so[i]:so[i + 1]] if keep else b'', (b'' if args.Q or not keep else qb[qo[i]:qo[i + 1]]),
+                                  cb[co[i]:co[i + 1]] if keep else b''))
+                    n_contigs += 1
+                    gbases += so[i + 1] - so[i]
+                    if len(group) >= 64 * world or gbases >= 400_000_000 * world:
+                        flush(group); group, gbases = [], 0
+    if group:
+        flush(group)
+    return lambda tail: 'vacmapx: %d contigs, %d SAM lines, %d contigs skipped, %.1f s%s\n' % (n_contigs, n_lines, n_skipped, max(time.time() - t_start, 0.001), tail)
 
-    rank_hashes = []
-    rank_hash_file = []
-    prog = {'t0': time.time(), 't': time.time(), 'n': 0, 'next': 100000}
 
-    def progress(count):
+class Window:
+    """a window of input (blobs) with the rank's plan of it; futs[i]: the SAM text of batch i, on its way through the emit pool"""
+
+    def __init__(self, wnd, plan):
+        self.wnd, self.plan = wnd, plan
+        self.has_q = bool(wnd['quals_off'][-1]); self.has_c = bool(wnd['comments_off'][-1])
+        self.futs = [None] * len(plan)
+        self.left = len(plan)
+        self.ready = threading.Event()              # every batch of the window has been aligned and handed to the emit pool
+        if not plan:
+            self.ready.set()
+
+
+class Batch:
+    """what an aligner thread is handed: batch i of window w, and what a feeder prepared of it — (read blob, offsets, the upload slot that
+    holds them in HBM) — or None when the aligner gathers and uploads the reads itself"""
+
+    def __init__(self, w, i, fed=None):
+        self.w, self.i, self.fed = w, i, fed
+
+
+class ReadStream:
+    """Stage 7 for the read modes. A reader thread parses windows of --window-batches x --batch-reads reads (wq), the aligner threads of
+    pipeline.Pipeline.run_stream take the batches of each window in schedule order (job_source; through the feeders, which gather and upload
+    ahead of them), hand the records to the emit pool, and the writer thread writes every window's lines in input order (oq). The first
+    error of any thread (errs) ends all of them. run() starts and joins the threads; leaving the `with` block releases the pinned pool and the
+    pipeline's contexts."""
+
+    def __init__(self, args, sw, net, lib, ctx, index, prm, opts, out, range_mode, device, t_start):
+        from . import lib as V, pipeline
+        self.V = V                                          # (the module, imported late: see the note at the imports)
+        self.args, self.sw, self.net, self.lib, self.index, self.prm, self.opts, self.out = args, sw, net, lib, index, prm, opts, out
+        self.range_mode, self.device, self.rank, self.world = range_mode, device, net.rank, net.world
+        self.ramp_on = sw['VMX_DRIVER_RAMP'] and not sw['VMX_NO_WARM']
+        # host threads (-t in all): `inflight` of them feed the GPU (gather a batch's reads, vm_align_batch) and mostly wait for it; the SAM
+        # text of finished batches is produced by a pool of emit_jobs concurrent vm_sam_emit calls of emit_threads threads each, so that the
+        # GPU never waits for text and the text never waits for the GPU
+        emit_total = sw['VMX_EMIT_THREADS'] or args.t
+        self.emit_jobs = max(1, min(4, emit_total // 4))
+        self.emit_threads = max(1, emit_total // self.emit_jobs)
+        self.emit_pool = None
+        self.counts = {'reads': 0, 'lines': 0, 'skipped': 0}
+        self.rank_hashes, self.rank_hash_file = [], []      # range mode: the names this rank has seen, compared across the ranks at the end
+        self.errs = []
+        self.n_slots = max(2, sw['VMX_DRIVER_WINDOWS'])      # (1.6 M-read run, profiles/r05_driver_long_*: 3 windows of 8 batches 145 k reads/s, 6 x 8: 180 k, 4 x 16: 195 k, 10 x 4: 205 k)
+        self.slots = threading.Semaphore(self.n_slots)      # windows in memory at a time (input blobs + SAM text)
+        self.wq = queue.Queue(maxsize=2)                    # reader -> job source
+        self.oq = queue.Queue()                             # windows in input order -> writer
+        self.pending = []                                   # windows taken from the reader ahead of the workers (the sizing run)
+        self.sizing = None                                  # the sizing batch (blob, offsets): also sizes the feeders' upload slots
+        self.feed_free, self.feed_ready, self.feed_lock = queue.Queue(), queue.Queue(), threading.Lock()
+        self.feed_ctxs, self.feed_slots, self.feed_threads = [], [], []
+        self.out_fd = out.fd() if (self.rank == 0 or range_mode) and sw['VMX_DRIVER_WRITEV'] else None
+        self.pinned = self.pipe = None
+        try:
+            self.pipe = pipeline.Pipeline(index, prm, device=device, inflight=1 if self.ramp_on else (args.inflight or 5), first_ctx=ctx)
+            self.blocking_sync(self.pipe.ctxs)
+            # the batch's reads are gathered into page-locked memory: vm_align_batch's upload becomes a DMA the aligner thread does not wait for
+            if sw['VMX_DRIVER_PINNED']:
+                self.pinned = V.PinnedPool(lib, device)
+        except BaseException:
+            self.close()
+            raise
+        # Feeders: threads with a context of their own take the next batch of the schedule, gather its reads into page-locked memory and stream
+        # them into HBM (vm_reads_reupload into a few reusable slots) AHEAD of the aligning contexts, which then run vm_align_resident — the
+        # aligner thread's context no longer idles through the gather, and the copy of batch i + 1 runs under the kernels of batch i
+        self.n_feed = sw['VMX_DRIVER_FEEDERS'] if self.pinned is not None else 0
+        now = time.time()
+        self.t0 = self.t_prog = now; self.n_prog = 0; self.next_prog = 100000
+        self.tm = {'setup': now - t_start, 'wait_input': 0.0, 'assemble_write': 0.0, 'job_gather': 0.0, 'job_align': 0.0, 'job_emit': 0.0}
+        self.tml = threading.Lock()
+
+    def close(self):
+        if self.pinned is not None:
+            self.pinned.close(); self.pinned = None
+        if self.pipe is not None:
+            self.pipe.close(drop_first=True); self.pipe = None       # (the first context is the caller's)
+
+    def blocking_sync(self, ctxs):
+        if not self.sw['VMX_SPIN_SYNC']:
+            for cx in ctxs:
+                cx.set_blocking_sync(True)                # the emitters need the cores the waiting aligner threads would spin on
+
+    def add_time(self, key, dt):
+        with self.tml:
+            self.tm[key] += dt
+
+    def progress(self, count):
         """the reference's progress line, every 100 000 sequences (vacmap:498-514)"""
-        if rank != 0 or count < prog['next']:
+        if self.rank != 0 or count < self.next_prog:
             return
         now = time.time()
-        dt, tt = max(now - prog['t'], 0.001), max(now - prog['t0'], 0.001)
+        dt, tt = max(now - self.t_prog, 0.001), max(now - self.t0, 0.001)
         sys.stderr.write('%d / sec in the last %d minutes, %d / sec AVG. %d sequences processed.\n'
-                         % (round((count - prog['n']) / dt), max(round(dt / 60), 1), round(count / tt), count))
-        prog['t'], prog['n'] = now, count
-        prog['next'] = (count // 100000 + 1) * 100000
+                         % (round((count - self.n_prog) / dt), max(round(dt / 60), 1), round(count / tt), count))
+        self.t_prog, self.n_prog = now, count
+        self.next_prog = (count // 100000 + 1) * 100000
 
-    tm = {'setup': time.time() - t_start, 'wait_input': 0.0, 'assemble_write': 0.0, 'job_gather': 0.0, 'job_align': 0.0, 'job_emit': 0.0}
-    tml = threading.Lock()
-    errs = []
-    n_slots = max(2, int(os.environ.get('VMX_DRIVER_WINDOWS', '10')))      # (1.6 M-read run, profiles/r05_driver_long_*: 3 windows of 8 batches 145 k reads/s, 6 x 8: 180 k, 4 x 16: 195 k, 10 x 4: 205 k)
-    slots = threading.Semaphore(n_slots)                # windows in memory at a time (input blobs + SAM text)
-    oq = queue.Queue()                                  # windows in input order -> writer
-    emit_pool = ThreadPoolExecutor(max_workers=emit_jobs)
+    def windows(self):
+        """input records in arrival order as blobs (names, upper-cased sequences, qualities, comments), de-duplicated by name
+        (vacmap:457,475,487; in range mode inside the rank's own part of the input), one window of at most win_reads reads at a time. A plain
+        file is parsed in slices by `parse_threads` threads ahead of the consumer (one thread parses ~3 GB/s: a third of what one GPU aligns)."""
+        import numpy as np
+        args, sw, seen = self.args, self.sw, set()
+        parse_threads = args.parse_threads or sw['VMX_PARSE_THREADS'] or max(1, min(4, args.t // 4))
+        win_reads = max(1, args.batch_reads * args.window_batches)
+        share = (self.rank, self.world) if self.range_mode else (0, 1)
+        slice_bytes = max(1 << 20, int(sw['VMX_SLICE_MB'] * (1 << 20)))
+        for file_no, path in enumerate(p for grp in args.read for p in grp):
+            with contextlib.closing(_input_chunks(path, win_reads, self.lib, self.device, args.bam_reader, parse_threads, share, slice_bytes)) as chunks:
+                for ch in _first_of_each_name(chunks, seen, self.lib):
+                    n = len(ch['seqs_off']) - 1
+                    if self.range_mode and n:
+                        self.rank_hashes.append(name_hashes(ch['names'], ch['names_off']))
+                        self.rank_hash_file.append(np.full(n, file_no, np.int32))          # ... in INPUT order: (file, byte range = rank)
+                    if args.Q:
+                        ch['quals_off'] = np.zeros(n + 1, np.int64)
+                    if not args.copycomments:
+                        ch['comments_off'] = np.zeros(n + 1, np.int64)
+                    if n:
+                        yield ch
 
-    class Window:
-        def __init__(self, wnd, plan):
-            self.wnd, self.plan = wnd, plan
-            self.has_q = bool(wnd['quals_off'][-1]); self.has_c = bool(wnd['comments_off'][-1])
-            self.futs = [None] * len(plan)
-            self.left = len(plan)
-            self.ready = threading.Event()              # every batch of the window has been aligned and handed to the emit pool
-            if not plan:
-                self.ready.set()
+    def to_workers(self, item):
+        """a window (None: the end, an exception: the reader's failure) into wq; False when the run failed meanwhile"""
+        while not self.errs:
+            try:
+                self.wq.put(item, timeout=0.2)
+                return True
+            except queue.Full:
+                pass
+        return False
 
-    pending = []                                        # windows taken from the reader ahead of the workers (the warm-up below)
+    def reader(self):
+        """input parsing runs ahead of the aligners (the FASTX reader releases the GIL)"""
+        try:
+            with contextlib.closing(self.windows()) as wins:
+                for wnd in wins:
+                    if not self.to_workers(wnd):
+                        return
+            self.to_workers(None)
+        except BaseException as e:
+            self.to_workers(e)
 
-    def job_source():
-        """(window, batch index) in schedule order; a window is planned when the first worker reaches it"""
+    def from_reader(self):
+        """the next item of wq; None (the end) once the run has failed and the reader may have given up"""
+        while True:
+            try:
+                return self.wq.get(timeout=0.2)
+            except queue.Empty:
+                if self.errs:
+                    return None
+
+    def size_run(self, cx):
+        self.V.align_batch_raw(cx, self.index, self.prm, self.sizing[0], self.sizing[1]).close()
+
+    def plan(self, wnd):
+        """the rank's batches of a window: lists of read indices in schedule order"""
+        import numpy as np
+        from . import pipeline
+        plan = pipeline.plan_batches(np.diff(wnd['seqs_off']), self.args.batch_reads, self.args.window_batches)
+        if not self.range_mode:
+            plan = [plan[i] for i in range(self.rank, len(plan), self.world)]       # static sharding: batch i -> rank i mod N (range mode: the rank's own reads)
+        return plan
+
+    def size_contexts(self):
+        """Size every context's grow-only work pools ONCE, before the stream starts: each context aligns the longest batch of the first window
+        (its result is dropped). Without this a context meets its first long-read batch windows later, outgrows the pools its earlier,
+        shorter batches sized, and pays for ~50 GB of re-allocation next to two other contexts' pools — seconds with the GPU idle
+        (rocprofv3 trace of a 131 k-read run: no kernel resident 73 % of the time, 2 s batches; `profiles/r03_l_*`).
+        Then contexts are given up or added by what the HBM holds. Returns Pipeline.run_stream's `ramp` (VMX_DRIVER_RAMP=1), else None."""
+        import numpy as np
+        pipe, args, size = self.pipe, self.args, self.size_run
+        if not self.sw['VMX_NO_WARM']:
+            first = self.from_reader()
+            self.tm['first_window'] = time.time() - self.t_loop
+            self.pending.append(first)
+            plan0 = self.plan(first) if first is not None and not isinstance(first, BaseException) else None
+            if plan0:
+                ix0 = max(plan0, key=lambda ix: int(np.diff(first['seqs_off'])[ix].sum()))
+                self.sizing = self.V.blob_gather(self.lib, first['seqs'], first['seqs_off'], ix0)
+                # (one context after the other: hipMalloc serialises anyway, and a context that finds no memory left for its pools — a first window of
+                # very long reads — is given up with the ones after it instead of failing the run: Pipeline.warm)
+                try:
+                    n_oom = pipe.warm(run=size, keep=2)
+                    if n_oom and self.rank == 0:
+                        sys.stderr.write('vacmapx: %d of %d batches in flight given up: no HBM left for their work pools\n' % (n_oom, n_oom + pipe.inflight))
+                except BaseException as e:
+                    self.errs.append(e)
+            dropped = pipe.trim_to_memory(self.sw['VMX_MIN_FREE_GB'])
+            if dropped and self.rank == 0:
+                sys.stderr.write('vacmapx: %d of %d batches in flight given up to keep HBM head-room\n' % (dropped, dropped + pipe.inflight))
+            if args.inflight == 0 and not self.ramp_on and not dropped and self.sizing is not None and not self.errs:
+                # the scheduler's rule (bench.py runs the same): more batches in flight while another context's pools + head-room fit the HBM
+                try:
+                    if pipe.grow_to_memory(run=size, max_inflight=8):
+                        self.blocking_sync(pipe.ctxs)
+                except BaseException as e:
+                    self.errs.append(e)
+            self.tm['warm'] = time.time() - self.t_loop
+        if self.ramp_on and self.sizing is not None and not self.errs:
+            return dict(run=size, target=args.inflight, max_inflight=8, on_ctx=None if self.sw['VMX_SPIN_SYNC'] else (lambda cx: cx.set_blocking_sync(True)))
+        return None
+
+    def job_source(self):
+        """the batches in schedule order; a window is planned when the first worker reaches it"""
+        errs, oq = self.errs, self.oq
         while not errs:
-            while not slots.acquire(timeout=0.2):       # (never parked for good: a failure elsewhere must end the run, not hang it)
+            while not self.slots.acquire(timeout=0.2):       # (never parked for good: a failure elsewhere must end the run, not hang it)
                 if errs:
                     oq.put(None)
                     return
             t0 = time.time()
-            wnd = pending.pop(0) if pending else wq.get()
-            with tml:
-                tm['wait_input'] += time.time() - t0
+            wnd = self.pending.pop(0) if self.pending else self.from_reader()
+            self.add_time('wait_input', time.time() - t0)
             if isinstance(wnd, BaseException):
                 errs.append(wnd); wnd = None
             if wnd is None:
-                slots.release()
+                self.slots.release()
                 break
-            counts['reads'] += len(wnd['seqs_off']) - 1
-            progress(counts['reads'])
-            plan = pipeline.plan_batches(np.diff(wnd['seqs_off']), args.batch_reads, args.window_batches)
-            if not range_mode:
-                plan = [plan[i] for i in range(rank, len(plan), world)]        # static sharding: batch i -> rank i mod N (range mode: the rank's own reads)
-            w = Window(wnd, plan)
+            self.counts['reads'] += len(wnd['seqs_off']) - 1
+            self.progress(self.counts['reads'])
+            w = Window(wnd, self.plan(wnd))
             oq.put(w)
-            for i in range(len(plan)):
-                yield w, i
+            for i in range(len(w.plan)):
+                yield Batch(w, i)
         oq.put(None)
 
-    # the batch's reads are gathered into page-locked memory: vm_align_batch's upload becomes a DMA the aligner thread does not wait for
-    # (VMX_DRIVER_PINNED=0: pageable numpy arrays, the runtime stages the copy on the calling thread)
-    pinned = PinnedPool(lib, device) if os.environ.get('VMX_DRIVER_PINNED', '1') != '0' else None
+    def start_feeders(self):
+        src = self.job_source()
+        for _ in range(self.n_feed):
+            fcx = self.V.Context(self.device, lib=self.lib)
+            self.feed_ctxs.append(fcx)
+            self.blocking_sync([fcx])
+        n_up = (max(self.args.inflight or 8, self.pipe.inflight) if self.ramp_on else self.pipe.inflight) + self.n_feed + 1
+        for _ in range(n_up):
+            sl = self.V.ResidentReads(self.feed_ctxs[0], concat=self.sizing[0], offsets=self.sizing[1])
+            self.feed_slots.append(sl); self.feed_free.put(sl)
+        self.feed_threads = [threading.Thread(target=self.feeder, args=(fcx, src)) for fcx in self.feed_ctxs]
+        for t in self.feed_threads:
+            t.start()
 
-    def emit(w, i, ix, sb, so, raw):
-        t0 = time.time()
+    def stop_feeders(self):
+        for _ in self.feed_threads if self.errs else ():
+            self.feed_free.put(None)                      # (wakes a feeder that waits for a slot)
+        for t in self.feed_threads:
+            t.join()
+        for sl in self.feed_slots:
+            sl.close()
+        for fcx in self.feed_ctxs:
+            fcx.close()
+        self.feed_threads, self.feed_slots, self.feed_ctxs = [], [], []
+
+    def feeder(self, fcx, src):
         try:
-            if os.environ.get('VMX_SKIP_EMIT') == '1':          # diagnostic: aligners alone
-                raw.close()
-                return ix, np.zeros(0, np.uint8), np.zeros(len(ix) + 1, np.int64), 0, 0
-            wnd = w.wnd
-            nb, no = blob_gather(lib, wnd['names'], wnd['names_off'], ix)
-            qb, qo = blob_gather(lib, wnd['quals'], wnd['quals_off'], ix) if w.has_q else (None, None)
-            cb, co = blob_gather(lib, wnd['comments'], wnd['comments_off'], ix) if w.has_c else (None, None)
-            text, toff, nl, ns = sam_emit(lib, index, opts, nb, no, sb, so, raw, quals=qb, qual_off=qo, comments=cb, com_off=co, nthreads=emit_threads)
-            if args.debug and ns:                       # the reference's per-read failure log (--debug, mammap_clrnano.py:24120-24123)
-                nbb = nb.tobytes() if hasattr(nb, 'tobytes') else bytes(nb)
-                for x in np.nonzero(np.asarray(raw.status) != 0)[0]:
-                    sys.stderr.write('vacmapx --debug: read %s skipped, status %d\n' % (nbb[int(no[x]):int(no[x + 1])].decode(errors='replace'), int(raw.status[x])))
-            raw.close()
-            with tml:
-                tm['job_emit'] += time.time() - t0
-            return ix, text, toff, nl, ns
-        finally:
-            if pinned is not None:
-                pinned.release(sb)
-
-    # Feeders (VMX_DRIVER_FEEDERS, default 2; 0 = the round-4 form: gather and upload on the aligner thread, inside vm_align_batch): threads with a context of
-    # their own take the next batch of the schedule, gather its reads into page-locked memory and stream them into HBM (vm_reads_reupload into a few reusable
-    # slots) AHEAD of the aligning contexts, which then run vm_align_resident — the aligner thread's context no longer idles through the gather, and the copy of
-    # batch i + 1 runs under the kernels of batch i (bench.py's host-input pass: Pipeline.run_host_blobs(prefetch=True))
-    n_feed = int(os.environ.get('VMX_DRIVER_FEEDERS', '2')) if pinned is not None else 0
-    feed = {'free': queue.Queue(), 'ready': queue.Queue(), 'ctxs': [], 'slots': [], 'lock': threading.Lock()}
-
-    def feeder(fcx, src):
-        try:
-            while not errs:
-                with feed['lock']:
+            while not self.errs:
+                with self.feed_lock:
                     job = next(src, None)
                 if job is None:
                     break
-                w, i = job
-                ix = w.plan[i]
                 t0 = time.time()
-                sb, so = blob_gather(lib, w.wnd['seqs'], w.wnd['seqs_off'], ix, alloc=pinned.get)
-                sl = feed['free'].get()
+                sb, so = self.V.blob_gather(self.lib, job.w.wnd['seqs'], job.w.wnd['seqs_off'], job.w.plan[job.i], alloc=self.pinned.get)
+                sl = self.feed_free.get()
                 while sl is None:                        # (a None is only queued to wake a feeder up on an error)
-                    if errs:
+                    if self.errs:
                         return
-                    sl = feed['free'].get()
+                    sl = self.feed_free.get()
                 sl.reupload(sb, so, ctx=fcx)
-                with tml:
-                    tm['job_gather'] += time.time() - t0
-                feed['ready'].put((w, i, ix, sb, so, sl))
+                self.add_time('job_gather', time.time() - t0)
+                job.fed = (sb, so, sl)
+                self.feed_ready.put(job)
         except BaseException as e:
-            errs.append(e)
+            self.errs.append(e)
         finally:
-            feed['ready'].put(None)
+            self.feed_ready.put(None)
 
-    def fed_jobs(n_feeders):
+    def fed_jobs(self):
         """what the feeders prepared, in completion order, until all of them are done"""
         done = 0
-        while done < n_feeders:
-            item = feed['ready'].get()
-            if item is None:
+        while done < self.n_feed:
+            job = self.feed_ready.get()
+            if job is None:
                 done += 1
                 continue
-            yield item
+            yield job
 
-    def align(job, cx):
+    def align(self, job, cx):
         """one batch: gather its reads from the window, align (GPU), hand the records to the emit pool; the library calls release the GIL"""
-        if len(job) == 6:                                # prepared by a feeder: reads already in HBM
-            w, i, ix, sb, so, sl = job
+        w, i = job.w, job.i
+        ix = w.plan[i]
+        if job.fed is not None:                          # reads already in HBM
+            sb, so, sl = job.fed
             t0 = t1 = time.time()
-            raw = sl.align_raw(index, prm, ctx=cx)
-            feed['free'].put(sl)
+            raw = sl.align_raw(self.index, self.prm, ctx=cx)
+            self.feed_free.put(sl)
         else:
-            w, i = job
-            ix = w.plan[i]
             t0 = time.time()
-            sb, so = blob_gather(lib, w.wnd['seqs'], w.wnd['seqs_off'], ix, alloc=pinned.get if pinned is not None else None)
+            sb, so = self.V.blob_gather(self.lib, w.wnd['seqs'], w.wnd['seqs_off'], ix, alloc=self.pinned.get if self.pinned is not None else None)
             t1 = time.time()
-            raw = align_batch_raw(cx, index, prm, sb, so)
+            raw = self.V.align_batch_raw(cx, self.index, self.prm, sb, so)
         t2 = time.time()
-        w.futs[i] = emit_pool.submit(emit, w, i, ix, sb, so, raw)
-        with tml:
+        w.futs[i] = self.emit_pool.submit(self.emit, w, ix, sb, so, raw)
+        with self.tml:
+            tm = self.tm
             tm['job_gather'] += t1 - t0; tm['job_align'] += t2 - t1; tm['device_s'] = tm.get('device_s', 0.0) + raw.stats['ms_total'] * 1e-3
-            if os.environ.get('VMX_DRIVER_TIMING') == '2':
-                sys.stderr.write('batch t=%.3f reads %d bases %d align %.3f device %.3f\n' % (t1 - t_loop, len(ix), int(so[-1]), t2 - t1, raw.stats['ms_total'] * 1e-3))
+            if self.sw['VMX_DRIVER_TIMING'] == '2':
+                sys.stderr.write('batch t=%.3f reads %d bases %d align %.3f device %.3f\n' % (t1 - self.t_loop, len(ix), int(so[-1]), t2 - t1, raw.stats['ms_total'] * 1e-3))
             w.left -= 1
             if w.left == 0:
                 w.ready.set()
 
-    out_fd = None
-    if (rank == 0 or range_mode) and os.environ.get('VMX_DRIVER_WRITEV', '1') != '0':
+    def emit(self, w, ix, sb, so, raw):
+        """the SAM text of one batch (emit pool): (read indices, text, line offsets, lines, reads skipped)"""
+        import numpy as np
+        t0 = time.time()
         try:
-            out_fd = out.fileno()
-        except Exception:
-            out_fd = None
+            if self.sw['VMX_SKIP_EMIT']:                 # diagnostic: aligners alone
+                raw.close()
+                return ix, np.zeros(0, np.uint8), np.zeros(len(ix) + 1, np.int64), 0, 0
+            wnd, gather = w.wnd, self.V.blob_gather
+            nb, no = gather(self.lib, wnd['names'], wnd['names_off'], ix)
+            qb, qo = gather(self.lib, wnd['quals'], wnd['quals_off'], ix) if w.has_q else (None, None)
+            cb, co = gather(self.lib, wnd['comments'], wnd['comments_off'], ix) if w.has_c else (None, None)
+            text, toff, nl, ns = self.V.sam_emit(self.lib, self.index, self.opts, nb, no, sb, so, raw, quals=qb, qual_off=qo, comments=cb, com_off=co, nthreads=self.emit_threads)
+            if self.args.debug and ns:                  # the reference's per-read failure log (--debug, mammap_clrnano.py:24120-24123)
+                nbb = nb.tobytes() if hasattr(nb, 'tobytes') else bytes(nb)
+                for x in np.nonzero(np.asarray(raw.status) != 0)[0]:
+                    sys.stderr.write('vacmapx --debug: read %s skipped, status %d\n' % (nbb[int(no[x]):int(no[x + 1])].decode(errors='replace'), int(raw.status[x])))
+            raw.close()
+            self.add_time('job_emit', time.time() - t0)
+            return ix, text, toff, nl, ns
+        finally:
+            if self.pinned is not None:
+                self.pinned.release(sb)
 
-    mmap_out = os.environ.get('VMX_DRIVER_MMAP_OUT', '0') == '1'      # (measured on the 1.6 M-read run: 7.4 s of writev against 24.6 s through the mapping — page faults of a fresh file do not scale; off)
-    write_threads = max(1, int(os.environ.get('VMX_WRITE_THREADS', '0')) or min(6, max(2, args.t // 3)))
-
-    def writer():
+    def writer(self):
         """a window's lines in input order (one more gather over the concatenated batch texts) while later windows align and emit"""
         t_cpu0 = time.thread_time()
         try:
             while True:
-                w = oq.get()
+                w = self.oq.get()
                 if w is None:
                     return
                 while not w.ready.wait(0.2):
-                    if errs:
+                    if self.errs:
                         return
                 done = [f.result() for f in w.futs]
-                nl, ns = sum(r[3] for r in done), sum(r[4] for r in done)
-                parts = [(ix, text, toff) for ix, text, toff, _, _ in done]
                 t0 = time.time()
-                if world > 1 and not range_mode:
-                    from .dist import gather_lines
-                    allp = gather_lines((parts, nl, ns), dst=0, group=text_group)
-                    if rank == 0:
-                        parts = [p for rp in allp for p in rp[0]]; nl = sum(rp[1] for rp in allp); ns = sum(rp[2] for rp in allp)
-                    else:
-                        parts = []
-                counts['lines'] += nl; counts['skipped'] += ns
-                if parts:
-                    if native_bam:                       # BAM records and BGZF members on the GPU, straight from the batches' texts
-                        out.write_parts([p[1] for p in parts], [p[2] for p in parts], [p[0] for p in parts])
-                    elif out_fd is not None:           # straight from the batches' texts to the file, no assembled copy of the window: into the file's own pages
-                        out.flush()                  # by a few threads when it is a regular file (mmap), else one writev stream
-                        pos = None
-                        if mmap_out:
-                            try:
-                                pos = os.lseek(out_fd, 0, os.SEEK_CUR)
-                            except OSError:
-                                pos = None
-                        blob_write_parts(lib, out_fd, [p[1] for p in parts], [p[2] for p in parts], [p[0] for p in parts], file_off=pos, nthreads=write_threads)
-                    else:
-                        txt = blob_gather_parts(lib, [p[1] for p in parts], [p[2] for p in parts], [p[0] for p in parts])
-                        out.write(memoryview(txt))
+                self.write_window([r[1] for r in done], [r[2] for r in done], [r[0] for r in done], sum(r[3] for r in done), sum(r[4] for r in done))
                 w.wnd = None; w.futs = None
-                slots.release()
-                with tml:
-                    tm['assemble_write'] += time.time() - t0
+                self.slots.release()
+                self.add_time('assemble_write', time.time() - t0)
         except BaseException as e:
-            errs.append(e)
+            self.errs.append(e)
         finally:
-            with tml:
-                tm['writer_cpu'] = time.thread_time() - t_cpu0
-            for _ in range(n_slots):                    # whatever ended the writer, nobody stays parked on a window slot
-                slots.release()
+            with self.tml:
+                self.tm['writer_cpu'] = time.thread_time() - t_cpu0
+            for _ in range(self.n_slots):                # whatever ended the writer, nobody stays parked on a window slot
+                self.slots.release()
 
-    wq = queue.Queue(maxsize=2)
+    def write_window(self, texts, toffs, keys, nl, ns):
+        """the batches' texts of one window (texts[b], toffs[b]: the lines of the reads keys[b]) to the output, in the order of the keys; with
+        N ranks in the batch scheme rank 0 gathers the other ranks' batches first"""
+        if self.world > 1 and not self.range_mode:
+            from .dist import gather_lines
+            allp = gather_lines((texts, toffs, keys, nl, ns), dst=0, group=self.net.text_group)
+            if self.rank == 0:
+                texts, toffs, keys = ([x for rp in allp for x in rp[j]] for j in range(3))
+                nl = sum(rp[3] for rp in allp); ns = sum(rp[4] for rp in allp)
+            else:
+                texts = []
+        self.counts['lines'] += nl; self.counts['skipped'] += ns
+        if not texts:
+            return
+        if self.args.native_bam:                         # BAM records and BGZF members on the GPU, straight from the batches' texts
+            self.out.write_parts(texts, toffs, keys)
+        elif self.out_fd is not None:                    # straight from the batches' texts to the descriptor, no assembled copy of the window
+            self.out.flush()
+            self.V.blob_write_parts(self.lib, self.out_fd, texts, toffs, keys)
+        else:
+            self.out.write(memoryview(self.V.blob_gather_parts(self.lib, texts, toffs, keys)))
 
-    def reader():
-        """input parsing runs ahead of the aligners (the FASTX reader releases the GIL)"""
+    def run(self):
+        """the stream from the first window to the last line; raises the first error of any thread once every thread has ended"""
+        errs, tm = self.errs, self.tm
+        self.emit_pool = concurrent.futures.ThreadPoolExecutor(max_workers=self.emit_jobs)
+        rt, wt = threading.Thread(target=self.reader, daemon=True), threading.Thread(target=self.writer)
+        rt.start(); wt.start()
+        self.t_loop = time.time()
         try:
-            for wnd in windows():
-                wq.put(wnd)
-            wq.put(None)
+            ramp = self.size_contexts()
+            if self.n_feed > 0 and self.sizing is not None:
+                self.start_feeders()
+                self.pipe.run_stream(self.fed_jobs(), self.align, errs, ramp=ramp)
+            else:
+                self.pipe.run_stream(self.job_source(), self.align, errs, ramp=ramp)
+            tm['aligners_done'] = time.time() - self.t_loop; tm['contexts'] = float(self.pipe.inflight)
         except BaseException as e:
-            wq.put(e)
-
-    threading.Thread(target=reader, daemon=True).start()
-    wt = threading.Thread(target=writer)
-    wt.start()
-    t_loop = time.time()
-    # Size every context's grow-only work pools ONCE, before the stream starts: each context aligns the longest batch of the first window
-    # (its result is dropped). Without this a context meets its first long-read batch windows later, outgrows the pools its earlier,
-    # shorter batches sized, and pays for ~50 GB of re-allocation next to two other contexts' pools — seconds with the GPU idle
-    # (rocprofv3 trace of a 131 k-read run: no kernel resident 73 % of the time, 2 s batches; `profiles/r03_l_*`).
-    sb0_keep = None                                     # the sizing batch: also sizes the feeders' upload slots
-    if os.environ.get('VMX_NO_WARM') != '1':
-        first = wq.get()
-        tm['first_window'] = time.time() - t_loop
-        pending.append(first)
-        if first is not None and not isinstance(first, BaseException):
-            plan0 = pipeline.plan_batches(np.diff(first['seqs_off']), args.batch_reads, args.window_batches)
-            if not range_mode:
-                plan0 = [plan0[i] for i in range(rank, len(plan0), world)]
-            if plan0:
-                ix0 = max(plan0, key=lambda ix: int(np.diff(first['seqs_off'])[ix].sum()))
-                sb0, so0 = blob_gather(lib, first['seqs'], first['seqs_off'], ix0)
-                sb0_keep = (sb0, so0)
-
-                # (one context after the other: hipMalloc serialises anyway, and a context that finds no memory left for its pools — a first window of
-                # very long reads — is given up with the ones after it instead of failing the run: Pipeline.warm)
-                try:
-                    n_oom = pipe.warm(run=lambda cx: align_batch_raw(cx, index, prm, sb0, so0).close(), keep=2)
-                    if n_oom and rank == 0:
-                        sys.stderr.write('vacmapx: %d of %d batches in flight given up: no HBM left for their work pools\n' % (n_oom, n_oom + pipe.inflight))
-                except BaseException as e:
-                    errs.append(e)
-        dropped = pipe.trim_to_memory(float(os.environ.get('VMX_MIN_FREE_GB', '10')))
-        if dropped and rank == 0:
-            sys.stderr.write('vacmapx: %d of %d batches in flight given up to keep HBM head-room\n' % (dropped, dropped + pipe.inflight))
-        if args.inflight == 0 and not ramp_on and not dropped and sb0_keep is not None and not errs:
-            # the scheduler's rule (bench.py runs the same): more batches in flight while another context's pools + head-room fit the HBM
-            try:
-                added = pipe.grow_to_memory(run=lambda cx: align_batch_raw(cx, index, prm, sb0_keep[0], sb0_keep[1]).close(), max_inflight=8)
-                if added and os.environ.get('VMX_SPIN_SYNC') != '1':
-                    for cx in pipe.ctxs:
-                        cx.set_blocking_sync(True)
-            except BaseException as e:
+            if not any(e is x for x in errs):            # (run_stream raises the first of errs itself)
                 errs.append(e)
-        tm['warm'] = time.time() - t_loop
-    fth = []
-    ramp = None
-    if ramp_on and sb0_keep is not None and not errs:
-        spin = os.environ.get('VMX_SPIN_SYNC') == '1'
-        ramp = dict(run=lambda cx: align_batch_raw(cx, index, prm, sb0_keep[0], sb0_keep[1]).close(), target=args.inflight, max_inflight=8,
-                    on_ctx=None if spin else (lambda cx: cx.set_blocking_sync(True)))
-    try:
-        if n_feed > 0 and sb0_keep is not None:
-            from .lib import Context as _Ctx, ResidentReads as _RR
-            src = job_source()
-            for f in range(n_feed):
-                fcx = _Ctx(device, lib=lib)
-                if os.environ.get('VMX_SPIN_SYNC') != '1':
-                    fcx.set_blocking_sync(True)
-                feed['ctxs'].append(fcx)
-            for _ in range((max(args.inflight or 8, pipe.inflight) if ramp_on else pipe.inflight) + n_feed + 1):
-                sl = _RR(feed['ctxs'][0], concat=sb0_keep[0], offsets=sb0_keep[1]); feed['slots'].append(sl); feed['free'].put(sl)
-            fth = [threading.Thread(target=feeder, args=(fcx, src)) for fcx in feed['ctxs']]
-            for t_ in fth:
-                t_.start()
-            pipe.run_stream(fed_jobs(n_feed), align, errs, ramp=ramp)
-        else:
-            pipe.run_stream(job_source(), align, errs, ramp=ramp)
-        tm['aligners_done'] = time.time() - t_loop; tm['contexts'] = float(pipe.inflight)
-    finally:
+        finally:
+            if errs:
+                self.oq.put(None)
+            self.stop_feeders()
+            wt.join()
+            self.emit_pool.shutdown(wait=True)
+            rt.join()                                    # (after a failure it has seen errs and let go of its input: to_workers)
         if errs:
-            oq.put(None)
-            for _ in fth:
-                feed['free'].put(None)
-        for t_ in fth:
-            t_.join()
-        for sl in feed['slots']:
-            sl.close()
-        for fcx in feed['ctxs']:
-            fcx.close()
-        wt.join()
-        emit_pool.shutdown(wait=True)
-    if errs:
-        raise errs[0]
-    tm['loop'] = time.time() - t_loop
-    last_timing.clear(); last_timing.update(tm); last_timing['reads'] = counts['reads']
-    if os.environ.get('VMX_DRIVER_TIMING'):
-        sys.stderr.write('vacmapx timing (s): %s\n' % ' '.join('%s=%.2f' % kv for kv in tm.items()))
-    pipe.close()
-    if pinned is not None:
-        pinned.close()
-    if range_mode:
-        # every rank wrote its own part; the counts travel to rank 0 (three integers), which joins the parts in rank order (the reference's output order
-        # is not the input's either: mammap_clrnano.py:24147-24150)
-        out.close()
+            raise errs[0]
+        tm['loop'] = time.time() - self.t_loop
+        last_timing.clear(); last_timing.update(tm); last_timing['reads'] = self.counts['reads']
+        if self.sw['VMX_DRIVER_TIMING']:
+            sys.stderr.write('vacmapx timing (s): %s\n' % ' '.join('%s=%.2f' % kv for kv in tm.items()))
+
+    def collect_parts(self):
+        """Range mode, after the stream: every rank wrote its own part; the counts travel to rank 0, which joins the parts in rank order (the
+        reference's output order is not the input's either: mammap_clrnano.py:24147-24150).
+        The reference drops a read name it has seen before, anywhere in the input (vacmap:457-487); a rank only sees its own byte ranges, so the
+        ranks' name hashes (8 bytes per read) travel with the counts and rank 0 leaves the later occurrences out while it joins the parts.
+        "Earlier" is the INPUT's order, not the rank's — every hash travels with the number of the input file it came from; inside a file the
+        ranks' byte ranges ascend with the rank. With two files, a name in file 1 inside rank 3's range and again in file 2 inside rank 0's
+        keeps the file-1 record (sorted by hash, then file, then rank: every occurrence but the first goes), as the reference's single pass over
+        the files does. No cross-rank duplicate — the rule — costs one sort."""
+        import numpy as np
         from .dist import gather_lines
-        # The reference drops a read name it has seen before, anywhere in the input (vacmap:457-487); a rank only sees its own byte ranges, so the
-        # ranks' name hashes (8 bytes per read) travel with the counts and rank 0 leaves the later occurrences out while it joins the parts:
-        # a name that also occurs in a lower rank's ranges (of any input file) goes. No cross-rank duplicate — the rule — costs one sort.
-        # Round 6 (ADVICE r5): "earlier" is the INPUT's order, not the rank's — every hash travels with the number of the input file it came from; inside a file
-        # the ranks' byte ranges ascend with the rank. With two files, a name in file 1 inside rank 3's range and again in file 2 inside rank 0's keeps the
-        # file-1 record (sorted by hash, then file, then rank: every occurrence but the first goes), as the reference's single pass over the files does.
-        myh = np.concatenate(rank_hashes) if rank_hashes else np.zeros(0, np.uint64)
-        myf = np.concatenate(rank_hash_file) if rank_hash_file else np.zeros(0, np.int32)
-        allc = gather_lines((counts['reads'], counts['lines'], counts['skipped'], myh, myf), dst=0, group=text_group)
-        if rank == 0:
-            counts['reads'], counts['lines'], counts['skipped'] = (sum(c[i] for c in allc) for i in range(3))
-            drop = cross_rank_duplicates([c[3] for c in allc], [c[4] for c in allc])
-            n_dup = sum(len(v) for v in drop.values())
-            if drop and args.parts:
-                sys.stderr.write('vacmapx: %d read names occur in more than one rank\'s part (--parts keeps the parts as written: later occurrences are NOT removed)\n' % n_dup)
-            if not args.parts:
-                tj = time.time()
-                gr, gl = _concat_parts(args.o, ['%s.part%03d' % (args.o, r) for r in range(world)], drop)
-                counts['reads'] -= gr; counts['lines'] -= gl
-                if gr:
-                    sys.stderr.write('vacmapx: %d reads whose name occurred earlier in the input (another rank\'s range) were left out, %d SAM lines\n' % (gr, gl))
-                last_timing['concat_parts'] = time.time() - tj
-    if rank == 0:
-        if proc is not None:
-            out.close()
-            rc = proc.wait()
-            if rc != 0:
-                sys.stderr.write('Error: samtools exited with code %d\n' % rc)
-        elif range_mode:
-            pass
-        elif args.o != '-':
-            out.close()
-        else:
-            out.flush()
-        tt = max(time.time() - prog['t0'], 0.001)     # vacmap:535-541
-        sys.stderr.write('User time (h:m:s): %d:%d:%d %d / sec AVG. %d sequences processed.\n' % (tt // 3600, (tt % 3600) // 60, tt % 60, round(counts['reads'] / tt), counts['reads']))
-        sys.stderr.write('vacmapx: %d reads, %d SAM lines, %d reads skipped%s\n' % (counts['reads'], counts['lines'], counts['skipped'], _index_note(out)))
-    if own_group:
-        comm.barrier(); comm.destroy_process_group()
+        args, counts = self.args, self.counts
+        self.out.finish()
+        myh = np.concatenate(self.rank_hashes) if self.rank_hashes else np.zeros(0, np.uint64)
+        myf = np.concatenate(self.rank_hash_file) if self.rank_hash_file else np.zeros(0, np.int32)
+        allc = gather_lines((counts['reads'], counts['lines'], counts['skipped'], myh, myf), dst=0, group=self.net.text_group)
+        if self.rank != 0:
+            return
+        counts['reads'], counts['lines'], counts['skipped'] = (sum(c[i] for c in allc) for i in range(3))
+        drop = cross_rank_duplicates([c[3] for c in allc], [c[4] for c in allc])
+        if drop and args.parts:
+            sys.stderr.write('vacmapx: %d read names occur in more than one rank\'s part (--parts keeps the parts as written: later occurrences are NOT removed)\n' % sum(len(v) for v in drop.values()))
+        if not args.parts:
+            tj = time.time()
+            gr, gl = _concat_parts(args.o, ['%s.part%03d' % (args.o, r) for r in range(self.world)], drop)
+            counts['reads'] -= gr; counts['lines'] -= gl
+            if gr:
+                sys.stderr.write('vacmapx: %d reads whose name occurred earlier in the input (another rank\'s range) were left out, %d SAM lines\n' % (gr, gl))
+            last_timing['concat_parts'] = time.time() - tj
+
+    def report(self, tail):
+        """the final stderr lines (vacmap:535-541)"""
+        tt, c = max(time.time() - self.t0, 0.001), self.counts
+        return ('User time (h:m:s): %d:%d:%d %d / sec AVG. %d sequences processed.\n' % (tt // 3600, (tt % 3600) // 60, tt % 60, round(c['reads'] / tt), c['reads'])
+                + 'vacmapx: %d reads, %d SAM lines, %d reads skipped%s\n' % (c['reads'], c['lines'], c['skipped'], tail))
+
+
+def main(argv=None, comm=None):
+    """comm: an initialised torch.distributed module (tests); under torchrun (WORLD_SIZE > 1) the process group is created here.
+    The stages in order; a stage that opens something is a context manager and releases it however the run ends."""
+    t_start = time.time()
+    sw = _switches()
+    args = _parse_args(argv, comm, sw)
+    with _process_groups(comm, sw) as net:
+        if net.rank == 0 and args.o != '-' and os.path.exists(args.o) and not args.force:
+            sys.exit('%s exists (use --force)' % args.o)
+        if comm is None and net.world == 1 and __name__ == '__main__':
+            os.environ.setdefault('VACMAPX_SKIP_TORCH', '1')        # one GPU from the command line: nothing here needs torch (its import is 1.5-2 s)
+        from .lib import load
+        lib = load()
+        device = args.device if args.device is not None else net.local_rank
+        with _context_and_index(args, net, device) as (ctx, index):
+            prm, rg, opts = _alignment_options(args, lib)
+            range_mode = _sharding(args, net)
+            with _open_output(args, net, range_mode, index, rg, argv, device) as out:
+                if args.mode == 'asm':
+                    report = _run_asm(args, net, lib, ctx, index, prm, opts, out, device, t_start)
+                else:
+                    with contextlib.closing(ReadStream(args, sw, net, lib, ctx, index, prm, opts, out, range_mode, device, t_start)) as stream:
+                        stream.run()
+                    if range_mode:
+                        stream.collect_parts()
+                    report = stream.report
+                _finish(out, net.rank, report)
     return 0
 
 

@@ -578,10 +578,11 @@ class PinnedPool:
                 self.free.append(ent)
 
     def close(self):
+        """frees every buffer, those still handed out too: nothing may use one after this"""
         with self.lock:
-            for cap, ptr in self.free:
+            for cap, ptr in self.free + list(self.owned.values()):
                 self.lib.L.vm_pinned_free(ptr)
-            self.free = []
+            self.free, self.owned = [], {}
 
 
 def blob_gather(lib, blob, off, idx, alloc=None):

@@ -115,14 +115,15 @@ class Pipeline:
         for cx in self.ctxs:
             cx.set_inflight(self.inflight)
 
-    def close(self):
+    def close(self, drop_first=False):
+        """closes every context but the first, which came from the caller; drop_first: the caller closes that one next, so it is let go of too"""
         if getattr(self, '_up', None) is not None:
             for sl in self._up[1]:
                 sl.close()
             self._up[0].close(); self._up = None
         for cx in self.ctxs[1:]:
             cx.close()
-        self.ctxs = self.ctxs[:1]
+        self.ctxs = [] if drop_first else self.ctxs[:1]
 
     def trim_to_memory(self, min_free_gb=10.0, keep=2):
         """after the sizing run of every context (warm): the grow-only pools scale with the longest batch, and four contexts' pools of a long-read
