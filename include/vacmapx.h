@@ -197,8 +197,10 @@ int vm_k_cigar_batch(vm_ctx*, const vm_score*, int eqx, int64_t n, const char* t
  * layout and queue order: longest-first device queue, banded eight-per-wavefront fill first (anti-diagonal form on a fixed band of 32 * ns
  * diagonals, traceback slots as wide as each problem's own band needs), the problems whose band is not PROVEN optimal filled again in full
  * by a second launch, per-problem layout flag for the traceback. CIGARs must equal vm_k_cigar_batch's. band_flag[n]: 16 + ns = the band's
- * result was proven and kept, 0 = full matrix. stats[4] = {small problems tried in a band, proven, sent to the second launch (not proven,
- * or small but never tried), problems outside the small class}. No scores (that form never captures them). */
+ * result was proven and kept, 1 = a larger problem of the second launch in the packed whole-wave layout, 0 = full matrix. stats[6] = {small
+ * problems tried in a band, proven, sent to the second launch (not proven, or small but never tried), problems outside the small class,
+ * second-launch problems kept from a wave-wide band, second-launch problems of that class filled in full}. No scores (that form never
+ * captures them). */
 int vm_k_cigar_batch_banded(vm_ctx*, const vm_score*, int eqx, int64_t n, const char* t, const int64_t* t_off, const char* q,
                             const int64_t* q_off, char** cigars, int64_t** cigar_off, int32_t** band_flag, int64_t* stats);
 /* `mp.k_cigar(..., 4,4,4,4, bw=100, zdropvalue=50)` (:2381): banded x-drop extension from (0,0) (spec VMX-DP-X); out t_e[n], q_e[n],
@@ -257,6 +259,8 @@ typedef struct vm_batch_stats {     /* measured on the device, for bench.py's ro
     int64_t n_local_general;        /* reads the guide-banded local seeding kernel handed to the general one (k_local_seed) */
     int64_t n_ext_retries;          /* times the batch was run again because a pool of the extend stage was too small (pools x4 per retry) */
     int64_t n_batch_retries;        /* times the whole batch was run again because an assumption made instead of a host wait did not hold (a pool sized from the context's history) */
+    int64_t n_dp_redo_wide;         /* of n_dp_redo: larger problems (whole-wave class) whose result the second launch kept from a wave-wide band */
+    int64_t n_dp_redo_full;         /* of n_dp_redo: larger problems the second launch filled in full (wide band not proven, no band holds both corners, or scores out of range) */
 } vm_batch_stats;
 
 /* Align n reads (replaces get_readmap_DP_test per read). seqs concatenated, offsets[n+1].

@@ -443,28 +443,66 @@ __device__ __forceinline__ void vmx_gapfill_fill_one(const uint8_t* __restrict__
 
 // order/counter: longest-first device work queue (order == nullptr: plain grid-stride over [0, n_prob))
 // SCORE = false: the batched path only consumes the traceback, so the small-problem form skips the score capture; out_score[p] then carries
-// the layout flag the traceback kernel reads (0: striped). redo_pass: the queue is the list the first launch of the batched path left
-// behind (redo_cnt[0] = entries, redo_cnt[1] = this launch's queue head).
-template <bool SCORE>
+// the layout flag the traceback kernel reads (0: striped). REDO (k_gapfill_redo, the second launch of the batched path): the queue is the list the
+// first launch left behind (redo_cnt[0] = entries, redo_cnt[1] = this launch's queue head, redo_cnt[2] = the head loop's, redo_cnt[6] / [7] = larger
+// problems kept from a wave-wide band / filled in full after all).
+template <bool SCORE, bool REDO = false>
 __device__ __forceinline__ void vmx_gapfill_fill_body(const uint8_t* __restrict__ tcodes, const uint8_t* __restrict__ qcodes,
                                                      const vmx_dp_prob* __restrict__ probs, int n_prob, int match, int mismatch,
                                                      int o1, int e1, int o2, int e2, uint8_t* __restrict__ tb_pool,
                                                      int32_t* __restrict__ bnd_pool, int32_t* __restrict__ out_score,
                                                      const int32_t* __restrict__ order, int32_t* __restrict__ counter,
-                                                     int32_t* __restrict__ redo_list = nullptr, int32_t* __restrict__ redo_cnt = nullptr, int redo_pass = 0,
+                                                     int32_t* __restrict__ redo_list = nullptr, int32_t* __restrict__ redo_cnt = nullptr,
                                                      uint8_t* __restrict__ redo_pool = nullptr) {
     const int lane = vmx_lane();
     int static_next = 4 * (int)blockIdx.x;
-    if (redo_pass) {
+    const bool redo_pass = REDO;
+    if constexpr (REDO) {
         n_prob = redo_cnt[0]; order = redo_list; counter = redo_cnt + 1;
-        // the larger problems of the list first, one per task on the whole wave in the packed two-rows-per-lane layout (flag VMX_PK_FLAG): on a
-        // single 16-lane row a 500 x 500 matrix is a millisecond-long serial chain that the rest of the launch would wait for
+        // The larger problems of the list first (VMX_REDO_PK; on a single 16-lane row a 500 x 500 matrix is a millisecond-long serial chain that the rest
+        // of the launch would wait for), TWO per task: X and Y share the wave in the wave-wide anti-diagonal band (vmx_gapfill_fill_ad with LW = 64:
+        // 128 ns diagonals, ns = 2 .. 4 by the rule of vmx_ad_ns over that geometry with the launch's own constants VMX_ADW_PCT / _MIN, the pair's larger
+        // ns for both), whose bytes go into the packed two-rows-per-lane layout the problem owns. One whose result the proof keeps (vmx_ad_proven) is done;
+        // one that is not proven, whose corners no band holds, or whose scoring is outside the tagged range runs in full right here (vmx_gapfill_fill16,
+        // which writes every byte of the same space). Either way the layout flag is VMX_PK_FLAG.
+        const bool ad_ok = vmx_ad_scores_ok(match, mismatch, o1, e1, o2, e2);
         while (true) {
-            int q; { int v = 0; if (lane == 0) v = atomicAdd(redo_cnt + 2, 1); q = vmx_bcast0(v); }
+            // two entries of the list at a time: a pair of the class shares the wave, a single one runs with Y idle
+            int q; { int v = 0; if (lane == 0) v = atomicAdd(redo_cnt + 2, 2); q = vmx_bcast0(v); }
             if (q >= n_prob) break;
-            const int p = order[q];
-            const int tl = probs[p].tl, ql = probs[p].ql;
-            if (VMX_REDO_PK(tl, ql)) vmx_gapfill_fill_one<SCORE>(tcodes, qcodes, probs, p, match, mismatch, o1, e1, o2, e2, tb_pool, bnd_pool, out_score, lane, VMX_PK_FLAG, redo_pool);
+            int pX = vmx_uniform_i32(order[q]), pY = q + 1 < n_prob ? vmx_uniform_i32(order[q + 1]) : -1;
+            if (pY >= 0 && !VMX_REDO_PK(probs[pY].tl, probs[pY].ql)) pY = -1;
+            if (!VMX_REDO_PK(probs[pX].tl, probs[pX].ql)) { pX = pY; pY = -1; }
+            if (pX < 0) continue;
+            vmx_dp_prob prX = probs[pX], prY = prX;
+            if (pY >= 0) prY = probs[pY];
+            const int tlX0 = vmx_uniform_i32(prX.tl), qlX0 = vmx_uniform_i32(prX.ql), tlY0 = pY >= 0 ? vmx_uniform_i32(prY.tl) : 0, qlY0 = pY >= 0 ? vmx_uniform_i32(prY.ql) : 0;
+            const int nsX = ad_ok ? vmx_ad_ns_nd(tlX0, qlX0, match, o1, e1, o2, e2, VMX_ADW_PCT, VMX_ADW_PCT_MIN, VMX_ADW_DPN, VMX_ADW_NS_MIN, VMX_AD_NS_MAX) : 0;
+            const int nsY = ad_ok ? vmx_ad_ns_nd(tlY0, qlY0, match, o1, e1, o2, e2, VMX_ADW_PCT, VMX_ADW_PCT_MIN, VMX_ADW_DPN, VMX_ADW_NS_MIN, VMX_AD_NS_MAX) : 0;
+            const int ns = nsX > nsY ? nsX : nsY;
+            bool keepX = false, keepY = false;
+            if (ns > 0) {
+                int dloX = 0, dloY = 0;
+                const int gX = nsX > 0 ? vmx_ad_geom_nd(tlX0, qlX0, VMX_ADW_DPN * ns, &dloX) : 0, gY = nsY > 0 ? vmx_ad_geom_nd(tlY0, qlY0, VMX_ADW_DPN * ns, &dloY) : 0;
+                const int tlX = gX > 0 ? tlX0 : 0, qlX = gX > 0 ? qlX0 : 0, tlY = gY > 0 ? tlY0 : 0, qlY = gY > 0 ? qlY0 : 0;
+                int scX = 0, scY = 0;
+#define VMX_ADW_RUN(NSV) vmx_gapfill_fill_ad<NSV, 64>(tcodes + prX.t_off, qcodes + prX.q_off, tlX, qlX, dloX, vmx_tb_ptr(tb_pool, redo_pool, prX.tb_off), tcodes + prY.t_off, qcodes + prY.q_off, \
+                                                      tlY, qlY, dloY, vmx_tb_ptr(tb_pool, redo_pool, prY.tb_off), match, mismatch, o1, e1, o2, e2, lane, scX, scY)
+                if (ns == 2) VMX_ADW_RUN(2); else if (ns == 3) VMX_ADW_RUN(3); else VMX_ADW_RUN(4);
+#undef VMX_ADW_RUN
+                keepX = gX > 0 && vmx_ad_proven(scX, tlX0, qlX0, gX, match, o1, e1, o2, e2);
+                keepY = gY > 0 && vmx_ad_proven(scY, tlY0, qlY0, gY, match, o1, e1, o2, e2);
+            }
+            if (lane == 0) {
+                if (keepX) out_score[pX] = VMX_PK_FLAG;
+                if (keepY) out_score[pY] = VMX_PK_FLAG;
+                const int kept = (int)keepX + (int)keepY, full = 1 + (int)(pY >= 0) - kept;
+                if (kept) atomicAdd(redo_cnt + 6, kept);
+                if (full) atomicAdd(redo_cnt + 7, full);
+            }
+            if (!keepX || (pY >= 0 && !keepY)) __syncthreads();        // the band's stores land before the full fill writes the same bytes
+            if (!keepX) vmx_gapfill_fill_one<SCORE>(tcodes, qcodes, probs, pX, match, mismatch, o1, e1, o2, e2, tb_pool, bnd_pool, out_score, lane, VMX_PK_FLAG, redo_pool);
+            if (pY >= 0 && !keepY) vmx_gapfill_fill_one<SCORE>(tcodes, qcodes, probs, pY, match, mismatch, o1, e1, o2, e2, tb_pool, bnd_pool, out_score, lane, VMX_PK_FLAG, redo_pool);
         }
     }
     while (true) {
@@ -497,8 +535,9 @@ __device__ __forceinline__ void vmx_gapfill_fill_body(const uint8_t* __restrict_
 
 // first launch of the batched path: EIGHT problems at a time. Those of the small class whose shape a band can hold (vmx_ad_ns) run together
 // in the anti-diagonal form (vmx_dp_ad.h), all with the widest band any of the eight asks for; a problem whose result is proven keeps it
-// (layout flag VMX_AD_FLAG + ns), the others — not proven, or small but not worth a band — are appended to redo_list for the second launch
-// (vmx_gapfill_fill_body with redo_pass = 1: full matrix, four per wave). Larger problems run one after the other on the whole wave.
+// (layout flag VMX_AD_FLAG + ns), the others — not proven, or small but not worth a band of 128 diagonals — are appended to redo_list for the second
+// launch (k_gapfill_redo: the larger ones get a wave-wide band of 256 .. 512 diagonals before anything is filled in full, the others are filled in full
+// four per wave). Problems outside the small class run one after the other on the whole wave.
 __device__ __forceinline__ void vmx_gapfill_ad_pass(const uint8_t* __restrict__ tcodes, const uint8_t* __restrict__ qcodes, vmx_dp_prob* __restrict__ probs, int n_prob,
                                                    int match, int mismatch, int o1, int e1, int o2, int e2, uint8_t* __restrict__ tb_pool, int32_t* __restrict__ bnd_pool,
                                                    int32_t* __restrict__ out_score, const int32_t* __restrict__ order, const int32_t* __restrict__ range, int32_t* __restrict__ counter,
@@ -595,12 +634,18 @@ __global__ void __launch_bounds__(64, 4) k_gapfill_fill_ns(const uint8_t* __rest
                                                         int o1, int e1, int o2, int e2, uint8_t* __restrict__ tb_pool,
                                                         int32_t* __restrict__ bnd_pool, int32_t* __restrict__ out_score,
                                                         const int32_t* __restrict__ order, const int32_t* __restrict__ range, int32_t* __restrict__ counter,
-                                                        int32_t* __restrict__ redo_list, int32_t* __restrict__ redo_cnt, int redo_pass, int ad_pct,
-                                                        uint8_t* __restrict__ redo_pool, unsigned long long* __restrict__ redo_bytes, const int32_t* __restrict__ n_ptr,
+                                                        int32_t* __restrict__ redo_list, int32_t* __restrict__ redo_cnt, int ad_pct,
+                                                        unsigned long long* __restrict__ redo_bytes, const int32_t* __restrict__ n_ptr,
                                                         unsigned long long redo_cap, int tb_by_ns) {
     if (n_ptr) n_prob = *n_ptr;                        // the count on the device (an unplanned pass: the host launched for an upper bound)
-    if (redo_pass) vmx_gapfill_fill_body<false>(tcodes, qcodes, probs, n_prob, match, mismatch, o1, e1, o2, e2, tb_pool, bnd_pool, out_score, order, counter, redo_list, redo_cnt, 1, redo_pool);
-    else vmx_gapfill_ad_pass(tcodes, qcodes, probs, n_prob, match, mismatch, o1, e1, o2, e2, tb_pool, bnd_pool, out_score, order, range, counter, redo_list, redo_cnt, ad_pct, redo_bytes, redo_cap, tb_by_ns);
+    vmx_gapfill_ad_pass(tcodes, qcodes, probs, n_prob, match, mismatch, o1, e1, o2, e2, tb_pool, bnd_pool, out_score, order, range, counter, redo_list, redo_cnt, ad_pct, redo_bytes, redo_cap, tb_by_ns);
+}
+// second launch of the batched path: the problems of redo_list in full (vmx_gapfill_fill_body with REDO), the larger ones two per wave in the wave-wide band first
+__global__ void __launch_bounds__(64) k_gapfill_redo(const uint8_t* __restrict__ tcodes, const uint8_t* __restrict__ qcodes, const vmx_dp_prob* __restrict__ probs,
+                                                     int match, int mismatch, int o1, int e1, int o2, int e2, uint8_t* __restrict__ tb_pool,
+                                                     int32_t* __restrict__ bnd_pool, int32_t* __restrict__ out_score, int32_t* __restrict__ redo_list,
+                                                     int32_t* __restrict__ redo_cnt, uint8_t* __restrict__ redo_pool) {
+    vmx_gapfill_fill_body<false, true>(tcodes, qcodes, probs, 0, match, mismatch, o1, e1, o2, e2, tb_pool, bnd_pool, out_score, nullptr, nullptr, redo_list, redo_cnt, redo_pool);
 }
 
 // serial traceback, one THREAD per problem (thousands of independent dependent-load chains hide each other's latency)

@@ -198,14 +198,14 @@ void vmx_gapfill_chunk(vm_ctx* c, vmx_batch_bufs& B, const vm_score& sc, int ad_
         vmx_lowprio lp(c);                                    // the long launch at the lowest dispatch priority (vmx_host.h)
         hipLaunchKernelGGL(k_gapfill_fill_ns, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(pn, (int64_t)c->num_cu * fill_waves))), dim3(64), 0, lp.stream(), B.tpool.as<uint8_t>(), B.qpool.as<uint8_t>(),
                            probs, (int)pn, sc.match, sc.mismatch, sc.o1, sc.e1, sc.o2, sc.e2, tb_base, B.bnd.as<int32_t>(), score, B.order.as<int32_t>(), d_range, d_cnt,
-                           redo_list, d_redo_cnt, 0, ad_pct, (uint8_t*)nullptr, d_redo_bytes, n_ptr, (unsigned long long)redo_cap, 1);
+                           redo_list, d_redo_cnt, ad_pct, d_redo_bytes, n_ptr, (unsigned long long)redo_cap, 1);
         lp.join();
     }
-    // second launch: the problems whose band was not proven (a few per cent), in full: the larger ones on a whole wave, the others four per wave (its queue is the list the
-    // first launch left; any grid works)
-    hipLaunchKernelGGL(k_gapfill_fill_ns, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(pn, (int64_t)c->num_cu * 4))), dim3(64), 0, c->stream, B.tpool.as<uint8_t>(), B.qpool.as<uint8_t>(),
-                       probs, (int)pn, sc.match, sc.mismatch, sc.o1, sc.e1, sc.o2, sc.e2, tb_base, B.bnd.as<int32_t>(), score, B.order.as<int32_t>(), d_range, d_cnt,
-                       redo_list, d_redo_cnt, 1, ad_pct, B.tbredo.as<uint8_t>(), d_redo_bytes, n_ptr, (unsigned long long)redo_cap, 1);
+    // second launch (k_gapfill_redo): the problems whose band was not proven or that were never tried in one (a few per cent). The larger ones go two per wave through a
+    // wave-wide band of 256 .. 512 diagonals and are filled in full, one per wave, only where that is not proven either; the others in full, four per wave. Its queue is the
+    // list the first launch left; any grid works. ctl[18] / ctl[19]: problems kept from a wide band / filled in full after all.
+    hipLaunchKernelGGL(k_gapfill_redo, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(pn, (int64_t)c->num_cu * 4))), dim3(64), 0, c->stream, B.tpool.as<uint8_t>(), B.qpool.as<uint8_t>(),
+                       probs, sc.match, sc.mismatch, sc.o1, sc.e1, sc.o2, sc.e2, tb_base, B.bnd.as<int32_t>(), score, redo_list, d_redo_cnt, B.tbredo.as<uint8_t>());
     if (ke) (void)hipEventRecord(ke[1], c->stream);
     hipLaunchKernelGGL(k_gapfill_trace, dim3((unsigned)std::max<int64_t>(1, (pn * tr_spread + 63) / 64)), dim3(64), 0, c->stream, B.tpool.as<uint8_t>(), B.qpool.as<uint8_t>(), probs, (int)pn, eqx,
                        tb_base, B.run.as<uint32_t>(), B.cig.as<char>(), B.ciglen.as<int32_t>() + p0, score, B.tbredo.as<uint8_t>(), tr_spread, B.cigq.as<int32_t>() + p0, n_ptr);
@@ -589,8 +589,8 @@ static int align_device_once(vm_ctx* c, const vm_index* mi, const vm_params* prm
     //    A read that asks for it (E.redo) is run again alone by align_device with both passes (c->run_pass1), like the reads that need the later tiers of the divergence filter.
     // The band-width rule (vmx_ad_ns: the narrowest band whose margin covers pct % of the problem) only decides which problems are TRIED in a band and how wide — the
     // proof decides what is kept, so the records do not depend on it. Round 6: pct follows the reads instead of the mode alone. Each context starts at the mode's
-    // default (90; mode L 40) and steps down (to 20 at the least) by 20 / 10 while fewer than 1 / 2.5 % of a batch's problems are tried in a band and not proven (they are
-    // filled again in full: ~4x a band attempt), back up when more than 3 % are, and then holds that floor for 256 batches. HiFi-shape reads settle at 20 (a 270-base
+    // default (90; mode L 40) and steps down (to 20 at the least) by 20 / 10 while fewer than 1 / 2.5 % of a batch's problems are tried in a band and not proven (they go
+    // to the second launch: in full at ~4x a band attempt when these thresholds were tuned; since round 8 the larger ones through a wave-wide band first, k_gapfill_redo), back up when more than 3 % are, and then holds that floor for 256 batches. HiFi-shape reads settle at 20 (a 270-base
     // problem runs on ONE diagonal pair per lane: margin 104 against ~8 points of errors), ONT reads at 80-90 (70 fails 6 %, 55 fails 29 %):
     // `profiles/r06_q_band_width_rule_sweep.txt`. VMX_AD_PCT / VMX_AD_PCT_MIN pin the rule (tuning runs).
     static std::mutex ad_m; static struct { int pct = 0, floor = 20, hold = 0; } ad_tab[16][8];      // per device and read mode, shared by the contexts of the process
@@ -765,7 +765,7 @@ static int align_device_once(vm_ctx* c, const vm_index* mi, const vm_params* prm
             for (int q = 0; q < gf_chunks[pass]; ++q) {
                 const int32_t* ctl = h_ctl.data() + (size_t)(pass * (VMX_MAX_CHUNKS + 1) + q) * VMX_GF_SLOT;
                 unsigned long long rb = 0; memcpy(&rb, ctl + 16, 8);
-                st.n_dp_redo += ctl[12]; st.dp_redo_tb_bytes += (int64_t)rb; st.dp_cells += (int64_t)rb; ad_failed += ctl[15];
+                st.n_dp_redo += ctl[12]; st.n_dp_redo_wide += ctl[18]; st.n_dp_redo_full += ctl[19]; st.dp_redo_tb_bytes += (int64_t)rb; st.dp_cells += (int64_t)rb; ad_failed += ctl[15];
                 need_max = std::max<int64_t>(need_max, (int64_t)rb);
             }
         c->redo_need_max = std::max<long long>(c->redo_need_max, need_max);
@@ -883,7 +883,7 @@ static int align_in_sub_batches(int64_t n, const int64_t* offsets, int64_t max_b
             tot.ms_total += st.ms_total; for (int i = 0; i < 16; ++i) tot.ms_stage[i] += st.ms_stage[i];
             tot.ms_gapfill_fill += st.ms_gapfill_fill; tot.ms_gapfill_trace += st.ms_gapfill_trace; tot.n_gapfill_launches += st.n_gapfill_launches;
             tot.n_ed_full += st.n_ed_full; tot.n_ed_tier2 += st.n_ed_tier2; tot.n_ed_tier1 += st.n_ed_tier1;
-            tot.n_dp_redo += st.n_dp_redo; tot.dp_redo_tb_bytes += st.dp_redo_tb_bytes; tot.ms_local_seed += st.ms_local_seed; tot.ms_cluster += st.ms_cluster; tot.n_host_syncs += st.n_host_syncs; tot.n_local_general += st.n_local_general; tot.n_ext_retries += st.n_ext_retries; tot.n_batch_retries += st.n_batch_retries;
+            tot.n_dp_redo += st.n_dp_redo; tot.n_dp_redo_wide += st.n_dp_redo_wide; tot.n_dp_redo_full += st.n_dp_redo_full; tot.dp_redo_tb_bytes += st.dp_redo_tb_bytes; tot.ms_local_seed += st.ms_local_seed; tot.ms_cluster += st.ms_cluster; tot.n_host_syncs += st.n_host_syncs; tot.n_local_general += st.n_local_general; tot.n_ext_retries += st.n_ext_retries; tot.n_batch_retries += st.n_batch_retries;
         }
     }
     *recs = (vm_record*)malloc(sizeof(vm_record) * std::max<size_t>(all.size(), 1)); *cigar_blob = (char*)malloc(std::max<size_t>(blob.size(), 1));

@@ -525,7 +525,8 @@ int vm_k_cigar_batch(vm_ctx* c, const vm_score* sc, int eqx, int64_t n, const ch
 
 // the gap fill of vm_align_batch (vmx_gapfill_chunk) on n problems as one chunk: the problem table is built here with the batch's traceback sizes and queue keys
 // (vmx_round.h), the second launch's pool is sized for its worst case (every small problem filled again in full). stats: small problems tried in a band, kept
-// (proven), queued for the second launch (incl. the small ones never tried), problems outside the small class.
+// (proven), queued for the second launch (incl. the small ones never tried), problems outside the small class, then the second launch's larger problems: kept from a
+// wave-wide band, filled in full (stats: six values).
 int vm_k_cigar_batch_banded(vm_ctx* c, const vm_score* sc, int eqx, int64_t n, const char* t, const int64_t* t_off, const char* q,
                             const int64_t* q_off, char** cigars, int64_t** cigar_off, int32_t** band_flag, int64_t* stats) {
     if (!c) { set_error("no context"); return VM_ERR_NO_CTX; }
@@ -571,7 +572,7 @@ int vm_k_cigar_batch_banded(vm_ctx* c, const vm_score* sc, int eqx, int64_t n, c
         small += sm; nb += sm && flag[i] > VMX_AD_FLAG;
         eligible += sm && vmx_ad_ns(probs[i].tl, probs[i].ql, sc->match, sc->o1, sc->e1, sc->o2, sc->e2, ad_pct & 0xffff, (ad_pct >> 16) & 0xffff) > 0;
     }
-    if (stats) { stats[0] = eligible; stats[1] = nb; stats[2] = ctl[12]; stats[3] = n - small; }
+    if (stats) { stats[0] = eligible; stats[1] = nb; stats[2] = ctl[12]; stats[3] = n - small; stats[4] = ctl[18]; stats[5] = ctl[19]; }
     if (band_flag) { *band_flag = host_alloc<int32_t>((size_t)n); memcpy(*band_flag, flag.data(), sizeof(int32_t) * (size_t)n); }
     cigar_strings(n, probs.data(), hc.data(), hl.data(), cigars, cigar_off);
     return VM_OK;

@@ -32,13 +32,16 @@ __device__ __forceinline__ int vmx_readlane(int v, int l) { return __builtin_amd
 #endif
 // systolic hand-off used by the DP kernels: vmx_shr1_in(v, in): lane i <- lane i-1 of v, lane 0 <- its own `in` (wave_shr:1 leaves
 // lane 0's destination untouched, so `in` rides in as the old value: one v_mov_dpp, no select);
+// vmx_shl1_in(v, in): the mirror image, lane i <- lane i+1 of v, lane 63 <- its own `in` (wave_shl:1);
 // vmx_rol1: lane i <- lane i+1, lane 63 <- lane 0; vmx_ror1: lane i <- lane i-1, lane 0 <- lane 63
 #ifdef VMX_EMU
 __device__ __forceinline__ int vmx_shr1_in(int v, int in) { int e = __shfl_up(v, 1); return vmx_lane() == 0 ? in : e; }
+__device__ __forceinline__ int vmx_shl1_in(int v, int in) { int e = __shfl(v, (vmx_lane() + 1) & 63); return vmx_lane() == 63 ? in : e; }
 __device__ __forceinline__ int vmx_rol1(int v) { return __shfl(v, (vmx_lane() + 1) & 63); }
 __device__ __forceinline__ int vmx_ror1(int v) { return __shfl(v, (vmx_lane() + 63) & 63); }
 #else
 __device__ __forceinline__ int vmx_shr1_in(int v, int in) { return __builtin_amdgcn_update_dpp(in, v, 0x138, 0xf, 0xf, false); }
+__device__ __forceinline__ int vmx_shl1_in(int v, int in) { return __builtin_amdgcn_update_dpp(in, v, 0x130, 0xf, 0xf, false); }
 __device__ __forceinline__ int vmx_rol1(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x134, 0xf, 0xf, false); }
 __device__ __forceinline__ int vmx_ror1(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x13C, 0xf, 0xf, false); }
 #endif

@@ -34,6 +34,11 @@ __device__ __forceinline__ unsigned vmx_perm(unsigned s0, unsigned s1, unsigned 
 __device__ __forceinline__ int vmx_r16_shl1_in(int v, int in) { return __builtin_amdgcn_update_dpp(in, v, 0x101, 0xf, 0xf, false); }   // row_shl:1
 __device__ __forceinline__ unsigned vmx_perm(unsigned s0, unsigned s1, unsigned sel) { return __builtin_amdgcn_perm(s0, s1, sel); }
 #endif
+// the hand-offs of a band that lives in LW lanes: one 16-lane DPP row (row_* moves) or the whole wavefront (wave_* moves, vmx_device.h)
+template <int LW> __device__ __forceinline__ int vmx_ad_shl1_in(int v, int in) { if constexpr (LW == 16) return vmx_r16_shl1_in(v, in); else return vmx_shl1_in(v, in); }
+template <int LW> __device__ __forceinline__ int vmx_ad_shr1_in(int v, int in) { if constexpr (LW == 16) return vmx_r16_shr1_in(v, in); else return vmx_shr1_in(v, in); }
+template <int LW> __device__ __forceinline__ int vmx_ad_rol1(int v) { if constexpr (LW == 16) return vmx_r16_rol1(v); else return vmx_rol1(v); }
+template <int LW> __device__ __forceinline__ int vmx_ad_ror1(int v) { if constexpr (LW == 16) return vmx_r16_ror1(v); else return vmx_ror1(v); }
 
 // TAGGED scores: a register half holds 8 * (score + bias) + tag, an unsigned 16-bit value. Every wave-instruction of the two-operand
 // 32-bit class (v_add_u32, v_sub_u32, v_and / or / xor) issues in 2.3 cycles on gfx950, everything in the VOP3 / VOP3P / DPP class — all
@@ -130,11 +135,18 @@ __device__ __forceinline__ unsigned vmx_ad_pick(const unsigned (&v)[NS], int k) 
 
 // X = the problem in the low halves, Y = the one in the high halves of this lane's 16-lane row (tl = 0: idle). Every lane of the wave
 // calls it; control flow is wave-uniform. scoreX / scoreY: H(tl, ql) of the band, the same in all lanes of the row.
-template <int NS>
+//   LW = 64 (the second launch, k_gapfill_redo): the band lives in the whole wavefront — lane l = the lane id owns the diagonals
+// [2 NS l, 2 NS l + 2 NS) of a band of 128 NS, X and Y are ONE problem each for the whole wave, the hand-offs are wave-wide moves and the chunk
+// registers hold 64 codes. The traceback bytes go into the packed two-rows-per-lane layout of vmx_gapfill_fill16 (the space a refilled problem
+// owns: VMX_PK_TB_BYTES), cell (i, j) at (s (ql + 127) + (j - 1) + r) 128 + r with s = (i - 1) >> 7, r = (i - 1) & 127: inside a stripe the NS
+// cells of a lane are NS adjacent bytes (k counts them downwards) and an anti-diagonal of the band is one run of 64 NS bytes. Only cells of
+// the matrix are stored (one outside it would alias a real cell's address); what the band does not cover stays unwritten — the walk of a
+// kept (proven) problem never leaves the band.
+template <int NS, int LW = 16>
 __device__ __forceinline__ void vmx_gapfill_fill_ad(const uint8_t* __restrict__ TX, const uint8_t* __restrict__ QX, int tlX, int qlX, int dloX, uint8_t* __restrict__ tbX,
                                                    const uint8_t* __restrict__ TY, const uint8_t* __restrict__ QY, int tlY, int qlY, int dloY, uint8_t* __restrict__ tbY,
                                                    int match, int mismatch, int o1, int e1, int o2, int e2, int lane, int& scoreX, int& scoreY) {
-    const int l = lane & 15;
+    const int l = LW == 16 ? lane & 15 : lane;
     vmx_ad_consts K;
     K.O1 = vmx_pk(8 * o1, 8 * o1); K.O2 = vmx_pk(8 * o2, 8 * o2); K.E1 = vmx_pk(8 * e1, 8 * e1); K.E2 = vmx_pk(8 * e2, 8 * e2);
     K.MATCH = vmx_pk(8 * match, 8 * match); K.PEN = vmx_pk(8 * (match - mismatch), 8 * (match - mismatch));
@@ -173,40 +185,55 @@ __device__ __forceinline__ void vmx_gapfill_fill_ad(const uint8_t* __restrict__ 
     const int lfX = xfX / (2 * NS), kfX = (xfX % (2 * NS)) >> 1, lfY = xfY / (2 * NS), kfY = (xfY % (2 * NS)) >> 1;
     int finX = 0, finY = 0;
     constexpr int W = VMX_AD_W(NS);                           // bytes of the lane's slot: as many as the lane has cells per step (round 6; 4 before, whatever NS)
-    uint8_t* const pX = tbX + VMX_AD_TB_OFF_W(0, l, W);       // the lane's slot of anti-diagonal 0; the step's part of the offset is added per store
-    uint8_t* const pY = tbY + VMX_AD_TB_OFF_W(0, l, W);
+    uint8_t* const pX = LW == 16 ? tbX + VMX_AD_TB_OFF_W(0, l, W) : tbX;       // the lane's slot of anti-diagonal 0; the step's part of the offset is added per store
+    uint8_t* const pY = LW == 16 ? tbY + VMX_AD_TB_OFF_W(0, l, W) : tbY;
     auto put = [&](uint8_t* at, unsigned w01, unsigned w23, bool hi) {
         if constexpr (W == 1) *at = (uint8_t)(hi ? (w01 >> 16) : w01);
         else if constexpr (W == 2) *(uint16_t*)at = (uint16_t)(hi ? (w01 >> 16) : w01);
         else *(uint32_t*)at = vmx_perm(w23, w01, hi ? 0x07060302u : 0x05040100u);
     };
-    // chunk of block b (pairs 16 b + 1 .. 16 b + 16): lane m holds the target code lane 0 takes in the block's pair m (row 16 b + 1 + m - h),
+    // LW = 64: the step's bytes at their cells' addresses in the packed layout. Cell k of the lane on anti-diagonal a is (i0 - k, a - i0 + k), i0 = i1 + 1
+    // the lane's largest row: inside the matrix when lo <= i - 1 < hi with lo = max(0, a - 1 - ql), hi = min(tl, a - 1) (both wave-uniform); its offset is
+    // s * 128 (ql - 2) + 128 (a - 2) + (i - 1) (129 r + 128 (j - 1) with r = i - 1 - 128 s: a 24-bit multiply, the stripe s < 8)
+    auto put_pk = [&](uint8_t* tb, int tl, int ql, int a, int i1, unsigned w01, unsigned w23, bool hi) {
+        const int lo = a - 1 - ql > 0 ? a - 1 - ql : 0, n = (tl < a - 1 ? tl : a - 1) - lo;
+        const int sb = (int)((unsigned)(128 * (ql - 2)) << 8) >> 8, ab = 128 * (a - 2);
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            const int ik = i1 - k;
+            if ((unsigned)(ik - lo) < (unsigned)n && n > 0) {
+                const unsigned w = k < 2 ? w01 : w23;
+                tb[(unsigned)(((ik >> 7) & 7) * sb + (ab + ik))] = (uint8_t)(w >> (8 * (k & 1) + (hi ? 16 : 0)));
+            }
+        }
+    };
+    // chunk of block b (pairs 16 b + 1 .. 16 b + 16; LW = 64: 64 b + 1 .. 64 b + 64, and so on: 16 stands for LW below): lane m holds the target code lane 0 takes in the block's pair m (row 16 b + 1 + m - h),
     // lane 15 - m the query code lane 15 takes in it (column 16 b + m + h + 16 NS)
     auto load_chunks = [&](int b16, unsigned& tch, unsigned& qch) {
         tch = vmx_pk(tcf(TX, tlX, b16 + 1 + l - hX), tcf(TY, tlY, b16 + 1 + l - hY));
-        qch = vmx_pk(qcf(QX, qlX, b16 + 15 - l + hX + 16 * NS), qcf(QY, qlY, b16 + 15 - l + hY + 16 * NS));
+        qch = vmx_pk(qcf(QX, qlX, b16 + (LW - 1) - l + hX + LW * NS), qcf(QY, qlY, b16 + (LW - 1) - l + hY + LW * NS));
     };
     unsigned tch, qch, ntch, nqch;
     load_chunks(0, ntch, nqch);
-    for (int p0 = 0; p0 < npairs; p0 += 16) {
+    for (int p0 = 0; p0 < npairs; p0 += LW) {
         tch = ntch; qch = nqch;
-        load_chunks(p0 + 16, ntch, nqch);                       // one block ahead
-        int pend = npairs - p0; if (pend > 16) pend = 16;
+        load_chunks(p0 + LW, ntch, nqch);                       // one block ahead
+        int pend = npairs - p0; if (pend > LW) pend = LW;
         for (int pp = 0; pp < pend; ++pp) {
             const int p = p0 + pp + 1;
             // query codes move up one diagonal pair
             {
-                const unsigned in = (unsigned)vmx_r16_shl1_in((int)qcode[0], (int)qch);
+                const unsigned in = (unsigned)vmx_ad_shl1_in<LW>((int)qcode[0], (int)qch);
 #pragma unroll
                 for (int k = 0; k + 1 < NS; ++k) qcode[k] = qcode[k + 1];
                 qcode[NS - 1] = in;
-                qch = (unsigned)vmx_r16_ror1((int)qch);
+                qch = (unsigned)vmx_ad_ror1<LW>((int)qch);
             }
             // odd step a = 2p - 1: C_k takes the cell above from A_{k+1} (the last one from the next lane) and the cell to its left from A_k
             unsigned w[NS][5];
             {
-                const unsigned nH = (unsigned)vmx_r16_shl1_in((int)HA[0], (int)K.NH), nE1 = (unsigned)vmx_r16_shl1_in((int)E1A[0], (int)K.NE1),
-                               nE2 = (unsigned)vmx_r16_shl1_in((int)E2A[0], (int)K.NE2);
+                const unsigned nH = (unsigned)vmx_ad_shl1_in<LW>((int)HA[0], (int)K.NH), nE1 = (unsigned)vmx_ad_shl1_in<LW>((int)E1A[0], (int)K.NE1),
+                               nE2 = (unsigned)vmx_ad_shl1_in<LW>((int)E2A[0], (int)K.NE2);
 #pragma unroll
                 for (int k = 0; k < NS; ++k) {
                     const unsigned uH = k + 1 < NS ? HA[k + 1 < NS ? k + 1 : 0] : nH, uE1 = k + 1 < NS ? E1A[k + 1 < NS ? k + 1 : 0] : nE1, uE2 = k + 1 < NS ? E2A[k + 1 < NS ? k + 1 : 0] : nE2;
@@ -216,22 +243,27 @@ __device__ __forceinline__ void vmx_gapfill_fill_ad(const uint8_t* __restrict__ 
             {
                 unsigned w01, w23;
                 vmx_ad_pack<NS>(w, w01, w23);
+                if constexpr (LW == 16) {
                 const size_t so = VMX_AD_TB_OFF_W(2 * p - 2, 0, W);   // anti-diagonal a = 2p - 1 is step s = a - 1
                 if (p <= poX) put(pX + so, w01, w23, false);
                 if (p <= poY) put(pY + so, w01, w23, true);
+                } else {
+                    if (p <= poX) put_pk(pX, tlX, qlX, 2 * p - 1, p - 2 - hX - NS * l, w01, w23, false);
+                    if (p <= poY) put_pk(pY, tlY, qlY, 2 * p - 1, p - 2 - hY - NS * l, w01, w23, true);
+                }
             }
             // target codes move down one diagonal pair
             {
-                const unsigned in = (unsigned)vmx_r16_shr1_in((int)tcode[NS - 1], (int)tch);
+                const unsigned in = (unsigned)vmx_ad_shr1_in<LW>((int)tcode[NS - 1], (int)tch);
 #pragma unroll
                 for (int k = NS - 1; k > 0; --k) tcode[k] = tcode[k - 1];
                 tcode[0] = in;
-                tch = (unsigned)vmx_r16_rol1((int)tch);
+                tch = (unsigned)vmx_ad_rol1<LW>((int)tch);
             }
             // even step a = 2p: A_k takes the cell above from C_k and the cell to its left from C_{k-1} (the first one from the previous lane)
             {
-                const unsigned nH = (unsigned)vmx_r16_shr1_in((int)HC[NS - 1], (int)K.NH), nF1 = (unsigned)vmx_r16_shr1_in((int)F1C[NS - 1], (int)K.NF1),
-                               nF2 = (unsigned)vmx_r16_shr1_in((int)F2C[NS - 1], (int)K.NF2);
+                const unsigned nH = (unsigned)vmx_ad_shr1_in<LW>((int)HC[NS - 1], (int)K.NH), nF1 = (unsigned)vmx_ad_shr1_in<LW>((int)F1C[NS - 1], (int)K.NF1),
+                               nF2 = (unsigned)vmx_ad_shr1_in<LW>((int)F2C[NS - 1], (int)K.NF2);
 #pragma unroll
                 for (int k = 0; k < NS; ++k) {
                     const unsigned lH = k > 0 ? HC[k > 0 ? k - 1 : 0] : nH, lF1 = k > 0 ? F1C[k > 0 ? k - 1 : 0] : nF1, lF2 = k > 0 ? F2C[k > 0 ? k - 1 : 0] : nF2;
@@ -241,9 +273,14 @@ __device__ __forceinline__ void vmx_gapfill_fill_ad(const uint8_t* __restrict__ 
             {
                 unsigned w01, w23;
                 vmx_ad_pack<NS>(w, w01, w23);
+                if constexpr (LW == 16) {
                 const size_t so = VMX_AD_TB_OFF_W(2 * p - 1, 0, W);
                 if (p <= peX) put(pX + so, w01, w23, false);
                 if (p <= peY) put(pY + so, w01, w23, true);
+                } else {
+                    if (p <= peX) put_pk(pX, tlX, qlX, 2 * p, p - 1 - hX - NS * l, w01, w23, false);
+                    if (p <= peY) put_pk(pY, tlY, qlY, 2 * p, p - 1 - hY - NS * l, w01, w23, true);
+                }
             }
             // the pair that holds the problem's last anti-diagonal: its cell (tl, ql) was written by this pair's odd or even step
             if (__any(p == poX || p == poY)) {
@@ -254,12 +291,14 @@ __device__ __forceinline__ void vmx_gapfill_fill_ad(const uint8_t* __restrict__ 
             }
         }
     }
-    scoreX = __shfl(finX, (lane & 48) | (lfX & 15));
-    scoreY = __shfl(finY, (lane & 48) | (lfY & 15));
+    scoreX = __shfl(finX, LW == 16 ? (lane & 48) | (lfX & 15) : lfX & 63);
+    scoreY = __shfl(finY, LW == 16 ? (lane & 48) | (lfY & 15) : lfY & 63);
 }
 
-// Is the band's result the true optimum with the true traceback? A path that leaves the band holds at least g inserted and g deleted bases
-// (vmx_ad_geom): impossible when g > min(tl, ql); otherwise it cannot score more than match * (min(tl, ql) - g) minus two gaps of g bases
+// Is the band's result the true optimum with the true traceback? Asked by both launches: the first one for its 16-lane bands (vmx_ad_geom: 32 ns
+// diagonals), the second one for the wave-wide band (vmx_ad_geom_nd over VMX_ADW_DPN ns diagonals); the argument only needs g and that every cell of the
+// band inside the matrix was computed from its three neighbours in the band, whichever layout the bytes went to.
+// A path that leaves the band holds at least g inserted and g deleted bases: impossible when g > min(tl, ql); otherwise it cannot score more than match * (min(tl, ql) - g) minus two gaps of g bases
 // (splitting a gap never makes it cheaper). If the band's score beats that bound, every optimal path lies inside the band, where all
 // cells it touches and all comparisons the traceback reads (they involve prefix-optimal values of cells on optimal paths only) are exact.
 __device__ __forceinline__ bool vmx_ad_proven(int score, int tl, int ql, int g, int match, int o1, int e1, int o2, int e2) {

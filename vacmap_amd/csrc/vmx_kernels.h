@@ -160,9 +160,10 @@ struct vmx_lseed_args {
 // above max(0, ql - tl) are as equal as that allows. vmx_ad_geom returns g: a path that leaves the band holds at least g inserted AND g deleted
 // bases (0: the band cannot hold both corners). The result is kept only when vmx_ad_proven (vmx_dp_ad.h) shows every such path is worse.
 #define VMX_AD_NS_MAX 4
-__host__ __device__ static inline int vmx_ad_geom(int tl, int ql, int ns, int* dlo_out) {
+// nd = the band's width in diagonals (even)
+__host__ __device__ static inline int vmx_ad_geom_nd(int tl, int ql, int nd, int* dlo_out) {
     const int dl = ql - tl, lo = dl < 0 ? dl : 0, hi = dl > 0 ? dl : 0;
-    const int slack = 32 * ns - (hi - lo + 1);
+    const int slack = nd - (hi - lo + 1);
     if (slack < 0) return 0;
     int mb = slack / 2, dlo = lo - mb;
     if (dlo & 1) {
@@ -174,6 +175,7 @@ __host__ __device__ static inline int vmx_ad_geom(int tl, int ql, int ns, int* d
     const int ma = slack - mb;
     return (mb < ma ? mb : ma) + 1;
 }
+__host__ __device__ static inline int vmx_ad_geom(int tl, int ql, int ns, int* dlo_out) { return vmx_ad_geom_nd(tl, ql, 32 * ns, dlo_out); }
 // what a path pays at least for leaving a band of margin g: g matches fewer and two gaps of g bases
 __host__ __device__ static inline long long vmx_ad_margin(int g, int match, int o1, int e1, int o2, int e2) {
     const long long c1 = o1 + (long long)g * e1, c2 = o2 + (long long)g * e2;
@@ -181,26 +183,45 @@ __host__ __device__ static inline long long vmx_ad_margin(int g, int match, int 
 }
 // band width (diagonal pairs per lane) a problem is tried with: the narrowest whose margin is at least pct % of min(tl, ql) (a 10 %-error
 // read loses ~0.7 per base against the all-match bound), the widest one if that still reaches pct_min %, 0 = not worth trying / impossible
-__host__ __device__ static inline int vmx_ad_ns(int tl, int ql, int match, int o1, int e1, int o2, int e2, int pct, int pct_min) {
+// (dpn = diagonals of the band per unit of ns, ns_lo .. ns_hi = the widths the caller has: 32 and 1 .. VMX_AD_NS_MAX for the eight-per-wave form)
+__host__ __device__ static inline int vmx_ad_ns_nd(int tl, int ql, int match, int o1, int e1, int o2, int e2, int pct, int pct_min, int dpn, int ns_lo, int ns_hi) {
     if (tl <= 0 || ql <= 0) return 0;
     const int mn = tl < ql ? tl : ql;
     int dlo, g = 0;
-    for (int ns = 1; ns <= VMX_AD_NS_MAX; ++ns) {
-        g = vmx_ad_geom(tl, ql, ns, &dlo);
+    for (int ns = ns_lo; ns <= ns_hi; ++ns) {
+        g = vmx_ad_geom_nd(tl, ql, dpn * ns, &dlo);
         if (g >= 1 && (g > mn || vmx_ad_margin(g, match, o1, e1, o2, e2) * 100 >= (long long)pct * mn)) return ns;
     }
-    return (g >= 1 && vmx_ad_margin(g, match, o1, e1, o2, e2) * 100 >= (long long)pct_min * mn) ? VMX_AD_NS_MAX : 0;
+    return (g >= 1 && vmx_ad_margin(g, match, o1, e1, o2, e2) * 100 >= (long long)pct_min * mn) ? ns_hi : 0;
+}
+__host__ __device__ static inline int vmx_ad_ns(int tl, int ql, int match, int o1, int e1, int o2, int e2, int pct, int pct_min) {
+    return vmx_ad_ns_nd(tl, ql, match, o1, e1, o2, e2, pct, pct_min, 32, 1, VMX_AD_NS_MAX);
 }
 #define VMX_AD_PCT_DEFAULT 100
 #define VMX_AD_PCT_MIN_DEFAULT 65
+// The wave-wide instance of the band form (second launch, k_gapfill_redo: the VMX_REDO_PK class, two problems per wavefront): lane = the lane id, VMX_ADW_DPN * ns
+// diagonals, ns = VMX_ADW_NS_MIN .. VMX_AD_NS_MAX (128 diagonals is what the first launch already had). Its rule is a constant of that launch, not the first launch's
+// adaptive value: what it does not keep is filled in full on the spot.
+#ifdef VMX_EMU
+#define VMX_ADW_DPN 36                 /* emulator build: the band is computed 128 ns wide like the product's, but only its lowest 36 ns diagonals are claimed (geometry, g, proof):
+                                          with tl + ql <= 160 the full width would hold every problem and the CPU tests would never see one that is not proven, at 32 ns never one
+                                          that the first launch's band could not have proven as well */
+#else
+#define VMX_ADW_DPN 128
+#endif
+#define VMX_ADW_NS_MIN 2
+#define VMX_ADW_PCT 100
+#define VMX_ADW_PCT_MIN 65
 #define VMX_AD_FLAG 16                 /* layout flag of a problem kept in the anti-diagonal layout: VMX_AD_FLAG + ns */
 #define VMX_PK_FLAG 1                  /* layout flag of a small-class problem the second launch ran on the whole wave (packed two-rows-per-lane layout) */
 #ifdef VMX_EMU
 #define VMX_REDO_PK(tl, ql) ((tl) > 0 && (ql) > 0 && VMX_DP16X4_OK(tl, ql) && (tl) + (ql) >= 120)
 #else
 #ifndef VMX_REDO_PK_MIN
-#define VMX_REDO_PK_MIN 384            /* redone problems of at least this perimeter take a whole wavefront each (the typical 270 x 270 problem included: the second
-                                          launch holds ~3.5 k problems per batch, a quarter of the machine's wave slots — four per wave left it waiting 2.75 ms for 900 waves) */
+#define VMX_REDO_PK_MIN 384            /* redone problems of at least this perimeter run on whole wavefronts (the typical 270 x 270 problem included: the second launch
+                                          holds ~3.5 k problems per batch, a quarter of the machine's wave slots — four per wave left it waiting 2.75 ms for 900 waves): two per
+                                          wave in the wave-wide band (VMX_ADW_*, below), one per wave in full (vmx_gapfill_fill16) where that band's result is not proven.
+                                          Either way in the packed two-rows-per-lane layout, flag VMX_PK_FLAG */
 #endif
 #define VMX_REDO_PK(tl, ql) ((tl) > 0 && (ql) > 0 && VMX_DP16X4_OK(tl, ql) && (tl) + (ql) >= VMX_REDO_PK_MIN)
 #endif

@@ -53,7 +53,7 @@ static inline void vmx_res_ptrs(vmx_batch_bufs& B, int64_t n, double** score, in
 // E5 on one chunk of the gap-fill problem table B.dptab: problems [p0, p0 + pn) (pn an upper bound when n_ptr names the count on the device), queue keys
 // in B.dpsz[0] (vmx_round_key), traceback space in B.tb from the chunk's first problem on (tb_off0: its traceback offset); the problems the band does not prove
 // take their full-matrix space from B.tbredo (redo_cap bytes; one that does not fit is emptied). ctl: the chunk's VMX_GF_SLOT ints, zeroed — control block
-// (queue range / counters / redo list length / redo bytes), then the size-order scratch; redo_list: room for pn entries. ke: three events (before the fill,
+// (queue range / counters / redo list length / redo bytes / second-launch problems kept from a wide band and filled in full: ctl[18], ctl[19]), then the size-order scratch; redo_list: room for pn entries. ke: three events (before the fill,
 // after the fill, after the traceback) or null. CIGARs in B.run / B.cig / B.ciglen / B.cigq; B.dpscore carries every problem's layout flag.
 #define VMX_GF_SLOT (32 + 544)
 void vmx_gapfill_chunk(vm_ctx* c, vmx_batch_bufs& B, const vm_score& sc, int ad_pct, int eqx, int p0, int64_t pn, const int32_t* n_ptr, int64_t tb_off0,

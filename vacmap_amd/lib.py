@@ -73,7 +73,8 @@ class BatchStats(C.Structure):
                                           'dp_string_bytes')] + \
                [('ms_total', C.c_double), ('ms_stage', C.c_double * 16), ('ms_gapfill_fill', C.c_double), ('ms_gapfill_trace', C.c_double),
                 ('n_gapfill_launches', C.c_int64), ('n_ed_full', C.c_int64), ('n_ed_tier2', C.c_int64), ('n_ed_tier1', C.c_int64),
-                ('n_dp_redo', C.c_int64), ('dp_redo_tb_bytes', C.c_int64), ('ms_local_seed', C.c_double), ('ms_cluster', C.c_double), ('n_host_syncs', C.c_int64), ('n_local_general', C.c_int64), ('n_ext_retries', C.c_int64), ('n_batch_retries', C.c_int64)]
+                ('n_dp_redo', C.c_int64), ('dp_redo_tb_bytes', C.c_int64), ('ms_local_seed', C.c_double), ('ms_cluster', C.c_double), ('n_host_syncs', C.c_int64), ('n_local_general', C.c_int64), ('n_ext_retries', C.c_int64), ('n_batch_retries', C.c_int64),
+                ('n_dp_redo_wide', C.c_int64), ('n_dp_redo_full', C.c_int64)]
 
 
 def _b(s):
@@ -320,14 +321,15 @@ class Context:
         t, to = _cat(targets); q, qo = _cat(queries)
         n = len(targets)
         sc = Score(match, mismatch, o1, e1, o2, e2)
-        cg = C.c_void_p(); co = C.POINTER(C.c_int64)(); fl = C.POINTER(C.c_int32)(); st = (C.c_int64 * 4)()
+        cg = C.c_void_p(); co = C.POINTER(C.c_int64)(); fl = C.POINTER(C.c_int32)(); st = (C.c_int64 * 6)()
         self.lib.check(self.lib.L.vm_k_cigar_batch_banded(self.h, C.byref(sc), int(eqx), n, t, to.ctypes.data, q, qo.ctypes.data,
                                                           C.byref(cg), C.byref(co), C.byref(fl), st))
         off = self._take(co, n + 1, np.int64)
         blob = C.string_at(cg.value, int(off[-1])) if off[-1] else b''
         self.lib.L.vm_free(cg)
         cigars = [blob[off[i]:off[i + 1] - 1].decode() for i in range(n)]
-        return cigars, self._take(fl, n, np.int32), {'eligible': st[0], 'proven': st[1], 'redo': st[2], 'not_eligible': st[3]}
+        return cigars, self._take(fl, n, np.int32), {'eligible': st[0], 'proven': st[1], 'redo': st[2], 'not_eligible': st[3],
+                                                          'redo_wide': st[4], 'redo_full': st[5]}
 
     def k_cigar(self, target, query, match=2, mismatch=-4, gap_open_1=4, gap_extend_1=2, gap_open_2=24, gap_extend_2=1,
                 bw=-1, zdropvalue=-1, eqx=False):
