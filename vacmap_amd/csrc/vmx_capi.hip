@@ -23,6 +23,7 @@ using namespace vmx;
 
 void vmx_ctx_free_local_bufs(vm_ctx* c);    // vmx_stage_local.hip
 void vmx_ctx_free_batch_bufs(vm_ctx* c);    // vmx_align.hip
+void vmx_ctx_free_sam_bufs(vm_ctx* c);      // vmx_sam_dev.hip
 
 static inline int grid_for(const vm_ctx* c, int64_t n_items, int per_cu = 8) {
     int64_t g = std::min<int64_t>(n_items, (int64_t)c->num_cu * per_cu);
@@ -308,6 +309,7 @@ void vm_ctx_destroy(vm_ctx* c) {
     for (int i = 0; i < VMX_NBUF; ++i) c->b[i].release();
     vmx_ctx_free_local_bufs(c);
     vmx_ctx_free_batch_bufs(c);
+    vmx_ctx_free_sam_bufs(c);
     c->tab_buf.release();
     vmx::devbuf_retired().flush();
     for (int i = 0; i < 24; ++i) (void)hipEventDestroy(c->ev[i]);

@@ -307,14 +307,20 @@ int vmx_index_upload_codes(vm_index* mi, const char* const* seqs) {
     DevBuf stage; struct Rel { DevBuf* b; ~Rel() { b->release(); } } rel{&stage};
     const int64_t CH = (int64_t)256 << 20;
     VMX_TRY(stage.reserve((size_t)std::min<int64_t>(std::max<int64_t>(tot, 1), CH)));
+    DevBuf other; struct Rel2 { DevBuf* b; ~Rel2() { b->release(); } } rel2{&other};      // letters that become code 4 without being N (the device SAM emitter cannot print them)
+    VMX_TRY(other.reserve(8)); VMX_HIP(hipMemsetAsync(other.p, 0, 8, st));
     for (size_t i = 0; i < mi->lens.size(); ++i)
         for (int64_t s = 0; s < mi->lens[i]; s += CH) {
             const int64_t m = std::min<int64_t>(CH, mi->lens[i] - s);
             VMX_HIP(hipMemcpyAsync(stage.p, seqs[i] + s, (size_t)m, hipMemcpyHostToDevice, st));
             hipLaunchKernelGGL(k_encode, dim3(grid1d(m, 8192)), dim3(256), 0, st, stage.as<char>(), mi->d_codes.as<uint8_t>() + mi->offsets[i] + s, m);
+            hipLaunchKernelGGL(k_sam_count_other, dim3(grid1d(m, 1024)), dim3(256), 0, st, stage.as<const char>(), m, other.as<unsigned long long>());
             VMX_HIP(hipStreamSynchronize(st));           // the staging buffer is reused
         }
     hipLaunchKernelGGL(k_fill_u8, dim3(1), dim3(256), 0, st, mi->d_codes.as<uint8_t>() + tot, (int64_t)64, (uint8_t)4);
+    unsigned long long n_other = 0;
+    VMX_HIP(hipMemcpyAsync(&n_other, other.p, 8, hipMemcpyDeviceToHost, st)); VMX_HIP(hipStreamSynchronize(st));
+    mi->n_other_letters = (int64_t)n_other;
     return 0;
 }
 

@@ -16,6 +16,7 @@ struct vm_index {
     int64_t n_min = 0, n_distinct = 0;
     vmx::DevBuf d_codes, d_pos, d_table, d_off;
     bool has_host_seq = true;
+    int64_t n_other_letters = 0;            // letters of the uploaded reference that are none of ACGTN (d_codes holds N for them; the host copy keeps them): counted once by vmx_index_upload_codes
     std::once_flag host_seq_once;           // replicas decode their host copy of the bases from HBM once, whichever emitter thread asks first (vmx_sam.hip)
 };
 
@@ -31,5 +32,7 @@ int vmx_index_finish_device(vm_index* mi, vmx::DevBuf& d_keys, int64_t n);
 // contig or whose strand bit is wrong) and the strict (hash, position) order check (err[1] += violations)
 __global__ void k_idx_pos_keys(const uint8_t* codes, const int64_t* coff, int nseq, const uint64_t* pos, int64_t n, int k, uint64_t* keys, int32_t* err);
 __global__ void k_idx_check_sorted(const uint64_t* keys, const uint64_t* pos, int64_t n, int32_t* err);
+// letters of n reference bytes that are none of ACGTN in either case (k_sam.hip; counted by vmx_index_upload_codes for the device SAM emitter)
+__global__ void k_sam_count_other(const char* in, int64_t n, unsigned long long* count);
 __global__ void k_idx_fill_hashes(const vmx_slot* tab, int64_t nslots, uint64_t* hashes);
 #endif

@@ -49,6 +49,7 @@ SWITCHES = (
     ('VMX_DRIVER_PINNED', '1', _not0, '0: gather a batch\'s reads into pageable instead of page-locked memory (the upload is then staged on the aligner thread); also turns the feeders off'),
     ('VMX_DRIVER_FEEDERS', '2', int, 'threads with a context of their own that gather and upload batches ahead of the aligners (0: the aligner thread does both)'),
     ('VMX_DRIVER_WRITEV', '1', _not0, '0: assemble a window\'s text and write() it instead of writing the batches\' texts straight to the descriptor'),
+    ('VMX_EMIT_CONTEXTS', '2', int, '--sam-emitter device: threads that make SAM text on the GPU, each with a context of its own (at least 1)'),
     ('VMX_SKIP_EMIT', '0', _is1, '1: diagnostic, no SAM text is produced: the aligners alone'),
     ('VMX_DRIVER_TIMING', '', str, 'set: one stderr line of seconds by phase at the end; 2: also one line per batch'),
 )
@@ -410,6 +411,9 @@ def build_parser():
     p.add_argument('--bam-reader', choices=['python', 'native'], default='python',
                    help='how -read x.bam is read: the Python reader on one host thread (default) or BGZF inflate and record decoding on the GPU '
                         '(lib.BamReader, on a context of its own); a .bam that is gzip but not BGZF falls back to the Python reader')
+    p.add_argument('--sam-emitter', choices=['host', 'device'], default='host',
+                   help='who makes the SAM text of a batch: -t host threads (default) or the GPU (merged CIGAR, NM, MD / cs, SA and the lines themselves, on '
+                        'VMX_EMIT_CONTEXTS contexts of their own); with --copycomments, or a reference that holds letters other than ACGTN, the host emitter is used')
     return p
 
 
@@ -668,14 +672,34 @@ def _blob(parts):
     return np.frombuffer(b''.join(parts) or b'\0', np.uint8), off
 
 
+VM_ERR_UNSUPPORTED = -7
+
+
+def _device_emitter_wanted(args, rank):
+    """--sam-emitter device, unless the run copies comments (the filter of :20686 stays on the host emitter): one stderr line says so"""
+    if args.sam_emitter != 'device':
+        return False
+    if args.copycomments:
+        if rank == 0:
+            sys.stderr.write('vacmapx: --copycomments needs the host SAM emitter: --sam-emitter device is not used\n')
+        return False
+    return True
+
+
+def _device_emitter_given_up(why, rank):
+    if rank == 0:
+        sys.stderr.write('vacmapx: the host SAM emitter is used for the whole run (%s)\n' % why)
+
+
 def _run_asm(args, net, lib, ctx, index, prm, opts, out, device, t_start):
     """-mode asm (src/vacmap/vacmap:245-255, :394-411; worker mammap_asm.py:23462-23511): every input sequence is an assembly contig. --eqx is
     forced and maxdivergence set to 1 by vm_params_default(VM_MODE_ASM); contigs are aligned in groups (the long ones of a group side by side on
     the GPU) and their SAM lines written in input order. A contig the reference would skip (raised) is logged and skipped.
     With N ranks every rank parses the input, contig c of it goes to rank c mod N (contigs are independent: no data-path collective), and
     rank 0 gathers each group's lines and writes them in input order. Returns the final stderr line as _finish takes it."""
-    from .lib import align_batch_raw, sam_emit
+    from .lib import align_batch_raw, sam_emit, sam_emit_device, VmxError
     world, rank = net.world, net.rank
+    on_device = [_device_emitter_wanted(args, rank)]
     if not args.workdir:
         sys.exit('workdir not provided! -workdir /path/to/workdir')                      # vacmap:247-249
     os.makedirs(args.workdir, exist_ok=True)
@@ -693,8 +717,18 @@ def _run_asm(args, net, lib, ctx, index, prm, opts, out, device, t_start):
             qb, qo = _blob([g[3] for g in share]); cb, co = _blob([g[4] for g in share])
             raw = align_batch_raw(ctx, index, prm, sb, so)
             # the asm emitter (iterator_get_bam_dict_str, mammap_asm.py:22757) in the native emitter: vm_sam_opts.asm_mode
-            text, toff, _, ns = sam_emit(lib, index, opts, nb, no, sb, so, raw, quals=qb, qual_off=qo, comments=cb if args.copycomments else None,
-                                         com_off=co if args.copycomments else None, nthreads=max(1, args.t))
+            text = None
+            if on_device[0]:                                                                # --sam-emitter device: on the run's own context
+                try:
+                    text, toff, _, ns = sam_emit_device(ctx, index, opts, nb, no, sb, so, raw, quals=qb, qual_off=qo)
+                except VmxError as e:
+                    if e.code != VM_ERR_UNSUPPORTED:
+                        raise
+                    on_device[0] = False
+                    _device_emitter_given_up(str(e), rank)
+            if text is None:
+                text, toff, _, ns = sam_emit(lib, index, opts, nb, no, sb, so, raw, quals=qb, qual_off=qo, comments=cb if args.copycomments else None,
+                                             com_off=co if args.copycomments else None, nthreads=max(1, args.t))
             for x, g in enumerate(share):
                 if raw.status[x] != 0:                                                      # the worker's except (:23493-23498)
                     sys.stderr.write('%s is not aligned.\n' % g[1].decode()); done[g[0]] = None
@@ -778,6 +812,13 @@ class ReadStream:
         self.emit_jobs = max(1, min(4, emit_total // 4))
         self.emit_threads = max(1, emit_total // self.emit_jobs)
         self.emit_pool = None
+        # --sam-emitter device: the emit jobs run on VMX_EMIT_CONTEXTS threads, each with a context of its own (as the feeders have); the aligner
+        # threads and their contexts are what they are without it
+        self.emit_device = _device_emitter_wanted(args, net.rank)
+        self.emit_ctxs, self.emit_free, self.emit_local = [], queue.Queue(), threading.local()
+        self.emit_total = emit_total
+        if self.emit_device:
+            self.emit_jobs = max(1, sw['VMX_EMIT_CONTEXTS'])
         self.counts = {'reads': 0, 'lines': 0, 'skipped': 0}
         self.rank_hashes, self.rank_hash_file = [], []      # range mode: the names this rank has seen, compared across the ranks at the end
         self.errs = []
@@ -797,6 +838,10 @@ class ReadStream:
             # the batch's reads are gathered into page-locked memory: vm_align_batch's upload becomes a DMA the aligner thread does not wait for
             if sw['VMX_DRIVER_PINNED']:
                 self.pinned = V.PinnedPool(lib, device)
+            for _ in range(self.emit_jobs if self.emit_device else 0):       # before the sizing run: trim_to_memory then sees their HBM (size_emitters)
+                ecx = V.Context(device, lib=lib)
+                self.emit_ctxs.append(ecx); self.emit_free.put(ecx)
+            self.blocking_sync(self.emit_ctxs)
         except BaseException:
             self.close()
             raise
@@ -810,6 +855,9 @@ class ReadStream:
         self.tml = threading.Lock()
 
     def close(self):
+        for ecx in self.emit_ctxs:
+            ecx.close()
+        self.emit_ctxs = []
         if self.pinned is not None:
             self.pinned.close(); self.pinned = None
         if self.pipe is not None:
@@ -892,6 +940,47 @@ class ReadStream:
     def size_run(self, cx):
         self.V.align_batch_raw(cx, self.index, self.prm, self.sizing[0], self.sizing[1]).close()
 
+    def size_emitters(self, has_q):
+        """--sam-emitter device: every emit context makes the sizing batch's text once (dropped), so that its buffers are in HBM when
+        trim_to_memory looks; a reference the device emitter cannot serve shows here, before any batch"""
+        import numpy as np
+        if not self.emit_device or self.sizing is None:
+            return
+        sb, so = self.sizing
+        n = len(so) - 1
+        nb, no = np.full(n, ord('r'), np.uint8), np.arange(n + 1, dtype=np.int64)
+        raw = self.V.align_batch_raw(self.pipe.ctxs[0], self.index, self.prm, sb, so)
+        try:
+            for ecx in self.emit_ctxs:
+                self.V.sam_emit_device(ecx, self.index, self.opts, nb, no, sb, so, raw, quals=np.full(int(so[-1]), ord('I'), np.uint8) if has_q else None, qual_off=so if has_q else None)
+        except self.V.VmxError as e:
+            if e.code != VM_ERR_UNSUPPORTED:
+                raise
+            self.give_up_device(str(e))
+        finally:
+            raw.close()
+
+    def give_up_device(self, why):
+        """the host emitter from here on: the emit jobs share the host threads a host run has, and the emit contexts no thread owns are closed
+        (a thread that owns one closes it when it next emits: drop_emit_context)"""
+        with self.tml:
+            if not self.emit_device:
+                return
+            self.emit_device = False
+            self.emit_threads = max(1, self.emit_total // self.emit_jobs)
+        _device_emitter_given_up(why, self.rank)
+        while True:
+            try:
+                self.emit_free.get_nowait().close()
+            except queue.Empty:
+                break
+        self.drop_emit_context()
+
+    def drop_emit_context(self):
+        cx = getattr(self.emit_local, 'cx', None)
+        if cx is not None:
+            cx.close(); self.emit_local.cx = None
+
     def plan(self, wnd):
         """the rank's batches of a window: lists of read indices in schedule order"""
         import numpy as np
@@ -923,6 +1012,7 @@ class ReadStream:
                     n_oom = pipe.warm(run=size, keep=2)
                     if n_oom and self.rank == 0:
                         sys.stderr.write('vacmapx: %d of %d batches in flight given up: no HBM left for their work pools\n' % (n_oom, n_oom + pipe.inflight))
+                    self.size_emitters(bool(first['quals_off'][-1]))
                 except BaseException as e:
                     self.errs.append(e)
             dropped = pipe.trim_to_memory(self.sw['VMX_MIN_FREE_GB'])
@@ -1047,6 +1137,13 @@ class ReadStream:
             if w.left == 0:
                 w.ready.set()
 
+    def emit_context(self):
+        """the calling emit thread's own context (taken when the thread makes its first text)"""
+        cx = getattr(self.emit_local, 'cx', None)
+        if cx is None:
+            cx = self.emit_local.cx = self.emit_free.get_nowait()
+        return cx
+
     def emit(self, w, ix, sb, so, raw):
         """the SAM text of one batch (emit pool): (read indices, text, line offsets, lines, reads skipped)"""
         import numpy as np
@@ -1059,7 +1156,17 @@ class ReadStream:
             nb, no = gather(self.lib, wnd['names'], wnd['names_off'], ix)
             qb, qo = gather(self.lib, wnd['quals'], wnd['quals_off'], ix) if w.has_q else (None, None)
             cb, co = gather(self.lib, wnd['comments'], wnd['comments_off'], ix) if w.has_c else (None, None)
-            text, toff, nl, ns = self.V.sam_emit(self.lib, self.index, self.opts, nb, no, sb, so, raw, quals=qb, qual_off=qo, comments=cb, com_off=co, nthreads=self.emit_threads)
+            text = None
+            if self.emit_device:
+                try:
+                    text, toff, nl, ns = self.V.sam_emit_device(self.emit_context(), self.index, self.opts, nb, no, sb, so, raw, quals=qb, qual_off=qo)
+                except self.V.VmxError as e:
+                    if e.code != VM_ERR_UNSUPPORTED:
+                        raise
+                    self.give_up_device(str(e))
+            if text is None:
+                self.drop_emit_context()
+                text, toff, nl, ns = self.V.sam_emit(self.lib, self.index, self.opts, nb, no, sb, so, raw, quals=qb, qual_off=qo, comments=cb, com_off=co, nthreads=self.emit_threads)
             if self.args.debug and ns:                  # the reference's per-read failure log (--debug, mammap_clrnano.py:24120-24123)
                 nbb = nb.tobytes() if hasattr(nb, 'tobytes') else bytes(nb)
                 for x in np.nonzero(np.asarray(raw.status) != 0)[0]:

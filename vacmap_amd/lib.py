@@ -166,6 +166,8 @@ class VmxLib:
         L.vm_align_batch.argtypes = [vp, vp, P(Params), i64, cp, vp, P(P(Record)), P(i64), P(vp), vp, P(BatchStats)]
         L.vm_align_trace.argtypes = [vp, vp, P(Params), i64, cp, vp, C.c_int, P(P(i64)), P(P(i64))]
         L.vm_sam_emit.argtypes = [vp, P(SamOpts), i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, C.c_int, P(vp), P(P(i64)), P(i64), P(i64)]
+        L.vm_sam_emit_device.argtypes = [vp, vp, P(SamOpts), i64, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, P(vp), P(P(i64)), P(i64), P(i64)]
+        L.vm_sam_emit_device_times.argtypes = [vp, P(dbl)]
         L.vm_blob_gather.argtypes = [vp, vp, vp, i64, vp, vp]; L.vm_blob_gather.restype = i64
         L.vm_blob_write_parts.argtypes = [C.c_int, vp, vp, vp, vp, i64]; L.vm_blob_write_parts.restype = i64
         L.vm_pinned_alloc.argtypes = [i64, C.c_int]; L.vm_pinned_alloc.restype = vp
@@ -527,6 +529,32 @@ def sam_emit(lib, index, opts, names, name_off, seqs, seq_off, raw, quals=None, 
     tot = int(off[-1])
     buf = _OwnedText(lib, text, tot)          # a view of the library's buffer (no copy of ~150 MB per batch); freed with the object
     return buf.array, off, nl.value, ns.value
+
+
+def sam_emit_device(ctx, index, opts, names, name_off, seqs, seq_off, raw, quals=None, qual_off=None):
+    """SAM lines of a batch made on the GPU (vm_sam_emit_device, on the context's stream): sam_emit's return tuple, byte for byte. Comments
+    are not copied; a reference with letters other than ACGTN raises VmxError(VM_ERR_UNSUPPORTED)."""
+    lib = ctx.lib
+    names = _u8(names); seqs = _u8(seqs)
+    name_off = np.ascontiguousarray(name_off, dtype=np.int64); seq_off = np.ascontiguousarray(seq_off, dtype=np.int64)
+    n = len(seq_off) - 1
+    q = _u8(quals) if quals is not None else None; qo = np.ascontiguousarray(qual_off, dtype=np.int64) if quals is not None else None
+    text = C.c_void_p(); toff = C.POINTER(C.c_int64)(); nl = C.c_int64(); ns = C.c_int64()
+    lib.check(lib.L.vm_sam_emit_device(ctx.h, index.h, C.byref(opts), n, names.ctypes.data, name_off.ctypes.data, seqs.ctypes.data, seq_off.ctypes.data,
+                                       q.ctypes.data if q is not None else None, qo.ctypes.data if qo is not None else None,
+                                       C.cast(raw.recs, C.c_void_p), raw.nrec, raw.blob, raw.status.ctypes.data if len(raw.status) else None,
+                                       C.byref(text), C.byref(toff), C.byref(nl), C.byref(ns)))
+    off = np.ctypeslib.as_array(toff, shape=(n + 1,)).copy()
+    lib.L.vm_free(toff)
+    buf = _OwnedText(lib, text, int(off[-1]))
+    return buf.array, off, nl.value, ns.value
+
+
+def sam_emit_device_times(ctx):
+    """(upload, passes, download) wall seconds of the context's latest sam_emit_device call"""
+    t = (C.c_double * 3)()
+    ctx.lib.check(ctx.lib.L.vm_sam_emit_device_times(ctx.h, t))
+    return tuple(t)
 
 
 class _OwnedText:
