@@ -6,6 +6,8 @@ these functions judge both. Scores and hashes are int64 / uint64; every DP is th
   dpg_score     VMX-DP-G   optimal global dual-affine score; cigar_score rescores a CIGAR under the same scoring
   dpx           VMX-DP-X   banded anti-diagonal x-drop extension: (score, t_e, q_e)
   sketch        VMX-S1     (w, k) window minimizers with minimap2's published hash64, all ties kept
+  map_read      VMX-S1     index lookup under the occurrence cap, hits sorted by (r, q, s), clusters cut at reference gaps > 5000, ranked by
+                           (size desc, first r asc), the first check_num emitted; default_mid_occ is the index's own cap
   ksw2_order_cigar         VMX-DP-G with ksw2's published tie order, cell by cell (small problems only)
 """
 import re
@@ -296,3 +298,98 @@ def index_minimizers(seqs, k, w):
     H, Pp = np.concatenate(hs), np.concatenate(ps)
     o = np.lexsort((Pp, H))
     return H[o], Pp[o]
+
+
+# ------------------------------------------------------------------------------------------------ VMX-S1 map()
+CLUSTER_GAP = 5000               # a new cluster starts where r exceeds the previous r by MORE than this
+MID_OCC_FLOOR = 10
+MID_OCC_TAIL = 2e-4              # the cap sits one above the count at the (1 - 2e-4) quantile of the distinct hashes
+
+
+def default_mid_occ(index_hashes):
+    """the index's own occurrence cap: max(10, counts_sorted[min(floor((1 - 2e-4) nd), nd - 1)] + 1) over the nd distinct hashes"""
+    _, counts = np.unique(np.asarray(index_hashes, dtype=np.uint64), return_counts=True)
+    nd = len(counts)
+    if nd == 0:
+        return MID_OCC_FLOOR
+    counts = np.sort(counts)
+    kth = min(int(np.floor((1.0 - MID_OCC_TAIL) * nd)), nd - 1)
+    return max(MID_OCC_FLOOR, int(counts[kth]) + 1)
+
+
+def lookup_hits(index_hashes, index_positions, k, w, read, mid_occ):
+    """every hit of the read, unordered: a read minimizer (hash h, position q, strand z) whose hash occurs c times in the index yields the c
+    rows (q, r, s, k), r = the occurrence's global position and s = +1 if its strand equals z, else -1 — if 1 <= c <= mid_occ, none
+    otherwise. mid_occ <= 0 stands for the index's default. index_hashes / index_positions as index_minimizers returns them."""
+    IH = np.asarray(index_hashes, dtype=np.uint64); IP = np.asarray(index_positions, dtype=np.uint64)
+    if mid_occ <= 0:
+        mid_occ = default_mid_occ(IH)
+    h, p, z = sketch(read, k, w)
+    lo = np.searchsorted(IH, h, 'left'); c = np.searchsorted(IH, h, 'right') - lo
+    ok = (c >= 1) & (c <= mid_occ)
+    lo, c, q, z = lo[ok].astype(np.int64), c[ok].astype(np.int64), p[ok].astype(np.int64), z[ok].astype(np.int64)
+    n = int(c.sum())
+    owner = np.repeat(np.arange(len(c)), c)                                  # hit -> its read minimizer
+    j = np.arange(n, dtype=np.int64) - np.repeat(np.cumsum(c) - c, c)        # ... and the how-manieth occurrence
+    pv = IP[lo[owner] + j]
+    out = np.empty((n, 4), np.int64)
+    out[:, 0] = q[owner]; out[:, 1] = (pv >> np.uint64(1)).astype(np.int64)
+    out[:, 2] = np.where((pv & np.uint64(1)).astype(np.int64) == z[owner], 1, -1); out[:, 3] = k
+    return out
+
+
+def cluster_hits(hits, check_num):
+    """(n, 4) rows (q, r, s, l) in any order -> the rows map() returns: sorted by (r, q, s); a new cluster starts where r exceeds the previous
+    r by more than 5000; clusters ranked by (size descending, first r ascending); the first check_num kept (all if check_num <= 0), emitted
+    one after another in rank order, hits in sorted order"""
+    hits = np.asarray(hits, dtype=np.int64).reshape(-1, 4)
+    n = len(hits)
+    if n == 0:
+        return hits.copy()
+    hits = hits[np.lexsort((hits[:, 2], hits[:, 0], hits[:, 1]))]
+    r = hits[:, 1]
+    first = np.concatenate([[True], np.diff(r) > CLUSTER_GAP])
+    start = np.nonzero(first)[0]
+    size = np.diff(np.concatenate([start, [n]]))
+    rank = np.lexsort((r[start], -size))
+    if check_num > 0:
+        rank = rank[:check_num]
+    sz = size[rank]
+    take = np.repeat(start[rank], sz) + (np.arange(int(sz.sum())) - np.repeat(np.cumsum(sz) - sz, sz))
+    return hits[take]
+
+
+def map_read(index_hashes, index_positions, k, w, read, check_num, mid_occ):
+    """VMX-S1 map(): lookup_hits, then cluster_hits"""
+    return cluster_hits(lookup_hits(index_hashes, index_positions, k, w, read, mid_occ), check_num)
+
+
+def cluster_hits_brute(hits, check_num):
+    """cluster_hits() with Python lists, one rule per line (tiny inputs)"""
+    hs = sorted((int(r), int(q), int(s), int(l)) for q, r, s, l in hits)
+    clusters = []
+    for h in hs:
+        if clusters and h[0] - clusters[-1][-1][0] <= CLUSTER_GAP:
+            clusters[-1].append(h)
+        else:
+            clusters.append([h])
+    clusters.sort(key=lambda c: (-len(c), c[0][0]))
+    if check_num > 0:
+        clusters = clusters[:check_num]
+    return np.array([(q, r, s, l) for c in clusters for r, q, s, l in c], dtype=np.int64).reshape(-1, 4)
+
+
+def map_read_brute(index_hashes, index_positions, k, w, read, check_num, mid_occ):
+    """map_read() with a dictionary and loops (tiny inputs)"""
+    occ = {}
+    for h, pv in zip(index_hashes.tolist(), index_positions.tolist()):
+        occ.setdefault(h, []).append(pv)
+    if mid_occ <= 0:
+        cs = sorted(len(v) for v in occ.values())
+        mid_occ = max(10, cs[min(int((1 - 2e-4) * len(cs)), len(cs) - 1)] + 1) if cs else 10
+    hits = []
+    for h, q, z in zip(*(a.tolist() for a in sketch_brute(read, k, w))):
+        pvs = occ.get(h, [])
+        if 1 <= len(pvs) <= mid_occ:
+            hits += [(q, pv >> 1, 1 if (pv & 1) == z else -1, k) for pv in pvs]
+    return cluster_hits_brute(hits, check_num)

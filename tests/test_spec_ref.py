@@ -192,6 +192,64 @@ def test_kmer_hashes_and_sketch():
                 assert all(np.array_equal(a, b) for a, b in zip(got, exp)), (k, w, s)
 
 
+def test_cluster_hits_on_hand_written_sets():
+    """VMX-S1's cluster rules on hit sets small enough to rank by eye; rows are (q, r, s, l)"""
+    H = lambda *rows: np.array([(q, r, s, 15) for q, r, s in rows], dtype=np.int64).reshape(-1, 4)
+    out = lambda hits, cn: [tuple(x[:3]) for x in R.cluster_hits(hits, cn).tolist()]
+    # a gap of exactly 5000 stays inside the cluster, 5001 cuts
+    assert out(H((7, 10000, 1), (3, 5000, 1)), 0) == [(3, 5000, 1), (7, 10000, 1)] and out(H((7, 10000, 1), (3, 5000, 1)), 1) == [(3, 5000, 1), (7, 10000, 1)]
+    assert out(H((7, 10001, 1), (3, 5000, 1)), 1) == [(3, 5000, 1)] and out(H((7, 10001, 1), (3, 5000, 1)), 2) == [(3, 5000, 1), (7, 10001, 1)]
+    # a chain of steps of 5000 is one cluster however long it gets
+    chain = H(*[(i, 5000 * i, 1) for i in range(6)])
+    assert out(chain, 1) == [(i, 5000 * i, 1) for i in range(6)]
+    # inside a cluster: r first, then q, then s (-1 before +1)
+    tie = H((9, 100, 1), (2, 100, 1), (2, 100, -1), (5, 50, -1))
+    assert out(tie, 0) == [(5, 50, -1), (2, 100, -1), (2, 100, 1), (9, 100, 1)]
+    # sizes 1, 2, 2, 3 in reference order 2 (at 0), 1 (at 20000), 3 (at 40000), 2 (at 60000): rank = 3, then the twos by first r, then the one
+    hits = H((0, 0, 1), (1, 10, 1), (2, 20000, -1), (3, 40000, 1), (4, 40010, 1), (5, 45010, 1), (6, 60000, 1), (7, 60001, -1))
+    three = [(3, 40000, 1), (4, 40010, 1), (5, 45010, 1)]; two_a = [(0, 0, 1), (1, 10, 1)]; two_b = [(6, 60000, 1), (7, 60001, -1)]; one = [(2, 20000, -1)]
+    assert out(hits, 1) == three and out(hits, 2) == three + two_a and out(hits, 3) == three + two_a + two_b
+    assert out(hits, 4) == out(hits, 5) == out(hits, 0) == out(hits, -1) == three + two_a + two_b + one
+    assert out(hits[::-1], 3) == three + two_a + two_b                                                  # the order handed in does not matter
+    assert R.cluster_hits(np.zeros((0, 4), np.int64), 3).shape == (0, 4)
+    rng = np.random.default_rng(6)
+    for _ in range(300):
+        n = int(rng.integers(0, 14))
+        h = np.stack([rng.integers(0, 6, n), rng.choice([0, 1, 4999, 5000, 5001, 5002, 10000, 10001, 15002, 30000, 30001], n), rng.choice([-1, 1], n), np.full(n, 15)], axis=1)
+        for cn in (-1, 0, 1, 2, 3, 20):
+            assert np.array_equal(R.cluster_hits(h, cn), R.cluster_hits_brute(h, cn)), (h.tolist(), cn)
+
+
+def test_default_mid_occ_on_hand_written_counts():
+    hs = lambda counts: np.repeat(np.arange(len(counts), dtype=np.uint64) * np.uint64(977), counts)
+    assert R.default_mid_occ(hs([])) == 10 and R.default_mid_occ(hs([1])) == 10 and R.default_mid_occ(hs([9])) == 10 and R.default_mid_occ(hs([10])) == 11
+    assert R.default_mid_occ(hs([30, 1, 1])) == 31                     # nd = 3: floor(0.9998 * 3) = 2, the largest count
+    assert R.default_mid_occ(hs([1] * 4998 + [50])) == 51               # nd = 4999: index 4998, the largest
+    assert R.default_mid_occ(hs([50, 30] + [1] * 4999)) == 31          # nd = 5001: floor(4999.9998) = 4999 of 0 ... 5000, the second largest
+    assert R.default_mid_occ(hs([50, 30] + [1] * 9999)) == 10          # nd = 10001: floor(9998.9998) = 9998 of 0 ... 10000, the third largest
+
+
+def test_map_read_on_a_hand_written_reference():
+    """k = 3, w = 1: ACG (canonical, strand 0), its reverse complement CGT (strand 1) and AAC, each between N"""
+    ref = ['NACGNNNNCGTN', 'AACNACG']                      # ACG at 1 and (second contig, offset 12) 16, CGT at 8, AAC at 12
+    IH, IP = R.index_minimizers(ref, 3, 1)
+    assert sorted((IP >> np.uint64(1)).tolist()) == [1, 8, 12, 16] and R.default_mid_occ(IH) == 10
+    rows = lambda read, cn, mo: R.map_read(IH, IP, 3, 1, read, cn, mo).tolist()
+    assert rows('ACG', 0, 3) == [[0, 1, 1, 3], [0, 8, -1, 3], [0, 16, 1, 3]]                   # one cluster: every gap <= 5000
+    assert rows('ACG', 0, 2) == [] and rows('ACG', 0, -1) == rows('ACG', 0, 3)                  # three occurrences against a cap of 2; -1 = the default (10)
+    assert rows('CGTNAAC', 0, 3) == [[0, 1, -1, 3], [0, 8, 1, 3], [4, 12, 1, 3], [0, 16, -1, 3]]
+    assert rows('CGTNAAC', 0, 1) == [[4, 12, 1, 3]] and rows('NN', 0, 3) == [] and rows('', 0, 3) == [] and rows('AC', 0, 3) == []
+    assert rows('GTT', 1, 1) == [[0, 12, -1, 3]]                                                # the reverse complement of AAC
+    rng = np.random.default_rng(7)
+    for k, w in ((3, 1), (3, 2), (4, 3), (5, 1)):
+        contigs = [_rs(rng, 60, 'ACGTN'), _rs(rng, 25, 'ACGT')]
+        ih, ip = R.index_minimizers(contigs, k, w)
+        for _ in range(12):
+            read = _rs(rng, int(rng.integers(0, 30)), 'ACGTN')
+            for cn, mo in ((0, 1), (1, 2), (2, 3), (3, -1), (-1, 50)):
+                assert np.array_equal(R.map_read(ih, ip, k, w, read, cn, mo), R.map_read_brute(ih, ip, k, w, read, cn, mo)), (contigs, read, k, w, cn, mo)
+
+
 # ------------------------------------------------------------------------------------------------ the oracle against the references
 def test_oracle_edit_distance_is_spec(oracle):
     qs, ts = SC.edit_distance_pairs(np.random.default_rng(10), (0, 1, 63, 64, 65, 127, 128, 129, 700))

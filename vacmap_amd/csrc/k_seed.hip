@@ -599,7 +599,7 @@ __device__ __forceinline__ void vmx_cluster_body(uint64_t* __restrict__ keys, ui
             const bool cf_done = tile >= VMX_CF_TOTAL_U64 && check_num > 0 && check_num <= 1024 &&
                                  vmx_cluster_filtered<BLOCK, false>(K, n, check_num, kmer, s_sort, tile, s_scan, rows + 4 * key_off[r], CK, &n_anchors[r]);
 #ifdef VMX_EMU
-            if (threadIdx.x == 0) ++(cf_done ? g_vmx_cf_taken : g_vmx_cf_declined);
+            if (threadIdx.x == 0) atomicAdd(cf_done ? &g_vmx_cf_taken : &g_vmx_cf_declined, 1);     // (blocks run on several OS threads)
 #endif
             if (!cf_done && threadIdx.x == 0) decl[atomicAdd(n_decl, 1)] = r;
             __syncthreads();
@@ -610,7 +610,7 @@ __device__ __forceinline__ void vmx_cluster_body(uint64_t* __restrict__ keys, ui
             const bool cf_done = tile >= VMX_SORT_LDS_BIG && check_num > 0 && check_num <= 1024 &&
                                  vmx_cluster_filtered<BLOCK, true>(K, n, check_num, kmer, s_sort, tile, s_scan, rows + 4 * key_off[r], CK, &n_anchors[r]);
 #ifdef VMX_EMU
-            if (threadIdx.x == 0) ++(cf_done ? g_vmx_cf_taken : g_vmx_cf_declined);
+            if (threadIdx.x == 0) atomicAdd(cf_done ? &g_vmx_cf_taken : &g_vmx_cf_declined, 1);     // (blocks run on several OS threads)
 #endif
             if (!cf_done && threadIdx.x == 0) decl[atomicAdd(n_decl, 1)] = r;
             __syncthreads();
