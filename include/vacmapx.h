@@ -379,14 +379,25 @@ int vm_bgzf_compress(vm_ctx*, const void* in, int64_t n, char** out, int64_t* n_
  * vm_bam_reader_open: VM_ERR_UNSUPPORTED when the file is gzip without the BGZF BC subfield, VM_ERR_ARG when the inflated stream does not begin
  * with BAM\1, VM_ERR_IO for everything else that is wrong with the file. vm_bam_reader_read has vm_fastx_read's signature and return
  * convention: names, bases (a reverse-strand record turned back to the read's orientation: reversed, ACGTN complemented) and qualities + 33
- * (empty when the record has none); comments are always empty; records without bases are dropped. The reader reads the file ahead on a thread
+ * (empty when the record has none); comments are empty unless the reader was opened with tags (vm_bam_reader_open_tags); records without bases are dropped. The reader reads the file ahead on a thread
  * of its own. vm_bam_reader_stats: seconds of I/O thread work, waiting for it, upload + inflate, record walk, sizes + scans + decode, download,
- * handing out; then windows, file bytes, inflated bytes, records handed to the caller's windows, records dropped (12 numbers), as of the
+ * handing out; then windows, file bytes, inflated bytes, records handed to the caller's windows, records dropped (12 numbers; a 13th with tags: auxiliary fields left out), as of the
  * latest window the caller has begun to take (the window decoded ahead is not in them yet).
  * An open reader owns its context (it decodes ahead on a thread of its own): close it before other calls use the context or destroy it. */
 int vm_bgzf_decompress(vm_ctx*, const void* in, int64_t n, char** out, int64_t* n_out);
 typedef struct vm_bam_reader vm_bam_reader;
 int vm_bam_reader_open(vm_ctx*, const char* path, vm_bam_reader** out);
+/* vm_bam_reader_open that also carries the records' auxiliary fields (SAMv1 4.2.4) to the caller: vm_bam_reader_read then fills comments / com_off
+ * with every read's selected fields as SAM text, `XX:T:value` joined by one tab in record order, made on the GPU (the form vm_sam_emit appends
+ * as a read's comment). tags: NULL or "" = exactly vm_bam_reader_open; "*" = every field; otherwise two-character tags separated by commas
+ * ("MM,ML,MN"); anything else is VM_ERR_ARG. A c C s S i I -> :A: / :i:, f -> :f: (the shortest %.{p}g, p = 1 ... 9, that strtod and a cast read
+ * back as the same float32), Z / H verbatim, B -> :B:t,v1,v2,... Duplicated tags are passed through; nothing is re-oriented for a reverse-strand
+ * record (MM / ML and the kinetics arrays are defined on the read as sequenced, which is what the reader restores). A field that SAM text
+ * cannot hold (a byte outside 0x20-0x7e in A or Z, an H that is not an even number of hex digits, a non-finite f or B:f element) is left out
+ * and counted: the 13th number of vm_bam_reader_stats. Malformed aux data (fewer than 3 bytes left, an unknown type or sub-type, a value,
+ * string or array that runs past the record) fails the read with VM_ERR_IO, the first bad record named. Aux bytes are looked at only when
+ * tags were asked for, and never in a record that is dropped for having no bases. */
+int vm_bam_reader_open_tags(vm_ctx*, const char* path, const char* tags, vm_bam_reader** out);
 int64_t vm_bam_reader_read(vm_bam_reader*, int64_t max_reads, int64_t max_bases, char** names, int64_t** name_off, char** seqs, int64_t** seq_off, char** quals,
                            int64_t** qual_off, char** comments, int64_t** com_off);
 int vm_bam_reader_stats(const vm_bam_reader*, double* out, int n);

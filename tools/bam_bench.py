@@ -18,6 +18,11 @@
         the reader's own phase times), a bench.py line of the same session (what the reader must feed), driver._bam_chunks on the first
         2 000 records (the parent's reader) and one host thread of gzip.decompress on the same file. --only reader: the first part alone,
         for a run under `rocprofv3 --kernel-trace --stats`.
+    python tools/bam_bench.py input --tags [--gb 2] [--tmp DIR] [--out profiles/bam_tags_reader.json]
+        the same file shape with MM / ML / MN on every read (one ML value per 8 bases, zlib level 6 members), read with tags=None (the reader as
+        it is without tags) and with tags='*' (the auxiliary fields turned into comment text on the device), two passes each: reads/s, the
+        producer's per-step clocks and the comment bytes per read of the second passes. Run it under `rocprofv3 --kernel-trace --stats` with a
+        smaller --gb for the aux kernels' own time next to k_bgzf_inflate's.
     python tools/bam_bench.py input-driver [--reads 40960] [--replicate 8] [--rounds 3] [--out profiles/bam_input_driver.json]
         the driver on the same reads as plain FASTQ and as unaligned BAM with --bam-reader native, alternated in fresh processes: the
         driver's own wait_input seconds and loop time per run.
@@ -247,6 +252,56 @@ def input_bench(args):
     _save(res, args.out)
 
 
+def tags_bench(args):
+    """lib.BamReader on 15 kb reads that carry MM / ML / MN, with and without tags"""
+    import struct
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import bam_input_cases as K
+    from vacmap_amd.lib import Context, BamReader
+    os.makedirs(args.tmp, exist_ok=True)
+    ctx = Context(0)
+    head, recs, _ = K.scale_records(int(args.gb * (1 << 30)))
+    rng = np.random.default_rng(23)
+    aux_of = {}
+
+    def tagged(rec):
+        n = struct.unpack_from('<i', rec, 20)[0]
+        if n not in aux_of:                                             # (64 read lengths in the pool: one aux region each)
+            k = n // 8
+            mm = b'MMZC+m?,' + b','.join(b'%d' % x for x in rng.integers(0, 12, k)) + b';\0'
+            aux_of[n] = mm + b'MLBC' + struct.pack('<I', k) + rng.integers(0, 256, k).astype(np.uint8).tobytes() + b'MNi' + struct.pack('<i', n)
+        return struct.pack('<i', len(rec) - 4 + len(aux_of[n])) + rec[4:] + aux_of[n]
+    recs = [tagged(r) for r in recs]
+    total = len(head) + sum(len(r) for r in recs)
+    p = os.path.join(args.tmp, 'in_tags.bam')
+    K.write_bgzf_zlib(p, [head] + recs)
+    n_reads = len(recs)
+    del recs
+    res = {'reads': n_reads, 'inflated_bytes': total, 'file_bytes': os.path.getsize(p), 'legs': {}}
+    for leg, tags in (('tags_none', None), ('tags_all', '*')):
+        runs = []
+        for rep in range(2):                                            # the first pass grows the reader's pools and warms the page cache
+            t0 = time.time()
+            rd = BamReader(ctx, p, tags=tags)
+            n = cbytes = 0
+            for ch in iter(lambda: rd.read(4096), None):
+                n += len(ch['seqs_off']) - 1; cbytes += int(ch['comments_off'][-1])
+            dt = time.time() - t0
+            st = rd.stats(); rd.close()
+            runs.append({'reads': n, 'wall_s': dt, 'reads_per_s': n / dt, 'inflated_GBps': total / dt / 1e9, 'comment_bytes_per_read': cbytes / max(n, 1), 'phases': st})
+        res['legs'][leg] = {'first_pass': runs[0], 'second_pass': runs[1]}
+        print(json.dumps({leg: runs[1]}), flush=True)
+    a, b = res['legs']['tags_none']['second_pass'], res['legs']['tags_all']['second_pass']
+    res['tags_all_over_tags_none_reads_per_s'] = b['reads_per_s'] / a['reads_per_s']
+    w = max(b['phases']['windows'], 1)
+    res['per_window_ms'] = {'inflate_tags_none': 1e3 * a['phases']['inflate_s'] / w, 'inflate_tags_all': 1e3 * b['phases']['inflate_s'] / w,
+                            'decode_tags_none': 1e3 * a['phases']['decode_s'] / w, 'decode_tags_all': 1e3 * b['phases']['decode_s'] / w,
+                            'note': 'decode_s holds sizes, scans, k_bam_in_decode and, with tags, both aux passes and their scan'}
+    os.remove(p)
+    ctx.close()
+    _save(res, args.out)
+
+
 def input_driver(args):
     """wait_input and loop seconds of the driver on FASTQ and on unaligned BAM (--bam-reader native) of the same reads, alternated"""
     sys.path.insert(0, os.path.join(ROOT, 'tests'))
@@ -319,13 +374,13 @@ def input_driver(args):
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('what', choices=['kernels', 'driver', 'sorted', 'input', 'input-driver'])
-    ap.add_argument('--only', default=None); ap.add_argument('--run-timeout', type=float, default=600.0); ap.add_argument('--bench-steps', type=int, default=12)
+    ap.add_argument('--only', default=None); ap.add_argument('--tags', action='store_true'); ap.add_argument('--run-timeout', type=float, default=600.0); ap.add_argument('--bench-steps', type=int, default=12)
     ap.add_argument('--gb', type=float, default=2.0); ap.add_argument('--reads', type=int, default=40960); ap.add_argument('--replicate', type=int, default=8); ap.add_argument('--ref-mb', type=float, default=100.0)
     ap.add_argument('--rounds', type=int, default=3); ap.add_argument('--t', type=int, default=16); ap.add_argument('--tmp', default='/tmp/vmx_bam_bench')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     if a.what == 'input':
-        input_bench(a)
+        tags_bench(a) if a.tags else input_bench(a)
     elif a.what == 'input-driver':
         input_driver(a)
     else:

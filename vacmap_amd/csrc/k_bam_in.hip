@@ -20,6 +20,7 @@
 //
 // Records: k_bam_in_walk follows the block_size chain (serial by nature: one dependent load per record), k_bam_in_sizes sizes every
 // record's name, bases and qualities, and after four scans (names, bases, qualities, kept records) k_bam_in_decode writes them, one wave per record, 64 bases per step.
+// Auxiliary fields (only when tags were asked for): k_bam_in_aux_size / k_bam_in_aux_write, at the end of this file.
 #include "vmx_bam.h"
 
 #ifdef VMX_EMU
@@ -389,4 +390,317 @@ __global__ void __launch_bounds__(256) k_bam_in_decode(const uint8_t* buf, const
         seqs[so + at] = (char)((c < 8 ? lo >> (8 * c) : hi >> (8 * (c - 8))) & 0xff);
         if (hasq) quals[qo + at] = (char)(qu[j] + 33);
     }
+}
+
+// ------------------------------------------------------------------------------------------------ auxiliary fields -> SAM text
+// k_bam_in_aux_size / k_bam_in_aux_write: the aux region of a record (SAMv1 §4.2.4: tag[2] type[1] value, from the end of the qualities to the
+// end of block_size) as the tab-separated `XX:T:value` text the emitters take as a read's comment. One wave per record, launched only when
+// tags were asked for; the size pass is the write pass without its stores (one body, bax_record<WRITE>). The field chain is serial and
+// wave-uniform (cursor, tag, type, count: scalar registers); what is inside a field belongs to the wave: the NUL of a Z / H value is found
+// by ballot, 64 bytes per step, with the printable / hex check in the same ballots; a B array is taken 64 elements per step, every lane
+// making the text of its own element in two 64-bit registers (`,` sign digits: at most 16 bytes), a 32-bit wave scan placing them.
+// A float's text is the shortest %.{p}g, p = 1 ... 9, that strtod followed by a cast reads back as the same float32: exact integer
+// arithmetic on a fixed 320-bit integer (bax_scaled), no floating point at all, so that BAM in -> BAM out keeps the bits.
+// WHAT BOUNDS EVERY ACCESS: a load is made at an offset below the record's end (4 + block_size, which k_bam_in_walk has checked against the
+// window) only after the field's extent has been compared with that end; a store is made at an offset that the size pass's arithmetic,
+// repeated here on the same bytes, has summed into the record's allotment coff[i + 1] - coff[i]; a record whose allotment is 0 (nothing
+// selected, or malformed) stores nothing. ORDERING: whether a field is kept or dropped needs a sweep over its value; the write pass makes
+// that sweep again on the input rather than taking a flag from the size pass, and no lane loads a byte that this launch stored, so
+// there is no store -> load ordering to keep and bzi_store_fence() is not needed here.
+// The first malformed record wins (atomicMin on record << 8 | code); fields that SAM text cannot express are left out and counted.
+
+struct BaxText { uint64_t lo, hi; int len; };       // up to 16 characters, the first in lo's low byte
+
+__device__ __forceinline__ void bax_put(BaxText& t, int pos, uint32_t c) { if (pos < 8) t.lo |= (uint64_t)c << (8 * pos); else t.hi |= (uint64_t)c << (8 * (pos - 8)); }
+__device__ __forceinline__ uint32_t bax_get(const BaxText& t, int pos) { return (uint32_t)((pos < 8 ? t.lo >> (8 * pos) : t.hi >> (8 * (pos - 8))) & 0xffu); }
+__device__ __forceinline__ int bax_ndig(uint32_t v) {
+    return 1 + (v >= 10u) + (v >= 100u) + (v >= 1000u) + (v >= 10000u) + (v >= 100000u) + (v >= 1000000u) + (v >= 10000000u) + (v >= 100000000u) + (v >= 1000000000u);
+}
+// the nd decimal digits of v (leading zeros where v has fewer) at positions [at, at + nd)
+__device__ __forceinline__ void bax_digits(BaxText& t, int at, uint32_t v, int nd) { for (int k = nd - 1; k >= 0; --k) { bax_put(t, at + k, '0' + v % 10u); v /= 10u; } }
+
+__device__ __forceinline__ BaxText bax_int(int64_t v, bool comma) {
+    BaxText t{0, 0, 0};
+    int at = 0;
+    if (comma) bax_put(t, at++, ',');
+    if (v < 0) bax_put(t, at++, '-');
+    const uint32_t a = (uint32_t)(v < 0 ? -v : v);
+    const int nd = bax_ndig(a);
+    bax_digits(t, at, a, nd);
+    t.len = at + nd;
+    return t;
+}
+
+#define BAX_W 10                        // 320 bits: a 55-bit integer times 10^62 is the largest value held
+struct BaxBig { uint32_t w[BAX_W]; };   // (indexed by unrolled loops only: registers, no scratch)
+__device__ __forceinline__ void bax_mul(BaxBig& b, uint32_t f) {
+    uint64_t c = 0;
+#pragma unroll
+    for (int i = 0; i < BAX_W; ++i) { c += (uint64_t)b.w[i] * f; b.w[i] = (uint32_t)c; c >>= 32; }
+}
+__device__ __forceinline__ uint32_t bax_div(BaxBig& b, uint32_t d) {
+    uint64_t r = 0;
+#pragma unroll
+    for (int i = BAX_W - 1; i >= 0; --i) { r = r << 32 | b.w[i]; b.w[i] = (uint32_t)(r / d); r %= d; }
+    return (uint32_t)r;
+}
+__device__ __forceinline__ void bax_shl(BaxBig& b, int n) {
+    for (; n >= 32; n -= 32) {
+#pragma unroll
+        for (int i = BAX_W - 1; i >= 1; --i) b.w[i] = b.w[i - 1];
+        b.w[0] = 0;
+    }
+    if (n) {
+#pragma unroll
+        for (int i = BAX_W - 1; i >= 1; --i) b.w[i] = b.w[i] << n | b.w[i - 1] >> (32 - n);
+        b.w[0] <<= n;
+    }
+}
+// true when a set bit was shifted out
+__device__ __forceinline__ bool bax_shr(BaxBig& b, int n) {
+    uint32_t lost = 0;
+    for (; n >= 32; n -= 32) {
+        lost |= b.w[0];
+#pragma unroll
+        for (int i = 0; i < BAX_W - 1; ++i) b.w[i] = b.w[i + 1];
+        b.w[BAX_W - 1] = 0;
+    }
+    if (n) {
+        lost |= b.w[0] & ((1u << n) - 1u);
+#pragma unroll
+        for (int i = 0; i < BAX_W - 1; ++i) b.w[i] = b.w[i] >> n | b.w[i + 1] << (32 - n);
+        b.w[BAX_W - 1] >>= n;
+    }
+    return lost != 0;
+}
+// floor(N * 2^q * 10^s), which the callers know to be below 2^64; *sticky: the exact value is not an integer
+__device__ static uint64_t bax_scaled(uint64_t N, int q, int s, bool* sticky) {
+    BaxBig b;
+#pragma unroll
+    for (int i = 2; i < BAX_W; ++i) b.w[i] = 0;
+    b.w[0] = (uint32_t)N; b.w[1] = (uint32_t)(N >> 32);
+    bool st = false;
+    if (s >= 0) {
+        for (; s >= 9; s -= 9) bax_mul(b, 1000000000u);
+        uint32_t f = 1;
+        for (; s > 0; --s) f *= 10u;
+        bax_mul(b, f);
+        if (q >= 0) bax_shl(b, q); else st = bax_shr(b, -q);
+    } else {
+        if (q >= 0) bax_shl(b, q); else st = bax_shr(b, -q);
+        s = -s;
+        for (; s >= 9; s -= 9) st |= bax_div(b, 1000000000u) != 0;
+        uint32_t f = 1;
+        for (; s > 0; --s) f *= 10u;
+        st |= bax_div(b, f) != 0;
+    }
+    *sticky = st;
+    return (uint64_t)b.w[0] | (uint64_t)b.w[1] << 32;
+}
+
+// a finite float32 as the shortest %.{p}g (p = 1 ... 9) that reads back: the value is m * 2^e exactly; V = its first 18 decimal digits
+// (and whether more follow) gives every p's correctly rounded candidate (ties to even); a candidate reads back when strtod's double lands
+// where the cast to float32 gives the value again, i.e. between the midpoints to the neighbouring floats, moved by half a double ulp
+// (outwards and inclusive for an even m, where both roundings tie towards it, inwards and exclusive for an odd m). Those two bounds
+// are dyadic too and go through the same scaling, so the test is a comparison of 64-bit integers.
+__device__ static BaxText bax_float(uint32_t bits, bool comma) {
+    BaxText t{0, 0, 0};
+    int at = 0;
+    if (comma) bax_put(t, at++, ',');
+    if (bits >> 31) bax_put(t, at++, '-');
+    const uint32_t ex = (bits >> 23) & 0xffu, fr = bits & 0x7fffffu;
+    if (ex == 0 && fr == 0) { bax_put(t, at++, '0'); t.len = at; return t; }
+    const uint32_t m = ex ? fr | 0x800000u : fr;
+    const int e = ex ? (int)ex - 150 : -149;
+    const int k = 31 - __clz((int)m) + e;                               // floor(log2 x)
+    int E = (k * 78913) >> 18;                                          // floor(k log10 2): floor(log10 x) or one less
+    bool sx, sl, su;
+    uint64_t V = bax_scaled(m, e, 17 - E, &sx);
+    if (V >= 1000000000000000000ull) { ++E; sx |= V % 10u != 0; V /= 10u; }
+    const bool low_edge = fr == 0 && ex > 1;                            // a power of two: the floats below are spaced half as wide
+    const uint64_t Ml = low_edge ? 4ull * m - 1 : 2ull * m - 1, Mh = 2ull * m + 1;
+    const int gl = low_edge ? e - 2 : e - 1, gh = e - 1;
+    const int bl = 64 - __clzll((long long)Ml), bh = 64 - __clzll((long long)Mh);
+    const bool even = (m & 1u) == 0;
+    const uint64_t TL = bax_scaled((Ml << (54 - bl)) + (even ? ~0ull : 1ull), gl + bl - 54, 17 - E, &sl);
+    const uint64_t TU = bax_scaled((Mh << (54 - bh)) + (even ? 1ull : ~0ull), gh + bh - 54, 17 - E, &su);
+    const uint64_t lo_ok = even ? TL + (sl ? 1u : 0u) : TL + 1u, hi_ok = even ? TU : TU - (su ? 0u : 1u);      // a candidate C reads back: lo_ok <= C <= hi_ok
+    uint64_t q = 0, pw = 100000000000000000ull, tp = 10;               // 10^(18 - p), 10^p
+    int p = 1;
+    for (;; ++p, pw /= 10u, tp *= 10u) {
+        q = V / pw;
+        const uint64_t rem = V % pw, half = pw / 2u;
+        if (rem > half || (rem == half && (sx || (q & 1u)))) ++q;
+        const uint64_t C = q * pw;
+        if ((C >= lo_ok && C <= hi_ok) || p == 9) break;
+    }
+    int X = E;
+    if (q == tp) { q /= 10u; ++X; }
+    int L = p;
+    uint32_t d = (uint32_t)q;
+    while (L > 1 && d % 10u == 0) { d /= 10u; --L; }
+    if (X < -4 || X >= p) {                                             // d.ddde+XX
+        uint32_t pl = 1;
+        for (int i = 1; i < L; ++i) pl *= 10u;
+        bax_put(t, at++, '0' + d / pl);
+        if (L > 1) { bax_put(t, at++, '.'); bax_digits(t, at, d % pl, L - 1); at += L - 1; }
+        bax_put(t, at++, 'e'); bax_put(t, at++, X < 0 ? '-' : '+');
+        bax_digits(t, at, (uint32_t)(X < 0 ? -X : X), 2); at += 2;
+    } else if (X >= 0) {
+        const int ip = X + 1;                                           // digits before the point
+        if (L <= ip) {
+            bax_digits(t, at, d, L); at += L;
+            for (int i = L; i < ip; ++i) bax_put(t, at++, '0');
+        } else {
+            uint32_t pl = 1;
+            for (int i = ip; i < L; ++i) pl *= 10u;
+            bax_digits(t, at, d / pl, ip); at += ip;
+            bax_put(t, at++, '.');
+            bax_digits(t, at, d % pl, L - ip); at += L - ip;
+        }
+    } else {
+        bax_put(t, at++, '0'); bax_put(t, at++, '.');
+        for (int i = -1; i > X; --i) bax_put(t, at++, '0');
+        bax_digits(t, at, d, L); at += L;
+    }
+    t.len = at;
+    return t;
+}
+
+template <bool WRITE>
+__device__ __forceinline__ void bax_record(const uint8_t* buf, const int64_t* roff, int64_t n, const uint16_t* sel, int n_sel, int all, const int64_t* coff, const int64_t* kidx,
+                                           int64_t* csz, char* out, int64_t* out_coff, unsigned long long* err_key, unsigned long long* n_drop) {
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = (int)(threadIdx.x & 63);
+    if (i > n) return;
+    if (i == n) {
+        if (lane == 0) { if (WRITE) out_coff[kidx[n]] = coff[n]; else csz[n] = 0; }
+        return;
+    }
+    const uint8_t* r = buf + vmx_uniform_i64(roff[i]);
+    const uint32_t bs = bzi_u(bin_u32(r)), l_name = bzi_u(r[12]), n_cig = bzi_u((uint32_t)r[16] | (uint32_t)r[17] << 8), l_seq = bzi_u(bin_u32(r + 20));
+    if (l_seq == 0) { if (!WRITE && lane == 0) csz[i] = 0; return; }      // a dropped record: its aux bytes are never looked at
+    char* o = nullptr;
+    if (WRITE) {
+        const int64_t at = coff[i];
+        if (lane == 0) out_coff[kidx[i]] = at;
+        if (coff[i + 1] == at) return;                                  // nothing to write
+        o = out + at;
+    }
+    uint32_t p = 36u + l_name + 4u * n_cig + (l_seq + 1u) / 2u + l_seq;   // (k_bam_in_walk: p <= end)
+    const uint32_t end = 4u + bs;
+    uint32_t w = 0, drops = 0;
+    int err = 0;
+#define BAX_PREFIX(tc) do { \
+        const uint32_t tab_ = w ? 1u : 0u; \
+        if (WRITE && (uint32_t)lane < 5u + tab_) { const int j_ = lane - (int)tab_; o[w + lane] = (char)(j_ < 0 ? '\t' : j_ == 0 ? t0 : j_ == 1 ? t1 : j_ == 3 ? (uint32_t)(tc) : (uint32_t)':'); } \
+        w += 5u + tab_; \
+    } while (0)
+    while (p < end) {
+        if (end - p < 3u) { err = VMX_BAM_IN_E_AUX_SHORT; break; }
+        const uint32_t t0 = bzi_u(r[p]), t1 = bzi_u(r[p + 1]), ty = bzi_u(r[p + 2]);
+        p += 3;
+        bool selected = all != 0;
+        if (!selected) {
+            const uint32_t tg = t0 | t1 << 8;
+            for (int b0 = 0; b0 < n_sel && !selected; b0 += 64) selected = __ballot(b0 + lane < n_sel && sel[b0 + lane] == tg) != 0;
+        }
+        const uint32_t fs = ty == 'A' || ty == 'c' || ty == 'C' ? 1u : ty == 's' || ty == 'S' ? 2u : ty == 'i' || ty == 'I' || ty == 'f' ? 4u : 0u;
+        if (fs) {
+            if (end - p < fs) { err = VMX_BAM_IN_E_AUX_FIXED; break; }
+            uint32_t v = 0;
+            for (uint32_t k = 0; k < fs; ++k) v |= (uint32_t)r[p + k] << (8 * k);
+            v = bzi_u(v);
+            if (selected) {
+                if (ty == 'A') {
+                    if (v < 0x20u || v > 0x7eu) ++drops;
+                    else { BAX_PREFIX('A'); if (WRITE && lane == 0) o[w] = (char)v; w += 1; }
+                } else if (ty == 'f' && ((v >> 23) & 0xffu) == 0xffu) ++drops;
+                else {
+                    const int64_t x = ty == 'c' ? (int64_t)(int8_t)v : ty == 's' ? (int64_t)(int16_t)v : ty == 'i' ? (int64_t)(int32_t)v : (int64_t)v;
+                    const BaxText t = ty == 'f' ? bax_float(v, false) : bax_int(x, false);
+                    BAX_PREFIX(ty == 'f' ? 'f' : 'i');
+                    if (WRITE && lane < t.len) o[w + lane] = (char)bax_get(t, lane);
+                    w += bzi_u((uint32_t)t.len);
+                }
+            }
+            p += fs;
+        } else if (ty == 'Z' || ty == 'H') {
+            uint32_t len = 0;
+            bool found = false, bad = false;
+            for (uint32_t q = p; q < end && !found; q += 64) {
+                const bool in = q + (uint32_t)lane < end;
+                const uint32_t b = in ? (uint32_t)r[q + lane] : 1u;
+                const bool isbad = ty == 'Z' ? (b < 0x20u || b > 0x7eu) : !(b - '0' < 10u || (b | 0x20u) - 'a' < 6u);
+                const unsigned long long mz = __ballot(in && b == 0), mb = __ballot(in && b != 0 && isbad);
+                if (mz) { const int f = __ffsll(mz) - 1; found = true; len = q - p + (uint32_t)f; bad |= (mb & ((1ull << f) - 1ull)) != 0; }
+                else bad |= mb != 0;
+            }
+            if (!found) { err = VMX_BAM_IN_E_AUX_NUL; break; }
+            if (ty == 'H' && (len & 1u)) bad = true;
+            if (selected) {
+                if (bad) ++drops;
+                else {
+                    BAX_PREFIX(ty);
+                    if (WRITE) for (uint32_t j = (uint32_t)lane; j < len; j += 64) o[w + j] = (char)r[p + j];
+                    w += len;
+                }
+            }
+            p += len + 1u;
+        } else if (ty == 'B') {
+            if (end - p < 5u) { err = VMX_BAM_IN_E_AUX_COUNT; break; }
+            const uint32_t st = bzi_u(r[p]), cnt = bzi_u(bin_u32(r + p + 1));
+            const uint32_t es = st == 'c' || st == 'C' ? 1u : st == 's' || st == 'S' ? 2u : st == 'i' || st == 'I' || st == 'f' ? 4u : 0u;
+            if (!es) { err = VMX_BAM_IN_E_AUX_SUBTYPE; break; }
+            if ((uint64_t)cnt * es > (uint64_t)(end - p - 5u)) { err = VMX_BAM_IN_E_AUX_COUNT; break; }
+            const uint8_t* a = r + p + 5u;
+            if (selected) {
+                bool drop = false;
+                if (st == 'f')                                              // one non-finite value drops the field, before anything of it is written
+                    for (uint32_t j0 = 0; j0 < cnt && !drop; j0 += 64) {
+                        const uint32_t j = j0 + (uint32_t)lane;
+                        drop = __ballot(j < cnt && (a[4 * (size_t)j + 3] & 0x7fu) == 0x7fu && (a[4 * (size_t)j + 2] & 0x80u)) != 0;
+                    }
+                if (drop) ++drops;
+                else {
+                    BAX_PREFIX('B');
+                    if (WRITE && lane == 0) o[w] = (char)st;
+                    w += 1;
+                    for (uint32_t j0 = 0; j0 < cnt; j0 += 64) {
+                        const uint32_t j = j0 + (uint32_t)lane;
+                        BaxText t{0, 0, 0};
+                        if (j < cnt) {
+                            const uint8_t* s = a + (size_t)j * es;
+                            uint32_t v = s[0];
+                            if (es >= 2) v |= (uint32_t)s[1] << 8;
+                            if (es == 4) v |= (uint32_t)s[2] << 16 | (uint32_t)s[3] << 24;
+                            if (st == 'f') t = bax_float(v, true);
+                            else t = bax_int(st == 'c' ? (int64_t)(int8_t)v : st == 's' ? (int64_t)(int16_t)v : st == 'i' ? (int64_t)(int32_t)v : (int64_t)v, true);
+                        }
+                        const int inc = vmx_wave_incl_scan_i32(t.len);
+                        if (WRITE) for (int k = 0; k < t.len; ++k) o[w + (uint32_t)(inc - t.len + k)] = (char)bax_get(t, k);
+                        w += (uint32_t)vmx_readlane(inc, 63);
+                    }
+                }
+            }
+            p += 5u + cnt * es;
+        } else { err = VMX_BAM_IN_E_AUX_TYPE; break; }
+    }
+#undef BAX_PREFIX
+    if (WRITE) return;
+    if (lane == 0) {
+        csz[i] = err ? 0 : (int64_t)w;
+        if (err) atomicMin(err_key, (unsigned long long)i << 8 | (unsigned long long)err);
+        else if (drops) atomicAdd(n_drop, (unsigned long long)drops);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_bam_in_aux_size(const uint8_t* buf, const int64_t* roff, int64_t n, const uint16_t* sel, int n_sel, int all, int64_t* csz,
+                                                         unsigned long long* err_key, unsigned long long* n_drop) {
+    bax_record<false>(buf, roff, n, sel, n_sel, all, nullptr, nullptr, csz, nullptr, nullptr, err_key, n_drop);
+}
+
+__global__ void __launch_bounds__(256) k_bam_in_aux_write(const uint8_t* buf, const int64_t* roff, int64_t n, const uint16_t* sel, int n_sel, int all, const int64_t* coff,
+                                                          const int64_t* kidx, char* out, int64_t* out_coff) {
+    bax_record<true>(buf, roff, n, sel, n_sel, all, coff, kidx, nullptr, out, out_coff, nullptr, nullptr);
 }

@@ -83,7 +83,8 @@ struct vmx_bgzf_member {
 struct vmx_crc_x2n { uint32_t v[32]; };
 enum { VMX_BGZF_E_BTYPE = 1, VMX_BGZF_E_STORED = 2, VMX_BGZF_E_INPUT = 3, VMX_BGZF_E_LONG = 4, VMX_BGZF_E_SHORT = 5, VMX_BGZF_E_CRC = 6, VMX_BGZF_E_LENS = 7,
        VMX_BGZF_E_CODE = 8, VMX_BGZF_E_DIST = 9, VMX_BGZF_E_TAIL = 10, VMX_BGZF_E_HEADER = 11 };
-enum { VMX_BAM_IN_E_SIZE = 1 };
+enum { VMX_BAM_IN_E_SIZE = 1, VMX_BAM_IN_E_AUX_SHORT = 2, VMX_BAM_IN_E_AUX_TYPE = 3, VMX_BAM_IN_E_AUX_SUBTYPE = 4, VMX_BAM_IN_E_AUX_FIXED = 5, VMX_BAM_IN_E_AUX_NUL = 6,
+       VMX_BAM_IN_E_AUX_COUNT = 7 };
 #define VMX_BAM_IN_MAX_RECORD (1 << 29)      // a larger block_size is taken for corrupt at once (a 300 Mb read is 450 MB), not carried window after window to the end of the file
 // what the record walk leaves: records found, where the incomplete tail begins, the first bad record (all ones: none)
 struct vmx_bam_in_walk { int64_t n_rec, end; uint64_t err_key; };
@@ -92,6 +93,11 @@ __global__ void k_bam_in_walk(const uint8_t* buf, int64_t begin, int64_t end, in
 __global__ void k_bam_in_sizes(const uint8_t* buf, const int64_t* roff, int64_t n, int64_t* nsz, int64_t* ssz, int64_t* qsz, int64_t* keep);
 __global__ void k_bam_in_decode(const uint8_t* buf, const int64_t* roff, int64_t n, const int64_t* noff, const int64_t* soff, const int64_t* qoff, const int64_t* kidx,
                                 char* names, char* seqs, char* quals, int64_t* out_noff, int64_t* out_soff, int64_t* out_qoff);
+// auxiliary fields as comment text: sel = the selected tags (first letter in the low byte), all != 0: every field; csz / coff: bytes per record and their exclusive scan
+__global__ void k_bam_in_aux_size(const uint8_t* buf, const int64_t* roff, int64_t n, const uint16_t* sel, int n_sel, int all, int64_t* csz, unsigned long long* err_key,
+                                  unsigned long long* n_drop);
+__global__ void k_bam_in_aux_write(const uint8_t* buf, const int64_t* roff, int64_t n, const uint16_t* sel, int n_sel, int all, const int64_t* coff, const int64_t* kidx,
+                                   char* out, int64_t* out_coff);
 
 // coordinate sort, merge and CSI (k_bam_sort.hip)
 #define VMX_BAM_RUN_SHIFT 40            // value of the merge sort: run << 40 | index in run

@@ -9,6 +9,8 @@
 #include <fcntl.h>
 #include <unistd.h>
 #include <algorithm>
+#include <cctype>
+#include <cstring>
 #include <cstdlib>
 #include <future>
 #include <thread>
@@ -776,7 +778,7 @@ struct Grow {
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-struct DecodedWin { HostPinned names, seqs, quals, off; int64_t n = 0; };     // a window's reads on the host: blobs and 3 x (n + 1) offsets
+struct DecodedWin { HostPinned names, seqs, quals, comments, off; int64_t n = 0; };     // a window's reads on the host: blobs and 3 (4 with tags) x (n + 1) offsets
 
 struct BamInChunk { HostPinned stage; MemberTab T; int64_t fpos = 0, got = 0; int rc = 0; std::string err; bool not_bgzf = false; double busy = 0; };
 
@@ -793,12 +795,16 @@ struct vm_bam_reader {
     DevBuf d_inf[2]; int which = 0; int64_t tail_off = 0, carry = 0;     // the bytes of d_inf[which] from tail_off on go in front of the next window
     bool hdr_done = false;
     DevBuf d_roff, d_walk, d_sz, d_off, d_tmp, d_names, d_seqs, d_quals, d_ooff;
+    // tags asked for (vm_bam_reader_open_tags): the selection on the device, per-record comment bytes, their scan, the blob, the kept records' offsets, error key + drop counter
+    bool tags_on = false; int tags_all = 0; std::vector<uint16_t> tags;
+    DevBuf d_sel, d_csz, d_coff, d_comments, d_ocoff, d_aux;
+    int64_t n_aux_dropped = 0;
     HostPinned pin;
     DecodedWin win[2]; int cur = 0; int64_t at = 0;     // records [at, win[cur].n) are not handed out yet; the other slot is being produced
     std::future<int> prod; bool prod_on = false; std::string prod_err;      // the next window, decoded ahead on a thread of its own
     int64_t n_seen = 0, n_dropped = 0;                  // records walked / without bases
-    double st[12] = {0};                                // written by whoever produces a window
-    double pub[12] = {0}; double handout_s = 0;         // what vm_bam_reader_stats reads: st as of the latest window the caller's thread has taken over
+    double st[13] = {0};                                // written by whoever produces a window
+    double pub[13] = {0}; double handout_s = 0;         // what vm_bam_reader_stats reads: st as of the latest window the caller's thread has taken over
 };
 
 namespace {
@@ -914,7 +920,7 @@ int bam_in_window(vm_bam_reader* r, int slot) {
         set_error("BAM record " + std::to_string((long long)(r->n_seen + (int64_t)(W.err_key >> 8)) + 1) + ": block_size is below 32, smaller than its name, CIGAR and bases, or above 512 MB");
         return VM_ERR_IO;
     }
-    const int64_t n = W.n_rec;
+    const int64_t n = W.n_rec, rec0 = r->n_seen;
     r->n_seen += n;
     r->tail_off = W.end; r->carry = avail - W.end;
     if (n == 0) return 1;
@@ -926,23 +932,56 @@ int bam_in_window(vm_bam_reader* r, int slot) {
     for (int j = 0; j < 4; ++j) VMX_TRY(prim_scan64_in(c, r->d_tmp, sz + j * col, off + j * col, col));
     int64_t* tot = (int64_t*)r->pin.p;
     for (int j = 0; j < 4; ++j) VMX_HIP(hipMemcpyAsync(tot + j, off + j * col + n, 8, hipMemcpyDeviceToHost, c->stream));
+    const unsigned aux_grid = (unsigned)((n + 1 + 3) / 4);
+    if (r->tags_on) {                                                   // the comment text's size pass, its scan, the first malformed record and the dropped fields
+        VMX_TRY(r->d_csz.reserve(col * 8)); VMX_TRY(r->d_coff.reserve(col * 8)); VMX_TRY(r->d_ocoff.reserve(col * 8)); VMX_TRY(r->d_aux.reserve(16));
+        VMX_HIP(hipMemsetAsync(r->d_aux.p, 0xff, 8, c->stream));
+        VMX_HIP(hipMemsetAsync(r->d_aux.as<uint8_t>() + 8, 0, 8, c->stream));
+        hipLaunchKernelGGL(k_bam_in_aux_size, dim3(aux_grid), dim3(256), 0, c->stream, dst.as<const uint8_t>(), r->d_roff.as<const int64_t>(), n, r->d_sel.as<const uint16_t>(),
+                           (int)r->tags.size(), r->tags_all, r->d_csz.as<int64_t>(), r->d_aux.as<unsigned long long>(), r->d_aux.as<unsigned long long>() + 1);
+        VMX_TRY(prim_scan64_in(c, r->d_tmp, r->d_csz.as<const int64_t>(), r->d_coff.as<int64_t>(), col));
+        VMX_HIP(hipMemcpyAsync(tot + 4, r->d_coff.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, c->stream));
+        VMX_HIP(hipMemcpyAsync(tot + 5, r->d_aux.p, 16, hipMemcpyDeviceToHost, c->stream));
+    }
     VMX_TRY(sync(c));
-    const int64_t tn = tot[0], ts = tot[1], tq = tot[2], nk = tot[3];
+    const int64_t tn = tot[0], ts = tot[1], tq = tot[2], nk = tot[3], tc = r->tags_on ? tot[4] : 0;
+    if (r->tags_on) {
+        uint64_t key; memcpy(&key, tot + 5, 8);
+        if (key != ~0ull) {
+            static const char* const why[] = {"fewer than 3 bytes are left for a field", "unknown field type", "unknown B array sub-type", "a fixed-size value runs past the record's end",
+                                              "a Z or H value has no NUL inside the record", "a B array runs past the record's end"};
+            const int code = (int)(key & 0xff);
+            set_error("BAM record " + std::to_string((long long)(rec0 + (int64_t)(key >> 8)) + 1) + ": malformed auxiliary data: " +
+                      (code >= VMX_BAM_IN_E_AUX_SHORT && code <= VMX_BAM_IN_E_AUX_COUNT ? why[code - VMX_BAM_IN_E_AUX_SHORT] : "unknown"));
+            return VM_ERR_IO;
+        }
+        r->n_aux_dropped += tot[6];
+    }
     r->n_dropped += n - nk;
     VMX_TRY(r->d_names.reserve((size_t)tn + 8)); VMX_TRY(r->d_seqs.reserve((size_t)ts + 8)); VMX_TRY(r->d_quals.reserve((size_t)tq + 8));
     hipLaunchKernelGGL(k_bam_in_decode, dim3((unsigned)((n + 1 + 3) / 4)), dim3(256), 0, c->stream, dst.as<const uint8_t>(), r->d_roff.as<const int64_t>(), n, off, off + col,
                        off + 2 * col, off + 3 * col, r->d_names.as<char>(), r->d_seqs.as<char>(), r->d_quals.as<char>(), oo, oo + col, oo + 2 * col);
+    if (r->tags_on) {
+        VMX_TRY(r->d_comments.reserve((size_t)tc + 8));
+        hipLaunchKernelGGL(k_bam_in_aux_write, dim3(aux_grid), dim3(256), 0, c->stream, dst.as<const uint8_t>(), r->d_roff.as<const int64_t>(), n, r->d_sel.as<const uint16_t>(),
+                           (int)r->tags.size(), r->tags_all, r->d_coff.as<const int64_t>(), off + 3 * col, r->d_comments.as<char>(), r->d_ocoff.as<int64_t>());
+    }
     VMX_TRY(sync(c));
     r->st[4] += now_s() - t0;
     t0 = now_s();
-    VMX_TRY(D.names.reserve((size_t)tn + 8)); VMX_TRY(D.seqs.reserve((size_t)ts + 8)); VMX_TRY(D.quals.reserve((size_t)tq + 8)); VMX_TRY(D.off.reserve((size_t)(nk + 1) * 8 * 3));
+    VMX_TRY(D.names.reserve((size_t)tn + 8)); VMX_TRY(D.seqs.reserve((size_t)ts + 8)); VMX_TRY(D.quals.reserve((size_t)tq + 8)); VMX_TRY(D.off.reserve((size_t)(nk + 1) * 8 * 4));
     if (tn) VMX_HIP(hipMemcpyAsync(D.names.p, r->d_names.p, (size_t)tn, hipMemcpyDeviceToHost, c->stream));
     if (ts) VMX_HIP(hipMemcpyAsync(D.seqs.p, r->d_seqs.p, (size_t)ts, hipMemcpyDeviceToHost, c->stream));
     if (tq) VMX_HIP(hipMemcpyAsync(D.quals.p, r->d_quals.p, (size_t)tq, hipMemcpyDeviceToHost, c->stream));
     for (int j = 0; j < 3; ++j) VMX_HIP(hipMemcpyAsync((int64_t*)D.off.p + j * (nk + 1), oo + j * col, (size_t)(nk + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    if (r->tags_on) {
+        VMX_TRY(D.comments.reserve((size_t)tc + 8));
+        if (tc) VMX_HIP(hipMemcpyAsync(D.comments.p, r->d_comments.p, (size_t)tc, hipMemcpyDeviceToHost, c->stream));
+        VMX_HIP(hipMemcpyAsync((int64_t*)D.off.p + 3 * (nk + 1), r->d_ocoff.p, (size_t)(nk + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    }
     VMX_TRY(sync(c));
     r->st[5] += now_s() - t0;
-    D.n = nk; r->st[10] += (double)nk; r->st[11] = (double)r->n_dropped;
+    D.n = nk; r->st[10] += (double)nk; r->st[11] = (double)r->n_dropped; r->st[12] = (double)r->n_aux_dropped;
     return 1;
 }
 
@@ -1002,19 +1041,32 @@ void vm_bam_reader_close(vm_bam_reader* r) {
     if (r->pre_on) r->pre.get();
     (void)hipStreamSynchronize(r->c->stream);
     if (r->fd >= 0) close(r->fd);
-    DevBuf* bufs[] = {&r->z.comp, &r->z.tab, &r->z.key, &r->d_inf[0], &r->d_inf[1], &r->d_roff, &r->d_walk, &r->d_sz, &r->d_off, &r->d_tmp, &r->d_names, &r->d_seqs, &r->d_quals, &r->d_ooff};
+    DevBuf* bufs[] = {&r->z.comp, &r->z.tab, &r->z.key, &r->d_inf[0], &r->d_inf[1], &r->d_roff, &r->d_walk, &r->d_sz, &r->d_off, &r->d_tmp, &r->d_names, &r->d_seqs, &r->d_quals, &r->d_ooff, &r->d_sel, &r->d_csz, &r->d_coff, &r->d_comments, &r->d_ocoff, &r->d_aux};
     for (DevBuf* b : bufs) b->release();
     delete r;
 }
 
-int vm_bam_reader_open(vm_ctx* c, const char* path, vm_bam_reader** out) {
+int vm_bam_reader_open(vm_ctx* c, const char* path, vm_bam_reader** out) { return vm_bam_reader_open_tags(c, path, nullptr, out); }
+
+int vm_bam_reader_open_tags(vm_ctx* c, const char* path, const char* tags, vm_bam_reader** out) {
     if (out) *out = nullptr;
     if (!c) return VM_ERR_NO_CTX;
     if (!out || !path) return VM_ERR_ARG;
+    std::vector<uint16_t> sel;
+    const bool all = tags && strcmp(tags, "*") == 0;
+    if (tags && *tags && !all) {                                        // XX(,XX)*, each [A-Za-z][A-Za-z0-9] (SAMv1 1.5)
+        for (const char* q = tags;; q += 3) {
+            const bool ok = isalpha((unsigned char)q[0]) && isalnum((unsigned char)q[1]) && (q[2] == ',' || q[2] == 0);
+            if (!ok) { set_error(std::string("vm_bam_reader_open_tags: the tag list is neither empty, \"*\" nor two-character tags separated by commas: ") + tags); return VM_ERR_ARG; }
+            sel.push_back((uint16_t)((uint8_t)q[0] | (uint16_t)(uint8_t)q[1] << 8));
+            if (q[2] == 0) break;
+        }
+    }
     const int fd = open(path, O_RDONLY);
     if (fd < 0) { set_error(std::string("cannot open ") + path); return VM_ERR_IO; }
     vm_bam_reader* r = new vm_bam_reader();
     r->c = c; r->fd = fd;
+    r->tags_on = all || !sel.empty(); r->tags_all = all ? 1 : 0; r->tags = sel;
     r->fsize = (int64_t)lseek(fd, 0, SEEK_END);
     // VMX_BAM_IN_CHUNK / VMX_BAM_IN_MAXINF: compressed bytes per read and inflated bytes per window (tests cross many windows with small files)
     r->chunk_bytes = 64 << 20; r->max_inf = (int64_t)512 << 20;
@@ -1026,6 +1078,8 @@ int vm_bam_reader_open(vm_ctx* c, const char* path, vm_bam_reader** out) {
     if (rc == 0) rc = r->ch[0].stage.reserve(stage);
     if (rc == 0) rc = r->ch[1].stage.reserve(stage);
     if (rc == 0) rc = r->pin.reserve(256);
+    if (rc == 0 && r->tags_on) rc = r->d_sel.reserve(sel.size() * 2 + 8);
+    if (rc == 0 && !sel.empty() && hipMemcpy(r->d_sel.p, sel.data(), sel.size() * 2, hipMemcpyHostToDevice) != hipSuccess) { set_error("vm_bam_reader_open_tags: upload failed"); rc = VM_ERR_HIP; }
     if (rc == 0 && r->fsize == 0) { set_error(std::string("empty file: ") + path); rc = VM_ERR_IO; }
     while (rc == 0 && !r->hdr_done) {
         rc = bam_in_window(r, 0);
@@ -1046,8 +1100,8 @@ int64_t vm_bam_reader_read(vm_bam_reader* r, int64_t max_reads, int64_t max_base
     if (!r || !r->c) return VM_ERR_NO_CTX;
     if (!names || !name_off || !seqs || !seq_off || !quals || !qual_off || !comments || !com_off) return VM_ERR_ARG;
     try {
-        Grow nb, sb, qb;
-        std::vector<int64_t> no(1, 0), so(1, 0), qo(1, 0);
+        Grow nb, sb, qb, cb;
+        std::vector<int64_t> no(1, 0), so(1, 0), qo(1, 0), co(1, 0);
         int64_t n = 0;
         bool end = false;
         while (n < max_reads && (int64_t)sb.n < max_bases && !end) {
@@ -1068,13 +1122,20 @@ int64_t vm_bam_reader_read(vm_bam_reader* r, int64_t max_reads, int64_t max_base
                 !qb.append(D.quals.p + hq[a], (size_t)(hq[a + m] - hq[a]))) { set_error("vm_bam_reader_read: out of host memory"); return VM_ERR_OOM; }
             const int64_t n0 = no.back() - hn[a], s0 = so.back() - hs[a], q0 = qo.back() - hq[a];
             for (int64_t j = 1; j <= m; ++j) { no.push_back(n0 + hn[a + j]); so.push_back(s0 + hs[a + j]); qo.push_back(q0 + hq[a + j]); }
+            if (r->tags_on) {                                           // the comments are cut where the records are
+                const int64_t* hc = hq + (nk + 1);
+                if (!cb.append(D.comments.p + hc[a], (size_t)(hc[a + m] - hc[a]))) { set_error("vm_bam_reader_read: out of host memory"); return VM_ERR_OOM; }
+                const int64_t c0 = co.back() - hc[a];
+                for (int64_t j = 1; j <= m; ++j) co.push_back(c0 + hc[a + j]);
+            }
             r->at += m; n += m;
             r->handout_s += now_s() - t0;
         }
         auto giveo = [](const std::vector<int64_t>& v, int64_t** p) { *p = (int64_t*)malloc(8 * v.size()); memcpy(*p, v.data(), 8 * v.size()); };
-        *names = nb.release(); *seqs = sb.release(); *quals = qb.release(); *comments = (char*)malloc(1);
+        *names = nb.release(); *seqs = sb.release(); *quals = qb.release(); *comments = cb.release();
         giveo(no, name_off); giveo(so, seq_off); giveo(qo, qual_off);
-        giveo(std::vector<int64_t>((size_t)n + 1, 0), com_off);
+        if (!r->tags_on) co.assign((size_t)n + 1, 0);
+        giveo(co, com_off);
         return n;
     }
     catch (const std::bad_alloc&) { set_error("vm_bam_reader_read: out of host memory"); return VM_ERR_OOM; }
@@ -1082,7 +1143,7 @@ int64_t vm_bam_reader_read(vm_bam_reader* r, int64_t max_reads, int64_t max_base
 
 int vm_bam_reader_stats(const vm_bam_reader* r, double* out, int n) {
     if (!r || !out) return VM_ERR_ARG;
-    for (int i = 0; i < n; ++i) out[i] = i == 6 ? r->handout_s : i < 12 ? r->pub[i] : 0.0;         // (both written by the caller's own thread)
+    for (int i = 0; i < n; ++i) out[i] = i == 6 ? r->handout_s : i < 13 ? r->pub[i] : 0.0;         // (both written by the caller's own thread)
     return 0;
 }
 

@@ -97,9 +97,97 @@ def _split_header(head):
 _BAM_NT16 = '=ACMGRSVTWYHKDBN'
 
 
-def read_bam(path):
-    """unaligned or aligned BAM -> (name, seq, qual or None, None), the fields the reference takes from pysam (vacmap:455-471): a
-    reverse-strand record is turned back to the read's own orientation, qualities 0xff mean absent. BGZF is a series of gzip members."""
+def _bam_tag_select(tags):
+    """--bam-tags / tags=: None (no tags), '*' (every field: 'all' or '*'), or the frozenset of two-character tags of a list or comma-separated string"""
+    if tags is None or tags == '' or tags == []:
+        return None
+    if isinstance(tags, str):
+        if tags in ('all', '*'):
+            return '*'
+        tags = tags.split(',')
+    tags = [t.decode('latin-1') if isinstance(t, bytes) else t for t in tags]
+    for t in tags:
+        if len(t) != 2 or not (t[0].isascii() and t[0].isalpha() and t[1].isascii() and t[1].isalnum()):
+            raise ValueError('--bam-tags: %r is not a two-character tag (give a comma-separated list such as MM,ML,MN, or all)' % t)
+    return frozenset(tags)
+
+
+_AUX_INT = {'c': 'b', 'C': 'B', 's': 'h', 'S': 'H', 'i': 'i', 'I': 'I'}
+
+
+def _f32_text(raw):
+    """4 bytes of a float32 -> the shortest %.{p}g (p = 1 ... 9) that strtod and a cast read back as the same bits; None when not finite"""
+    x, = struct.unpack('<f', raw)
+    if x != x or x in (float('inf'), float('-inf')):
+        return None
+    for p in range(1, 10):
+        s = '%.*g' % (p, x)
+        try:
+            if struct.pack('<f', float(s)) == raw:
+                return s
+        except OverflowError:                              # (rounds beyond FLT_MAX)
+            pass
+    return '%.9g' % x
+
+
+def _bam_aux_text(aux, sel):
+    """the aux bytes of a BAM record (SAMv1 4.2.4) as the tab-separated XX:T:value text of the selected fields (sel: '*' or a set of tags), in
+    record order: the rule of vm_bam_reader_open_tags (include/vacmapx.h). A field SAM text cannot hold is left out; malformed bytes raise ValueError."""
+    out, p, n = [], 0, len(aux)
+    while p < n:
+        if n - p < 3:
+            raise ValueError('malformed BAM auxiliary data: fewer than 3 bytes are left for a field')
+        tag, ty = aux[p:p + 2].decode('latin-1'), chr(aux[p + 2])
+        p += 3
+        val = None
+        if ty in 'AcCsSiIf':
+            size = 1 if ty in 'AcC' else 2 if ty in 'sS' else 4
+            if p + size > n:
+                raise ValueError('malformed BAM auxiliary data: a fixed-size value runs past the record')
+            raw = aux[p:p + size]; p += size
+            if ty == 'A':
+                val = 'A:' + chr(raw[0]) if 0x20 <= raw[0] <= 0x7e else None
+            elif ty == 'f':
+                t = _f32_text(raw); val = None if t is None else 'f:' + t
+            else:
+                val = 'i:%d' % struct.unpack('<' + _AUX_INT[ty], raw)[0]
+        elif ty in 'ZH':
+            e = aux.find(b'\0', p)
+            if e < 0:
+                raise ValueError('malformed BAM auxiliary data: a Z or H value has no NUL inside the record')
+            raw = aux[p:e]; p = e + 1
+            ok = all(0x20 <= b <= 0x7e for b in raw) if ty == 'Z' else (len(raw) % 2 == 0 and all(b in b'0123456789abcdefABCDEF' for b in raw))
+            val = ty + ':' + raw.decode('latin-1') if ok else None
+        elif ty == 'B':
+            if p + 5 > n:
+                raise ValueError('malformed BAM auxiliary data: a B array runs past the record')
+            sub, cnt = chr(aux[p]), struct.unpack_from('<I', aux, p + 1)[0]
+            if sub not in 'cCsSiIf':
+                raise ValueError('malformed BAM auxiliary data: unknown B array sub-type')
+            size = 1 if sub in 'cC' else 2 if sub in 'sS' else 4
+            if p + 5 + cnt * size > n:
+                raise ValueError('malformed BAM auxiliary data: a B array runs past the record')
+            p += 5
+            if sel == '*' or tag in sel:                   # (an array nobody asked for is not turned into text)
+                if sub == 'f':
+                    ts = [_f32_text(aux[p + 4 * j:p + 4 * j + 4]) for j in range(cnt)]
+                    val = None if any(t is None for t in ts) else 'B:f' + ''.join(',' + t for t in ts)
+                else:
+                    val = 'B:' + sub + ''.join(',%d' % v for v in struct.unpack_from('<%d%s' % (cnt, _AUX_INT[sub]), aux, p))
+            p += cnt * size
+        else:
+            raise ValueError('malformed BAM auxiliary data: unknown field type')
+        if val is not None and (sel == '*' or tag in sel):
+            out.append(tag + ':' + val)
+    return '\t'.join(out)
+
+
+def read_bam(path, tags=None):
+    """unaligned or aligned BAM -> (name, seq, qual or None, comment), the fields the reference takes from pysam (vacmap:455-471): a
+    reverse-strand record is turned back to the read's own orientation, qualities 0xff mean absent. BGZF is a series of gzip members.
+    comment: None, or with tags (None, 'all' / '*', a list or comma-separated string of two-character tags) the selected auxiliary fields as
+    SAM text (_bam_aux_text), which the reference drops; they are not re-oriented (MM / ML are defined on the read as sequenced)."""
+    sel = _bam_tag_select(tags)
     with gzip.open(path, 'rb') as f:
         if f.read(4) != b'BAM\x01':
             raise ValueError('not a BAM file: %s' % path)
@@ -126,43 +214,44 @@ def read_bam(path):
                 continue                                   # "no sequence in BAM record" (vacmap:462)
             if flag & 16:
                 seq = sam.revcomp(seq.upper()); qual = qual[::-1] if qual is not None else None
-            yield name, seq, qual, None
+            yield name, seq, qual, (None if sel is None else _bam_aux_text(rec[p + l_seq:], sel))
 
 
-def _bam_chunks(path, n_max):
-    """BAM records as the blob chunks the FASTX reader yields (names, upper-cased sequences, qualities, no comments)"""
+def _bam_chunks(path, n_max, tags=None):
+    """BAM records as the blob chunks the FASTX reader yields (names, upper-cased sequences, qualities; comments: the auxiliary fields that `tags`
+    selects, as read_bam gives them, none without it)"""
     import numpy as np
     cur = []
 
     def pack(rows):
         out = {}
-        for key, col in (('names', 0), ('seqs', 1), ('quals', 2)):
-            bs = [(r[col] or '').encode() for r in rows]
+        for key, col in (('names', 0), ('seqs', 1), ('quals', 2), ('comments', 3)):
+            bs = [(r[col] or '').encode('latin-1' if col == 3 else 'utf-8') for r in rows]
             out[key] = np.frombuffer(b''.join(bs), dtype=np.uint8)
             out[key + '_off'] = np.concatenate([[0], np.cumsum([len(b) for b in bs])]).astype(np.int64)
-        out['comments'] = np.zeros(0, np.uint8); out['comments_off'] = np.zeros(len(rows) + 1, np.int64)
         return out
-    for name, seq, qual, _ in read_bam(path):
-        cur.append((name, seq.upper(), qual))
+    for name, seq, qual, com in read_bam(path, tags):
+        cur.append((name, seq.upper(), qual, com))
         if len(cur) >= n_max:
             yield pack(cur); cur = []
     if cur:
         yield pack(cur)
 
 
-def _native_bam_chunks(path, n_max, lib, device):
-    """--bam-reader native: the chunks of _bam_chunks from lib.BamReader (BGZF inflate and record decoding on the GPU) on a context of its own.
+def _native_bam_chunks(path, n_max, lib, device, tags=None):
+    """--bam-reader native: the chunks of _bam_chunks from lib.BamReader (BGZF inflate, record and auxiliary-field decoding on the GPU) on a context of its own.
     A .bam that is gzip but not BGZF (no member boundaries to inflate side by side) goes to the Python reader, with one line on stderr."""
     from .lib import BamReader, Context, VmxError
     ctx = Context(device, lib=lib)
     try:
         try:
-            rd = BamReader(ctx, path)
+            sel = _bam_tag_select(tags)
+            rd = BamReader(ctx, path, None if sel is None else '*' if sel == '*' else sorted(sel))
         except VmxError as e:
             if e.code != -7:                               # VM_ERR_UNSUPPORTED
                 raise
             sys.stderr.write('[vacmap_amd] --bam-reader native: %s is gzip but not BGZF, reading it with the Python BAM reader\n' % path)
-            yield from _bam_chunks(path, n_max)
+            yield from _bam_chunks(path, n_max, tags)
             return
         try:
             yield from iter(lambda: rd.read(n_max), None)
@@ -189,7 +278,7 @@ def _parse_slice(path, lib, a, b, n_max):
         rd.close()
 
 
-def _input_chunks(path, n_max, lib, device=0, bam_reader='python', parse_threads=0, share=(0, 1), slice_bytes=1 << 30):
+def _input_chunks(path, n_max, lib, device=0, bam_reader='python', parse_threads=0, share=(0, 1), slice_bytes=1 << 30, bam_tags=None):
     """blob chunks (names, upper-cased sequences, qualities, comments; at most n_max records each) of one input in file order: a .bam through
     the native or the Python reader, a compressed FASTA / FASTQ file through one library reader. parse_threads > 0: a plain file is cut into
     record-aligned slices of about slice_bytes (vm_fastx_open_range) which that many threads parse ahead of the consumer, and share = (i, n)
@@ -197,7 +286,7 @@ def _input_chunks(path, n_max, lib, device=0, bam_reader='python', parse_threads
     Closing the generator early releases the reader, its threads and the native BAM reader's context."""
     from .lib import Fastx
     if path.endswith('.bam'):
-        yield from (_native_bam_chunks(path, n_max, lib, device) if bam_reader == 'native' else _bam_chunks(path, n_max))
+        yield from (_native_bam_chunks(path, n_max, lib, device, bam_tags) if bam_reader == 'native' else _bam_chunks(path, n_max, bam_tags))
         return
     if not parse_threads or not _is_plain_fastx(path):
         rd = Fastx(path, lib=lib)
@@ -411,6 +500,10 @@ def build_parser():
     p.add_argument('--bam-reader', choices=['python', 'native'], default='python',
                    help='how -read x.bam is read: the Python reader on one host thread (default) or BGZF inflate and record decoding on the GPU '
                         '(lib.BamReader, on a context of its own); a .bam that is gzip but not BGZF falls back to the Python reader')
+    p.add_argument('--bam-tags', metavar='LIST|all', default=None,
+                   help='carry auxiliary fields of -read x.bam records to the output as optional fields (the reference drops them): a comma-separated list '
+                        'of two-character tags (MM,ML,MN) or `all`; with --bam-reader native they are turned into SAM text on the GPU. They travel as the '
+                        "read's comment, with or without --copycomments, through the host SAM emitter")
     p.add_argument('--sam-emitter', choices=['host', 'device'], default='host',
                    help='who makes the SAM text of a batch: -t host threads (default) or the GPU (merged CIGAR, NM, MD / cs, SA and the lines themselves, on '
                         'VMX_EMIT_CONTEXTS contexts of their own); with --copycomments, or a reference that holds letters other than ACGTN, the host emitter is used')
@@ -445,6 +538,10 @@ def _parse_args(argv, comm, sw):
     args, _unknown = build_parser().parse_known_args(argv)          # unknown flags are ignored like the reference's parse_known_args (vacmap:152)
     if comm is None:                            # (a process of its own, not a test harness that shares the interpreter)
         _keep_heap_pages(sw)
+    try:
+        _bam_tag_select(args.bam_tags)
+    except ValueError as e:
+        sys.exit(str(e))
     if args.o != '-' and not (args.o.endswith('.sam') or args.o.endswith('.bam')):
         sys.exit("Output path must end with .sam, .bam, .sorted.bam, or be '-' for stdout.")
     args.native_bam = args.bam_writer in ('native', 'native-sort') and args.o.endswith('.bam')
@@ -675,6 +772,11 @@ def _blob(parts):
 VM_ERR_UNSUPPORTED = -7
 
 
+def _carries_comments(args, path):
+    """a .bam input's comments are the tags --bam-tags selected and go to the emitter with or without --copycomments; FASTA / FASTQ comments need --copycomments"""
+    return bool(args.bam_tags) if path.endswith('.bam') else args.copycomments
+
+
 def _device_emitter_wanted(args, rank):
     """--sam-emitter device, unless the run copies comments (the filter of :20686 stays on the host emitter): one stderr line says so"""
     if args.sam_emitter != 'device':
@@ -682,6 +784,9 @@ def _device_emitter_wanted(args, rank):
     if args.copycomments:
         if rank == 0:
             sys.stderr.write('vacmapx: --copycomments needs the host SAM emitter: --sam-emitter device is not used\n')
+        return False
+    if args.bam_tags:                                       # the tags travel as comments, which only the host emitter copies
+        _device_emitter_given_up('--bam-tags carries the tags as comments, which --sam-emitter device does not copy', rank)
         return False
     return True
 
@@ -727,8 +832,9 @@ def _run_asm(args, net, lib, ctx, index, prm, opts, out, device, t_start):
                     on_device[0] = False
                     _device_emitter_given_up(str(e), rank)
             if text is None:
-                text, toff, _, ns = sam_emit(lib, index, opts, nb, no, sb, so, raw, quals=qb, qual_off=qo, comments=cb if args.copycomments else None,
-                                             com_off=co if args.copycomments else None, nthreads=max(1, args.t))
+                with_c = args.copycomments or bool(args.bam_tags)
+                text, toff, _, ns = sam_emit(lib, index, opts, nb, no, sb, so, raw, quals=qb, qual_off=qo, comments=cb if with_c else None,
+                                             com_off=co if with_c else None, nthreads=max(1, args.t))
             for x, g in enumerate(share):
                 if raw.status[x] != 0:                                                      # the worker's except (:23493-23498)
                     sys.stderr.write('%s is not aligned.\n' % g[1].decode()); done[g[0]] = None
@@ -754,8 +860,11 @@ def _run_asm(args, net, lib, ctx, index, prm, opts, out, device, t_start):
     group, gbases = [], 0
     for path in (p for grp in args.read for p in grp):
         # (.bam input like every other mode: vacmap:452-470)
-        with contextlib.closing(_input_chunks(path, 64, lib, device, args.bam_reader)) as chunks:
+        with contextlib.closing(_input_chunks(path, 64, lib, device, args.bam_reader, bam_tags=args.bam_tags)) as chunks:
             for ch in _first_of_each_name(chunks, seen, lib):
+                if not _carries_comments(args, path):
+                    import numpy as np
+                    ch['comments_off'] = np.zeros(len(ch['seqs_off']), np.int64)
                 nb, no, sb, so = ch['names'].tobytes(), ch['names_off'], ch['seqs'].tobytes(), ch['seqs_off']
                 qb, qo, cb, co = ch['quals'].tobytes(), ch['quals_off'], ch['comments'].tobytes(), ch['comments_off']
                 for i in range(len(so) - 1):
@@ -894,7 +1003,7 @@ class ReadStream:
         share = (self.rank, self.world) if self.range_mode else (0, 1)
         slice_bytes = max(1 << 20, int(sw['VMX_SLICE_MB'] * (1 << 20)))
         for file_no, path in enumerate(p for grp in args.read for p in grp):
-            with contextlib.closing(_input_chunks(path, win_reads, self.lib, self.device, args.bam_reader, parse_threads, share, slice_bytes)) as chunks:
+            with contextlib.closing(_input_chunks(path, win_reads, self.lib, self.device, args.bam_reader, parse_threads, share, slice_bytes, args.bam_tags)) as chunks:
                 for ch in _first_of_each_name(chunks, seen, self.lib):
                     n = len(ch['seqs_off']) - 1
                     if self.range_mode and n:
@@ -902,7 +1011,7 @@ class ReadStream:
                         self.rank_hash_file.append(np.full(n, file_no, np.int32))          # ... in INPUT order: (file, byte range = rank)
                     if args.Q:
                         ch['quals_off'] = np.zeros(n + 1, np.int64)
-                    if not args.copycomments:
+                    if not _carries_comments(args, path):
                         ch['comments_off'] = np.zeros(n + 1, np.int64)
                     if n:
                         yield ch

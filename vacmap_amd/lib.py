@@ -193,7 +193,7 @@ class VmxLib:
         L.vm_bam_sorter_index.argtypes = [vp, P(vp), P(i64)]
         L.vm_bgzf_compress.argtypes = [vp, vp, i64, P(vp), P(i64)]
         L.vm_bgzf_decompress.argtypes = [vp, vp, i64, P(vp), P(i64)]
-        L.vm_bam_reader_open.argtypes = [vp, cp, P(vp)]; L.vm_bam_reader_close.argtypes = [vp]; L.vm_bam_reader_close.restype = None
+        L.vm_bam_reader_open.argtypes = [vp, cp, P(vp)]; L.vm_bam_reader_open_tags.argtypes = [vp, cp, cp, P(vp)]; L.vm_bam_reader_close.argtypes = [vp]; L.vm_bam_reader_close.restype = None
         L.vm_bam_reader_read.argtypes = [vp, i64, i64] + [P(vp), P(P(i64))] * 4; L.vm_bam_reader_read.restype = i64
         L.vm_bam_reader_stats.argtypes = [vp, P(C.c_double), C.c_int]
 
@@ -694,13 +694,20 @@ def bgzf_decompress(ctx, data):
 
 
 class BamReader:
-    """BAM reader into blobs (vm_bam_reader_*): BGZF inflate and record decoding on the device; read() as Fastx.read()"""
-    STATS = ('io_busy_s', 'io_wait_s', 'inflate_s', 'walk_s', 'decode_s', 'download_s', 'handout_s', 'windows', 'file_bytes', 'inflated_bytes', 'records', 'dropped')
+    """BAM reader into blobs (vm_bam_reader_*): BGZF inflate and record decoding on the device; read() as Fastx.read().
+    tags: None (comments stay empty), '*' or 'all' (every auxiliary field), or a list / comma-separated string of two-character tags: the
+    selected fields become each read's comment, `XX:T:value` joined by tabs, made on the device (vm_bam_reader_open_tags)"""
+    STATS = ('io_busy_s', 'io_wait_s', 'inflate_s', 'walk_s', 'decode_s', 'download_s', 'handout_s', 'windows', 'file_bytes', 'inflated_bytes', 'records', 'dropped',
+             'fields_dropped')
 
-    def __init__(self, ctx, path):
+    def __init__(self, ctx, path, tags=None):
         self.ctx, self.lib = ctx, ctx.lib
         h = C.c_void_p()
-        self.lib.check(self.lib.L.vm_bam_reader_open(ctx.h, _b(path), C.byref(h)))
+        if tags is None:
+            self.lib.check(self.lib.L.vm_bam_reader_open(ctx.h, _b(path), C.byref(h)))
+        else:
+            spec = '*' if tags in ('*', 'all') else tags if isinstance(tags, str) else ','.join(tags)
+            self.lib.check(self.lib.L.vm_bam_reader_open_tags(ctx.h, _b(path), _b(spec), C.byref(h)))
         self.h = h
 
     def read(self, max_reads, max_bases=1 << 62):
@@ -721,8 +728,8 @@ class BamReader:
         return out if n > 0 else None
 
     def stats(self):
-        v = (C.c_double * 12)()
-        self.lib.check(self.lib.L.vm_bam_reader_stats(self.h, v, 12))
+        v = (C.c_double * 13)()
+        self.lib.check(self.lib.L.vm_bam_reader_stats(self.h, v, 13))
         return dict(zip(self.STATS, list(v)))
 
     def close(self):
