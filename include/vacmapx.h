@@ -320,12 +320,20 @@ int vm_sam_emit(const vm_index*, const vm_sam_opts*, int64_t n_reads, const char
  * fetches the text): vm_sam_emit's arguments without comments and nthreads, plus the context whose stream and buffers the call uses (one call at a
  * time per context; any number of contexts may share an index). Returns what vm_sam_emit returns for the same inputs byte for byte, text_off, n_lines
  * and n_skipped included (text and text_off: vm_free). VM_ERR_UNSUPPORTED when the index keeps a host copy of a reference with letters other than
- * ACGTN (the device holds N for them, vm_sam_emit prints them); comment copying stays with vm_sam_emit. VM_ERR_ARG for what vm_sam_emit refuses, for
+ * ACGTN (the device holds N for them, vm_sam_emit prints them); comments are copied by vm_sam_emit_device_comments below. VM_ERR_ARG for what vm_sam_emit refuses, for
  * a record of an unknown contig and for a CIGAR operator count of 2^31 or more. Three host waits per call.
- * vm_sam_emit_device_times: wall seconds of the context's latest call: upload, passes, the text's way back. */
+ * vm_sam_emit_device_times: wall seconds of the context's latest call (either entry): upload, passes, the text's way back. */
 int vm_sam_emit_device(vm_ctx*, const vm_index*, const vm_sam_opts*, int64_t n_reads, const char* names, const int64_t* name_off, const char* seqs,
                        const int64_t* seq_off, const char* quals, const int64_t* qual_off, const vm_record* recs, int64_t n_recs, const char* cigar_blob,
                        const int32_t* status, char** text, int64_t** text_off, int64_t* n_lines, int64_t* n_skipped);
+/* vm_sam_emit_device that also copies the reads' comments (emit_read()'s rule of :20686, applied by k_sam_lines): comments / com_off as vm_sam_emit
+ * takes them, after qual_off. comments == NULL or com_off == NULL: no comments, exactly vm_sam_emit_device. The blob is uploaded from its first to its
+ * last used byte. VM_ERR_ARG also for decreasing com_off and for a NULL blob under offsets that span bytes. Returns vm_sam_emit's bytes, text_off,
+ * n_lines and n_skipped for the same inputs. */
+int vm_sam_emit_device_comments(vm_ctx*, const vm_index*, const vm_sam_opts*, int64_t n_reads, const char* names, const int64_t* name_off, const char* seqs,
+                                const int64_t* seq_off, const char* quals, const int64_t* qual_off, const char* comments, const int64_t* com_off,
+                                const vm_record* recs, int64_t n_recs, const char* cigar_blob, const int32_t* status, char** text, int64_t** text_off,
+                                int64_t* n_lines, int64_t* n_skipped);
 int vm_sam_emit_device_times(vm_ctx*, double* seconds3);
 /* `mp.fastx_read(path, read_comment=)` (vacmap:445): FASTA / FASTQ, plain or gzip. vm_fastx_read returns up to max_reads records (stopping
  * early once max_bases bases are held) as blobs: names, UPPER-CASED sequences (vacmap:476), qualities (empty for FASTA), comments (header

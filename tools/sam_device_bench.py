@@ -6,6 +6,8 @@
         --eqx --MD. sam_emit at --threads threads and sam_emit_device alternate in one process after a warm-up call of each: wall seconds and
         process CPU seconds (resource.getrusage) per call, and the device call's upload / passes / download shares from the context's clocks.
         --only device: the device calls alone, for a run under `rocprofv3 --kernel-trace --stats -d DIR -- python tools/sam_device_bench.py ...`.
+        --comments: every read carries its uBAM tags as a comment of about 10 KB (MM:Z:, ML:B:C with one value per 8 bases, MN:i:, the shape of
+        profiles/bam_tags_reader.json), copied by both emitters (k_sam_lines' comment stage on the device).
     python tools/sam_device_bench.py kernels --set default|eqx_md --stats DIR/.../*_kernel_stats.csv --calls N [--out profiles/sam_device_kernels.json]
         sums the k_sam_* rows of the statistics of an `emitter --only device --set ...` run per batch (N = device calls of the run: --calls + 1
         warm-up; k_sam_count_other, part of the index build, left out), copies the rows to profiles/sam_device_kernel_stats_<set>.csv, compares
@@ -48,7 +50,15 @@ def emitter(args):
     qb = np.concatenate([bam_bench.quals(int(so[i + 1] - so[i]), rng) for i in range(args.reads)])
     names = [b'%08x-read%d' % (int(rng.integers(0, 1 << 31)), i) for i in range(args.reads)]
     nb = np.frombuffer(b''.join(names), np.uint8); no = np.concatenate([[0], np.cumsum([len(x) for x in names])]).astype(np.int64)
-    res = {'reads': args.reads, 'bases': int(so[-1]), 'host_threads': args.threads, 'calls': args.calls, 'sets': {}}
+    cb = co = None
+    if args.comments:
+        coms = []
+        for i in range(args.reads):
+            n = int(so[i + 1] - so[i]); k = n // 8
+            coms.append(b'MM:Z:C+m?,' + b','.join(b'%d' % x for x in rng.integers(0, 12, k)) + b';\tML:B:C,' + b','.join(b'%d' % x for x in rng.integers(0, 256, k)) + b'\tMN:i:%d' % n)
+        cb = np.frombuffer(b''.join(coms), np.uint8); co = np.concatenate([[0], np.cumsum([len(x) for x in coms])]).astype(np.int64)
+        del coms
+    res = {'reads': args.reads, 'bases': int(so[-1]), 'host_threads': args.threads, 'calls': args.calls, 'comment_bytes': int(co[-1]) if co is not None else 0, 'sets': {}}
     for tag, eqx, opts in (('default', 0, VL.SamOpts(0, 1, 0, 0, 0, 0, b'1', 0)), ('eqx_md', 1, VL.SamOpts(1, 1, 0, 0, 0, 0, b'1', 0))):
         if args.set not in ('both', tag):
             continue
@@ -56,10 +66,12 @@ def emitter(args):
         blob_bytes = int(max((raw.recs[i].cigar_off + raw.recs[i].cigar_len for i in range(raw.nrec)), default=0))
 
         def host():
-            return VL.sam_emit(ctx.lib, idx, opts, nb, no, sb, so, raw, quals=qb, qual_off=so, nthreads=args.threads)
+            return VL.sam_emit(ctx.lib, idx, opts, nb, no, sb, so, raw, quals=qb, qual_off=so, comments=cb, com_off=co, nthreads=args.threads)
 
         def device():
-            return VL.sam_emit_device(ctx, idx, opts, nb, no, sb, so, raw, quals=qb, qual_off=so)
+            if cb is None:
+                return VL.sam_emit_device(ctx, idx, opts, nb, no, sb, so, raw, quals=qb, qual_off=so)
+            return VL.sam_emit_device(ctx, idx, opts, nb, no, sb, so, raw, quals=qb, qual_off=so, comments=cb, com_off=co)
         d = device()                                                    # warm-up of each (pools, page-locked landing block)
         same = None
         if args.only != 'device':
@@ -184,6 +196,7 @@ if __name__ == '__main__':
     ap.add_argument('what', choices=['emitter', 'kernels', 'driver'])
     ap.add_argument('--reads', type=int, default=None); ap.add_argument('--calls', type=int, default=5); ap.add_argument('--threads', type=int, default=16)
     ap.add_argument('--set', choices=['both', 'default', 'eqx_md'], default='both', help='emitter: the option set(s) to run; kernels: the set the statistics belong to')
+    ap.add_argument('--comments', action='store_true', help='emitter: a 10 KB uBAM-tag comment on every read')
     ap.add_argument('--only', choices=['both', 'device'], default='both'); ap.add_argument('--stats'); ap.add_argument('--out')
     ap.add_argument('--replicate', type=int, default=8); ap.add_argument('--ref-mb', type=float, default=100); ap.add_argument('--rounds', type=int, default=3)
     ap.add_argument('--tmp', default='/dev/shm/sam_device_bench'); ap.add_argument('-t', type=int, default=16)

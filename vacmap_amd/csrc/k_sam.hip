@@ -5,7 +5,8 @@
 //   k_sam_ops                   one wavefront per record, run twice (sizes, then bytes): the raw CIGAR text is tokenised 64 bytes per step, equal
 //                               neighbours are merged by a segmented sum that carries from step to step, and every batch of up to 64 merged operators
 //                               is handled by the wave at once: merged text, query / reference prefix sums, NM, MD and cs.
-//   k_sam_lines                 one wavefront per output line, run twice (sizes, then bytes), with the scan of the line sizes in between.
+//   k_sam_lines                 one wavefront per output line, run twice (sizes, then bytes), with the scan of the line sizes in between. The
+//                               read's comment (FASTA / FASTQ comment, uBAM tags as text) is filtered and appended by the same wave (sam_comment).
 //
 // ORDERING. Lanes hand data to one another through ballots, shuffles and LDS (vmx_wave_lds_fence between an LDS store and another lane's load:
 // workgroups are one wavefront). No kernel here loads a global byte that the same launch stored: the merged text, MD and cs that k_sam_lines
@@ -329,6 +330,55 @@ template <bool W> __device__ __forceinline__ void sam_fake_cigar(SamOut<W>& O, c
     if (qlen - y.q_en > 0) { O.num(qlen - y.q_en); O.ch(clip); }
 }
 
+// ---- the read's comment (emit_read()'s rule, mammap_clrnano.py:20686): the tab-separated fields of shape XX:T:value whose tag the line does not
+// carry yet. One field at a time, wave-uniform state; inside a field the wave works 64 bytes per step.
+// The field that begins at p: e = its end (the next tab, or L), colons = its ':' count (3 = three or more), head = bytes 2 and 4 are ':',
+// tag = bytes 0-1 packed, type = byte 3 (the last three mean something only under head). Loads: i < L only; beyond L a lane holds a tab.
+__device__ __forceinline__ void sam_field(const char* com, int64_t L, int64_t p, int lane, int64_t& e, int& colons, bool& head, int& tag, int& type) {
+    colons = 0;
+    for (int64_t base = p;; base += 64) {
+        const int64_t i = base + lane;
+        const int c = i < L ? (int)(unsigned char)com[i] : '\t';
+        const unsigned long long tm = __ballot(c == '\t');
+        const unsigned long long cm = __ballot(c == ':') & (tm ? (tm & (0ull - tm)) - 1ull : ~0ull);      // the colons before the field's end
+        if (base == p) { head = (cm & 0x14ull) == 0x14ull; tag = __shfl(c, 0) | (__shfl(c, 1) << 8); type = __shfl(c, 3); }
+        colons += __popcll(cm); if (colons > 3) colons = 3;
+        if (tm) { e = base + (__ffsll((long long)tm) - 1); return; }    // (base + 63 >= L makes tm non-zero: e <= L)
+    }
+}
+__device__ __forceinline__ bool sam_com_type(int t) { return t == 'A' || t == 'i' || t == 'f' || t == 'Z' || t == 'H' || t == 'B'; }
+#define SAM_TAG(a, b) ((int)(a) | ((int)(b) << 8))
+
+// A field qualifies by its own bytes and the line's tags; it is kept when no earlier qualifying field of the comment has its tag (only kept
+// fields enter the host's `seen`, and the first qualifying field of a tag is always kept). Lane k holds the k-th kept tag, compared by ballot;
+// beyond 64 kept tags the fields behind the 64th kept one are walked again (exact for any number of tags).
+template <bool W>
+__device__ __forceinline__ void sam_comment(SamOut<W>& O, const char* com, int64_t L, bool t_rg, bool t_cg, int lane) {
+    int mine = -1, nkept = 0; int64_t p64 = 0;
+    for (int64_t p = 0; p <= L;) {
+        int64_t e; int colons, tag, type; bool head;
+        sam_field(com, L, p, lane, e, colons, head, tag, type);
+        const bool fixed = tag == SAM_TAG('S', 'A') || tag == SAM_TAG('N', 'M') || tag == SAM_TAG('M', 'D') || tag == SAM_TAG('c', 's') ||
+                           (tag == SAM_TAG('R', 'G') && t_rg) || (tag == SAM_TAG('C', 'G') && t_cg);
+        if (head && colons == 2 && sam_com_type(type) && !fixed) {
+            bool dup = __ballot(mine == tag) != 0;
+            if (!dup && nkept == 64) {
+                for (int64_t q = p64; q < p && !dup;) {
+                    int64_t e2; int c2, tag2, type2; bool head2;
+                    sam_field(com, L, q, lane, e2, c2, head2, tag2, type2);
+                    dup = head2 && c2 == 2 && tag2 == tag && sam_com_type(type2);
+                    q = e2 + 1;
+                }
+            }
+            if (!dup) {
+                if (nkept < 64) { if (lane == nkept) mine = tag; if (++nkept == 64) p64 = e + 1; }
+                O.ch('\t'); O.bytes(com + p, e - p);
+            }
+        }
+        p = e + 1;
+    }
+}
+
 template <bool W>
 __device__ __forceinline__ void sam_line(const vmx_sam_in& A, const vmx_sam_work& K, int64_t p, int lane, char* text) {
     const vm_record rec = A.recs[K.ord[p]];
@@ -380,6 +430,10 @@ __device__ __forceinline__ void sam_line(const vmx_sam_in& A, const vmx_sam_work
     }
     O.bytes("\tNM:i:", 6); O.num(ri.nm);
     if (A.md) { O.bytes("\tMD:Z:", 6); O.bytes(cig + ri.cig_len, ri.md_len); O.bytes("\tcs:Z:", 6); O.bytes(cig + ri.cig_len + ri.md_len, ri.cs_len); }
+    if (A.comments) {
+        const int64_t cl = A.com_off[r + 1] - A.com_off[r];
+        if (cl > 0) sam_comment<W>(O, A.comments + (A.com_off[r] - A.com_base), cl, A.rg != nullptr, cg, lane);
+    }
     O.ch('\n');
     if (!W && lane == 0) K.lsz[p] = O.pos;
 }

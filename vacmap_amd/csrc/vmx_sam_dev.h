@@ -10,6 +10,7 @@ struct vmx_sam_in {
     const char* names; const int64_t* name_off; int64_t name_base;
     const char* seqs; const int64_t* seq_off; int64_t seq_base;
     const char* quals; const int64_t* qual_off; int64_t qual_base;      // quals == nullptr: no qualities at all
+    const char* comments; const int64_t* com_off; int64_t com_base;     // comments == nullptr: no read has a comment
     const vm_record* recs; const char* cigars; int64_t cigars_len;
     const int32_t* status;                                              // nullptr: every read has status 0
     const uint8_t* codes; const int64_t* coff; int32_t nseq;            // the index's reference codes (0..3 = ACGT, 4 = N) and contig offsets[nseq + 1]
@@ -42,14 +43,14 @@ __global__ void k_sam_text_off(vmx_sam_in A, vmx_sam_work K, int64_t* text_off);
 
 // grow-only buffers of a context's device emitter
 struct vmx_sam_bufs {
-    vmx::DevBuf names, name_off, seqs, seq_off, quals, qual_off, recs, cigars, status, rg;
+    vmx::DevBuf names, name_off, seqs, seq_off, quals, qual_off, comments, com_off, recs, cigars, status, rg;
     vmx::DevBuf cnt, first, keep, ord, mq, flag, rflag, ri, tsz, toff, scratch, lsz, loff, res, tmp;
     vmx::DevBuf text, text_off;
     vmx::DevBuf cnames, cname_off; const struct vm_index* names_of = nullptr;       // the contig-name blob of the index it was made for
     std::string h_cnames; std::vector<int64_t> h_cname_off;
     double s_upload = 0, s_kernel = 0, s_download = 0;                              // wall seconds of the last call by phase
     void release() {
-        vmx::DevBuf* all[] = {&names, &name_off, &seqs, &seq_off, &quals, &qual_off, &recs, &cigars, &status, &rg, &cnt, &first, &keep, &ord, &mq, &flag, &rflag, &ri, &tsz, &toff,
+        vmx::DevBuf* all[] = {&names, &name_off, &seqs, &seq_off, &quals, &qual_off, &comments, &com_off, &recs, &cigars, &status, &rg, &cnt, &first, &keep, &ord, &mq, &flag, &rflag, &ri, &tsz, &toff,
                               &scratch, &lsz, &loff, &res, &tmp, &text, &text_off, &cnames, &cname_off};
         for (vmx::DevBuf* b : all) b->release();
         names_of = nullptr;

@@ -1,5 +1,5 @@
-// vmx_sam_dev.hip — host side of the device SAM emitter (kernels: k_sam.hip): vmx_sam_emit_dev works on device pointers only, vm_sam_emit_device
-// is the C-ABI around it (validation, uploads through the context's upload helpers, the text's way back through the mailbox's page-locked landing
+// vmx_sam_dev.hip — host side of the device SAM emitter (kernels: k_sam.hip): vmx_sam_emit_dev works on device pointers only, vm_sam_emit_device_comments
+// (and vm_sam_emit_device, the same without comments) is the C-ABI around it (validation, uploads through the context's upload helpers, the text's way back through the mailbox's page-locked landing
 // block). Three host waits per call: the operator pass's sizes, the lines' sizes, the text.
 #include "vmx_sam_dev.h"
 #include "vmx_index_priv.h"
@@ -101,6 +101,13 @@ extern "C" {
 int vm_sam_emit_device(vm_ctx* c, const vm_index* mi, const vm_sam_opts* o, int64_t n_reads, const char* names, const int64_t* name_off, const char* seqs,
                        const int64_t* seq_off, const char* quals, const int64_t* qual_off, const vm_record* recs, int64_t n_recs, const char* cigar_blob,
                        const int32_t* status, char** text, int64_t** text_off, int64_t* n_lines, int64_t* n_skipped) {
+    return vm_sam_emit_device_comments(c, mi, o, n_reads, names, name_off, seqs, seq_off, quals, qual_off, nullptr, nullptr, recs, n_recs, cigar_blob, status, text, text_off,
+                                       n_lines, n_skipped);
+}
+
+int vm_sam_emit_device_comments(vm_ctx* c, const vm_index* mi, const vm_sam_opts* o, int64_t n_reads, const char* names, const int64_t* name_off, const char* seqs,
+                                const int64_t* seq_off, const char* quals, const int64_t* qual_off, const char* comments, const int64_t* com_off, const vm_record* recs,
+                                int64_t n_recs, const char* cigar_blob, const int32_t* status, char** text, int64_t** text_off, int64_t* n_lines, int64_t* n_skipped) {
     if (text) *text = nullptr;
     if (text_off) *text_off = nullptr;
     if (n_lines) *n_lines = 0;
@@ -125,10 +132,11 @@ int vm_sam_emit_device(vm_ctx* c, const vm_index* mi, const vm_sam_opts* o, int6
         for (int64_t r = 0; r < n_reads; ++r) { if (off[r] < 0 || off[r + 1] < off[r]) return false; *lo = std::min(*lo, off[r]); *hi = std::max(*hi, off[r + 1]); }
         return true;
     };
-    int64_t nlo, nhi, slo, shi, qlo = 0, qhi = 0;
+    int64_t nlo, nhi, slo, shi, qlo = 0, qhi = 0, clo = 0, chi = 0;
     const bool with_q = quals && qual_off;
-    if (!range(name_off, &nlo, &nhi) || !range(seq_off, &slo, &shi) || (with_q && !range(qual_off, &qlo, &qhi))) { set_error("vm_sam_emit_device: offsets must not decrease"); return VM_ERR_ARG; }
-    if ((nhi > nlo && !names) || (shi > slo && !seqs)) { set_error("vm_sam_emit_device: bad arguments"); return VM_ERR_ARG; }
+    if (!range(name_off, &nlo, &nhi) || !range(seq_off, &slo, &shi) || (with_q && !range(qual_off, &qlo, &qhi)) || (com_off && !range(com_off, &clo, &chi))) { set_error("vm_sam_emit_device: offsets must not decrease"); return VM_ERR_ARG; }
+    if ((nhi > nlo && !names) || (shi > slo && !seqs) || (chi > clo && !comments)) { set_error("vm_sam_emit_device: bad arguments"); return VM_ERR_ARG; }
+    const bool with_c = comments && com_off && chi > clo;                // (no comment byte at all: the run is the one without comments)
     VMX_HIP(hipSetDevice(c->device));
     vmx_fetch_scope fs(c);
     vmx_sam_bufs* S = vmx_ctx_sam_bufs(c);
@@ -137,6 +145,7 @@ int vm_sam_emit_device(vm_ctx* c, const vm_index* mi, const vm_sam_opts* o, int6
     VMX_TRY(upload(S->names, names ? names + nlo : names, (size_t)(nhi - nlo), st)); VMX_TRY(upload(S->name_off, name_off, (size_t)n_reads + 1, st));
     VMX_TRY(upload(S->seqs, seqs ? seqs + slo : seqs, (size_t)(shi - slo), st)); VMX_TRY(upload(S->seq_off, seq_off, (size_t)n_reads + 1, st));
     if (with_q) { VMX_TRY(upload(S->quals, quals + qlo, (size_t)(qhi - qlo), st)); VMX_TRY(upload(S->qual_off, qual_off, (size_t)n_reads + 1, st)); }
+    if (with_c) { VMX_TRY(upload(S->comments, comments + clo, (size_t)(chi - clo), st)); VMX_TRY(upload(S->com_off, com_off, (size_t)n_reads + 1, st)); }
     VMX_TRY(upload(S->recs, recs, (size_t)n_recs, st)); VMX_TRY(upload(S->cigars, cigar_blob, (size_t)cig_len, st));
     if (status) VMX_TRY(upload(S->status, status, (size_t)n_reads, st));
     const size_t rg_len = o->rg_id ? strlen(o->rg_id) : 0;
@@ -146,6 +155,7 @@ int vm_sam_emit_device(vm_ctx* c, const vm_index* mi, const vm_sam_opts* o, int6
     A.names = S->names.as<const char>(); A.name_off = S->name_off.as<const int64_t>(); A.name_base = nlo;
     A.seqs = S->seqs.as<const char>(); A.seq_off = S->seq_off.as<const int64_t>(); A.seq_base = slo;
     A.quals = with_q ? S->quals.as<const char>() : nullptr; A.qual_off = with_q ? S->qual_off.as<const int64_t>() : nullptr; A.qual_base = qlo;
+    A.comments = with_c ? S->comments.as<const char>() : nullptr; A.com_off = with_c ? S->com_off.as<const int64_t>() : nullptr; A.com_base = clo;
     A.recs = S->recs.as<const vm_record>(); A.cigars = S->cigars.as<const char>(); A.cigars_len = cig_len;
     A.status = status ? S->status.as<const int32_t>() : nullptr;
     A.md = o->md; A.shortcs = o->shortcs; A.cigar2cg = o->cigar2cg; A.markunbalancetra = o->markunbalancetra; A.hardclip = o->hardclip; A.fakecigar = o->fakecigar; A.asm_mode = o->asm_mode;

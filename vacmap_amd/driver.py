@@ -503,10 +503,11 @@ def build_parser():
     p.add_argument('--bam-tags', metavar='LIST|all', default=None,
                    help='carry auxiliary fields of -read x.bam records to the output as optional fields (the reference drops them): a comma-separated list '
                         'of two-character tags (MM,ML,MN) or `all`; with --bam-reader native they are turned into SAM text on the GPU. They travel as the '
-                        "read's comment, with or without --copycomments, through the host SAM emitter")
-    p.add_argument('--sam-emitter', choices=['host', 'device'], default='host',
+                        "read's comment, with or without --copycomments, through the host SAM emitter (the device's with --sam-emitter device-comments)")
+    p.add_argument('--sam-emitter', choices=['host', 'device', 'device-comments'], default='host',
                    help='who makes the SAM text of a batch: -t host threads (default) or the GPU (merged CIGAR, NM, MD / cs, SA and the lines themselves, on '
-                        'VMX_EMIT_CONTEXTS contexts of their own); with --copycomments, or a reference that holds letters other than ACGTN, the host emitter is used')
+                        'VMX_EMIT_CONTEXTS contexts of their own); with --copycomments, --bam-tags, or a reference that holds letters other than ACGTN, the host '
+                        'emitter is used. device-comments: the GPU also copies the comments (--copycomments, --bam-tags), so only such a reference falls back')
     return p
 
 
@@ -778,7 +779,10 @@ def _carries_comments(args, path):
 
 
 def _device_emitter_wanted(args, rank):
-    """--sam-emitter device, unless the run copies comments (the filter of :20686 stays on the host emitter): one stderr line says so"""
+    """--sam-emitter device, unless the run copies comments (with `device` the filter of :20686 stays on the host emitter): one stderr line says
+    so. --sam-emitter device-comments hands the comments to the device emitter instead."""
+    if args.sam_emitter == 'device-comments':               # the comment stage of k_sam_lines: neither fallback below is taken
+        return True
     if args.sam_emitter != 'device':
         return False
     if args.copycomments:
@@ -805,6 +809,7 @@ def _run_asm(args, net, lib, ctx, index, prm, opts, out, device, t_start):
     from .lib import align_batch_raw, sam_emit, sam_emit_device, VmxError
     world, rank = net.world, net.rank
     on_device = [_device_emitter_wanted(args, rank)]
+    with_c = args.copycomments or bool(args.bam_tags)
     if not args.workdir:
         sys.exit('workdir not provided! -workdir /path/to/workdir')                      # vacmap:247-249
     os.makedirs(args.workdir, exist_ok=True)
@@ -825,14 +830,15 @@ def _run_asm(args, net, lib, ctx, index, prm, opts, out, device, t_start):
             text = None
             if on_device[0]:                                                                # --sam-emitter device: on the run's own context
                 try:
-                    text, toff, _, ns = sam_emit_device(ctx, index, opts, nb, no, sb, so, raw, quals=qb, qual_off=qo)
+                    dev_c = with_c and args.sam_emitter == 'device-comments'
+                    text, toff, _, ns = sam_emit_device(ctx, index, opts, nb, no, sb, so, raw, quals=qb, qual_off=qo, comments=cb if dev_c else None,
+                                                        com_off=co if dev_c else None)
                 except VmxError as e:
                     if e.code != VM_ERR_UNSUPPORTED:
                         raise
                     on_device[0] = False
                     _device_emitter_given_up(str(e), rank)
             if text is None:
-                with_c = args.copycomments or bool(args.bam_tags)
                 text, toff, _, ns = sam_emit(lib, index, opts, nb, no, sb, so, raw, quals=qb, qual_off=qo, comments=cb if with_c else None,
                                              com_off=co if with_c else None, nthreads=max(1, args.t))
             for x, g in enumerate(share):
@@ -924,6 +930,7 @@ class ReadStream:
         # --sam-emitter device: the emit jobs run on VMX_EMIT_CONTEXTS threads, each with a context of its own (as the feeders have); the aligner
         # threads and their contexts are what they are without it
         self.emit_device = _device_emitter_wanted(args, net.rank)
+        self.emit_comments = args.sam_emitter == 'device-comments'
         self.emit_ctxs, self.emit_free, self.emit_local = [], queue.Queue(), threading.local()
         self.emit_total = emit_total
         if self.emit_device:
@@ -1268,7 +1275,9 @@ class ReadStream:
             text = None
             if self.emit_device:
                 try:
-                    text, toff, nl, ns = self.V.sam_emit_device(self.emit_context(), self.index, self.opts, nb, no, sb, so, raw, quals=qb, qual_off=qo)
+                    dev_c = self.emit_comments and cb is not None
+                    text, toff, nl, ns = self.V.sam_emit_device(self.emit_context(), self.index, self.opts, nb, no, sb, so, raw, quals=qb, qual_off=qo,
+                                                                comments=cb if dev_c else None, com_off=co if dev_c else None)
                 except self.V.VmxError as e:
                     if e.code != VM_ERR_UNSUPPORTED:
                         raise

@@ -167,6 +167,7 @@ class VmxLib:
         L.vm_align_trace.argtypes = [vp, vp, P(Params), i64, cp, vp, C.c_int, P(P(i64)), P(P(i64))]
         L.vm_sam_emit.argtypes = [vp, P(SamOpts), i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, C.c_int, P(vp), P(P(i64)), P(i64), P(i64)]
         L.vm_sam_emit_device.argtypes = [vp, vp, P(SamOpts), i64, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, P(vp), P(P(i64)), P(i64), P(i64)]
+        L.vm_sam_emit_device_comments.argtypes = [vp, vp, P(SamOpts), i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, P(vp), P(P(i64)), P(i64), P(i64)]
         L.vm_sam_emit_device_times.argtypes = [vp, P(dbl)]
         L.vm_blob_gather.argtypes = [vp, vp, vp, i64, vp, vp]; L.vm_blob_gather.restype = i64
         L.vm_blob_write_parts.argtypes = [C.c_int, vp, vp, vp, vp, i64]; L.vm_blob_write_parts.restype = i64
@@ -531,19 +532,24 @@ def sam_emit(lib, index, opts, names, name_off, seqs, seq_off, raw, quals=None, 
     return buf.array, off, nl.value, ns.value
 
 
-def sam_emit_device(ctx, index, opts, names, name_off, seqs, seq_off, raw, quals=None, qual_off=None):
-    """SAM lines of a batch made on the GPU (vm_sam_emit_device, on the context's stream): sam_emit's return tuple, byte for byte. Comments
-    are not copied; a reference with letters other than ACGTN raises VmxError(VM_ERR_UNSUPPORTED)."""
+def sam_emit_device(ctx, index, opts, names, name_off, seqs, seq_off, raw, quals=None, qual_off=None, *, comments=None, com_off=None):
+    """SAM lines of a batch made on the GPU (vm_sam_emit_device, on the context's stream): sam_emit's return tuple, byte for byte. With
+    comments / com_off (keywords only) the reads' comments are copied as sam_emit copies them (vm_sam_emit_device_comments); a reference with
+    letters other than ACGTN raises VmxError(VM_ERR_UNSUPPORTED)."""
     lib = ctx.lib
     names = _u8(names); seqs = _u8(seqs)
     name_off = np.ascontiguousarray(name_off, dtype=np.int64); seq_off = np.ascontiguousarray(seq_off, dtype=np.int64)
     n = len(seq_off) - 1
     q = _u8(quals) if quals is not None else None; qo = np.ascontiguousarray(qual_off, dtype=np.int64) if quals is not None else None
     text = C.c_void_p(); toff = C.POINTER(C.c_int64)(); nl = C.c_int64(); ns = C.c_int64()
-    lib.check(lib.L.vm_sam_emit_device(ctx.h, index.h, C.byref(opts), n, names.ctypes.data, name_off.ctypes.data, seqs.ctypes.data, seq_off.ctypes.data,
-                                       q.ctypes.data if q is not None else None, qo.ctypes.data if qo is not None else None,
-                                       C.cast(raw.recs, C.c_void_p), raw.nrec, raw.blob, raw.status.ctypes.data if len(raw.status) else None,
-                                       C.byref(text), C.byref(toff), C.byref(nl), C.byref(ns)))
+    tail = (C.cast(raw.recs, C.c_void_p), raw.nrec, raw.blob, raw.status.ctypes.data if len(raw.status) else None, C.byref(text), C.byref(toff), C.byref(nl), C.byref(ns))
+    head = (ctx.h, index.h, C.byref(opts), n, names.ctypes.data, name_off.ctypes.data, seqs.ctypes.data, seq_off.ctypes.data,
+            q.ctypes.data if q is not None else None, qo.ctypes.data if qo is not None else None)
+    if comments is None and com_off is None:
+        lib.check(lib.L.vm_sam_emit_device(*head, *tail))
+    else:
+        cm = _u8(comments) if comments is not None else None; co = np.ascontiguousarray(com_off, dtype=np.int64) if com_off is not None else None
+        lib.check(lib.L.vm_sam_emit_device_comments(*head, cm.ctypes.data if cm is not None and len(cm) else None, co.ctypes.data if co is not None else None, *tail))
     off = np.ctypeslib.as_array(toff, shape=(n + 1,)).copy()
     lib.L.vm_free(toff)
     buf = _OwnedText(lib, text, int(off[-1]))
