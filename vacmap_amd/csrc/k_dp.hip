@@ -8,6 +8,7 @@
 // normative spec VMX-DP and are parity-tested bit-for-bit against oracle/vmo_dp.cc. Integer, wave64,
 // anti-diagonal kernels ("one lane = one row of a 64-row stripe"): no MFMA (nothing here is a contraction); one wavefront per
 // problem, problems taken longest-first from a device-side queue (k_size_order in k_ed.hip).
+#define VMX_GAPFILL_CHECKS          // this file evaluates the layouts' build-time checks (vmx_gapfill.h)
 #include "vmx_device.h"
 #include "vmx_kernels.h"
 
@@ -112,7 +113,7 @@ __global__ void __launch_bounds__(64) k_extend(const uint8_t* __restrict__ tcode
 // the value lane 0 needs rides into the wave_shr:1 move as its old operand; chunks are refilled with one coalesced load per 64
 // steps and lane 63's outputs leave through a rotating register FIFO flushed once per 64 columns — nothing on the per-step path
 // waits for memory. Chunks in which every lane is inside its row run without the per-step activity test.
-// Traceback bytes are stored as tb[(stripe*(ql+63) + step)*64 + lane]: one coalesced 64-byte line per step.
+// Traceback bytes: the 64-row striped layout (vmx_tb_rows64, vmx_gapfill.h): one coalesced 64-byte line per step.
 // (The batched path runs its small problems — nearly all of them — in the anti-diagonal band form of vmx_dp_ad.h first.)
 __device__ __forceinline__ int vmx_gap_open_row(int i, int o1, int e1, int o2, int e2) {   // H(i,0) = H(0,i), i >= 1
     int a = -(o1 + i * e1), b = -(o2 + i * e2);
@@ -123,23 +124,48 @@ __device__ __forceinline__ int vmx_gap_open_row(int i, int o1, int e1, int o2, i
 // row 2l+1 in the low half and row 2l+2 in the high half of each register, the high row one column behind the low one, so both cells
 // of a step only need values of the step before: up(lo) = the lane above's high half, up(hi) = the own low half — one DPP move and one
 // v_alignbit per quantity. The recurrence runs on v_pk_add/sub/max_i16; comparison results are sign masks (v_pk_ashrrev_i16 15) merged
-// with v_bfi. Traceback bytes: tb[((stripe*(ql+127) + step)*64 + lane)*2 + half]. NEG16 stands for -infinity: a real score never gets
+// with v_bfi. Traceback bytes: the 128-row striped layout (vmx_tb_rows128, vmx_gapfill.h), a lane's two bytes side by side. NEG16 stands for -infinity: a real score never gets
 // within reach of it, and it is never the larger operand of a max whose result is used.
 #define VMX_NEG16 (-20000)
+struct vmx_pk_consts { unsigned O1, O2, E1C, E2C, MATCH, MISM, ONE; };
+__device__ __forceinline__ vmx_pk_consts vmx_pk_consts_of(int match, int mismatch, int o1, int e1, int o2, int e2) {
+    return {vmx_pk(o1, o1), vmx_pk(o2, o2), vmx_pk(e1, e1), vmx_pk(e2, e2), vmx_pk(match, match), vmx_pk(mismatch, mismatch), vmx_pk(1, 1)};
+}
+// one packed cell (both halves) of the full-matrix int16 forms: up = (H, E1, E2) of the cell above, (Hleft, F1, F2) of the cell to the left, Hdiag the diagonal
+// predecessor, ti2 / qc the target / query codes. Gives the cell's h, E1, E2, F1, F2 and returns its two traceback bytes (low half's in bits 0-7).
+__device__ __forceinline__ unsigned vmx_pk_cell(const vmx_pk_consts& K, unsigned upH, unsigned upE1, unsigned upE2, unsigned Hleft, unsigned F1, unsigned F2, unsigned Hdiag,
+                                                unsigned ti2, unsigned qc, unsigned& h, unsigned& e1v, unsigned& e2v, unsigned& nF1, unsigned& nF2) {
+    const unsigned a1 = vmx_pk_sub(upH, K.O1), a2 = vmx_pk_sub(upH, K.O2);
+    unsigned b = vmx_pk_neg(vmx_pk_sub(a1, upE1)) & 0x00080008u;                       // upE1 > a1
+    b |= vmx_pk_neg(vmx_pk_sub(a2, upE2)) & 0x00100010u;
+    e1v = vmx_pk_sub(vmx_pk_max(a1, upE1), K.E1C); e2v = vmx_pk_sub(vmx_pk_max(a2, upE2), K.E2C);
+    const unsigned c1 = vmx_pk_sub(Hleft, K.O1), c2 = vmx_pk_sub(Hleft, K.O2);
+    b |= vmx_pk_neg(vmx_pk_sub(c1, F1)) & 0x00200020u;                                  // F1 > c1
+    b |= vmx_pk_neg(vmx_pk_sub(c2, F2)) & 0x00400040u;
+    nF1 = vmx_pk_sub(vmx_pk_max(c1, F1), K.E1C); nF2 = vmx_pk_sub(vmx_pk_max(c2, F2), K.E2C);
+    const unsigned eqm = vmx_pk_neg(vmx_pk_sub(ti2 ^ qc, K.ONE));                       // codes are 0..5: x - 1 < 0 iff x == 0
+    h = vmx_pk_add(Hdiag, vmx_bfi(eqm, K.MATCH, K.MISM));
+    unsigned src = 0, m;
+    m = vmx_pk_neg(vmx_pk_sub(h, e1v)); src = vmx_bfi(m, 0x00010001u, src); h = vmx_pk_max(h, e1v);
+    m = vmx_pk_neg(vmx_pk_sub(h, nF1)); src = vmx_bfi(m, 0x00030003u, src); h = vmx_pk_max(h, nF1);
+    m = vmx_pk_neg(vmx_pk_sub(h, e2v)); src = vmx_bfi(m, 0x00020002u, src); h = vmx_pk_max(h, e2v);
+    m = vmx_pk_neg(vmx_pk_sub(h, nF2)); src = vmx_bfi(m, 0x00040004u, src); h = vmx_pk_max(h, nF2);
+    return vmx_pk_bytes(b | src);
+}
 __device__ __forceinline__ void vmx_gapfill_fill16(const uint8_t* __restrict__ T, const uint8_t* __restrict__ Q, int tl, int ql, int match, int mismatch,
                                                    int o1, int e1, int o2, int e2, uint8_t* __restrict__ tb, int32_t* __restrict__ bH,
                                                    int32_t* __restrict__ score_out, int lane) {
     int32_t* bE1 = bH + (ql + 1);
     int32_t* bE2 = bE1 + (ql + 1);
-    const int W = ql + 127;
-    const int nstr = (tl + 127) >> 7;
-    const unsigned O1 = vmx_pk(o1, o1), O2 = vmx_pk(o2, o2), E1C = vmx_pk(e1, e1), E2C = vmx_pk(e2, e2);
-    const unsigned MATCH = vmx_pk(match, match), MISM = vmx_pk(mismatch, mismatch), ONE = vmx_pk(1, 1);
+    typedef vmx_tb_rows128 TB;                                  // a step's line: TB::R bytes, this lane's two at 2 * lane (rows 2 * lane, 2 * lane + 1 of the stripe)
+    const int W = TB::W(ql);
+    const int nstr = TB::nstr(tl);
+    const vmx_pk_consts K = vmx_pk_consts_of(match, mismatch, o1, e1, o2, e2);
     const int rf = (tl - 1) & 127;                              // row tl inside the last stripe: lane rf / 2, half rf & 1
     const int t_fin = ql - 1 + rf;                              // step at which that lane computes column ql
     unsigned fin = 0;
     for (int s = 0; s < nstr; ++s) {
-        const int i0 = s * 128 + 2 * lane + 1;                  // low-half row; the high half is row i0 + 1
+        const int i0 = s * TB::R + 2 * lane + 1;                 // low-half row; the high half is row i0 + 1
         const unsigned ti2 = vmx_pk(i0 <= tl ? vmx_tcode(T[i0 - 1]) : 5, i0 + 1 <= tl ? vmx_tcode(T[i0]) : 5);     // 5 never equals a query code (rows past tl)
         unsigned Hleft = vmx_pk(vmx_gap_open_row(i0, o1, e1, o2, e2), vmx_gap_open_row(i0 + 1, o1, e1, o2, e2));
         unsigned F1 = vmx_pk(VMX_NEG16, VMX_NEG16), F2 = F1;
@@ -147,7 +173,7 @@ __device__ __forceinline__ void vmx_gapfill_fill16(const uint8_t* __restrict__ T
         unsigned outH = 0, outE1 = F1, outE2 = F1, qc = vmx_pk(4, 4);
         int sH = 0, sE1 = 0, sE2 = 0;                           // lane 63's high-half outputs of the last 64 steps (register FIFO, newest in lane 0)
         const bool store_bnd = s + 1 < nstr;
-        uint8_t* tbs = tb + (size_t)s * (size_t)W * 128 + 2 * lane;
+        uint8_t* tbs = tb + TB::row_off(s, W, 0, 2 * lane);
         for (int t0 = 0; t0 < W; t0 += 64) {
             // 64-column chunks for lane 0's low row, pre-shifted into the high half (the hand-off shifts them down): query bases Q[t0 ..] and
             // the row above the stripe for columns t0+1 ..
@@ -167,23 +193,8 @@ __device__ __forceinline__ void vmx_gapfill_fill16(const uint8_t* __restrict__ T
                 const unsigned upE2 = vmx_alignbit16(outE2, (unsigned)vmx_shr1_in((int)outE2, (int)cE2));
                 qc = vmx_alignbit16(qc, (unsigned)vmx_shr1_in((int)qc, (int)qchunk));
                 cH = (unsigned)vmx_rol1((int)cH); cE1 = (unsigned)vmx_rol1((int)cE1); cE2 = (unsigned)vmx_rol1((int)cE2); qchunk = (unsigned)vmx_rol1((int)qchunk);
-                const unsigned a1 = vmx_pk_sub(upH, O1), a2 = vmx_pk_sub(upH, O2);
-                unsigned b = vmx_pk_neg(vmx_pk_sub(a1, upE1)) & 0x00080008u;                       // upE1 > a1
-                b |= vmx_pk_neg(vmx_pk_sub(a2, upE2)) & 0x00100010u;
-                const unsigned e1v = vmx_pk_sub(vmx_pk_max(a1, upE1), E1C), e2v = vmx_pk_sub(vmx_pk_max(a2, upE2), E2C);
-                const unsigned c1 = vmx_pk_sub(Hleft, O1), c2 = vmx_pk_sub(Hleft, O2);
-                b |= vmx_pk_neg(vmx_pk_sub(c1, F1)) & 0x00200020u;                                  // F1 > c1
-                b |= vmx_pk_neg(vmx_pk_sub(c2, F2)) & 0x00400040u;
-                const unsigned nF1 = vmx_pk_sub(vmx_pk_max(c1, F1), E1C), nF2 = vmx_pk_sub(vmx_pk_max(c2, F2), E2C);
-                const unsigned eqm = vmx_pk_neg(vmx_pk_sub(ti2 ^ qc, ONE));                         // codes are 0..5: x - 1 < 0 iff x == 0
-                unsigned h = vmx_pk_add(Hdiag, vmx_bfi(eqm, MATCH, MISM));
-                unsigned src = 0, m;
-                m = vmx_pk_neg(vmx_pk_sub(h, e1v)); src = vmx_bfi(m, 0x00010001u, src); h = vmx_pk_max(h, e1v);
-                m = vmx_pk_neg(vmx_pk_sub(h, nF1)); src = vmx_bfi(m, 0x00030003u, src); h = vmx_pk_max(h, nF1);
-                m = vmx_pk_neg(vmx_pk_sub(h, e2v)); src = vmx_bfi(m, 0x00020002u, src); h = vmx_pk_max(h, e2v);
-                m = vmx_pk_neg(vmx_pk_sub(h, nF2)); src = vmx_bfi(m, 0x00040004u, src); h = vmx_pk_max(h, nF2);
-                b |= src;
-                *(uint16_t*)(tbs + (size_t)t * 128) = (uint16_t)vmx_pk_bytes(b);
+                unsigned h, e1v, e2v, nF1, nF2;
+                *(uint16_t*)(tbs + (size_t)t * TB::R) = (uint16_t)vmx_pk_cell(K, upH, upE1, upE2, Hleft, F1, F2, Hdiag, ti2, qc, h, e1v, e2v, nF1, nF2);
                 if (ramp_up) {
                     // low half active from step 2*lane, high half from step 2*lane + 1
                     const unsigned pm = (t >= 2 * lane ? 0xffffu : 0u) | (t >= 2 * lane + 1 ? 0xffff0000u : 0u);
@@ -212,7 +223,7 @@ __device__ __forceinline__ void vmx_gapfill_fill16(const uint8_t* __restrict__ T
 // row_ror:15, the last row's FIFO with row_ror:1. A stripe is W = (ql + 31 rounded up to 16) steps wide, so every row starts its stripes
 // on a multiple of 16 steps and all four rows refill their 16-column chunks together although they are in different stripes and
 // columns. Small problems pad far less this way: rows to a multiple of 32 instead of 128, ramp 31 columns instead of 127.
-// Traceback bytes: tb[((stripe*W + step)*16 + l)*2 + half].
+// Traceback bytes: the 32-row striped layout (vmx_tb_rows32, vmx_gapfill.h).
 #ifdef VMX_EMU
 __device__ __forceinline__ int vmx_r16_shr1_in(int v, int in) { const int l = vmx_lane(); const int e = __shfl(v, (l & 48) | ((l + 15) & 15)); return (l & 15) == 0 ? in : e; }
 __device__ __forceinline__ int vmx_r16_rol1(int v) { const int l = vmx_lane(); return __shfl(v, (l & 48) | ((l + 1) & 15)); }
@@ -233,10 +244,10 @@ __device__ __forceinline__ int vmx_gapfill_fill16x4(const uint8_t* __restrict__ 
     const int l = lane & 15;
     int32_t* bE1 = bH + (ql + 1);
     int32_t* bE2 = bE1 + (ql + 1);
-    const int W = VMX_X4_W(ql);
-    const int nstr = (tl + 31) >> 5;
-    const unsigned O1 = vmx_pk(o1, o1), O2 = vmx_pk(o2, o2), E1C = vmx_pk(e1, e1), E2C = vmx_pk(e2, e2);
-    const unsigned MATCH = vmx_pk(match, match), MISM = vmx_pk(mismatch, mismatch), ONE = vmx_pk(1, 1);
+    typedef vmx_tb_rows32 TB;                                   // a step's line: TB::R bytes, this lane's two at 2 * l
+    const int W = TB::W(ql);
+    const int nstr = TB::nstr(tl);
+    const vmx_pk_consts K = vmx_pk_consts_of(match, mismatch, o1, e1, o2, e2);
     const unsigned NEGP = vmx_pk(VMX_NEG16, VMX_NEG16);
     const int rf = (tl - 1) & 31;                               // row tl inside the last stripe: lane rf / 2 of the row, half rf & 1
     const int t_fin = ql - 1 + rf;
@@ -263,7 +274,7 @@ __device__ __forceinline__ int vmx_gapfill_fill16x4(const uint8_t* __restrict__ 
         if (__any(act && t == 0 && s > 0)) __syncthreads();    // a row is about to read the boundary rows its previous stripe stored
         unsigned qchunk, cH, cE1, cE2;
         if (act && t == 0) {
-            const int i0 = s * 32 + 2 * l + 1;
+            const int i0 = s * TB::R + 2 * l + 1;
             ti2 = vmx_pk(i0 <= tl ? vmx_tcode(T[i0 - 1]) : 5, i0 + 1 <= tl ? vmx_tcode(T[i0]) : 5);
             Hleft = vmx_pk(vmx_gap_open_row(i0, o1, e1, o2, e2), vmx_gap_open_row(i0 + 1, o1, e1, o2, e2));
             Hdiag = vmx_pk(i0 - 1 == 0 ? 0 : vmx_gap_open_row(i0 - 1, o1, e1, o2, e2), vmx_gap_open_row(i0, o1, e1, o2, e2));
@@ -271,7 +282,7 @@ __device__ __forceinline__ int vmx_gapfill_fill16x4(const uint8_t* __restrict__ 
             outH = 0; outE1 = NEGP; outE2 = NEGP; qc = vmx_pk(4, 4);
             sHE = 0; sE2 = 0;
             store_bnd = s + 1 < nstr;
-            tbp = tb + (size_t)s * (size_t)W * 32 + 2 * l;
+            tbp = tb + TB::row_off(s, W, 0, 2 * l);
         }
         // a stripe's first chunk is loaded here (the previous stripe has only just stored it); the others were prefetched a block ago
         const bool first = __any(act && t == 0);
@@ -288,23 +299,9 @@ __device__ __forceinline__ int vmx_gapfill_fill16x4(const uint8_t* __restrict__ 
                 qc = vmx_alignbit16(qc, (unsigned)vmx_r16_shr1_in((int)qc, (int)qchunk));                                          \
                 cH = (unsigned)vmx_r16_rol1((int)cH); cE1 = (unsigned)vmx_r16_rol1((int)cE1); cE2 = (unsigned)vmx_r16_rol1((int)cE2); \
                 qchunk = (unsigned)vmx_r16_rol1((int)qchunk);                                                                      \
-                const unsigned a1 = vmx_pk_sub(upH, O1), a2 = vmx_pk_sub(upH, O2);                                                 \
-                unsigned b = vmx_pk_neg(vmx_pk_sub(a1, upE1)) & 0x00080008u;                                                       \
-                b |= vmx_pk_neg(vmx_pk_sub(a2, upE2)) & 0x00100010u;                                                               \
-                const unsigned e1v = vmx_pk_sub(vmx_pk_max(a1, upE1), E1C), e2v = vmx_pk_sub(vmx_pk_max(a2, upE2), E2C);           \
-                const unsigned c1 = vmx_pk_sub(Hleft, O1), c2 = vmx_pk_sub(Hleft, O2);                                             \
-                b |= vmx_pk_neg(vmx_pk_sub(c1, F1)) & 0x00200020u;                                                                 \
-                b |= vmx_pk_neg(vmx_pk_sub(c2, F2)) & 0x00400040u;                                                                 \
-                const unsigned nF1 = vmx_pk_sub(vmx_pk_max(c1, F1), E1C), nF2 = vmx_pk_sub(vmx_pk_max(c2, F2), E2C);               \
-                const unsigned eqm = vmx_pk_neg(vmx_pk_sub(ti2 ^ qc, ONE));                                                        \
-                unsigned h = vmx_pk_add(Hdiag, vmx_bfi(eqm, MATCH, MISM));                                                         \
-                unsigned src = 0, m;                                                                                               \
-                m = vmx_pk_neg(vmx_pk_sub(h, e1v)); src = vmx_bfi(m, 0x00010001u, src); h = vmx_pk_max(h, e1v);                    \
-                m = vmx_pk_neg(vmx_pk_sub(h, nF1)); src = vmx_bfi(m, 0x00030003u, src); h = vmx_pk_max(h, nF1);                    \
-                m = vmx_pk_neg(vmx_pk_sub(h, e2v)); src = vmx_bfi(m, 0x00020002u, src); h = vmx_pk_max(h, e2v);                    \
-                m = vmx_pk_neg(vmx_pk_sub(h, nF2)); src = vmx_bfi(m, 0x00040004u, src); h = vmx_pk_max(h, nF2);                    \
-                b |= src;                                                                                                          \
-                if (act) *(uint16_t*)(tbp + (TT) * 32) = (uint16_t)vmx_pk_bytes(b);                                                \
+                unsigned h, e1v, e2v, nF1, nF2;                                                                                    \
+                const unsigned bytes = vmx_pk_cell(K, upH, upE1, upE2, Hleft, F1, F2, Hdiag, ti2, qc, h, e1v, e2v, nF1, nF2);      \
+                if (act) *(uint16_t*)(tbp + (TT) * TB::R) = (uint16_t)bytes;                                                       \
                 if (RAMP) {                                                                                                        \
                     const int tc = t + (TT);                                                                                       \
                     const unsigned pm = (tc >= 2 * l ? 0xffffu : 0u) | (tc >= 2 * l + 1 ? 0xffff0000u : 0u);                       \
@@ -333,7 +330,7 @@ __device__ __forceinline__ int vmx_gapfill_fill16x4(const uint8_t* __restrict__ 
         }
 #undef VMX_X4_STEP
         if (act) {
-            t += 16; tbp += 16 * 32;
+            t += 16; tbp += 16 * TB::R;
             if (t == W) {
                 // the columns behind the last multiple of 16 are still in the FIFO (W - 31 >= ql): lane k holds column W - 31 - k
                 const int colr = W - 31 - l, col = colr;
@@ -366,11 +363,12 @@ __device__ __forceinline__ void vmx_gapfill_fill_one(const uint8_t* __restrict__
         int32_t* bE1 = bH + (ql + 1);
         int32_t* bE2 = bE1 + (ql + 1);
         const bool pk = !trivial && VMX_DP16_OK(tl, ql);      // two rows per lane in packed int16 (below); larger problems keep int32
-        const int W = ql + 63;
-        const int nstr = (trivial || pk) ? 0 : (tl + 63) >> 6;
+        typedef vmx_tb_rows64 TB;                             // a step's line: TB::R bytes, this lane's at `lane` (its row of the stripe)
+        const int W = TB::W(ql);
+        const int nstr = (trivial || pk) ? 0 : TB::nstr(tl);
         int outH = 0;
         for (int s = 0; s < nstr; ++s) {
-            const int i = s * 64 + lane + 1;
+            const int i = s * TB::R + lane + 1;
             const int ti = i <= tl ? (int)T[i - 1] : 4;       // rows past tl (last stripe) compute unused cells into the stripe's padding
             int Hleft = vmx_gap_open_row(i, o1, e1, o2, e2);
             int F1 = VMX_NEG, F2 = VMX_NEG;
@@ -380,7 +378,7 @@ __device__ __forceinline__ void vmx_gapfill_fill_one(const uint8_t* __restrict__
             int qc_cur = 4;
             int sH = 0, sE1 = 0, sE2 = 0;                    // lane 63's H/E1/E2 of the last 64 steps, newest in lane 0 (rotating register FIFO)
             const bool store_bnd = s + 1 < nstr;              // the row below this stripe exists
-            uint8_t* tbs = tb + (size_t)s * (size_t)W * 64 + lane;
+            uint8_t* tbs = tb + TB::row_off(s, W, 0, lane);
             // one step of the stripe: hand-off from the lane above (lane 0: head of the rotating chunk registers), the cell, lane 63's FIFO
 #define VMX_GF_STEP(PRED)                                                                                             \
             {                                                                                                         \
@@ -403,7 +401,7 @@ __device__ __forceinline__ void vmx_gapfill_fill_one(const uint8_t* __restrict__
                     if (F1 > h) { h = F1; src = 3; }                                                                  \
                     if (e2v > h) { h = e2v; src = 2; }                                                                \
                     if (F2 > h) { h = F2; src = 4; }                                                                  \
-                    tbs[(size_t)t * 64] = (uint8_t)(b | src);                                                         \
+                    tbs[(size_t)t * TB::R] = (uint8_t)(b | src);                                                        \
                     Hdiag = upH; Hleft = h;                                                                           \
                     outH = h; outE1 = e1v; outE2 = e2v;                                                               \
                 }                                                                                                     \
@@ -443,22 +441,21 @@ __device__ __forceinline__ void vmx_gapfill_fill_one(const uint8_t* __restrict__
 
 // order/counter: longest-first device work queue (order == nullptr: plain grid-stride over [0, n_prob))
 // SCORE = false: the batched path only consumes the traceback, so the small-problem form skips the score capture; out_score[p] then carries
-// the layout flag the traceback kernel reads (0: striped). REDO (k_gapfill_redo, the second launch of the batched path): the queue is the list the
-// first launch left behind (redo_cnt[0] = entries, redo_cnt[1] = this launch's queue head, redo_cnt[2] = the head loop's, redo_cnt[6] / [7] = larger
-// problems kept from a wave-wide band / filled in full after all).
+// the layout flag the traceback kernel reads (vmx_gapfill.h). REDO (k_gapfill_redo, the second launch of the batched path): the queue is the list the
+// first launch left behind, its length, this launch's two heads and its two result counters are fields of the chunk's control block (vmx_gf_ctl).
 template <bool SCORE, bool REDO = false>
 __device__ __forceinline__ void vmx_gapfill_fill_body(const uint8_t* __restrict__ tcodes, const uint8_t* __restrict__ qcodes,
                                                      const vmx_dp_prob* __restrict__ probs, int n_prob, int match, int mismatch,
                                                      int o1, int e1, int o2, int e2, uint8_t* __restrict__ tb_pool,
                                                      int32_t* __restrict__ bnd_pool, int32_t* __restrict__ out_score,
                                                      const int32_t* __restrict__ order, int32_t* __restrict__ counter,
-                                                     int32_t* __restrict__ redo_list = nullptr, int32_t* __restrict__ redo_cnt = nullptr,
+                                                     int32_t* __restrict__ redo_list = nullptr, vmx_gf_ctl* __restrict__ ctl = nullptr,
                                                      uint8_t* __restrict__ redo_pool = nullptr) {
     const int lane = vmx_lane();
     int static_next = 4 * (int)blockIdx.x;
     const bool redo_pass = REDO;
     if constexpr (REDO) {
-        n_prob = redo_cnt[0]; order = redo_list; counter = redo_cnt + 1;
+        n_prob = ctl->redo_n; order = redo_list; counter = &ctl->redo_head;
         // The larger problems of the list first (VMX_REDO_PK; on a single 16-lane row a 500 x 500 matrix is a millisecond-long serial chain that the rest
         // of the launch would wait for), TWO per task: X and Y share the wave in the wave-wide anti-diagonal band (vmx_gapfill_fill_ad with LW = 64:
         // 128 ns diagonals, ns = 2 .. 4 by the rule of vmx_ad_ns over that geometry with the launch's own constants VMX_ADW_PCT / _MIN, the pair's larger
@@ -468,7 +465,7 @@ __device__ __forceinline__ void vmx_gapfill_fill_body(const uint8_t* __restrict_
         const bool ad_ok = vmx_ad_scores_ok(match, mismatch, o1, e1, o2, e2);
         while (true) {
             // two entries of the list at a time: a pair of the class shares the wave, a single one runs with Y idle
-            int q; { int v = 0; if (lane == 0) v = atomicAdd(redo_cnt + 2, 2); q = vmx_bcast0(v); }
+            int q; { int v = 0; if (lane == 0) v = atomicAdd(&ctl->redo_pair_head, 2); q = vmx_bcast0(v); }
             if (q >= n_prob) break;
             int pX = vmx_uniform_i32(order[q]), pY = q + 1 < n_prob ? vmx_uniform_i32(order[q + 1]) : -1;
             if (pY >= 0 && !VMX_REDO_PK(probs[pY].tl, probs[pY].ql)) pY = -1;
@@ -497,8 +494,8 @@ __device__ __forceinline__ void vmx_gapfill_fill_body(const uint8_t* __restrict_
                 if (keepX) out_score[pX] = VMX_PK_FLAG;
                 if (keepY) out_score[pY] = VMX_PK_FLAG;
                 const int kept = (int)keepX + (int)keepY, full = 1 + (int)(pY >= 0) - kept;
-                if (kept) atomicAdd(redo_cnt + 6, kept);
-                if (full) atomicAdd(redo_cnt + 7, full);
+                if (kept) atomicAdd(&ctl->redo_kept, kept);
+                if (full) atomicAdd(&ctl->redo_full, full);
             }
             if (!keepX || (pY >= 0 && !keepY)) __syncthreads();        // the band's stores land before the full fill writes the same bytes
             if (!keepX) vmx_gapfill_fill_one<SCORE>(tcodes, qcodes, probs, pX, match, mismatch, o1, e1, o2, e2, tb_pool, bnd_pool, out_score, lane, VMX_PK_FLAG, redo_pool);
@@ -519,7 +516,7 @@ __device__ __forceinline__ void vmx_gapfill_fill_body(const uint8_t* __restrict_
             vmx_dp_prob pr; pr.tl = 0; pr.ql = 0; pr.t_off = 0; pr.q_off = 0; pr.tb_off = 0; pr.bnd_off = 0;
             if (pg >= 0) pr = probs[pg];
             skip = redo_pass && pg >= 0 && VMX_REDO_PK(pr.tl, pr.ql);          // done above
-            x4 = pg >= 0 && !skip && pr.tl > 0 && pr.ql > 0 && VMX_DP16X4_OK(pr.tl, pr.ql);
+            x4 = pg >= 0 && !skip && vmx_gf_small(pr.tl, pr.ql);
             if (!SCORE && x4 && (lane & 15) == 0) out_score[pg] = 0;
             if (__any(x4))
                 vmx_gapfill_fill16x4<SCORE>(tcodes + pr.t_off, qcodes + pr.q_off, x4 ? pr.tl : 0, x4 ? pr.ql : 0, match, mismatch, o1, e1, o2, e2, vmx_tb_ptr(tb_pool, redo_pool, pr.tb_off),
@@ -540,24 +537,35 @@ __device__ __forceinline__ void vmx_gapfill_fill_body(const uint8_t* __restrict_
 // four per wave). Problems outside the small class run one after the other on the whole wave.
 __device__ __forceinline__ void vmx_gapfill_ad_pass(const uint8_t* __restrict__ tcodes, const uint8_t* __restrict__ qcodes, vmx_dp_prob* __restrict__ probs, int n_prob,
                                                    int match, int mismatch, int o1, int e1, int o2, int e2, uint8_t* __restrict__ tb_pool, int32_t* __restrict__ bnd_pool,
-                                                   int32_t* __restrict__ out_score, const int32_t* __restrict__ order, const int32_t* __restrict__ range, int32_t* __restrict__ counter,
-                                                   int32_t* __restrict__ redo_list, int32_t* __restrict__ redo_cnt, int ad_pct, unsigned long long* __restrict__ redo_bytes,
-                                                   unsigned long long redo_cap, int tb_by_ns) {
+                                                   int32_t* __restrict__ out_score, const int32_t* __restrict__ order, vmx_gf_ctl* __restrict__ ctl,
+                                                   int32_t* __restrict__ redo_list, int ad_pct, unsigned long long redo_cap, int tb_by_ns) {
     const int lane = vmx_lane();
     const int pct = ad_pct & 0xffff, pct_min = (ad_pct >> 16) & 0xffff;
     const bool ad_ok = vmx_ad_scores_ok(match, mismatch, o1, e1, o2, e2);
-    // the head of the longest-first queue (range[0] entries: the size classes above the small one) goes one problem per task: eight of them in
+    // the head of the longest-first queue (ctl->range[0] entries: the size classes above the small one) goes one problem per task: eight of them in
     // a row on one wave would be a multi-millisecond serial chain at the start of the launch; then eight at a time
-    const int n_head = range[0] < n_prob ? range[0] : n_prob;
+    const int n_head = ctl->range[0] < n_prob ? ctl->range[0] : n_prob;
+    // a small problem after the band attempt (called by lane 0 of the problem's row): kept, its flag names the band; otherwise it goes on the list for the
+    // second launch and takes its full-matrix traceback space out of the second pool
+    auto settle = [&](int p, const vmx_dp_prob& pr, int ns, bool keep, bool tried) {
+        out_score[p] = keep ? VMX_AD_FLAG + ns : 0;
+        if (keep) return;
+        if (tried) atomicAdd(&ctl->n_not_proven, 1);
+        // (round 6: the second pool is sized from history, not from a read-back of this counter: an allocation that does not fit EMPTIES the problem — no
+        //  fill, an empty CIGAR — and the host, which reads the counter with the batch's results, grows the pool and runs the batch again)
+        const unsigned long long need = (unsigned long long)vmx_gf_tb_bytes_redo(pr.tl, pr.ql), at = atomicAdd(&ctl->redo_bytes, need);
+        if (at + need > redo_cap) { probs[p].tl = 0; probs[p].ql = 0; probs[p].tb_off = 0; }
+        else { probs[p].tb_off = -(int64_t)at - 1; redo_list[atomicAdd(&ctl->redo_n, 1)] = p; }
+    };
     bool head = n_head > 0;
     while (true) {
         int pX = -1, pY = -1;                                  // this lane's row's two problems (-1: none)
         if (head) {
-            int q; { int v = 0; if (lane == 0) v = atomicAdd(counter + 1, 1); q = vmx_bcast0(v); }
+            int q; { int v = 0; if (lane == 0) v = atomicAdd(&ctl->head[1], 1); q = vmx_bcast0(v); }
             if (q >= n_head) { head = false; continue; }
             if (lane < 16) pX = order[q];
         } else {
-            int q0; { int v = 0; if (lane == 0) v = atomicAdd(counter, 8); q0 = n_head + vmx_bcast0(v); }
+            int q0; { int v = 0; if (lane == 0) v = atomicAdd(&ctl->head[0], 8); q0 = n_head + vmx_bcast0(v); }
             if (q0 >= n_prob) break;
             const int qX = q0 + 2 * (lane >> 4), qY = qX + 1;
             if (qX < n_prob) pX = order[qX];
@@ -567,7 +575,7 @@ __device__ __forceinline__ void vmx_gapfill_ad_pass(const uint8_t* __restrict__ 
         prX.tl = 0; prX.ql = 0; prX.t_off = 0; prX.q_off = 0; prX.tb_off = 0; prY = prX;
         if (pX >= 0) prX = probs[pX];
         if (pY >= 0) prY = probs[pY];
-        const bool x4X = pX >= 0 && prX.tl > 0 && prX.ql > 0 && VMX_DP16X4_OK(prX.tl, prX.ql), x4Y = pY >= 0 && prY.tl > 0 && prY.ql > 0 && VMX_DP16X4_OK(prY.tl, prY.ql);
+        const bool x4X = pX >= 0 && vmx_gf_small(prX.tl, prX.ql), x4Y = pY >= 0 && vmx_gf_small(prY.tl, prY.ql);
         // scores whose values do not fit the band's tagged 16-bit halves (vmx_ad_scores_ok: never the gap fill's own) send every problem to the second launch
         const int nsX = x4X && ad_ok ? vmx_ad_ns(prX.tl, prX.ql, match, o1, e1, o2, e2, pct, pct_min) : 0, nsY = x4Y && ad_ok ? vmx_ad_ns(prY.tl, prY.ql, match, o1, e1, o2, e2, pct, pct_min) : 0;
         const int ns = vmx_uniform_i32(vmx_wave_max_i32(nsX > nsY ? nsX : nsY));
@@ -590,29 +598,8 @@ __device__ __forceinline__ void vmx_gapfill_ad_pass(const uint8_t* __restrict__ 
             keepY = gY > 0 && vmx_ad_proven(scY, prY.tl, prY.ql, gY, match, o1, e1, o2, e2);
         }
         if ((lane & 15) == 0) {
-            // a problem for the second launch takes its full-matrix traceback space out of the second pool
-            if (x4X) {
-                out_score[pX] = keepX ? VMX_AD_FLAG + ns : 0;
-                if (!keepX) {
-                    if (triedX) atomicAdd(redo_cnt + 3, 1);          // tried in a band and not proven (the host adapts the band-width rule to this rate)
-                    // (round 6: the second pool is sized from history, not from a read-back of this counter: an allocation that does not fit EMPTIES the problem — no
-                    //  fill, an empty CIGAR — and the host, which reads the counter with the batch's results, grows the pool and runs the batch again)
-                    const unsigned long long need = (unsigned long long)VMX_REDO_TB_BYTES(prX.tl, prX.ql), at = atomicAdd(redo_bytes, need);
-                    if (at + need > redo_cap) { probs[pX].tl = 0; probs[pX].ql = 0; probs[pX].tb_off = 0; }
-                    else { probs[pX].tb_off = -(int64_t)at - 1; redo_list[atomicAdd(redo_cnt, 1)] = pX; }
-                }
-            }
-            if (x4Y) {
-                out_score[pY] = keepY ? VMX_AD_FLAG + ns : 0;
-                if (!keepY) {
-                    if (triedY) atomicAdd(redo_cnt + 3, 1);          // tried in a band and not proven (the host adapts the band-width rule to this rate)
-                    // (round 6: the second pool is sized from history, not from a read-back of this counter: an allocation that does not fit EMPTIES the problem — no
-                    //  fill, an empty CIGAR — and the host, which reads the counter with the batch's results, grows the pool and runs the batch again)
-                    const unsigned long long need = (unsigned long long)VMX_REDO_TB_BYTES(prY.tl, prY.ql), at = atomicAdd(redo_bytes, need);
-                    if (at + need > redo_cap) { probs[pY].tl = 0; probs[pY].ql = 0; probs[pY].tb_off = 0; }
-                    else { probs[pY].tb_off = -(int64_t)at - 1; redo_list[atomicAdd(redo_cnt, 1)] = pY; }
-                }
-            }
+            if (x4X) settle(pX, prX, ns, keepX, triedX);
+            if (x4Y) settle(pY, prY, ns, keepY, triedY);
         }
         for (int gk = 0; gk < 8; ++gk) {
             const int p = vmx_readlane((gk & 1) ? pY : pX, 16 * (gk >> 1));
@@ -633,19 +620,17 @@ __global__ void __launch_bounds__(64, 4) k_gapfill_fill_ns(const uint8_t* __rest
                                                         vmx_dp_prob* __restrict__ probs, int n_prob, int match, int mismatch,
                                                         int o1, int e1, int o2, int e2, uint8_t* __restrict__ tb_pool,
                                                         int32_t* __restrict__ bnd_pool, int32_t* __restrict__ out_score,
-                                                        const int32_t* __restrict__ order, const int32_t* __restrict__ range, int32_t* __restrict__ counter,
-                                                        int32_t* __restrict__ redo_list, int32_t* __restrict__ redo_cnt, int ad_pct,
-                                                        unsigned long long* __restrict__ redo_bytes, const int32_t* __restrict__ n_ptr,
-                                                        unsigned long long redo_cap, int tb_by_ns) {
+                                                        const int32_t* __restrict__ order, vmx_gf_ctl* __restrict__ ctl, int32_t* __restrict__ redo_list, int ad_pct,
+                                                        const int32_t* __restrict__ n_ptr, unsigned long long redo_cap, int tb_by_ns) {
     if (n_ptr) n_prob = *n_ptr;                        // the count on the device (an unplanned pass: the host launched for an upper bound)
-    vmx_gapfill_ad_pass(tcodes, qcodes, probs, n_prob, match, mismatch, o1, e1, o2, e2, tb_pool, bnd_pool, out_score, order, range, counter, redo_list, redo_cnt, ad_pct, redo_bytes, redo_cap, tb_by_ns);
+    vmx_gapfill_ad_pass(tcodes, qcodes, probs, n_prob, match, mismatch, o1, e1, o2, e2, tb_pool, bnd_pool, out_score, order, ctl, redo_list, ad_pct, redo_cap, tb_by_ns);
 }
 // second launch of the batched path: the problems of redo_list in full (vmx_gapfill_fill_body with REDO), the larger ones two per wave in the wave-wide band first
 __global__ void __launch_bounds__(64) k_gapfill_redo(const uint8_t* __restrict__ tcodes, const uint8_t* __restrict__ qcodes, const vmx_dp_prob* __restrict__ probs,
                                                      int match, int mismatch, int o1, int e1, int o2, int e2, uint8_t* __restrict__ tb_pool,
                                                      int32_t* __restrict__ bnd_pool, int32_t* __restrict__ out_score, int32_t* __restrict__ redo_list,
-                                                     int32_t* __restrict__ redo_cnt, uint8_t* __restrict__ redo_pool) {
-    vmx_gapfill_fill_body<false, true>(tcodes, qcodes, probs, 0, match, mismatch, o1, e1, o2, e2, tb_pool, bnd_pool, out_score, nullptr, nullptr, redo_list, redo_cnt, redo_pool);
+                                                     vmx_gf_ctl* __restrict__ ctl, uint8_t* __restrict__ redo_pool) {
+    vmx_gapfill_fill_body<false, true>(tcodes, qcodes, probs, 0, match, mismatch, o1, e1, o2, e2, tb_pool, bnd_pool, out_score, nullptr, nullptr, redo_list, ctl, redo_pool);
 }
 
 // serial traceback, one THREAD per problem (thousands of independent dependent-load chains hide each other's latency)
@@ -668,15 +653,8 @@ __global__ void k_gapfill_trace(const uint8_t* __restrict__ tcodes, const uint8_
     const uint8_t* tb = vmx_tb_ptr(tb_pool, redo_pool, pr.tb_off);
     uint32_t* runs = run_pool + pr.run_off;
     char* cig = cig_pool + pr.cig_off;
-    bool x4 = tl > 0 && ql > 0 && VMX_DP16X4_OK(tl, ql);         // layout of vmx_gapfill_fill16x4
-    bool pk = !x4 && tl > 0 && ql > 0 && VMX_DP16_OK(tl, ql);           // packed layout of vmx_gapfill_fill16
-    const int flag = (x4 && band_flag != nullptr) ? band_flag[p] : 0;
-    const int ns = flag > VMX_AD_FLAG ? flag - VMX_AD_FLAG : 0;          // anti-diagonal layout (vmx_dp_ad.h) with 2 * ns diagonals per lane
-    if (flag == VMX_PK_FLAG) { x4 = false; pk = true; }                  // a small-class problem the second launch ran on the whole wave
-    int dlo = 0;
-    if (ns) vmx_ad_geom(tl, ql, ns, &dlo);
-    const int AW = ns ? VMX_AD_W(ns) : 4;                                // bytes of a lane's slot in the anti-diagonal layout (vmx_kernels.h)
-    const int W = x4 ? VMX_X4_W(ql) : ql + (pk ? 127 : 63);
+    // which layout the bytes are in, and its parameters (vmx_gapfill.h); only a small-class problem's word in band_flag is a flag
+    const vmx_tb_layout L = vmx_tb_layout_of(tl, ql, (band_flag != nullptr && vmx_gf_small(tl, ql)) ? band_flag[p] : 0);
     int nruns = 0; int cur_op = -1; uint32_t cur_len = 0;
 #define VMX_EMIT(op)                                                                   \
     do {                                                                               \
@@ -686,18 +664,17 @@ __global__ void k_gapfill_trace(const uint8_t* __restrict__ tcodes, const uint8_
     int i = tl, j = ql, state = 0;
     while (i > 0 && j > 0) {
         int b;
-        if (ns && state == 0) {
+        if (L.kind == VMX_TB_AD && state == 0) {
             // Anti-diagonal layout, H state: nine steps in ten are diagonal moves (a 10 % error read), and a diagonal move keeps the diagonal
             // x and goes back two anti-diagonals, i.e. 128 bytes. The bytes (and, for =/X, the codes) of the next eight cells down the
             // diagonal are loaded TOGETHER and consumed as long as the path stays on it: one memory latency per eight steps instead
             // of one per step (the walk is a chain of dependent loads, this kernel's whole cost).
-            const int x = (j - i) - dlo, l = x / (2 * ns), k = (x - 2 * ns * l) >> 1;
-            const uint8_t* cell = tb + VMX_AD_TB_OFF_W(0, l, AW) + k;
+            const uint8_t* cell = tb + vmx_tb_ad_lane_off(L, i, j);
             const int s0 = i + j - 1;
             int m = i < j ? i : j; if (m > 8) m = 8;
             uint8_t bb[8], ta[8], qa[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) if (u < m) { bb[u] = cell[VMX_AD_TB_OFF_W(s0 - 2 * u, 0, AW)]; if (eqx) { ta[u] = T[i - 1 - u]; qa[u] = Q[j - 1 - u]; } }
+            for (int u = 0; u < 8; ++u) if (u < m) { bb[u] = cell[vmx_tb_ad_step_off(L, s0 - 2 * u)]; if (eqx) { ta[u] = T[i - 1 - u]; qa[u] = Q[j - 1 - u]; } }
             int u = 0;
 #pragma unroll
             for (int v = 0; v < 8; ++v) {
@@ -710,10 +687,7 @@ __global__ void k_gapfill_trace(const uint8_t* __restrict__ tcodes, const uint8_
             if (state == 0) continue;                 // the whole batch was diagonal (or the matrix edge was reached)
             // a gap starts at cell (i, j): the generic step below re-reads its byte in the gap state
         }
-        if (ns) { const int x = (j - i) - dlo, l = x / (2 * ns), k = (x - 2 * ns * l) >> 1; b = tb[VMX_AD_TB_OFF_W(i + j - 1, l, AW) + k]; }
-        else if (x4) { const int s = (i - 1) >> 5, r = (i - 1) & 31, t = (j - 1) + r; b = tb[(((size_t)s * (size_t)W + (size_t)t) * 16 + (r >> 1)) * 2 + (r & 1)]; }
-        else if (pk) { const int s = (i - 1) >> 7, r = (i - 1) & 127, t = (j - 1) + r; b = tb[(((size_t)s * (size_t)W + (size_t)t) * 64 + (r >> 1)) * 2 + (r & 1)]; }
-        else { const int s = (i - 1) >> 6, l = (i - 1) & 63, t = (j - 1) + l; b = tb[((size_t)s * (size_t)W + (size_t)t) * 64 + l]; }
+        b = tb[vmx_tb_cell_off(L, i, j)];
         if (state == 0) {
             int src = b & 7;
             if (src == 0) {

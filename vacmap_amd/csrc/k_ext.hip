@@ -5,7 +5,7 @@
 //                 descriptors of the next one. Phases: 0 rebuild + divergence problems, 1 filter + right-end extensions,
 //                 2 left-end extensions, 3 drop_misplaced (+ right ends again), 4 left ends again, 5 merge / fix_simple_inv /
 //                 checkpoints -> gap-fill problems, 6 records (+ pairedindel -> redo with nofilter, :24079-24080).
-//   k_desc_lens / k_gather   materialise the (target, query) strings of all problems of a round into code pools
+//   k_gather      materialises the (target, query) strings of all problems of a round into code pools
 //                 (plain / reversed / complemented / reverse-complemented views of the read or the reference).
 #include "vmx_device.h"
 #include "vmx_kernels.h"
@@ -23,8 +23,7 @@ __device__ __forceinline__ vmx_segs vmx_read_segs(const vmx_ext_args& A, int r, 
 }
 
 // allocate n contiguous problem slots of the current round
-// (round 6: the slots' owner — prob_read[slot] = read — is written here by the allocating lane, or by the caller's whole wavefront with `own` false;
-//  k_prob_owner, a launch per round, did that before)
+// (the slots' owner — prob_read[slot] = read — is written here by the allocating lane, or by the caller's whole wavefront with `own` false)
 __device__ __forceinline__ int vmx_alloc_probs(const vmx_ext_args& A, int n, int r, bool own = true) {
     if (n <= 0) return 0;
     // one atomic add (a compare-and-swap loop on this single word serialises thousands of lanes: measured 14 -> 100 ms per batch); a
@@ -362,12 +361,6 @@ __global__ void k_ext_phase(vmx_ext_args A, int phase) {
     }
 }
 
-// lengths of the strings of every problem of the round (for the offset scans)
-__global__ void k_desc_lens(const vmx_pair_desc* __restrict__ desc, const int32_t* __restrict__ n_prob, int64_t* __restrict__ tl, int64_t* __restrict__ ql) {
-    const int n = *n_prob;
-    for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i < n; i += (int)(gridDim.x * blockDim.x)) { tl[i] = desc[i].t.len; ql[i] = desc[i].q.len; }
-}
-
 __device__ __forceinline__ void vmx_gather_one(const vmx_sdesc& d, const uint8_t* rd, const uint8_t* ref, uint8_t* out) {
     const uint8_t* src = d.src == 0 ? rd : ref;
     const int n = d.len;
@@ -398,37 +391,6 @@ __global__ void __launch_bounds__(256) k_gather(const vmx_pair_desc* __restrict_
         const uint8_t* rd = ocodes + roff[prob_read[i]];
         vmx_gather_one(d.t, rd, ref, tpool + t_off[i]);
         vmx_gather_one(d.q, rd, ref, qpool + q_off[i]);
-    }
-}
-
-// mark which read owns each problem slot of the round
-__global__ void k_prob_owner(const vmx_ext_read* __restrict__ er, int n_reads, int use_dp, int32_t* __restrict__ prob_read) {
-    const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (r >= n_reads) return;
-    const vmx_ext_read E = er[r];
-    if (!E.active || E.status != 0) return;
-    if (use_dp /* redo_only */ && !(E.redo == 1 && E.pass == 1)) return;
-    for (int i = 0; i < E.prob_n; ++i) prob_read[E.prob_base + i] = r;
-}
-
-// gap-fill problem table from the descriptors + offsets; tb/bnd/run/cig sizes per problem go to size arrays for the scans
-__global__ void k_dp_sizes(const vmx_pair_desc* __restrict__ desc, const int32_t* __restrict__ n_prob, int64_t* __restrict__ tb_sz, int64_t* __restrict__ bnd_sz,
-                           int64_t* __restrict__ run_sz, int64_t* __restrict__ cig_sz) {
-    const int n = *n_prob;
-    for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i < n; i += (int)(gridDim.x * blockDim.x)) {
-        const long long tl = desc[i].t.len, ql = desc[i].q.len;
-        tb_sz[i] = VMX_TB_BYTES_NS(tl, ql);
-        bnd_sz[i] = 3 * (ql + 1); run_sz[i] = tl + ql + 2; cig_sz[i] = 2 * (tl + ql) + 16;
-    }
-}
-__global__ void k_dp_table(const vmx_pair_desc* __restrict__ desc, const int32_t* __restrict__ n_prob, const int64_t* __restrict__ t_off, const int64_t* __restrict__ q_off,
-                           const int64_t* __restrict__ tb_off, const int64_t* __restrict__ bnd_off, const int64_t* __restrict__ run_off,
-                           const int64_t* __restrict__ cig_off, vmx_dp_prob* __restrict__ probs) {
-    const int n = *n_prob;
-    for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i < n; i += (int)(gridDim.x * blockDim.x)) {
-        vmx_dp_prob p; p.t_off = t_off[i]; p.q_off = q_off[i]; p.tl = desc[i].t.len; p.ql = desc[i].q.len;
-        p.tb_off = tb_off[i]; p.bnd_off = bnd_off[i]; p.run_off = run_off[i]; p.cig_off = cig_off[i];
-        probs[i] = p;
     }
 }
 

@@ -34,7 +34,8 @@ __device__ __forceinline__ void vmx_round_values(const vmx_round_args& A, const 
     v[0] = tl; v[1] = ql;
     if constexpr (DP) {
         v[2] = vmx_round_tb_bytes(A, tl, ql);
-        v[3] = 3 * (ql + 1); v[4] = tl + ql + 2; v[5] = 2 * (tl + ql) + 16;      // (k_dp_sizes of round 1-5)
+        const vmx_gf_pool_sizes ps = vmx_gf_pools(tl, ql);
+        v[3] = ps.bnd; v[4] = ps.run; v[5] = ps.cig;
     }
 }
 

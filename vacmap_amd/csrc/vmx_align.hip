@@ -21,13 +21,8 @@ __global__ void k_scan_i64(const int64_t* in, int64_t* out, int64_t n, int pow2_
 __global__ void k_ext_phase(vmx_ext_args A, int phase);
 __global__ void k_ed_anchor_bound(vmx_ext_args A, const int32_t* probread, const uint8_t* qpool, const int64_t* qoff, const uint8_t* tpool, const int64_t* toff,
                                   int64_t* ub_out);
-__global__ void k_desc_lens(const vmx_pair_desc* desc, const int32_t* n_prob, int64_t* tl, int64_t* ql);
 __global__ void k_gather(const vmx_pair_desc* desc, const int32_t* n_prob, const int32_t* prob_read, const uint8_t* ocodes, const int64_t* roff,
                          const uint8_t* ref, const int64_t* t_off, const int64_t* q_off, uint8_t* tpool, uint8_t* qpool, int64_t pool_cap, vmx_ext_read* er);
-__global__ void k_prob_owner(const vmx_ext_read* er, int n_reads, int use_dp, int32_t* prob_read);
-__global__ void k_dp_sizes(const vmx_pair_desc* desc, const int32_t* n_prob, int64_t* tb_sz, int64_t* bnd_sz, int64_t* run_sz, int64_t* cig_sz);
-__global__ void k_dp_table(const vmx_pair_desc* desc, const int32_t* n_prob, const int64_t* t_off, const int64_t* q_off, const int64_t* tb_off,
-                           const int64_t* bnd_off, const int64_t* run_off, const int64_t* cig_off, vmx_dp_prob* probs);
 __global__ void k_ext_records(vmx_ext_args A, const vmx_dp_prob* probs, const char* cig_pool, const int32_t* cig_len, const int32_t* cig_q);
 __global__ void k_res_sizes(const vmx_ext_read* er, const vm_record* rec, const int64_t* soff, int n_reads, int64_t* recn, int64_t* blobn);
 __global__ void k_res_pack(const vmx_ext_read* er, const vm_record* rec, const char* blob, const int64_t* soff, const int64_t* blob_off, int n_reads,
@@ -48,9 +43,8 @@ __global__ void k_readlens(const int64_t* __restrict__ roff, int64_t* __restrict
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) lens[i] = roff[i + 1] - roff[i];
 }
 
-// scalars the host wants are gathered by one-thread kernels into one block and read back with ONE copy (a hipMemcpyAsync per scalar is a
+// scalars the host wants are gathered on the device into one block and read back with ONE copy (a hipMemcpyAsync per scalar is a
 // runtime copy kernel each: ~100 of them per batch before)
-__global__ void k_stat_put(const int32_t* __restrict__ src, int32_t* __restrict__ dst) { *dst = *src; }
 // (gap-fill sizing on the device — pool totals and the cut of the problems into traceback chunks — is the last step of k_round_prep<true>, k_round.hip)
 __global__ void k_final_scalars(const int64_t* nr, const int64_t* nb, const int32_t* oflow, const int32_t* edc, const int32_t* rounds, int64_t* __restrict__ out) {
     out[0] = *nr; out[1] = *nb; out[2] = *oflow; out[3] = edc[0]; out[4] = edc[1]; out[5] = edc[2];
@@ -182,30 +176,28 @@ int vmx_global_stage(vm_ctx* c, vmx_batch_bufs& B, const vm_params* prm, int k, 
 
 // one gap-fill chunk (vmx_stage.h)
 void vmx_gapfill_chunk(vm_ctx* c, vmx_batch_bufs& B, const vm_score& sc, int ad_pct, int eqx, int p0, int64_t pn, const int32_t* n_ptr, int64_t tb_off0,
-                       int32_t* ctl, int32_t* redo_list, int64_t redo_cap, hipEvent_t* ke) {
+                       vmx_gf_ctl* ctl, int32_t* redo_list, int64_t redo_cap, hipEvent_t* ke) {
     int fill_waves = 16;                                              // waves per CU of the fill kernel (tuning knob: VMX_FILL_WAVES)
     if (const char* e = getenv("VMX_FILL_WAVES")) { const int v = atoi(e); if (v >= 1 && v <= 32) fill_waves = v; }
     static const int tr_spread = [] { const char* e = getenv("VMX_TRACE_SPREAD"); const int v = e ? atoi(e) : 1; return v >= 1 && v <= 64 ? v : 1; }();
-    int32_t* d_range = ctl; int32_t* d_cnt = ctl + 4; int32_t* d_redo_cnt = ctl + 12;
-    unsigned long long* d_redo_bytes = (unsigned long long*)(ctl + 16); int32_t* scratch = ctl + 32;
     uint8_t* tb_base = B.tb.as<uint8_t>() - tb_off0;           // the problems' absolute traceback offsets index a buffer that holds this chunk only
     vmx_dp_prob* probs = B.dptab.as<vmx_dp_prob>() + p0; int32_t* score = B.dpscore.as<int32_t>() + p0;
     const unsigned Gs = (unsigned)std::max<int64_t>(1, std::min<int64_t>((pn + 1023) / 1024, (int64_t)c->num_cu * 2));
-    hipLaunchKernelGGL(k_size_hist, dim3(Gs), dim3(256), 0, c->stream, B.dpsz[0].as<int64_t>() + p0, n_ptr, (int64_t)((1LL << 42) - 1), scratch);        // (queue keys: vmx_round.h)
-    hipLaunchKernelGGL(k_size_scatter, dim3(Gs), dim3(256), 0, c->stream, B.dpsz[0].as<int64_t>() + p0, n_ptr, (const int32_t*)scratch, scratch + 257, B.order.as<int32_t>(), d_range, d_cnt);
+    hipLaunchKernelGGL(k_size_hist, dim3(Gs), dim3(256), 0, c->stream, B.dpsz[0].as<int64_t>() + p0, n_ptr, (int64_t)((1LL << 42) - 1), ctl->scratch);        // (queue keys: vmx_round.h)
+    hipLaunchKernelGGL(k_size_scatter, dim3(Gs), dim3(256), 0, c->stream, B.dpsz[0].as<int64_t>() + p0, n_ptr, (const int32_t*)ctl->scratch, ctl->scratch + 257, B.order.as<int32_t>(), ctl->range, ctl->head);
     if (ke) (void)hipEventRecord(ke[0], c->stream);
     {
         vmx_lowprio lp(c);                                    // the long launch at the lowest dispatch priority (vmx_host.h)
         hipLaunchKernelGGL(k_gapfill_fill_ns, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(pn, (int64_t)c->num_cu * fill_waves))), dim3(64), 0, lp.stream(), B.tpool.as<uint8_t>(), B.qpool.as<uint8_t>(),
-                           probs, (int)pn, sc.match, sc.mismatch, sc.o1, sc.e1, sc.o2, sc.e2, tb_base, B.bnd.as<int32_t>(), score, B.order.as<int32_t>(), d_range, d_cnt,
-                           redo_list, d_redo_cnt, ad_pct, d_redo_bytes, n_ptr, (unsigned long long)redo_cap, 1);
+                           probs, (int)pn, sc.match, sc.mismatch, sc.o1, sc.e1, sc.o2, sc.e2, tb_base, B.bnd.as<int32_t>(), score, B.order.as<int32_t>(), ctl,
+                           redo_list, ad_pct, n_ptr, (unsigned long long)redo_cap, 1);
         lp.join();
     }
     // second launch (k_gapfill_redo): the problems whose band was not proven or that were never tried in one (a few per cent). The larger ones go two per wave through a
     // wave-wide band of 256 .. 512 diagonals and are filled in full, one per wave, only where that is not proven either; the others in full, four per wave. Its queue is the
-    // list the first launch left; any grid works. ctl[18] / ctl[19]: problems kept from a wide band / filled in full after all.
+    // list the first launch left; any grid works. ctl->redo_kept / redo_full: problems kept from a wide band / filled in full after all.
     hipLaunchKernelGGL(k_gapfill_redo, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(pn, (int64_t)c->num_cu * 4))), dim3(64), 0, c->stream, B.tpool.as<uint8_t>(), B.qpool.as<uint8_t>(),
-                       probs, sc.match, sc.mismatch, sc.o1, sc.e1, sc.o2, sc.e2, tb_base, B.bnd.as<int32_t>(), score, redo_list, d_redo_cnt, B.tbredo.as<uint8_t>());
+                       probs, sc.match, sc.mismatch, sc.o1, sc.e1, sc.o2, sc.e2, tb_base, B.bnd.as<int32_t>(), score, redo_list, ctl, B.tbredo.as<uint8_t>());
     if (ke) (void)hipEventRecord(ke[1], c->stream);
     hipLaunchKernelGGL(k_gapfill_trace, dim3((unsigned)std::max<int64_t>(1, (pn * tr_spread + 63) / 64)), dim3(64), 0, c->stream, B.tpool.as<uint8_t>(), B.qpool.as<uint8_t>(), probs, (int)pn, eqx,
                        tb_base, B.run.as<uint32_t>(), B.cig.as<char>(), B.ciglen.as<int32_t>() + p0, score, B.tbredo.as<uint8_t>(), tr_spread, B.cigq.as<int32_t>() + p0, n_ptr);
@@ -216,41 +208,15 @@ void vmx_gapfill_chunk(vm_ctx* c, vmx_batch_bufs& B, const vm_score& sc, int ad_
 
 __global__ void k_ext_geometry(const int32_t* la_cnt, const int64_t* roff, int n, int mul, int tmask, long long tdiv, long long capA, long long capS, long long capB, int64_t* coff3,
                                int64_t* soff2, int64_t* bloboff, int64_t* tot);
-__global__ void k_scan_part_dev(const int64_t* in, int64_t* part, const int32_t* n_ptr);
-__global__ void k_scan_apply_dev(const int64_t* in, int64_t* out, const int64_t* part_off, const int32_t* n_ptr);
-__global__ void k_scan_part(const int64_t* in, int64_t* part, int64_t n, int64_t chunk);
-__global__ void k_scan_apply(const int64_t* in, int64_t* out, const int64_t* part_off, int64_t n, int64_t chunk);
-
-// exclusive scan on the stream (out[n] = total): one workgroup for small n, three phases otherwise
-static int dev_scan(vm_ctx* c, vmx_batch_bufs& B, const int64_t* in, int64_t* out, int64_t n) {
-    if (n <= 16384) { hipLaunchKernelGGL(k_scan_i64, dim3(1), dim3(256), 0, c->stream, in, out, n, 0); return 0; }
-    int64_t chunk = (n + 511) / 512; const int64_t nb = (n + chunk - 1) / chunk;
-    VMX_TRY(B.scanpart.reserve(8 * (size_t)(nb + 2))); VMX_TRY(B.scanoff.reserve(8 * (size_t)(nb + 2)));
-    hipLaunchKernelGGL(k_scan_part, dim3((unsigned)nb), dim3(256), 0, c->stream, in, B.scanpart.as<int64_t>(), n, chunk);
-    hipLaunchKernelGGL(k_scan_i64, dim3(1), dim3(256), 0, c->stream, B.scanpart.as<int64_t>(), B.scanoff.as<int64_t>(), nb, 0);
-    hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nb), dim3(256), 0, c->stream, in, out, B.scanoff.as<int64_t>(), n, chunk);
-    return 0;
-}
-
-// the same with the element count on the device (*n_ptr <= cap): no host read-back; out[n] = total
-static int dev_scan_dev(vm_ctx* c, vmx_batch_bufs& B, const int64_t* in, int64_t* out, const int32_t* n_ptr) {
-    const int nb = 512;
-    VMX_TRY(B.scanpart.reserve(8 * (size_t)(nb + 2))); VMX_TRY(B.scanoff.reserve(8 * (size_t)(nb + 2)));
-    hipLaunchKernelGGL(k_scan_part_dev, dim3(nb), dim3(256), 0, c->stream, in, B.scanpart.as<int64_t>(), n_ptr);
-    hipLaunchKernelGGL(k_scan_i64, dim3(1), dim3(256), 0, c->stream, B.scanpart.as<int64_t>(), B.scanoff.as<int64_t>(), (int64_t)nb, 0);
-    hipLaunchKernelGGL(k_scan_apply_dev, dim3(nb), dim3(256), 0, c->stream, in, out, B.scanoff.as<int64_t>(), n_ptr);
-    return 0;
-}
-
 static const vm_score gf_score = {2, -4, 4, 2, 24, 1};           // the gap fill's scoring (E5: ext_gather_round's band-width rule, vmx_gapfill_chunk)
 
 // one DP round of the extend stage: descriptors (count on device) -> offsets -> gathered pools. The round's problem count stays on the
 // device (B.rcount; every consumer reads it there and launches a grid sized for the hardware, not for the count); it is copied into
 // slot `stat_slot` of the batch's counter block, which the host reads once at the end. want_cnt: also return a host copy (one wait) —
 // only the gap-fill rounds, whose pools are sized by it, ask for that.
-static int ext_gather_round(vm_ctx* c, vmx_batch_bufs& B, const vm_index_view& ix, int64_t n, const uint8_t* d_ocodes, const int64_t* d_roff, int cur, int redo_only,
-                            int64_t round_cap, int64_t pool_cap, int stat_slot, bool dp, int64_t tb_limit, const int64_t* caps = nullptr, int64_t* plan_out = nullptr, int ad_pct = 0) {
-    (void)n; (void)redo_only; (void)round_cap;    // (the slots' owners are written when the phase kernel allocates them; vmx_alloc_probs never lets the published count pass the capacity)
+// (The slots' owners are written when the phase kernel allocates them; vmx_alloc_probs never lets the published count pass the capacity.)
+static int ext_gather_round(vm_ctx* c, vmx_batch_bufs& B, const vm_index_view& ix, const uint8_t* d_ocodes, const int64_t* d_roff, int cur,
+                            int64_t pool_cap, int stat_slot, bool dp, int64_t tb_limit, const int64_t* caps = nullptr, int64_t* plan_out = nullptr, int ad_pct = 0) {
     if (!B.roundpart.p) { VMX_TRY(B.roundpart.reserve(8 * (size_t)VMX_ROUND_PART_WORDS)); VMX_HIP(hipMemsetAsync(B.roundpart.p, 0, 8 * (size_t)VMX_ROUND_PART_WORDS, c->stream)); }
     vmx_round_args R; memset(&R, 0, sizeof R);
     R.desc = B.desc[cur].as<vmx_pair_desc>(); R.n_prob = c->rc_cur;
@@ -523,7 +489,7 @@ static int align_device_once(vm_ctx* c, const vm_index* mi, const vm_params* prm
     VMX_TRY(B.recclen.reserve(4 * (size_t)(cS + 1))); VMX_TRY(B.dupd.reserve((size_t)cB + 64));
     VMX_HIP(hipMemsetAsync(B.oflow.p, 0, 4, c->stream));
     VMX_TRY(B.statblk.reserve(2048)); VMX_HIP(hipMemsetAsync(B.statblk.p, 0, 2048, c->stream));     // [0..7] i32 round counts | i64 [32..45] final scalars | i64 [64..121] chunk plan of pass 0 | i64 [128..185] of pass 1
-    const size_t gfctl_bytes = (size_t)2 * (VMX_MAX_CHUNKS + 1) * VMX_GF_SLOT * 4;
+    const size_t gfctl_bytes = (size_t)2 * (VMX_MAX_CHUNKS + 1) * sizeof(vmx_gf_ctl);
     VMX_TRY(B.gfctl.reserve(gfctl_bytes)); VMX_HIP(hipMemsetAsync(B.gfctl.p, 0, gfctl_bytes, c->stream));      // the gap fill's per-chunk control blocks and size-order scratch (below), cleared once
     vmx_ext_args A; memset(&A, 0, sizeof A);
     A.n_reads = (int)n; A.nseq = ix.nseq; A.local_maxdiff = preset ? 50 : prm->local_maxdiff /* ass_extend_func: large_cost 50, mammap_asm.py:23426 */; A.asm_long = preset ? 1 : 0; A.nodiscard = prm->nodiscard; A.hardclip = prm->hardclip; A.redo_only = 0; A.mode = prm->mode; A.maxdivergence = prm->maxdivergence;
@@ -570,7 +536,7 @@ static int align_device_once(vm_ctx* c, const vm_index* mi, const vm_params* prm
                                } };
     int ext_rounds = 0;
     auto ext_round = [&](int redo_only) -> int {   // x-drop extension of the problems of the current round (their count stays on the device)
-        int rc = ext_gather_round(c, B, ix, n, B.ocodes.as<uint8_t>(), d_roff, cur, redo_only, round_cap, pool_cap, 1 + ext_rounds++, false, 0);
+        int rc = ext_gather_round(c, B, ix, B.ocodes.as<uint8_t>(), d_roff, cur, pool_cap, 1 + ext_rounds++, false, 0);
         if (rc < 0) return rc;
         hipLaunchKernelGGL(k_extend, dim3((unsigned)((int64_t)c->num_cu * 16)), dim3(64), 0, c->stream, B.tpool.as<uint8_t>(), B.toff.as<int64_t>(), B.qpool.as<uint8_t>(),
                            B.qoff.as<int64_t>(), 0, 2, -4, 4, 4, 100, 50, B.ext3.as<int32_t>(), B.ext3.as<int32_t>() + round_cap, B.ext3.as<int32_t>() + 2 * round_cap, c->rc_cur);
@@ -579,7 +545,7 @@ static int align_device_once(vm_ctx* c, const vm_index* mi, const vm_params* prm
     };
     std::vector<int64_t> dp_tot(5, 0);
     // ---- gap fill of one pass (E5). Round 6: ONE host wait per batch in here (the chunk plan of pass 0), none per chunk and none in pass 1.
-    //  * every chunk has its own control block (queue range / counters / redo list length / redo bytes: 32 ints) and its own zeroed scratch for the size ordering
+    //  * every chunk has its own control block (struct vmx_gf_ctl, vmx_gapfill.h: queue range and heads, the second launch's list and counters, the size ordering's scratch)
     //    in B.gfctl, cleared once per batch: nothing is cleared between chunks, and the host reads all of them with the batch's final results;
     //  * the full-matrix traceback space of the problems whose band was not proven (the SECOND launch's pool) is sized from the context's history (largest chunk
     //    seen x 1.3, 512 MB to begin with) instead of by a read-back between the two launches; the band pass checks every allocation against the pool and a problem
@@ -602,7 +568,7 @@ static int align_device_once(vm_ctx* c, const vm_index* mi, const vm_params* prm
     int gf_chunks[2] = {0, 0}; int64_t gf_redo_cap = 0;
     // one chunk: problems [p0, p0 + pn) — pn an upper bound when n_ptr names the count on the device; control block q of the pass's in B.gfctl
     auto gf_chunk = [&](int pass, int q, int p0, int64_t pn, const int32_t* n_ptr, int64_t tb_off0) {
-        int32_t* ctl = B.gfctl.as<int32_t>() + (size_t)(pass * (VMX_MAX_CHUNKS + 1) + q) * VMX_GF_SLOT;
+        vmx_gf_ctl* ctl = B.gfctl.as<vmx_gf_ctl>() + (size_t)(pass * (VMX_MAX_CHUNKS + 1) + q);
         hipEvent_t* ke = q < 8 ? c->gev + (pass ? 24 : 0) + 3 * q : nullptr;      // HIP events around the dominant kernel, on the stream it runs on
         vmx_gapfill_chunk(c, B, gf_score, ad_pct, prm->eqx, p0, pn, n_ptr, tb_off0, ctl, B.order.as<int32_t>() + round_cap + 32, gf_redo_cap, ke);
         if (ke) c->n_gev[pass] = q + 1;
@@ -623,7 +589,7 @@ static int align_device_once(vm_ctx* c, const vm_index* mi, const vm_params* prm
         c->n_gev[redo_only ? 1 : 0] = 0;
         {
             // ONE launch: string offsets, the four pool-size scans, the problem table and the chunk plan (at most VMX_TB_CHUNK traceback bytes per chunk), then the gather
-            int rcg = ext_gather_round(c, B, ix, n, B.ocodes.as<uint8_t>(), d_roff, cur, redo_only, round_cap, pool_cap, 6 + redo_only, true, tb_chunk, nullptr, B.statblk.as<int64_t>() + 64 + (redo_only ? 64 : 0), ad_pct);
+            int rcg = ext_gather_round(c, B, ix, B.ocodes.as<uint8_t>(), d_roff, cur, pool_cap, 6 + redo_only, true, tb_chunk, nullptr, B.statblk.as<int64_t>() + 64 + (redo_only ? 64 : 0), ad_pct);
             if (rcg < 0) return rcg;
             // the sizing wait of the batch: problem count, pool totals, chunk cuts
             int64_t plan[8 + 2 * (VMX_MAX_CHUNKS + 1)];
@@ -654,7 +620,7 @@ static int align_device_once(vm_ctx* c, const vm_index* mi, const vm_params* prm
     // pass 0
     phase(0);
     {   // divergence filter: edit distance of every segment (:19251)
-        int rc0 = ext_gather_round(c, B, ix, n, B.ocodes.as<uint8_t>(), d_roff, cur, 0, round_cap, pool_cap, 0, false, 0);
+        int rc0 = ext_gather_round(c, B, ix, B.ocodes.as<uint8_t>(), d_roff, cur, pool_cap, 0, false, 0);
         if (rc0 < 0) return rc0;
         const int64_t cnt = round_cap;                           // launch widths only: every kernel below reads the real count on the device
         {
@@ -746,7 +712,7 @@ static int align_device_once(vm_ctx* c, const vm_index* mi, const vm_params* prm
     VMX_TRY(vmx_fetch(c, fin, B.statblk.as<int64_t>() + 32, 14));          // record / blob totals, overflow flag, tier counters, per-round problem counts: one copy
     int64_t geo[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (fast_local) VMX_TRY(vmx_fetch(c, geo, B.geotot.p, 6));             // what the geometry kernel found: totals (history), local anchors (statistics)
-    std::vector<int32_t> h_ctl(gfctl_bytes / 4);
+    std::vector<vmx_gf_ctl> h_ctl(gfctl_bytes / sizeof(vmx_gf_ctl));
     VMX_TRY(vmx_fetch(c, h_ctl.data(), B.gfctl.p, h_ctl.size()));          // the gap fill's per-chunk control blocks (second-launch queue length and pool need)
     VMX_TRY(vmx_fetch(c, er.data(), B.er.p, (size_t)n)); VMX_TRY(vmx_fetch(c, h_gmax.data(), B.gmax.p, (size_t)n));
     VMX_TRY(vmx_fetch(c, *recs, B.totals.p, (size_t)g_nr)); VMX_TRY(vmx_fetch(c, *cigar_blob, B.dupd.p, (size_t)g_nb));
@@ -763,9 +729,9 @@ static int align_device_once(vm_ctx* c, const vm_index* mi, const vm_params* prm
         bool again = false; int64_t need_max = 0, ad_failed = 0;
         for (int pass = 0; pass < 2; ++pass)
             for (int q = 0; q < gf_chunks[pass]; ++q) {
-                const int32_t* ctl = h_ctl.data() + (size_t)(pass * (VMX_MAX_CHUNKS + 1) + q) * VMX_GF_SLOT;
-                unsigned long long rb = 0; memcpy(&rb, ctl + 16, 8);
-                st.n_dp_redo += ctl[12]; st.n_dp_redo_wide += ctl[18]; st.n_dp_redo_full += ctl[19]; st.dp_redo_tb_bytes += (int64_t)rb; st.dp_cells += (int64_t)rb; ad_failed += ctl[15];
+                const vmx_gf_ctl& ctl = h_ctl[(size_t)(pass * (VMX_MAX_CHUNKS + 1) + q)];
+                const unsigned long long rb = ctl.redo_bytes;
+                st.n_dp_redo += ctl.redo_n; st.n_dp_redo_wide += ctl.redo_kept; st.n_dp_redo_full += ctl.redo_full; st.dp_redo_tb_bytes += (int64_t)rb; st.dp_cells += (int64_t)rb; ad_failed += ctl.n_not_proven;
                 need_max = std::max<int64_t>(need_max, (int64_t)rb);
             }
         c->redo_need_max = std::max<long long>(c->redo_need_max, need_max);

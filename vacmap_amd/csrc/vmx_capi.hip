@@ -499,8 +499,9 @@ int vm_k_cigar_batch(vm_ctx* c, const vm_score* sc, int eqx, int64_t n, const ch
         vmx_dp_prob& p = probs[i];
         p.t_off = t_off[i]; p.q_off = q_off[i]; p.tl = (int32_t)(t_off[i + 1] - t_off[i]); p.ql = (int32_t)(q_off[i + 1] - q_off[i]);
         p.tb_off = tb; p.bnd_off = bnd; p.run_off = run; p.cig_off = cig;
-        tb += VMX_TB_BYTES((int64_t)p.tl, (int64_t)p.ql);
-        bnd += 3 * (int64_t)(p.ql + 1); run += (int64_t)p.tl + p.ql + 2; cig += 2 * ((int64_t)p.tl + p.ql) + 16;
+        tb += vmx_gf_tb_bytes_full(p.tl, p.ql);
+        const vmx_gf_pool_sizes ps = vmx_gf_pools(p.tl, p.ql);
+        bnd += ps.bnd; run += ps.run; cig += ps.cig;
     }
     VMX_TRY(upload(c->b[6], probs.data(), (size_t)n, c->stream));
     VMX_TRY(c->b[7].reserve((size_t)tb + 64)); VMX_TRY(c->b[8].reserve(sizeof(int32_t) * (size_t)(bnd + 4)));
@@ -549,8 +550,9 @@ int vm_k_cigar_batch_banded(vm_ctx* c, const vm_score* sc, int eqx, int64_t n, c
         p.t_off = t_off[i]; p.q_off = q_off[i]; p.tl = (int32_t)(t_off[i + 1] - t_off[i]); p.ql = (int32_t)(q_off[i + 1] - q_off[i]);
         p.tb_off = tb; p.bnd_off = bnd; p.run_off = run; p.cig_off = cig;
         tb += vmx_round_tb_bytes(R, p.tl, p.ql); keys[i] = vmx_round_key(R, p.tl, p.ql);
-        if (p.tl > 0 && p.ql > 0 && VMX_DP16X4_OK(p.tl, p.ql)) redo += VMX_REDO_TB_BYTES((int64_t)p.tl, (int64_t)p.ql);
-        bnd += 3 * (int64_t)(p.ql + 1); run += (int64_t)p.tl + p.ql + 2; cig += 2 * ((int64_t)p.tl + p.ql) + 16;
+        if (vmx_gf_small(p.tl, p.ql)) redo += vmx_gf_tb_bytes_redo(p.tl, p.ql);
+        const vmx_gf_pool_sizes ps = vmx_gf_pools(p.tl, p.ql);
+        bnd += ps.bnd; run += ps.run; cig += ps.cig;
     }
     const int32_t nn = (int32_t)n;
     VMX_TRY(upload(B.dptab, probs.data(), (size_t)n, c->stream)); VMX_TRY(upload(B.dpsz[0], keys.data(), (size_t)n, c->stream)); VMX_TRY(upload(B.chunkn, &nn, 1, c->stream));
@@ -558,23 +560,24 @@ int vm_k_cigar_batch_banded(vm_ctx* c, const vm_score* sc, int eqx, int64_t n, c
     VMX_TRY(B.run.reserve(sizeof(uint32_t) * (size_t)(run + 4))); VMX_TRY(B.cig.reserve((size_t)cig + 16));
     VMX_TRY(B.ciglen.reserve(4 * (size_t)(n + 1))); VMX_TRY(B.cigq.reserve(4 * (size_t)(n + 1))); VMX_TRY(B.dpscore.reserve(4 * (size_t)(n + 1)));
     VMX_TRY(B.order.reserve(4 * (size_t)(2 * n + 64)));
-    VMX_TRY(B.gfctl.reserve(4 * VMX_GF_SLOT)); VMX_HIP(hipMemsetAsync(B.gfctl.p, 0, 4 * VMX_GF_SLOT, c->stream));
-    if (n) vmx_gapfill_chunk(c, B, *sc, ad_pct, eqx, 0, n, B.chunkn.as<int32_t>(), 0, B.gfctl.as<int32_t>(), B.order.as<int32_t>() + n + 32, redo, nullptr);
-    std::vector<char> hc((size_t)cig + 16); std::vector<int32_t> hl((size_t)n), flag((size_t)n), ctl(32);
+    VMX_TRY(B.gfctl.reserve(sizeof(vmx_gf_ctl))); VMX_HIP(hipMemsetAsync(B.gfctl.p, 0, sizeof(vmx_gf_ctl), c->stream));
+    if (n) vmx_gapfill_chunk(c, B, *sc, ad_pct, eqx, 0, n, B.chunkn.as<int32_t>(), 0, B.gfctl.as<vmx_gf_ctl>(), B.order.as<int32_t>() + n + 32, redo, nullptr);
+    std::vector<char> hc((size_t)cig + 16); std::vector<int32_t> hl((size_t)n), flag((size_t)n);
+    vmx_gf_ctl ctl;                                                  // its counters; the size-order scratch behind them is not fetched
     VMX_TRY(download(hc.data(), B.cig.p, (size_t)cig, c->stream));
     VMX_TRY(download(hl.data(), B.ciglen.p, (size_t)n, c->stream));
     VMX_TRY(download(flag.data(), B.dpscore.p, (size_t)n, c->stream));          // the _ns form leaves the layout flag where the score would be (it never captures scores)
-    VMX_TRY(download(ctl.data(), B.gfctl.p, ctl.size(), c->stream));
+    VMX_TRY(download((char*)&ctl, B.gfctl.p, offsetof(vmx_gf_ctl, scratch), c->stream));
     VMX_HIP(vmx_stream_sync(c));
     VMX_HIP(hipGetLastError());
     int64_t nb = 0, eligible = 0, small = 0;
     for (int64_t i = 0; i < n; ++i) {
-        const bool sm = probs[i].tl > 0 && probs[i].ql > 0 && VMX_DP16X4_OK(probs[i].tl, probs[i].ql);
+        const bool sm = vmx_gf_small(probs[i].tl, probs[i].ql);
         if (!sm) flag[i] = 0;                                     // (the larger forms leave their score there)
         small += sm; nb += sm && flag[i] > VMX_AD_FLAG;
         eligible += sm && vmx_ad_ns(probs[i].tl, probs[i].ql, sc->match, sc->o1, sc->e1, sc->o2, sc->e2, ad_pct & 0xffff, (ad_pct >> 16) & 0xffff) > 0;
     }
-    if (stats) { stats[0] = eligible; stats[1] = nb; stats[2] = ctl[12]; stats[3] = n - small; stats[4] = ctl[18]; stats[5] = ctl[19]; }
+    if (stats) { stats[0] = eligible; stats[1] = nb; stats[2] = ctl.redo_n; stats[3] = n - small; stats[4] = ctl.redo_kept; stats[5] = ctl.redo_full; }
     if (band_flag) { *band_flag = host_alloc<int32_t>((size_t)n); memcpy(*band_flag, flag.data(), sizeof(int32_t) * (size_t)n); }
     cigar_strings(n, probs.data(), hc.data(), hl.data(), cigars, cigar_off);
     return VM_OK;

@@ -14,8 +14,8 @@
 // cells past tl / ql compute garbage that only ever feeds other garbage. Target codes move down the lanes one diagonal pair per two
 // steps, query codes move up (one DPP each per step pair), fed at lane 0 / lane 15 from 16-entry chunk registers that rotate one lane
 // per use and are refilled with one coalesced load every 16 pairs.
-// Traceback bytes: tb[VMX_AD_TB_OFF_W(a - 1, l, W) + k] for the cell of anti-diagonal a on diagonal x = 2 NS l + 2 k + (a & 1): W = VMX_AD_W(NS) bytes per lane,
-// problem and step (vmx_kernels.h: 64-byte lines of VMX_AD_AB anti-diagonals x 64 / (AB W) lanes).
+// Traceback bytes: tb[vmx_ad_tb_off(a - 1, l, W) + k] for the cell of anti-diagonal a on diagonal x = 2 NS l + 2 k + (a & 1): W = VMX_AD_W(NS) bytes per lane,
+// problem and step (vmx_gapfill.h: 64-byte lines of VMX_AD_AB anti-diagonals x 64 / (AB W) lanes).
 #ifndef VMX_DP_AD_H
 #define VMX_DP_AD_H
 
@@ -138,10 +138,27 @@ __device__ __forceinline__ unsigned vmx_ad_pick(const unsigned (&v)[NS], int k) 
 //   LW = 64 (the second launch, k_gapfill_redo): the band lives in the whole wavefront — lane l = the lane id owns the diagonals
 // [2 NS l, 2 NS l + 2 NS) of a band of 128 NS, X and Y are ONE problem each for the whole wave, the hand-offs are wave-wide moves and the chunk
 // registers hold 64 codes. The traceback bytes go into the packed two-rows-per-lane layout of vmx_gapfill_fill16 (the space a refilled problem
-// owns: VMX_PK_TB_BYTES), cell (i, j) at (s (ql + 127) + (j - 1) + r) 128 + r with s = (i - 1) >> 7, r = (i - 1) & 127: inside a stripe the NS
+// owns: vmx_tb_rows128, vmx_gapfill.h), cell (i, j) at (s (ql + 127) + (j - 1) + r) 128 + r with s = (i - 1) >> 7, r = (i - 1) & 127: inside a stripe the NS
 // cells of a lane are NS adjacent bytes (k counts them downwards) and an anti-diagonal of the band is one run of 64 NS bytes. Only cells of
 // the matrix are stored (one outside it would alias a real cell's address); what the band does not cover stays unwritten — the walk of a
 // kept (proven) problem never leaves the band.
+// The wave-wide band's store address, strength-reduced by hand (a measured choice): cell (i, j) of anti-diagonal a = i + j, row i = ik + 1, is at
+// s * 128 (ql - 2) + 128 (a - 2) + ik in the 128-row layout (129 r + 128 (j - 1) with r = ik - 128 s) — sb * s is a 24-bit multiply, the stripe s < 8.
+__host__ __device__ constexpr int vmx_adw_sb(int ql) { return (int)((unsigned)(128 * (ql - 2)) << 8) >> 8; }
+__host__ __device__ constexpr int vmx_adw_ab(int a) { return 128 * (a - 2); }
+__host__ __device__ constexpr unsigned vmx_adw_off(int sb, int ab, int ik) { return (unsigned)(((ik >> 7) & 7) * sb + (ab + ik)); }
+constexpr bool vmx_adw_off_ok(int tl) {
+    const int qls[5] = {1, 15, 16, 17, 33};
+    for (int q = 0; q < 5; ++q)
+        for (int i = 1; i <= tl; ++i)
+            for (int j = 1; j <= qls[q]; ++j)
+                if (vmx_adw_off(vmx_adw_sb(qls[q]), vmx_adw_ab(i + j), i - 1) != vmx_tb_rows128::cell_off(vmx_tb_rows128::W(qls[q]), i, j)) return false;
+    return true;
+}
+static_assert(vmx_adw_off_ok(1) && vmx_adw_off_ok(127) && vmx_adw_off_ok(128) && vmx_adw_off_ok(129), "vmx_adw_off is cell_off of the 128-row layout");
+static_assert(vmx_adw_off_ok(256), "vmx_adw_off is cell_off of the 128-row layout");
+static_assert(vmx_adw_off_ok(257), "vmx_adw_off is cell_off of the 128-row layout");
+
 template <int NS, int LW = 16>
 __device__ __forceinline__ void vmx_gapfill_fill_ad(const uint8_t* __restrict__ TX, const uint8_t* __restrict__ QX, int tlX, int qlX, int dloX, uint8_t* __restrict__ tbX,
                                                    const uint8_t* __restrict__ TY, const uint8_t* __restrict__ QY, int tlY, int qlY, int dloY, uint8_t* __restrict__ tbY,
@@ -185,25 +202,24 @@ __device__ __forceinline__ void vmx_gapfill_fill_ad(const uint8_t* __restrict__ 
     const int lfX = xfX / (2 * NS), kfX = (xfX % (2 * NS)) >> 1, lfY = xfY / (2 * NS), kfY = (xfY % (2 * NS)) >> 1;
     int finX = 0, finY = 0;
     constexpr int W = VMX_AD_W(NS);                           // bytes of the lane's slot: as many as the lane has cells per step (round 6; 4 before, whatever NS)
-    uint8_t* const pX = LW == 16 ? tbX + VMX_AD_TB_OFF_W(0, l, W) : tbX;       // the lane's slot of anti-diagonal 0; the step's part of the offset is added per store
-    uint8_t* const pY = LW == 16 ? tbY + VMX_AD_TB_OFF_W(0, l, W) : tbY;
+    uint8_t* const pX = LW == 16 ? tbX + vmx_ad_tb_off(0, l, W) : tbX;       // the lane's slot of anti-diagonal 0; the step's part of the offset is added per store
+    uint8_t* const pY = LW == 16 ? tbY + vmx_ad_tb_off(0, l, W) : tbY;
     auto put = [&](uint8_t* at, unsigned w01, unsigned w23, bool hi) {
         if constexpr (W == 1) *at = (uint8_t)(hi ? (w01 >> 16) : w01);
         else if constexpr (W == 2) *(uint16_t*)at = (uint16_t)(hi ? (w01 >> 16) : w01);
         else *(uint32_t*)at = vmx_perm(w23, w01, hi ? 0x07060302u : 0x05040100u);
     };
     // LW = 64: the step's bytes at their cells' addresses in the packed layout. Cell k of the lane on anti-diagonal a is (i0 - k, a - i0 + k), i0 = i1 + 1
-    // the lane's largest row: inside the matrix when lo <= i - 1 < hi with lo = max(0, a - 1 - ql), hi = min(tl, a - 1) (both wave-uniform); its offset is
-    // s * 128 (ql - 2) + 128 (a - 2) + (i - 1) (129 r + 128 (j - 1) with r = i - 1 - 128 s: a 24-bit multiply, the stripe s < 8)
+    // the lane's largest row: inside the matrix when lo <= i - 1 < hi with lo = max(0, a - 1 - ql), hi = min(tl, a - 1) (both wave-uniform); its offset: vmx_adw_off
     auto put_pk = [&](uint8_t* tb, int tl, int ql, int a, int i1, unsigned w01, unsigned w23, bool hi) {
         const int lo = a - 1 - ql > 0 ? a - 1 - ql : 0, n = (tl < a - 1 ? tl : a - 1) - lo;
-        const int sb = (int)((unsigned)(128 * (ql - 2)) << 8) >> 8, ab = 128 * (a - 2);
+        const int sb = vmx_adw_sb(ql), ab = vmx_adw_ab(a);
 #pragma unroll
         for (int k = 0; k < NS; ++k) {
             const int ik = i1 - k;
             if ((unsigned)(ik - lo) < (unsigned)n && n > 0) {
                 const unsigned w = k < 2 ? w01 : w23;
-                tb[(unsigned)(((ik >> 7) & 7) * sb + (ab + ik))] = (uint8_t)(w >> (8 * (k & 1) + (hi ? 16 : 0)));
+                tb[vmx_adw_off(sb, ab, ik)] = (uint8_t)(w >> (8 * (k & 1) + (hi ? 16 : 0)));
             }
         }
     };
@@ -244,7 +260,7 @@ __device__ __forceinline__ void vmx_gapfill_fill_ad(const uint8_t* __restrict__ 
                 unsigned w01, w23;
                 vmx_ad_pack<NS>(w, w01, w23);
                 if constexpr (LW == 16) {
-                const size_t so = VMX_AD_TB_OFF_W(2 * p - 2, 0, W);   // anti-diagonal a = 2p - 1 is step s = a - 1
+                const size_t so = vmx_ad_tb_off(2 * p - 2, 0, W);   // anti-diagonal a = 2p - 1 is step s = a - 1
                 if (p <= poX) put(pX + so, w01, w23, false);
                 if (p <= poY) put(pY + so, w01, w23, true);
                 } else {
@@ -274,7 +290,7 @@ __device__ __forceinline__ void vmx_gapfill_fill_ad(const uint8_t* __restrict__ 
                 unsigned w01, w23;
                 vmx_ad_pack<NS>(w, w01, w23);
                 if constexpr (LW == 16) {
-                const size_t so = VMX_AD_TB_OFF_W(2 * p - 1, 0, W);
+                const size_t so = vmx_ad_tb_off(2 * p - 1, 0, W);
                 if (p <= peX) put(pX + so, w01, w23, false);
                 if (p <= peY) put(pY + so, w01, w23, true);
                 } else {

@@ -35,20 +35,19 @@ template <bool DP> __global__ void k_round_prep(vmx_round_args A);
 __host__ __device__ __forceinline__ int vmx_round_w(const vmx_round_args& A, long long tl, long long ql) {
     return VMX_AD_W(vmx_ad_ns((int)tl, (int)ql, A.ad_match, A.ad_o1, A.ad_e1, A.ad_o2, A.ad_e2, A.ad_pct & 0xffff, (A.ad_pct >> 16) & 0xffff));
 }
-// traceback bytes of a problem
+// traceback bytes of a problem: a small one's slots are as wide as its own band asks (4 bytes where the caller has no band rule)
 __host__ __device__ __forceinline__ long long vmx_round_tb_bytes(const vmx_round_args& A, long long tl, long long ql) {
-    const bool small = tl > 0 && ql > 0 && VMX_DP16X4_OK(tl, ql);
-    return (small && A.ad_on) ? VMX_AD_TB_BYTES_W(tl, ql, vmx_round_w(A, tl, ql)) : VMX_TB_BYTES_NS(tl, ql);
+    return vmx_gf_tb_bytes_batched(tl, ql, (A.ad_on && vmx_gf_small(tl, ql)) ? vmx_round_w(A, tl, ql) : 4);
 }
 // the queue key (vmx_round_args.tb_size)
 __host__ __device__ __forceinline__ long long vmx_round_key(const vmx_round_args& A, long long tl, long long ql) {
     if (tl <= 0 || ql <= 0) return 0;
     if (!VMX_DP16X4_OK(tl, ql)) {
-        const long long b = VMX_TB_BYTES(tl, ql);
+        const long long b = vmx_gf_tb_bytes_full(tl, ql);
         if (b > VMX_HEAD_THRESH) return (b < (1LL << 38) ? b : (1LL << 38)) << 24;
         return b << 23;
     }
-    const long long b64 = VMX_AD_TB_BYTES(tl, ql);                       // (tl + ql) * 64: 2^7 .. 2^16
+    const long long b64 = vmx_gf_key_size_small(tl, ql);                 // (tl + ql) * 64: 2^7 .. 2^16
     if (!A.ad_on) return b64;
     const int w = vmx_round_w(A, tl, ql);
     return w == 4 ? b64 << 16 : (w == 2 ? b64 << 6 : (w == 1 ? b64 >> 4 : (b64 >> 14) + 1));

@@ -34,7 +34,7 @@ struct vmx_batch_bufs {
     // extend stage
     vmx::DevBuf er, coff3, soff2, segA, st, en, segA_s, st_s, en_s, segprob, dup, desc[2], rcount, oflow, probread, tl, ql, toff, qoff, tpool, qpool;
     vmx::DevBuf edout, carry, ext3, dpsz[4], dpoff[4], dptab, tb, tbredo, bnd, run, cig, ciglen, dpscore, rec, blob, bloboff, reccoff, recclen, dupd, totals;
-    vmx::DevBuf raw, codes, off, order, qrange, scanpart, scanoff, si, tg, cntp, fp, pp, chunkn, sellist, cigq, statblk, szh, side_codes, side_off, roundpart, gfctl, geotot;
+    vmx::DevBuf raw, codes, off, order, qrange, si, tg, cntp, fp, pp, chunkn, sellist, cigq, statblk, szh, side_codes, side_off, roundpart, gfctl, geotot;
     void release() { vmx::DevBuf* p = (vmx::DevBuf*)this; for (size_t i = 0; i < sizeof(*this) / sizeof(vmx::DevBuf); ++i) p[i].release(); }
 };
 vmx_batch_bufs* vmx_ctx_batch_bufs(vm_ctx* c);
@@ -52,12 +52,10 @@ static inline void vmx_res_ptrs(vmx_batch_bufs& B, int64_t n, double** score, in
 
 // E5 on one chunk of the gap-fill problem table B.dptab: problems [p0, p0 + pn) (pn an upper bound when n_ptr names the count on the device), queue keys
 // in B.dpsz[0] (vmx_round_key), traceback space in B.tb from the chunk's first problem on (tb_off0: its traceback offset); the problems the band does not prove
-// take their full-matrix space from B.tbredo (redo_cap bytes; one that does not fit is emptied). ctl: the chunk's VMX_GF_SLOT ints, zeroed — control block
-// (queue range / counters / redo list length / redo bytes / second-launch problems kept from a wide band and filled in full: ctl[18], ctl[19]), then the size-order scratch; redo_list: room for pn entries. ke: three events (before the fill,
-// after the fill, after the traceback) or null. CIGARs in B.run / B.cig / B.ciglen / B.cigq; B.dpscore carries every problem's layout flag.
-#define VMX_GF_SLOT (32 + 544)
+// take their full-matrix space from B.tbredo (redo_cap bytes; one that does not fit is emptied). ctl: the chunk's control block (vmx_gf_ctl, vmx_gapfill.h), zeroed;
+// redo_list: room for pn entries. ke: three events (before the fill, after the fill, after the traceback) or null. CIGARs in B.run / B.cig / B.ciglen / B.cigq; B.dpscore carries every problem's layout flag.
 void vmx_gapfill_chunk(vm_ctx* c, vmx_batch_bufs& B, const vm_score& sc, int ad_pct, int eqx, int p0, int64_t pn, const int32_t* n_ptr, int64_t tb_off0,
-                       int32_t* ctl, int32_t* redo_list, int64_t redo_cap, hipEvent_t* ke);
+                       vmx_gf_ctl* ctl, int32_t* redo_list, int64_t redo_cap, hipEvent_t* ke);
 
 extern "C" int vmx_seed_stage(vm_ctx* c, const vm_index* mi, int check_num, int mid_occ, int64_t n, const uint8_t* d_codes, const int64_t* d_roff, int64_t total_bases,
                    vmx::DevBuf* B, std::vector<int64_t>& h_koff, std::vector<int64_t>& h_nhits, vmx::DevBuf* arena = nullptr, int64_t** rows_out = nullptr);
