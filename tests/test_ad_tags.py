@@ -9,7 +9,7 @@ import kernel_cases as KC
 import spec_cases as SC
 import spec_ref as R
 
-GF_SCORE = (2, -4, 4, 2, 24, 1)          # the product's gap-fill scoring (vmx_align.hip: gf_score, every mode)
+GF_SCORE = (2, -4, 4, 2, 24, 1)          # the product's gap-fill scoring (vmx_stage_extend.hip: gf_score, every mode)
 
 
 def _cross_len(o1, e1, o2, e2):

@@ -128,6 +128,26 @@ def test_reference_with_other_letters_is_unsupported(env):
     SD.check(VL, ctx, low, case)
 
 
+def test_contig_names_follow_the_index_not_its_address(env):
+    """the context keeps the contig-name blob of the index it last emitted for. An index that is closed hands its address to the next one, which has
+    other names: the lines must carry the new names. (Indexes are made and closed until one lands on the first one's address; the lines are checked
+    against the host emitter either way.)"""
+    VL, ctx, _ = env
+    case = SD.Case('addr', [SD.one(np.random.default_rng(3), 'r', [(40, '=')], r_st=480)])
+    first = VL.Index.from_seqs(ctx, ['oldA', 'oldB'], SD.REF, k=15, w=10)
+    assert b'\toldA\t' in SD.check(VL, ctx, first, case)[0]
+    addr = first.h.value if hasattr(first.h, 'value') else first.h
+    first.close()
+    for i in range(8):
+        nxt = VL.Index.from_seqs(ctx, ['new%dA' % i, 'new%dB' % i], SD.REF, k=15, w=10)
+        same = (nxt.h.value if hasattr(nxt.h, 'value') else nxt.h) == addr
+        text = SD.check(VL, ctx, nxt, case)[0]
+        assert b'\tnew%dA\t' % i in text and b'oldA' not in text, (i, same)
+        nxt.close()
+        if same:
+            break
+
+
 def test_bad_records_are_refused(env):
     VL, ctx, idx = env
     rng = np.random.default_rng(2)

@@ -13,6 +13,7 @@
 #include "vmx_kernels.h"
 #include "vmx_extend.h"
 #include "vmx_round.h"
+#include "vmx_batch_policy.h"
 
 #ifdef VMX_EMU
 #define VMX_LD_ACQ(p) __atomic_load_n((p), __ATOMIC_ACQUIRE)
@@ -43,8 +44,9 @@ __device__ __forceinline__ void vmx_round_values(const vmx_round_args& A, const 
 __device__ void vmx_round_plan(const vmx_round_args& A, int n, const long long* tot) {
     int64_t* out = A.plan_out;
     const int64_t* tboff = A.off[2];
-    out[0] = n; out[1] = tot[2]; out[2] = tot[3]; out[3] = tot[4]; out[4] = tot[5]; out[5] = tot[0]; out[6] = tot[1];
-    int64_t* cuts = out + 8; int64_t* offs = out + 8 + VMX_MAX_CHUNKS + 1;
+    out[VMX_PLAN_N] = n; out[VMX_PLAN_POOLS] = tot[2]; out[VMX_PLAN_POOLS + 1] = tot[3]; out[VMX_PLAN_POOLS + 2] = tot[4]; out[VMX_PLAN_POOLS + 3] = tot[5];
+    out[VMX_PLAN_TBYTES] = tot[0]; out[VMX_PLAN_QBYTES] = tot[1];
+    int64_t* cuts = out + VMX_PLAN_CUTS; int64_t* offs = out + VMX_PLAN_OFFS;
     int m = 0, p = 0;
     cuts[0] = 0; offs[0] = 0;
     while (p < n) {
@@ -55,7 +57,7 @@ __device__ void vmx_round_plan(const vmx_round_args& A, int n, const long long* 
         if (m > VMX_MAX_CHUNKS) { m = -1; break; }
         cuts[m] = p; offs[m] = p == n ? (int64_t)tot[2] : VMX_LD_RLX(tboff + p);
     }
-    out[7] = m;
+    out[VMX_PLAN_CHUNKS] = m;
 }
 
 template <bool DP>
@@ -162,7 +164,6 @@ __global__ void __launch_bounds__(1024) k_ext_geometry(const int32_t* __restrict
     __shared__ long long s_base[3];
     __shared__ long long s_acc[3];
     const int tid = (int)threadIdx.x, lane = vmx_lane(), wv = tid >> 6;
-    auto pool = [&](int bit, long long x) -> long long { const long long y = x * mul; return (tmask & bit) ? (y / tdiv > 1 ? y / tdiv : 1) : y; };
     if (tid < 3) s_base[tid] = 0;
     if (tid == 0) { s_acc[0] = 0; s_acc[1] = 0; s_acc[2] = 0; }
     __syncthreads();
@@ -172,7 +173,7 @@ __global__ void __launch_bounds__(1024) k_ext_geometry(const int32_t* __restrict
         long long x[3] = {0, 0, 0};
         if (r < n) {
             const long long cl = la_cnt[r], len = roff[r + 1] - roff[r];
-            if (cl > 0) { x[0] = pool(1, 3 * cl + 8); x[1] = pool(2, cl + 2); x[2] = (pool(4, 3 * len + 64 * (cl / 2 + 2) + 56) + 7) & ~7LL; full += cl + 2; la += cl; }
+            if (cl > 0) { const vmx_read_geo g = vmx_read_geometry(cl, len, mul, tmask, tdiv); x[0] = g.anchors; x[1] = g.segs; x[2] = g.blob; full += g.full; la += cl; }      // (the waiting path's host loop applies the same rule)
         }
         long long inc[3];
         for (int v = 0; v < 3; ++v) {
@@ -206,5 +207,5 @@ __global__ void __launch_bounds__(1024) k_ext_geometry(const int32_t* __restrict
     full = vmx_wave_sum_i64(full); la = vmx_wave_sum_i64(la); cut = vmx_wave_sum_i64(cut);
     if (lane == 0) { atomicAdd((unsigned long long*)&s_acc[0], (unsigned long long)full); atomicAdd((unsigned long long*)&s_acc[1], (unsigned long long)la); atomicAdd((unsigned long long*)&s_acc[2], (unsigned long long)cut); }
     __syncthreads();
-    if (tid == 0) { tot[0] = s_base[0]; tot[1] = s_base[1]; tot[2] = s_base[2]; tot[3] = s_acc[0]; tot[4] = s_acc[1]; tot[5] = s_acc[2]; }
+    if (tid == 0) { tot[VMX_GEO_ANCHORS] = s_base[0]; tot[VMX_GEO_SEGS] = s_base[1]; tot[VMX_GEO_BLOB] = s_base[2]; tot[VMX_GEO_FULL] = s_acc[0]; tot[VMX_GEO_LOCAL] = s_acc[1]; tot[VMX_GEO_CUT] = s_acc[2]; }
 }

@@ -82,7 +82,7 @@ __host__ __device__ constexpr bool vmx_ad_scores_ok(int match, int mismatch, int
            vmx_ad_imin(mismatch, 0) * (VMX_DP16X4_MAX / 2) - vmx_ad_imin(o1 + (long long)e1 * VMX_DP16X4_MAX, o2 + (long long)e2 * VMX_DP16X4_MAX)
                - vmx_ad_imax(o1, o2) - vmx_ad_imax(e1, e2) > (long long)VMX_AD_NEGINF + vmx_ad_imax(o1, o2);
 }
-static_assert(vmx_ad_scores_ok(2, -4, 4, 2, 24, 1), "the gap fill's own scoring (vmx_align.hip: gf_score) must fit the tagged 16-bit domain");
+static_assert(vmx_ad_scores_ok(2, -4, 4, 2, 24, 1), "the gap fill's own scoring (vmx_stage_extend.hip: gf_score) must fit the tagged 16-bit domain");
 struct vmx_ad_consts { unsigned O1, O2, E1, E2, MATCH, PEN, NH, NE1, NE2, NF1, NF2; };
 
 // one cell (both halves): up = (H, E1, E2) of the cell above, left = (H, F1, F2) of the cell to the left, H = the diagonal predecessor on

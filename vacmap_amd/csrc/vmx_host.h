@@ -4,6 +4,7 @@
 #include "vmx_device.h"
 #include "vmx_kernels.h"
 #include "../../include/vacmapx.h"
+#include "vmx_batch_policy.h"
 #include <algorithm>
 #include <map>
 #include <cstring>
@@ -323,7 +324,7 @@ __global__ void k_gapfill_redo(const uint8_t* tcodes, const uint8_t* qcodes, con
 // (round 4: the default follows the read mode — HiFi problems score near the all-match bound, so a band whose margin covers 40 % of the problem
 // is proven as often as one that covers 100 %: fill 7.0 -> 6.0 ms per batch; ONT modes 100 -> 90: 8.9 -> 8.6; profiles/r04_x_*)
 static inline int vmx_ad_pct_env(int mode = 0) {
-    int pct = mode == 1 ? 40 : 90, pmin = mode == 1 ? 40 : VMX_AD_PCT_MIN_DEFAULT;
+    int pct = vmx_ad_rule::start_pct(mode), pmin = mode == 1 ? 40 : VMX_AD_PCT_MIN_DEFAULT;
     if (const char* e = getenv("VMX_AD_PCT")) { const int v = atoi(e); if (v >= 0 && v <= 60000) pct = v; }
     if (const char* e = getenv("VMX_AD_PCT_MIN")) { const int v = atoi(e); if (v >= 0 && v <= 60000) pmin = v; }
     return pct | (pmin << 16);

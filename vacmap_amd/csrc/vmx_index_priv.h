@@ -7,8 +7,11 @@
 #include <vector>
 
 #include <mutex>
+// every index object of the process has a number of its own: what a cache remembers an index by (a freed index's ADDRESS is handed to the next one)
+static inline uint64_t vmx_index_next_serial() { static std::atomic<uint64_t> n{0}; return ++n; }
 struct vm_index {
     vm_ctx* ctx = nullptr;
+    const uint64_t serial = vmx_index_next_serial();
     int k = 0, w = 0, mid_occ = 10, table_bits = 0;
     std::vector<std::string> names;
     std::vector<int64_t> lens, offsets;     // offsets has nseq+1 entries

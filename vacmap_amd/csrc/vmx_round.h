@@ -9,6 +9,33 @@
 #define VMX_ROUND_WGS 128            // workgroups of k_round_prep (<= 256: one look-back step per thread)
 #define VMX_ROUND_PART_WORDS (256 * 8 + 8)      // int64 words of the publication area: 8 per workgroup (sums [0..5], flag [7]) + the finished-workgroups counter
 
+// ---- layouts of the small device blocks the host reads back once per batch (vmx_batch_bufs: statblk, qrange, geotot), shared by the kernels that fill them and the host
+// B.statblk, 2048 bytes, cleared once per batch
+enum {
+    VMX_STAT_BYTES = 2048,
+    VMX_STAT_ROUND_ED = 0,          // int32 [0..7]: the rounds' problem counts (k_round_prep's stat_out): the divergence filter's,
+    VMX_STAT_ROUND_EXT = 1,         //   the four x-drop rounds' ([1..4]),
+    VMX_STAT_ROUND_GF = 6,          //   the gap fill's of pass 0 and ([7]) pass 1
+    VMX_STAT_ROUNDS = 8,
+    VMX_STAT_FIN = 32,              // int64 [32..45]: the final scalars (k_final_scalars, VMX_FIN_*)
+    VMX_STAT_PLAN = 64,             // int64 [64..121]: the chunk plan of pass 0 (k_round_prep<true>, VMX_PLAN_*)
+    VMX_STAT_PLAN_STRIDE = 64       // int64 [128..185]: of pass 1
+};
+// the final scalars
+enum { VMX_FIN_NREC = 0, VMX_FIN_NBLOB = 1, VMX_FIN_OFLOW = 2, VMX_FIN_ED_FULL = 3, VMX_FIN_ED_TIER2 = 4, VMX_FIN_ED_TIER1 = 5, VMX_FIN_ROUNDS = 6, VMX_FIN_WORDS = VMX_FIN_ROUNDS + VMX_STAT_ROUNDS };
+// a gap-fill round's plan (vmx_round_args.plan_out)
+enum { VMX_PLAN_N = 0, VMX_PLAN_POOLS = 1 /* [1..4] traceback, boundary, run, CIGAR totals */, VMX_PLAN_TBYTES = 5, VMX_PLAN_QBYTES = 6, VMX_PLAN_CHUNKS = 7, VMX_PLAN_CUTS = 8,
+       VMX_PLAN_OFFS = VMX_PLAN_CUTS + VMX_MAX_CHUNKS + 1, VMX_PLAN_WORDS = VMX_PLAN_CUTS + 2 * (VMX_MAX_CHUNKS + 1) };
+// B.qrange (int32): the size ordering's queue range and heads, then the divergence filter's tier counters in k_final_scalars' order
+enum { VMX_QR_RANGE = 0, VMX_QR_CNT = 4, VMX_QR_NFULL = 8, VMX_QR_NT2 = 9, VMX_QR_NT1 = 10, VMX_QR_BYTES = 128 };
+// B.geotot (int64): what k_ext_geometry found
+enum { VMX_GEO_ANCHORS = 0, VMX_GEO_SEGS = 1, VMX_GEO_BLOB = 2, VMX_GEO_FULL = 3, VMX_GEO_LOCAL = 4, VMX_GEO_CUT = 5, VMX_GEO_WORDS = 6 };
+static_assert(VMX_STAT_ROUND_ED == 0 && VMX_STAT_ROUND_EXT == 1 && VMX_STAT_ROUND_GF == 6 && VMX_STAT_FIN == 32 && VMX_STAT_PLAN == 64 && VMX_STAT_PLAN + VMX_STAT_PLAN_STRIDE == 128, "statblk layout");
+static_assert(VMX_FIN_WORDS == 14 && VMX_FIN_ROUNDS == 6 && 8 * (VMX_STAT_FIN + VMX_FIN_WORDS) <= 8 * VMX_STAT_PLAN, "final scalars end before the plans");
+static_assert(VMX_PLAN_WORDS == 58 && VMX_PLAN_WORDS <= VMX_STAT_PLAN_STRIDE && 8 * (VMX_STAT_PLAN + VMX_STAT_PLAN_STRIDE + VMX_PLAN_WORDS) <= VMX_STAT_BYTES, "both plans fit the block");
+static_assert(VMX_QR_CNT == 4 && VMX_QR_NFULL == 8 && VMX_QR_NT2 == 9 && VMX_QR_NT1 == 10 && 4 * (VMX_QR_NT1 + 1) <= VMX_QR_BYTES, "qrange layout");
+static_assert(VMX_GEO_ANCHORS == 0 && VMX_GEO_SEGS == 1 && VMX_GEO_BLOB == 2 && VMX_GEO_FULL == 3 && VMX_GEO_LOCAL == 4 && VMX_GEO_CUT == 5, "geotot layout");
+
 struct vmx_round_args {
     const vmx_pair_desc* desc; const int32_t* n_prob;
     int64_t* off[6];            // exclusive prefix sums, n + 1 entries each: [0] target string bytes, [1] query string bytes; gap-fill rounds: [2] traceback bytes,

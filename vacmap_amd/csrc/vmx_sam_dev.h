@@ -46,14 +46,14 @@ struct vmx_sam_bufs {
     vmx::DevBuf names, name_off, seqs, seq_off, quals, qual_off, comments, com_off, recs, cigars, status, rg;
     vmx::DevBuf cnt, first, keep, ord, mq, flag, rflag, ri, tsz, toff, scratch, lsz, loff, res, tmp;
     vmx::DevBuf text, text_off;
-    vmx::DevBuf cnames, cname_off; const struct vm_index* names_of = nullptr;       // the contig-name blob of the index it was made for
+    vmx::DevBuf cnames, cname_off; uint64_t names_of = 0;                           // the contig-name blob and the serial of the index it was made for (vm_index.serial: never 0)
     std::string h_cnames; std::vector<int64_t> h_cname_off;
     double s_upload = 0, s_kernel = 0, s_download = 0;                              // wall seconds of the last call by phase
     void release() {
         vmx::DevBuf* all[] = {&names, &name_off, &seqs, &seq_off, &quals, &qual_off, &comments, &com_off, &recs, &cigars, &status, &rg, &cnt, &first, &keep, &ord, &mq, &flag, &rflag, &ri, &tsz, &toff,
                               &scratch, &lsz, &loff, &res, &tmp, &text, &text_off, &cnames, &cname_off};
         for (vmx::DevBuf* b : all) b->release();
-        names_of = nullptr;
+        names_of = 0;
     }
 };
 struct vmx_sam_totals { int64_t text_bytes, n_lines, n_skipped; };

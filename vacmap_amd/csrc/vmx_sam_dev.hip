@@ -38,12 +38,12 @@ int scan64(vm_ctx* c, DevBuf& tmp, const int64_t* in, int64_t* out, size_t n) {
 
 // the contig names of `mi` as one device blob, kept until the context meets another index
 int contig_names(vm_ctx* c, vmx_sam_bufs* S, const vm_index* mi) {
-    if (S->names_of == mi && S->cnames.p) return 0;
+    if (S->names_of == mi->serial && S->cnames.p) return 0;      // (by serial, not by address: a closed index's address is reused by the next one, with other names)
     S->h_cnames.clear(); S->h_cname_off.assign(1, 0);                    // (the host sources of the copies live as long as the device blob)
     for (const std::string& s : mi->names) { S->h_cnames += s; S->h_cname_off.push_back((int64_t)S->h_cnames.size()); }
     VMX_TRY(upload(S->cnames, S->h_cnames.data(), S->h_cnames.size(), c->stream));
     VMX_TRY(upload(S->cname_off, S->h_cname_off.data(), S->h_cname_off.size(), c->stream));
-    S->names_of = mi;
+    S->names_of = mi->serial;
     return 0;
 }
 

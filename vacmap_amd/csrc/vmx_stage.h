@@ -1,4 +1,7 @@
 // vmx_stage.h — device-buffer bundles and internal stage functions shared by the stage entry points and vm_align_batch.
+// The stages of one batch: vmx_seed_stage, vmx_global_stage, vmx_local_stage (below) and, over the batch's state vmx_batch_run (vmx_batch.h, included at the end):
+// batch_front / batch_front_preset, vmx_extend_stage (vmx_stage_extend.hip), batch_results, batch_check_assumptions, batch_results_tail, batch_read_statuses, batch_times.
+// The host's decisions on that path are pure functions in vmx_batch_policy.h; the environment knobs of the path are vmx_align_knobs (vmx_batch.h).
 #ifndef VMX_STAGE_H
 #define VMX_STAGE_H
 #include "vmx_host.h"
@@ -66,4 +69,5 @@ int vmx_local_stage(vm_ctx* c, const vm_index_view& ix, const vm_params* prm, in
 int vmx_launch_chain_select(vm_ctx* c, int64_t n, const int64_t* h_aoff, vmx::DevBuf& d_list, const vmx_anchor* sorted, const int64_t* d_aoff, const int64_t* d_lens,
                             const double* S, const int32_t* P, const int32_t* SA, const int64_t* gmax, const int32_t* flip, int mode, char* scr, const int64_t* soff,
                             int32_t* d_mapq, double* d_score, int32_t* d_np, int32_t* plen, vmx_anchor* prow);
+#include "vmx_batch.h"
 #endif
