@@ -561,6 +561,7 @@ int vm_k_cigar_batch_banded(vm_ctx* c, const vm_score* sc, int eqx, int64_t n, c
     VMX_TRY(B.ciglen.reserve(4 * (size_t)(n + 1))); VMX_TRY(B.cigq.reserve(4 * (size_t)(n + 1))); VMX_TRY(B.dpscore.reserve(4 * (size_t)(n + 1)));
     VMX_TRY(B.order.reserve(4 * (size_t)(2 * n + 64)));
     VMX_TRY(B.gfctl.reserve(sizeof(vmx_gf_ctl))); VMX_HIP(hipMemsetAsync(B.gfctl.p, 0, sizeof(vmx_gf_ctl), c->stream));
+    if (!vmx_tb_base_ok(B.tb.p, 0)) { set_error("gap fill: the traceback space does not start on a 64-byte line"); return VM_ERR_ARG; }
     if (n) vmx_gapfill_chunk(c, B, *sc, ad_pct, eqx, 0, n, B.chunkn.as<int32_t>(), 0, B.gfctl.as<vmx_gf_ctl>(), B.order.as<int32_t>() + n + 32, redo, nullptr);
     std::vector<char> hc((size_t)cig + 16); std::vector<int32_t> hl((size_t)n), flag((size_t)n);
     vmx_gf_ctl ctl;                                                  // its counters; the size-order scratch behind them is not fetched

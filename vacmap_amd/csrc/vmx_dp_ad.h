@@ -15,7 +15,8 @@
 // steps, query codes move up (one DPP each per step pair), fed at lane 0 / lane 15 from 16-entry chunk registers that rotate one lane
 // per use and are refilled with one coalesced load every 16 pairs.
 // Traceback bytes: tb[vmx_ad_tb_off(a - 1, l, W) + k] for the cell of anti-diagonal a on diagonal x = 2 NS l + 2 k + (a & 1): W = VMX_AD_W(NS) bytes per lane,
-// problem and step (vmx_gapfill.h: 64-byte lines of VMX_AD_AB anti-diagonals x 64 / (AB W) lanes).
+// problem and step (vmx_gapfill.h: 64-byte lines of VMX_AD_AB = 4 anti-diagonals x 64 / (AB W) lanes, a lane's four slots of a line side by side). The band
+// loop runs a block of four steps per turn and stores it once: one 16-byte store per lane and problem for the 4-byte slots, 8 for W = 2, 4 for W = 1.
 #ifndef VMX_DP_AD_H
 #define VMX_DP_AD_H
 
@@ -56,7 +57,8 @@ template <int LW> __device__ __forceinline__ int vmx_ad_ror1(int v) { if constex
 // order the stores want, the source comes out of a v_perm lookup on the h tags, the four flags out of three v_bfi. The match score is
 // min(tc ^ qc, PEN) with the codes held << VMX_AD_CSH: 0 on a match, PEN = 8 (match - mismatch) on any mismatch.
 // Compiled (gfx950, NS = 4), one step of four cell pairs with its DPP hand-offs and store: 137 VALU = 62 two-cycle + 75 four-cycle,
-// ~458 cycles by the table, where the int16 form took 203 = 56 + 147, ~746 (profiles/r07_tagged_fill_ab.md).
+// ~458 cycles by the table, where the int16 form took 203 = 56 + 147, ~746 (profiles/r07_tagged_fill_ab.md). With the block stores a turn of
+// four steps is 628 VALU and 2 stores where four such steps were 656 and 8 (profiles/ad_block_store_ab.md).
 //   Range (vmx_ad_bias, vmx_ad_scores_ok): every value a step computes is at most match * (VMX_DP16X4_MAX / 2 + 1) (one match more than the
 // best a problem with tl + ql <= VMX_DP16X4_MAX reaches); "-infinity" is VMX_AD_NEGINF and every value, -infinity included, loses at most
 // max(e1, e2) per step (E = max(..., E_prev) - e), plus one gap opening or mismatch for the candidates fed to a max. The bias lifts that
@@ -159,6 +161,17 @@ static_assert(vmx_adw_off_ok(1) && vmx_adw_off_ok(127) && vmx_adw_off_ok(128) &&
 static_assert(vmx_adw_off_ok(256), "vmx_adw_off is cell_off of the 128-row layout");
 static_assert(vmx_adw_off_ok(257), "vmx_adw_off is cell_off of the 128-row layout");
 
+// a value the compiler has to have in a register HERE: left alone it moves the packing of a step's bytes (vmx_ad_bytes) down to the block's store and keeps the
+// 5 NS words per step it reads alive across the block's other steps instead of the two words it makes — spills in the NS = 4 loop
+#ifdef VMX_EMU
+__device__ __forceinline__ void vmx_ad_pin(unsigned&) {}
+#else
+__device__ __forceinline__ void vmx_ad_pin(unsigned& v) { asm volatile("" : "+v"(v)); }
+#endif
+// what a lane stores for a block of four steps (W = 2, W = 4): one 8- / 16-byte store through an aligned pointer
+struct alignas(8) vmx_u32x2 { unsigned x, y; };
+struct alignas(16) vmx_u32x4 { unsigned x, y, z, w; };
+
 template <int NS, int LW = 16>
 __device__ __forceinline__ void vmx_gapfill_fill_ad(const uint8_t* __restrict__ TX, const uint8_t* __restrict__ QX, int tlX, int qlX, int dloX, uint8_t* __restrict__ tbX,
                                                    const uint8_t* __restrict__ TY, const uint8_t* __restrict__ QY, int tlY, int qlY, int dloY, uint8_t* __restrict__ tbY,
@@ -173,7 +186,12 @@ __device__ __forceinline__ void vmx_gapfill_fill_ad(const uint8_t* __restrict__ 
     K.NF1 = (neg + VMX_AD_TF1) * 0x00010001u; K.NF2 = (neg + VMX_AD_TF2) * 0x00010001u;
     const int afX = (tlX > 0 && qlX > 0) ? tlX + qlX : 0, afY = (tlY > 0 && qlY > 0) ? tlY + qlY : 0;     // the last anti-diagonal: cell (tl, ql)
     const int total = vmx_uniform_i32(vmx_wave_max_i32(afX > afY ? afX : afY));
-    const int npairs = (total + 1) >> 1;                        // pair p = 1 ..: the odd step a = 2p - 1 (C sets), then the even step a = 2p (A sets)
+    // pair p = 1 ..: the odd step a = 2p - 1 (C sets), then the even step a = 2p (A sets). LW = 16 runs the pairs two at a time, a block of four anti-diagonals
+    // whose bytes go out in one store: an odd count gets ONE JUNK PAIR at the end (rather than a flush after the loop: no second copy of the store, and a turn
+    // without a branch in it). Its steps lie past every problem's last anti-diagonal, like the steps a shorter problem of the wave always ran: garbage that feeds
+    // garbage (the steps stay <= VMX_DP16X4_MAX, a multiple of 4: inside the range the bias is sized for), bytes no walk reads, in space rounded up to whole blocks.
+    static_assert(VMX_DP16X4_MAX % 4 == 0, "the junk pair of the 16-lane band must not take the step count past the small class's limit");
+    const int npairs = LW == 16 ? (((total + 1) >> 1) + 1) & ~1 : (total + 1) >> 1;
     const int poX = (afX + 1) >> 1, peX = afX >> 1, poY = (afY + 1) >> 1, peY = afY >> 1;     // last pair whose odd / even step stores
     const int hX = dloX >> 1, hY = dloY >> 1;                   // dlo is even
     // set k of lane l in pair p: target row p - 1 - h - NS l - k on the odd step and one more on the even step, query column p + h + NS l + k on both
@@ -202,12 +220,26 @@ __device__ __forceinline__ void vmx_gapfill_fill_ad(const uint8_t* __restrict__ 
     const int lfX = xfX / (2 * NS), kfX = (xfX % (2 * NS)) >> 1, lfY = xfY / (2 * NS), kfY = (xfY % (2 * NS)) >> 1;
     int finX = 0, finY = 0;
     constexpr int W = VMX_AD_W(NS);                           // bytes of the lane's slot: as many as the lane has cells per step (round 6; 4 before, whatever NS)
-    uint8_t* const pX = LW == 16 ? tbX + vmx_ad_tb_off(0, l, W) : tbX;       // the lane's slot of anti-diagonal 0; the step's part of the offset is added per store
+    constexpr int PB = LW == 16 ? VMX_AD_AB / 2 : 1;          // step pairs per turn of the band loop: LW = 16 runs a block of the traceback layout per turn (below)
+    static_assert(LW != 16 || PB == 2, "the 16-lane band stores blocks of four anti-diagonals");
+    uint8_t* const pX = LW == 16 ? tbX + vmx_ad_tb_off(0, l, W) : tbX;       // the lane's run of anti-diagonals 0 .. 3; the block's part of the offset is added per store
     uint8_t* const pY = LW == 16 ? tbY + vmx_ad_tb_off(0, l, W) : tbY;
-    auto put = [&](uint8_t* at, unsigned w01, unsigned w23, bool hi) {
-        if constexpr (W == 1) *at = (uint8_t)(hi ? (w01 >> 16) : w01);
-        else if constexpr (W == 2) *(uint16_t*)at = (uint16_t)(hi ? (w01 >> 16) : w01);
-        else *(uint32_t*)at = vmx_perm(w23, w01, hi ? 0x07060302u : 0x05040100u);
+    // LW = 16: the words of the FOUR steps of a block (two pairs: the anti-diagonals s = 2p - 2 .. 2p + 1 of an odd p, one line block of the layout) stay in
+    // registers and go out as one store of 4 W bytes per lane and problem: bw[t] = {w01, w23} of the block's step t. The problem's space starts on a 64-byte
+    // line (vmx_tb_base_ok and the sizes' check, vmx_gapfill.h) and the lane's run in it is aligned to its length (vmx_ad_tb_ok).
+    auto put_block = [&](uint8_t* at, const unsigned (&bw)[4][2], bool hi) {
+        if constexpr (W == 1) {          // byte 0 (X) / 2 (Y) of every step's w01
+            const unsigned t01 = vmx_perm(bw[1][0], bw[0][0], 0x06040200u), t23 = vmx_perm(bw[3][0], bw[2][0], 0x06040200u);      // [0.X, 0.Y, 1.X, 1.Y], [2.X, 2.Y, 3.X, 3.Y]
+            *(uint32_t*)at = vmx_perm(t23, t01, hi ? 0x07050301u : 0x06040200u);
+        } else if constexpr (W == 2) {   // the low (X) / high (Y) half of every step's w01
+            const unsigned sel = hi ? 0x07060302u : 0x05040100u;
+            vmx_u32x2 v; v.x = vmx_perm(bw[1][0], bw[0][0], sel); v.y = vmx_perm(bw[3][0], bw[2][0], sel);
+            *(vmx_u32x2*)at = v;
+        } else {                         // the low (X) / high (Y) halves of every step's w01 and w23
+            const unsigned sel = hi ? 0x07060302u : 0x05040100u;
+            vmx_u32x4 v; v.x = vmx_perm(bw[0][1], bw[0][0], sel); v.y = vmx_perm(bw[1][1], bw[1][0], sel); v.z = vmx_perm(bw[2][1], bw[2][0], sel); v.w = vmx_perm(bw[3][1], bw[3][0], sel);
+            *(vmx_u32x4*)at = v;
+        }
     };
     // LW = 64: the step's bytes at their cells' addresses in the packed layout. Cell k of the lane on anti-diagonal a is (i0 - k, a - i0 + k), i0 = i1 + 1
     // the lane's largest row: inside the matrix when lo <= i - 1 < hi with lo = max(0, a - 1 - ql), hi = min(tl, a - 1) (both wave-uniform); its offset: vmx_adw_off
@@ -235,7 +267,13 @@ __device__ __forceinline__ void vmx_gapfill_fill_ad(const uint8_t* __restrict__ 
         tch = ntch; qch = nqch;
         load_chunks(p0 + LW, ntch, nqch);                       // one block ahead
         int pend = npairs - p0; if (pend > LW) pend = LW;
-        for (int pp = 0; pp < pend; ++pp) {
+        // LW = 16: PB = 2 pairs per turn, one block of the traceback layout (p0 is a multiple of 16, so a turn's first pair is odd and a block never straddles a
+        // chunk refill; npairs is even, above).
+        for (int pp0 = 0; pp0 < pend; pp0 += PB) {
+          unsigned bw[2 * PB][2];
+#pragma unroll
+          for (int hf = 0; hf < PB; ++hf) {
+            const int pp = pp0 + hf;
             const int p = p0 + pp + 1;
             // query codes move up one diagonal pair
             {
@@ -259,11 +297,8 @@ __device__ __forceinline__ void vmx_gapfill_fill_ad(const uint8_t* __restrict__ 
             {
                 unsigned w01, w23;
                 vmx_ad_pack<NS>(w, w01, w23);
-                if constexpr (LW == 16) {
-                const size_t so = vmx_ad_tb_off(2 * p - 2, 0, W);   // anti-diagonal a = 2p - 1 is step s = a - 1
-                if (p <= poX) put(pX + so, w01, w23, false);
-                if (p <= poY) put(pY + so, w01, w23, true);
-                } else {
+                if constexpr (LW == 16) { vmx_ad_pin(w01); if constexpr (NS > 2) vmx_ad_pin(w23); bw[2 * hf][0] = w01; bw[2 * hf][1] = w23; }      // anti-diagonal a = 2p - 1 is step s = a - 1 = 2p - 2
+                else {
                     if (p <= poX) put_pk(pX, tlX, qlX, 2 * p - 1, p - 2 - hX - NS * l, w01, w23, false);
                     if (p <= poY) put_pk(pY, tlY, qlY, 2 * p - 1, p - 2 - hY - NS * l, w01, w23, true);
                 }
@@ -289,11 +324,8 @@ __device__ __forceinline__ void vmx_gapfill_fill_ad(const uint8_t* __restrict__ 
             {
                 unsigned w01, w23;
                 vmx_ad_pack<NS>(w, w01, w23);
-                if constexpr (LW == 16) {
-                const size_t so = vmx_ad_tb_off(2 * p - 1, 0, W);
-                if (p <= peX) put(pX + so, w01, w23, false);
-                if (p <= peY) put(pY + so, w01, w23, true);
-                } else {
+                if constexpr (LW == 16) { vmx_ad_pin(w01); if constexpr (NS > 2) vmx_ad_pin(w23); bw[2 * hf + 1][0] = w01; bw[2 * hf + 1][1] = w23; }
+                else {
                     if (p <= peX) put_pk(pX, tlX, qlX, 2 * p, p - 1 - hX - NS * l, w01, w23, false);
                     if (p <= peY) put_pk(pY, tlY, qlY, 2 * p, p - 1 - hY - NS * l, w01, w23, true);
                 }
@@ -305,6 +337,14 @@ __device__ __forceinline__ void vmx_gapfill_fill_ad(const uint8_t* __restrict__ 
                 if (p == poX && l == lfX) finX = (int)((vX & 0xffffu) >> 3) - bias;
                 if (p == poY && l == lfY) finY = (int)(vY >> 19) - bias;
             }
+          }
+          // the block's store: for every problem that has the block's first anti-diagonal (a = 2p - 1 of the turn's first pair p)
+          if constexpr (LW == 16) {
+              const int p = p0 + pp0 + 1;
+              const size_t so = vmx_ad_tb_off(2 * p - 2, 0, W);
+              if (p <= poX) put_block(pX + so, bw, false);
+              if (p <= poY) put_block(pY + so, bw, true);
+          }
         }
     }
     scoreX = __shfl(finX, LW == 16 ? (lane & 48) | (lfX & 15) : lfX & 63);

@@ -140,25 +140,28 @@ typedef vmx_tb_stripes<128> vmx_tb_rows128;
 typedef vmx_tb_stripes<32> vmx_tb_rows32;
 
 /* The anti-diagonal layout: one slot of W bytes per lane and anti-diagonal, in 64-byte lines of VMX_AD_AB consecutive anti-diagonals x 64 / (AB W) consecutive
-   lanes. AB = 1 (rounds 2-3): a line = one anti-diagonal of a problem, the fill's row store is one line, but the traceback walk — nine steps in ten go down a
-   diagonal, two anti-diagonals back in the same lane — fetched a new 64-byte sector per step (5.2 GB per step of the pipeline for ~80 MB of bytes used). With AB
-   anti-diagonals per line a diagonal stretch reads a line per AB / 2 steps.
-   Round 6: the slot is as wide as the band needs — W = 1 byte per lane and anti-diagonal for ns = 1 (one cell per lane and step), 2 for ns = 2, 4 for ns = 3 / 4.
-   A HiFi problem (ns = 1 under the mode-L rule) wrote 64 bytes per anti-diagonal of which 16 were cells: its fill ran at 0.38 of the VALU peak behind 1.95 TB/s
-   of stores. */
+   lanes, LANE-MAJOR inside a line: the AB slots a lane has in a line are one aligned run of AB W bytes (16 for the 4-byte slots), so the band fill keeps the
+   bytes of AB steps in registers and writes them with ONE store per lane and problem (vmx_dp_ad.h: 16 / 8 / 4 bytes for W = 4 / 2 / 1) — a wave store covers
+   whole lines once instead of a quarter of each of them AB times.
+   Why lines of several anti-diagonals at all: with one anti-diagonal per line (rounds 2-3) the traceback walk — nine steps in ten go down a diagonal, two
+   anti-diagonals back in the same lane — fetched a new 64-byte sector per step (5.2 GB per step of the pipeline for ~80 MB of bytes used). With AB
+   anti-diagonals per line a diagonal stretch reads a line per AB / 2 steps, and the bytes of anti-diagonals s and s - 2 are in the same run.
+   The slot is as wide as the band needs — W = 1 byte per lane and anti-diagonal for ns = 1 (one cell per lane and step), 2 for ns = 2, 4 for ns = 3 / 4
+   (round 6: a HiFi problem, ns = 1 under the mode-L rule, wrote 64 bytes per anti-diagonal of which 16 were cells). */
 #ifndef VMX_AD_AB
 #define VMX_AD_AB 4     /* round 6: 4 (8 in rounds 4-5). With the step bound by the fill and the walk a narrow kernel that rides along, the fill's coalescing is worth more than the walk's
                            locality: ONT 15.35 / 15.68 -> 14.96 / 15.16 ms per step, HiFi unchanged (profiles/r06_u_traceback_line_blocking_ab.txt) */
 #endif
-static_assert(VMX_AD_AB == 1 || 64 / VMX_AD_AB <= 16, "a 64-byte line of the anti-diagonal traceback holds at most the 16 lanes of a row per anti-diagonal (1-byte slots): AB = 1, 4 or 8");
+static_assert(VMX_AD_AB == 4, "the band fill (vmx_dp_ad.h) stores blocks of exactly four anti-diagonals, two step pairs, with one store: AB = 1 or 8 needs another band loop");
 #define VMX_AD_W(ns) ((ns) <= 0 ? 0 : ((ns) == 1 ? 1 : ((ns) == 2 ? 2 : 4)))
-// byte offset of lane l's slot on anti-diagonal s (0-based: the cells with i + j = s + 1). Slot widths are powers of two, and the offset is written with the
-// width's log2 (wsh): the fills know it at compile time, the traceback walk holds it in a register, and neither depends on the compiler proving a divisor to be
-// a power of two.
-#define VMX_AD_LSH (VMX_AD_AB == 1 ? 6 : VMX_AD_AB == 4 ? 4 : 3)      /* log2 of the 64 / AB bytes an anti-diagonal has in a line */
-static_assert(64 / VMX_AD_AB == 1 << VMX_AD_LSH, "VMX_AD_AB is 1, 4 or 8");
+// byte offset of lane l's slot on anti-diagonal s (0-based: the cells with i + j = s + 1): the block of AB anti-diagonals, the line of the lane in the block,
+// the lane's run in the line, the slot in the run. It is the sum of a part of l and a part of s (vmx_tb_ad_lane_off / vmx_tb_ad_step_off). Slot widths are
+// powers of two, and the offset is written with the width's log2 (wsh): the fills know it at compile time, the traceback walk holds it in a register, and
+// neither depends on the compiler proving a divisor to be a power of two.
+#define VMX_AD_LSH 4      /* log2 of the 64 / AB bytes an anti-diagonal has in a line */
+static_assert(64 / VMX_AD_AB == 1 << VMX_AD_LSH, "VMX_AD_LSH is log2(64 / VMX_AD_AB)");
 __host__ __device__ __forceinline__ constexpr size_t vmx_ad_tb_off_sh(size_t s, size_t l, int wsh) {
-    return (s / VMX_AD_AB) * (size_t)((VMX_AD_AB * 16) << wsh) + (l >> (VMX_AD_LSH - wsh)) * 64 + (s % VMX_AD_AB) * (64 / VMX_AD_AB) + ((l & (((size_t)1 << (VMX_AD_LSH - wsh)) - 1)) << wsh);
+    return (s / VMX_AD_AB) * (size_t)((VMX_AD_AB * 16) << wsh) + (l >> (VMX_AD_LSH - wsh)) * 64 + (l & (((size_t)1 << (VMX_AD_LSH - wsh)) - 1)) * (size_t)(VMX_AD_AB << wsh) + ((s % VMX_AD_AB) << wsh);
 }
 #define VMX_AD_WSH(W) ((W) == 1 ? 0 : (W) == 2 ? 1 : 2)
 __host__ __device__ __forceinline__ constexpr size_t vmx_ad_tb_off(size_t s, size_t l, int W) { return vmx_ad_tb_off_sh(s, l, VMX_AD_WSH(W)); }      // W = 1, 2 or 4 bytes
@@ -208,6 +211,15 @@ __host__ __device__ __forceinline__ uint8_t* vmx_tb_ptr(const uint8_t* tb_pool, 
     const unsigned long long base = off >= 0 ? (unsigned long long)tb_pool : (unsigned long long)redo_pool;
     return (uint8_t*)(base + (unsigned long long)(off >= 0 ? off : -off - 1));
 }
+// a chunk's traceback buffer and the offset of its first problem (the prefix sum at the chunk's cut): both multiples of 64, so that with sizes that are
+// multiples of 64 (checked below) every problem's space starts on a line — what the band fill's 16-byte stores rely on. The host checks it per chunk.
+// (The emulator build's buffers come from malloc: 16 bytes, which is what the stores themselves need.)
+#ifdef VMX_EMU
+#define VMX_TB_BUF_ALIGN 16
+#else
+#define VMX_TB_BUF_ALIGN 64
+#endif
+__host__ __forceinline__ bool vmx_tb_base_ok(const void* buf, int64_t tb_off0) { return ((unsigned long long)buf & (VMX_TB_BUF_ALIGN - 1)) == 0 && (tb_off0 & 63) == 0; }
 // the other per-problem pools (vmx_dp_prob): boundary rows (H, E1, E2 of ql + 1 columns), run words of the walk, CIGAR text
 struct vmx_gf_pool_sizes { int64_t bnd, run, cig; };      // int32 units, uint32 units, bytes
 __host__ __device__ constexpr vmx_gf_pool_sizes vmx_gf_pools(int64_t tl, int64_t ql) { return {3 * (ql + 1), tl + ql + 2, 2 * (tl + ql) + 16}; }
@@ -266,16 +278,45 @@ VMX_TB_STRIPES_CHECK(vmx_tb_rows64);
 VMX_TB_STRIPES_CHECK(vmx_tb_rows128);
 VMX_TB_STRIPES_CHECK(vmx_tb_rows32);
 #undef VMX_TB_STRIPES_CHECK
-// every slot of the anti-diagonal layout (16 lanes x the anti-diagonals 1 .. tl + ql of a problem) lies inside the problem's bytes, for each slot width
+// the anti-diagonal layout, for each slot width, over 16 lanes x the anti-diagonals of a problem ROUNDED UP to whole blocks of AB (the band fill stores whole
+// blocks): every slot lies inside the problem's bytes; a lane's AB slots of a block are one run of AB W bytes aligned to its length, in step order; and the map
+// is one-to-one on (s, l) — the slots start at multiples of W below bytes = W x (number of slots), so it is enough that no two of them start at the same place
 constexpr bool vmx_ad_tb_ok(int W) {
     const int tls[6] = {1, 31, 32, 33, 64, 65}, qls[5] = {1, 15, 16, 17, 33};
     for (int t = 0; t < 6; ++t)
-        for (int q = 0; q < 5; ++q)
-            for (int s = 0; s < tls[t] + qls[q]; ++s)
-                for (int l = 0; l < 16; ++l)
-                    if (vmx_ad_tb_off(s, l, W) + W > (size_t)vmx_ad_tb_bytes(tls[t], qls[q], W)) return false;
+        for (int q = 0; q < 5; ++q) {
+            const size_t bytes = (size_t)vmx_ad_tb_bytes(tls[t], qls[q], W);
+            const int ns = (tls[t] + qls[q] + VMX_AD_AB - 1) / VMX_AD_AB * VMX_AD_AB;
+            if (bytes != (size_t)ns * 16 * (size_t)W) return false;
+            bool used[(65 + 33 + VMX_AD_AB) * 16] = {};
+            for (int s = 0; s < ns; ++s)
+                for (int l = 0; l < 16; ++l) {
+                    const size_t at = vmx_ad_tb_off(s, l, W);
+                    if (at + W > bytes || at % W || used[at / W]) return false;
+                    used[at / W] = true;
+                    if (s % VMX_AD_AB == 0 ? at % (size_t)(VMX_AD_AB * W) != 0 : at != vmx_ad_tb_off(s - 1, l, W) + W) return false;
+                    if (at != vmx_ad_tb_off(s, 0, W) + vmx_ad_tb_off(0, l, W)) return false;      // a part of the lane plus a part of the anti-diagonal
+                }
+        }
     return true;
 }
-static_assert(vmx_ad_tb_ok(1) && vmx_ad_tb_ok(2) && vmx_ad_tb_ok(4), "anti-diagonal traceback layout: a slot outside the problem's bytes");
+static_assert(vmx_ad_tb_ok(1), "anti-diagonal traceback layout, 1-byte slots: not one-to-one into the problem's bytes in aligned runs per lane");
+static_assert(vmx_ad_tb_ok(2), "anti-diagonal traceback layout, 2-byte slots: not one-to-one into the problem's bytes in aligned runs per lane");
+static_assert(vmx_ad_tb_ok(4), "anti-diagonal traceback layout, 4-byte slots: not one-to-one into the problem's bytes in aligned runs per lane");
+// The band fill's 16-byte stores need every problem's traceback space to start at a multiple of 16: the spaces are handed out by a prefix sum over these
+// size functions (k_round_prep, vm_k_cigar_batch_banded) from a chunk base that the host checks (vmx_tb_base_ok), so every one of them returns multiples of 64
+constexpr bool vmx_tb_sizes_ok() {
+    const int ls[28] = {0, 1, 2, 3, 4, 5, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 5001};      // around every stripe height, padding and class edge
+    for (int t = 0; t < 28; ++t)
+        for (int q = 0; q < 28; ++q) {
+            const int tl = ls[t], ql = ls[q];
+            if (vmx_ad_tb_bytes(tl, ql, 1) % 64 || vmx_ad_tb_bytes(tl, ql, 2) % 64 || vmx_ad_tb_bytes(tl, ql, 4) % 64) return false;
+            if (vmx_tb_rows32::bytes(tl, ql) % 64 || vmx_tb_rows64::bytes(tl, ql) % 64 || vmx_tb_rows128::bytes(tl, ql) % 64) return false;
+            if (vmx_gf_tb_bytes_full(tl, ql) % 64 || vmx_gf_tb_bytes_redo(tl, ql) % 64) return false;
+            for (int w = 0; w <= 4; w += (w ? w : 1)) if (vmx_gf_tb_bytes_batched(tl, ql, w) % 64) return false;
+        }
+    return true;
+}
+static_assert(vmx_tb_sizes_ok(), "a traceback size that is no multiple of 64 bytes would misalign the next problem's space for the band fill's wide stores");
 #endif
 #endif

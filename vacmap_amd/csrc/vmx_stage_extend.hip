@@ -295,6 +295,8 @@ static int ext_gapfill_chunks(vmx_batch_run& run, int pass) {
     if (!cnt) return 0;
     std::vector<int32_t> csz; for (size_t q = 0; q + 1 < cuts.size(); ++q) csz.push_back(cuts[q + 1] - cuts[q]);
     VMX_TRY(vmx_push(c, B.chunkn, csz.data(), csz.size()));
+    for (size_t q = 0; q + 1 < cuts.size(); ++q)
+        if (!vmx_tb_base_ok(B.tb.p, h_tboff_at[q])) { set_error("gap fill: a chunk's traceback space does not start on a 64-byte line"); return VM_ERR_ARG; }
     for (int q = 0; q + 1 < (int)cuts.size(); ++q) {      // pn = the chunk's size; the kernels read it on the device (B.chunkn)
         vmx_gf_ctl* ctl = B.gfctl.as<vmx_gf_ctl>() + (size_t)(pass * (VMX_MAX_CHUNKS + 1) + q);
         hipEvent_t* ke = q < 8 ? c->gev + (pass ? 24 : 0) + 3 * q : nullptr;      // HIP events around the dominant kernel, on the stream it runs on
