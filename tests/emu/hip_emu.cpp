@@ -138,3 +138,6 @@ void run_grid(dim3 grid, dim3 block, size_t shmem, std::function<void()> body) {
 }
 
 }  // namespace hipemu
+
+// live device (which = 0) / page-locked host (1) allocations of the process: what hipMalloc / hipHostMalloc handed out and nobody has freed
+extern "C" long long vmx_emu_live_allocs(int which) { return hipemu::live_allocs(which).load(); }

@@ -189,11 +189,17 @@ template <class T> inline T atomicCAS(T* p, T c, T v) { __atomic_compare_exchang
 template <class T> inline T atomicOr(T* p, T v) { return __atomic_fetch_or(p, v, __ATOMIC_RELAXED); }
 
 // host API subset
-inline hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
-inline hipError_t hipFree(void* p) { free(p); return hipSuccess; }
+// live allocations, device and page-locked host counted apart (the ownership tests read them: vmx_emu_live_allocs, hip_emu.cpp)
+namespace hipemu {
+inline std::atomic<long long>& live_allocs(int host) { static std::atomic<long long> n[2]; return n[host ? 1 : 0]; }
+inline hipError_t alloc(void** p, size_t n, int host) { *p = malloc(n ? n : 1); if (!*p) return hipErrorOutOfMemory; ++live_allocs(host); return hipSuccess; }
+inline hipError_t dealloc(void* p, int host) { if (p) { free(p); --live_allocs(host); } return hipSuccess; }
+}
+inline hipError_t hipMalloc(void** p, size_t n) { return hipemu::alloc(p, n, 0); }
+inline hipError_t hipFree(void* p) { return hipemu::dealloc(p, 0); }
 enum { hipHostMallocDefault = 0, hipHostMallocPortable = 1, hipHostMallocMapped = 2 };
-inline hipError_t hipHostMalloc(void** p, size_t n, unsigned = 0) { return hipMalloc(p, n); }
-inline hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
+inline hipError_t hipHostMalloc(void** p, size_t n, unsigned = 0) { return hipemu::alloc(p, n, 1); }
+inline hipError_t hipHostFree(void* p) { return hipemu::dealloc(p, 1); }
 inline hipError_t hipHostGetDevicePointer(void** d, void* h, unsigned) { *d = h; return hipSuccess; }
 inline hipError_t hipStreamQuery(hipStream_t) { return hipSuccess; }
 inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { if (n) memcpy(d, s, n); return hipSuccess; }

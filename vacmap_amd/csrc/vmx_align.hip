@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <cstddef>
 #include <cstring>
+#include <memory>
 #include <string>
 
 using namespace vmx;
@@ -51,7 +52,6 @@ __global__ void k_final_scalars(const int64_t* nr, const int64_t* nb, const int3
 struct vm_reads { vm_ctx* ctx; int64_t n; std::vector<int64_t> h_off; DevBuf raw, codes, off; };
 
 vmx_batch_bufs* vmx_ctx_batch_bufs(vm_ctx* c) { if (!c->bbufs) c->bbufs = new vmx_batch_bufs(); return c->bbufs; }
-void vmx_ctx_free_batch_bufs(vm_ctx* c) { if (c->bbufs) { c->bbufs->release(); delete c->bbufs; c->bbufs = nullptr; } }
 
 // the one place this file and vmx_stage_extend.hip read the environment (vmx_align_knobs, vmx_batch.h: which knob is latched and which is read per call, and why)
 vmx_align_knobs vmx_align_knobs_read() {
@@ -330,14 +330,14 @@ int batch_front(vmx_batch_run& run) {
     st.n_minimizers = c->last_n_minimizers;
     // compact anchors: aoff = scan(n_anchors)
     VMX_TRY(B.nanc64.reserve(8 * (size_t)(n + 2))); VMX_TRY(B.aoff.reserve(8 * (size_t)(n + 2)));
-    LAUNCH1D(k_i32_to_i64, n, B.seed[11].as<int32_t>(), B.nanc64.as<int64_t>(), n);
+    LAUNCH1D(k_i32_to_i64, n, B.seed.nanc.as<int32_t>(), B.nanc64.as<int64_t>(), n);
     hipLaunchKernelGGL(k_scan_i64, dim3(1), dim3(256), 0, c->stream, B.nanc64.as<int64_t>(), B.aoff.as<int64_t>(), n, 0);
     VMX_TRY(vmx_fetch(c, run.h_aoff.data(), B.aoff.p, (size_t)n + 1));
     VMX_HIP(vmx_stream_sync(c));
     const int64_t tot = run.h_aoff[n];
     st.n_anchors = tot;
     VMX_TRY(B.rows.reserve(32 * (size_t)(tot + 1)));
-    hipLaunchKernelGGL(k_compact_rows, dim3((unsigned)std::min<int64_t>(n, (int64_t)c->num_cu * 8)), dim3(128), 0, c->stream, d_seed_rows, B.seed[7].as<int64_t>(),
+    hipLaunchKernelGGL(k_compact_rows, dim3((unsigned)std::min<int64_t>(n, (int64_t)c->num_cu * 8)), dim3(128), 0, c->stream, d_seed_rows, B.seed.koff.as<int64_t>(),
                        B.aoff.as<int64_t>(), (int)n, B.rows.as<int64_t>());
     VMX_TRY(B.lens.reserve(8 * (size_t)(n + 1)));
     LAUNCH1D(k_readlens, n, run.d_roff, B.lens.as<int64_t>(), n);
@@ -610,14 +610,13 @@ int vm_reads_upload(vm_ctx* c, int64_t n, const char* seqs, const int64_t* offse
     *out = nullptr;
     if (!c) { set_error("no context"); return VM_ERR_NO_CTX; }
     VMX_HIP(hipSetDevice(c->device));
-    vm_reads* R = new vm_reads(); R->ctx = c; R->n = n; R->h_off.assign(offsets, offsets + n + 1);
+    std::unique_ptr<vm_reads> R(new vm_reads()); R->ctx = c; R->n = n; R->h_off.assign(offsets, offsets + n + 1);
     const int64_t tot = offsets[n];
-    int rc = 0;
-    if ((rc = upload(R->raw, seqs, (size_t)tot, c->stream)) < 0 || (rc = R->codes.reserve((size_t)tot + 64)) < 0 || (rc = upload(R->off, offsets, (size_t)n + 1, c->stream)) < 0) { delete R; return rc; }
+    VMX_TRY(upload(R->raw, seqs, (size_t)tot, c->stream)); VMX_TRY(R->codes.reserve((size_t)tot + 64)); VMX_TRY(upload(R->off, offsets, (size_t)n + 1, c->stream));
     if (tot) LAUNCH1D(k_encode, tot, R->raw.as<char>(), R->codes.as<uint8_t>(), tot);
     VMX_HIP(vmx_stream_sync(c));
-    R->raw.release();
-    *out = R;
+    R->raw.release();                  // early: a resident read set keeps its codes and offsets; the ASCII (as large as the codes) makes room for the batch's pools
+    *out = R.release();
     return VM_OK;
 }
 // the same into an existing object (its device buffers are kept and only grow): an uploader that streams batches ahead of the aligning contexts
@@ -632,7 +631,7 @@ int vm_reads_reupload(vm_ctx* c, vm_reads* R, int64_t n, const char* seqs, const
     VMX_HIP(vmx_stream_sync(c));
     return VM_OK;
 }
-void vm_reads_free(vm_reads* R) { if (!R) return; R->raw.release(); R->codes.release(); R->off.release(); delete R; }
+void vm_reads_free(vm_reads* R) { delete R; }
 
 int vm_align_resident(vm_ctx* c, const vm_index* mi, const vm_params* prm, const vm_reads* R, vm_record** recs, int64_t* n_recs, char** cigar_blob,
                       int32_t* status_per_read, vm_batch_stats* stats) {

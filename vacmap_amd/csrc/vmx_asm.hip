@@ -20,7 +20,7 @@ __global__ void k_link_sort_gather(const vmx_anchor* rows, const uint64_t* idx, 
 __global__ void k_chain_linked_fast(vmx_link_job* jobs, int n_jobs, vmx_tables tab, const double* gapcost_list, double skipcost, int maxdiff, int maxgap);
 
 namespace {
-struct Bufs { Bufs() = default; Bufs(const Bufs&) = delete; DevBuf st, preS, preP, preR, rows, S, P, SA, job, gap; ~Bufs() { st.release(); preS.release(); preP.release(); preR.release(); rows.release(); S.release(); P.release(); SA.release(); job.release(); gap.release(); } };
+struct Bufs { DevBuf st, preS, preP, preR, rows, S, P, SA, job, gap; };
 }
 
 extern "C" void vm_linked_out_free(vm_linked_out* o) {
@@ -70,7 +70,7 @@ extern "C" int vm_chain_linked(vm_ctx* c, int which, int kmersize, double skipco
     vmx_link_job hj; memset(&hj, 0, sizeof hj);
     hj.state = B.st.as<vmx_link_state>(); hj.rows = B.rows.as<vmx_anchor>(); hj.S = B.S.as<double>(); hj.P = B.P.as<int32_t>(); hj.SA = B.SA.as<int32_t>();
     hj.cap_pre = cap_pre; hj.n_new = (int32_t)n_new;
-    DevBuf fSi, fT, fCNT; struct RelF { DevBuf *a, *b, *c3; ~RelF() { a->release(); b->release(); c3->release(); } } relf{&fSi, &fT, &fCNT};
+    DevBuf fSi, fT, fCNT;
     if (which == 1) {                                            // the fork's linked GC-fast on its own (:21871; with n_pre = 0 its plain GC-fast, :20738)
         VMX_TRY(fSi.reserve(4 * tot)); VMX_TRY(fT.reserve(8 * tot)); VMX_TRY(fCNT.reserve(4 * ((size_t)hr.back().q + 50 + 64)));
         hj.Si = fSi.as<int32_t>(); hj.T = fT.as<int64_t>(); hj.CNT = fCNT.as<int32_t>(); hj.ran = 1; hj.gmax = -1;
@@ -138,8 +138,6 @@ struct LinkRound {
     DevBuf st, preS, preP, preR, rows, S, P, SA, job, gap, fSi, fT, fCNT;
     std::vector<std::vector<vmx_anchor>> saved_rows; std::vector<std::vector<int32_t>> saved_P;
     int64_t pre_g_max_index = 0; bool have = false; int cur_n_pre = 0;
-    LinkRound() = default; LinkRound(const LinkRound&) = delete;
-    ~LinkRound() { for (DevBuf* b : {&st, &preS, &preP, &preR, &rows, &S, &P, &SA, &job, &gap, &fSi, &fT, &fCNT}) b->release(); }
     int init(vm_ctx* ctx, int lc_, int k, double skip, int md, int mg) {
         c = ctx; lc = lc_; kmersize = k; skipcost = skip; maxdiff = md; maxgap = mg;
         if (md > 62) { set_error("maxdiff > 62 unsupported"); return VM_ERR_UNSUPPORTED; }
@@ -215,8 +213,8 @@ int run_jobs(vm_ctx* c, DevBuf& d_jobs, const std::vector<LinkRound*>& rounds, c
     if (!nj) return 0;
     std::vector<vmx_link_job> hj(nj); std::vector<vmx_link_state> hs(nj);
     for (size_t i = 0; i < nj; ++i) VMX_TRY(rounds[i]->stage(*news[i], hj[i]));
-    static DevBuf d_dbg; static const bool dbg_on = getenv("VMX_ASM_TIME") != nullptr;
-    if (dbg_on) { if (!d_dbg.p) { VMX_TRY(d_dbg.reserve(64)); VMX_HIP(hipMemsetAsync(d_dbg.p, 0, 64, c->stream)); } for (size_t i = 0; i < nj; ++i) hj[i].dbg = d_dbg.as<long long>(); }
+    static long long* d_dbg = nullptr; static const bool dbg_on = getenv("VMX_ASM_TIME") != nullptr;      // 64 bytes for the process, never freed (as the chain kernels' counter block)
+    if (dbg_on) { if (!d_dbg) { VMX_HIP(hipMalloc((void**)&d_dbg, 64)); VMX_HIP(hipMemsetAsync(d_dbg, 0, 64, c->stream)); } for (size_t i = 0; i < nj; ++i) hj[i].dbg = d_dbg; }
     VMX_TRY(upload(d_jobs, hj.data(), nj, c->stream));
     const LinkRound& R0 = *rounds[0];
     vmx_link_job* dj = d_jobs.as<vmx_link_job>(); const double* d_gap = R0.gap.as<double>(); const vmx_tables tabs = c->tables; hipStream_t stq = c->stream;
@@ -255,7 +253,7 @@ int run_jobs(vm_ctx* c, DevBuf& d_jobs, const std::vector<LinkRound*>& rounds, c
             for (size_t b = 0; b < bailed.size(); ++b) hj[bailed[b]] = fj[b];
         }
     }
-    if (dbg_on) { long long h[8]; VMX_TRY(download(h, d_dbg.p, 8, c->stream)); VMX_HIP(vmx_stream_sync(c));
+    if (dbg_on) { long long h[8]; VMX_TRY(download(h, d_dbg, 8, c->stream)); VMX_HIP(vmx_stream_sync(c));
                   fprintf(stderr, "[asm] linked DP so far: %lld anchors, %lld insertions through HBM, %lld scan blocks past the window, %lld position advances, %lld candidates\n", h[0], h[1], h[2], h[3], h[4]); }
     for (size_t i = 0; i < nj; ++i) {
         const int r = rounds[i]->finish(hj[i], hs[i], *news[i]);
@@ -266,8 +264,6 @@ int run_jobs(vm_ctx* c, DevBuf& d_jobs, const std::vector<LinkRound*>& rounds, c
 
 struct SeedBufs {
     DevBuf guide, glen, ngu, aoff, order, head, epoch, next, sq, dst, hkey, hkey2, hval, hq, goff, pcnt, pc2, stg, gkey, gq, gr, la_rows, la_ekey, la_sorted, la_off, la_cnt, status, rdoff, rdlen, rst, ren;
-    SeedBufs() = default; SeedBufs(const SeedBufs&) = delete;
-    ~SeedBufs() { for (DevBuf* b : {&guide, &glen, &ngu, &aoff, &order, &head, &epoch, &next, &sq, &dst, &hkey, &hkey2, &hval, &hq, &goff, &pcnt, &pc2, &stg, &gkey, &gq, &gr, &la_rows, &la_ekey, &la_sorted, &la_off, &la_cnt, &status, &rdoff, &rdlen, &rst, &ren}) b->release(); }
 };
 
 struct Tuple { int64_t st_read, en_read, lo, hi; };
@@ -393,7 +389,7 @@ static int second_round_seed_once(vm_ctx* c, const vm_index_view& ix, int k, con
 namespace {
 
 // one_mapinfo[np.argsort(one_mapinfo[:, 0])] (:22431, stable) on the device: radix sort of (read position, index) pairs, gather, back to the host copy
-struct SortBufs { DevBuf in, out, k0, k1, v0, v1, tmp; SortBufs() = default; SortBufs(const SortBufs&) = delete; ~SortBufs() { for (DevBuf* b : {&in, &out, &k0, &k1, &v0, &v1, &tmp}) b->release(); } };
+struct SortBufs { DevBuf in, out, k0, k1, v0, v1, tmp; };
 int device_sort_by_q(vm_ctx* c, SortBufs& B, std::vector<vmx_anchor>& rows) {
     const size_t n = rows.size();
     if (n < 2) return 0;
@@ -424,8 +420,6 @@ struct LongContig {
     std::vector<Tuple> tuples;
     DevBuf d_codes;
     vm_record* recs = nullptr; int64_t n_recs = 0; char* blob = nullptr;
-    LongContig() = default; LongContig(const LongContig&) = delete;
-    ~LongContig() { d_codes.release(); }
     void fail(int st) { status = st; done = true; }
 };
 
@@ -437,7 +431,7 @@ int asm_long_group(vm_ctx* c, const vm_index* mi, const vm_params* prm, std::vec
     auto now_s = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double t_mark = now_s(), t_seed = 0, t_dp1 = 0, t_seed2 = 0, t_dp2 = 0, t_ext = 0; int64_t n_a1 = 0, n_a2 = 0, bases = 0;
     auto lap = [&](double& acc) { const double t = now_s(); acc += t - t_mark; t_mark = t; };
-    DevBuf d_jobs; struct RelJ { DevBuf* a; ~RelJ() { a->release(); } } relj{&d_jobs};
+    DevBuf d_jobs;
     SortBufs sortb;
     // ---- first round :23214-23292: the batches of every contig (yield_mapinfo :22411-22443)
     for (LongContig* Cn : G) {
@@ -516,7 +510,7 @@ int asm_long_group(vm_ctx* c, const vm_index* mi, const vm_params* prm, std::vec
         if (C.done) continue;
         VMX_TRY(C.r2.init(c, 1, k2, prm->local_skipcost, prm->local_maxdiff, 99));
         {
-            DevBuf d_raw; struct Rel { DevBuf* a; ~Rel() { a->release(); } } rel{&d_raw};
+            DevBuf d_raw;
             VMX_TRY(upload(d_raw, C.seq.data(), (size_t)C.len, c->stream)); VMX_TRY(C.d_codes.reserve((size_t)C.len + 64));
             const char* dr = d_raw.as<char>(); uint8_t* dc = C.d_codes.as<uint8_t>(); const int64_t nn = C.len; hipStream_t stq = c->stream;
             hipLaunchKernelGGL(k_encode, dim3((unsigned)std::min<int64_t>((nn + 255) / 256, 65535)), dim3(256), 0, stq, dr, dc, nn);
@@ -577,14 +571,14 @@ int asm_long_group(vm_ctx* c, const vm_index* mi, const vm_params* prm, std::vec
         const int64_t nx = (int64_t)X.size();
         std::vector<int64_t> h_off((size_t)nx + 1, 0);
         for (int64_t i = 0; i < nx; ++i) h_off[(size_t)i + 1] = h_off[(size_t)i] + X[(size_t)i]->len;
-        DevBuf d_off, d_all; struct Rel1 { DevBuf *a, *b; ~Rel1() { a->release(); b->release(); } } rel1{&d_off, &d_all};
+        DevBuf d_off, d_all;
         VMX_TRY(upload(d_off, h_off.data(), (size_t)nx + 1, c->stream));
         const uint8_t* codes = X[0]->d_codes.as<uint8_t>();
         if (nx > 1) {
             VMX_TRY(d_all.reserve((size_t)h_off[(size_t)nx] + 64));
             for (int64_t i = 0; i < nx; ++i) VMX_HIP(hipMemcpyAsync(d_all.as<uint8_t>() + h_off[(size_t)i], X[(size_t)i]->d_codes.p, (size_t)X[(size_t)i]->len, hipMemcpyDeviceToDevice, c->stream));
             VMX_HIP(vmx_stream_sync(c));
-            for (int64_t i = 0; i < nx; ++i) X[(size_t)i]->d_codes.release();
+            for (int64_t i = 0; i < nx; ++i) X[(size_t)i]->d_codes.release();      // early: the contigs now lie side by side in d_all; their own copies make room for the extend stage's pools
             codes = d_all.as<uint8_t>();
         }
         std::vector<vmx_preset> ps((size_t)nx);
@@ -603,7 +597,7 @@ int asm_long_group(vm_ctx* c, const vm_index* mi, const vm_params* prm, std::vec
                 y.cigar_off = (int64_t)bo; bo += (size_t)r0[x].cigar_len + 1; C.recs[w++] = y;
             }
             C.n_recs = cnt; C.status = st[(size_t)i]; C.done = true;
-            C.d_codes.release();
+            C.d_codes.release();       // early: a finished contig's codes make room for the groups that follow
         }
         free(r0); free(cb);
     }

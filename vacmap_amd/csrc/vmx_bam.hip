@@ -5,7 +5,7 @@
 // errors, compressed size) and the few float tokens the device cannot convert exactly (vmx_bam_patch).
 #include "vmx_host.h"
 #include "vmx_bam.h"
-#include "vmx_index_prim.h"
+#include "vmx_index_priv.h"
 #include <fcntl.h>
 #include <unistd.h>
 #include <algorithm>
@@ -22,23 +22,6 @@ using namespace vmx;
 namespace {
 
 struct BgzfBufs { DevBuf slots, msize, match, prev, out; };
-
-// grow-only page-locked buffer with head-room. An outgrown buffer is parked, not freed: hipHostFree waits for the whole device (the aligner
-// contexts' batches included), so the parked ones go when the writer does, as DevBuf parks its outgrown device buffers
-struct HostPinned {
-    char* p = nullptr; size_t cap = 0;
-    std::vector<char*> parked;
-    int reserve(size_t n) {
-        if (n <= cap && p) return 0;
-        if (p) parked.push_back(p);
-        p = nullptr; cap = 0;
-        const size_t want = n + n / 2 + 4096;
-        if (hipHostMalloc((void**)&p, want, 0) != hipSuccess) { p = nullptr; set_error("page-locked host allocation failed"); return VM_ERR_OOM; }
-        cap = want;
-        return 0;
-    }
-    ~HostPinned() { for (char* q : parked) (void)hipHostFree(q); if (p) (void)hipHostFree(p); }
-};
 
 // vm_blob_gather_parts by several threads (one memcpy stream runs at a few GB/s: a window's text is hundreds of MB)
 int64_t gather_parts_mt(const char* const* blobs, const int64_t* const* offs, const int32_t* part, const int64_t* idx, int64_t n, char* out) {
@@ -255,9 +238,6 @@ int vm_bam_writer_create(vm_ctx* c, const char* sam_header, int64_t len, vm_bam_
 void vm_bam_writer_free(vm_bam_writer* w) {
     if (!w) return;
     (void)hipStreamSynchronize(w->c->stream);
-    DevBuf* bufs[] = {&w->d_names, &w->d_off, &w->d_htab, &w->d_text, &w->d_cnt, &w->d_nl, &w->d_rsz, &w->d_rec, &w->d_st, &w->d_patch, &w->d_poff, &w->d_pval,
-                      &w->z.slots, &w->z.msize, &w->z.match, &w->z.prev, &w->z.out};
-    for (DevBuf* b : bufs) b->release();
     delete w;
 }
 
@@ -315,8 +295,6 @@ int vm_bgzf_compress(vm_ctx* c, const void* in, int64_t n, char** out, int64_t* 
     if (rc == 0 && n && hipMemcpyAsync(d_in.p, in, (size_t)n, hipMemcpyHostToDevice, c->stream) != hipSuccess) { set_error("vm_bgzf_compress: upload failed"); rc = VM_ERR_HIP; }
     if (rc == 0) rc = bgzf_run(c, z, pin, d_in.p, n, out, n_out);
     (void)hipStreamSynchronize(c->stream);
-    DevBuf* bufs[] = {&d_in, &z.slots, &z.msize, &z.match, &z.prev, &z.out};
-    for (DevBuf* b : bufs) b->release();
     return rc;
 }
 
@@ -328,7 +306,6 @@ int vm_bgzf_compress(vm_ctx* c, const void* in, int64_t n, char** out, int64_t* 
 // more with the value run << 40 | index and cuts the result into chunks; vm_bam_sorter_chunk reads one contiguous range per run, gathers
 // the chunk in global order, compresses it and records the index entries; vm_bam_sorter_index reduces them to the CSI.
 
-#define VMX_PRIM_TRY(expr) do { int _e = (expr); if (_e != 0) return vmx::hip_fail((hipError_t)_e, #expr, __FILE__, __LINE__); } while (0)
 
 struct vm_bam_sorter {
     vm_bam_writer* w = nullptr;
@@ -354,17 +331,9 @@ namespace {
 
 int prim_sort64(vm_ctx* c, DevBuf& tmp, const uint64_t* kin, uint64_t* kout, const uint64_t* vin, uint64_t* vout, size_t n) {
     size_t tb = 0;
-    VMX_PRIM_TRY(vmx_prim_sort_pairs_u64(nullptr, &tb, kin, kout, vin, vout, n, 64, c->stream));
+    VMX_PRIM(vmx_prim_sort_pairs_u64(nullptr, &tb, kin, kout, vin, vout, n, 64, c->stream));
     VMX_TRY(tmp.reserve(tb ? tb : 8));
-    VMX_PRIM_TRY(vmx_prim_sort_pairs_u64(tmp.p, &tb, kin, kout, vin, vout, n, 64, c->stream));
-    return 0;
-}
-
-int prim_scan64(vm_ctx* c, DevBuf& tmp, const int64_t* in, int64_t* out, size_t n) {
-    size_t tb = 0;
-    VMX_PRIM_TRY(vmx_prim_excl_scan_i64(nullptr, &tb, in, out, n, c->stream));
-    VMX_TRY(tmp.reserve(tb ? tb : 8));
-    VMX_PRIM_TRY(vmx_prim_excl_scan_i64(tmp.p, &tb, in, out, n, c->stream));
+    VMX_PRIM(vmx_prim_sort_pairs_u64(tmp.p, &tb, kin, kout, vin, vout, n, 64, c->stream));
     return 0;
 }
 
@@ -423,10 +392,6 @@ void vm_bam_sorter_free(vm_bam_sorter* s) {
     if (s->pre_k >= 0) (void)s->pre.get();
     (void)hipStreamSynchronize(s->w->c->stream);
     for (int fd : s->fds) if (fd >= 0) close(fd);
-    DevBuf* bufs[] = {&s->d_k0, &s->d_k1, &s->d_v0, &s->d_v1, &s->d_tmp, &s->d_ssz, &s->d_soff, &s->d_so, &s->d_out, &s->d_gval, &s->d_goff, &s->d_roff_all, &s->d_rstart,
-                      &s->d_cut, &s->d_cutoff, &s->d_rmax, &s->d_sbase, &s->d_stage, &s->d_chunk, &s->e_key, &s->e_vbeg, &s->e_vend, &s->e_beg, &s->e_end, &s->e_unm,
-                      &s->d_ckey, &s->d_cbeg, &s->d_cend, &s->d_cloff, &s->d_wbase, &s->d_lin, &s->d_rbeg, &s->d_rend, &s->d_cnt};
-    for (DevBuf* b : bufs) b->release();
     delete s;
 }
 
@@ -456,7 +421,7 @@ int vm_bam_sorter_add_parts(vm_bam_sorter* s, const char* const* blobs, const in
     VMX_TRY(prim_sort64(c, s->d_tmp, s->d_k0.as<const uint64_t>(), s->d_k1.as<uint64_t>(), s->d_v0.as<const uint64_t>(), s->d_v1.as<uint64_t>(), (size_t)m));
     hipLaunchKernelGGL(k_bam_sort_sizes, dim3(grid256(m + 1)), dim3(256), 0, c->stream, w->d_rsz.as<const int64_t>(), s->d_v1.as<const uint64_t>(), m, s->d_ssz.as<int64_t>(),
                        s->d_so.as<int64_t>());
-    VMX_TRY(prim_scan64(c, s->d_tmp, s->d_ssz.as<const int64_t>(), s->d_soff.as<int64_t>(), (size_t)m + 1));
+    VMX_TRY(vmx_scan64(c, s->d_tmp, s->d_ssz.as<const int64_t>(), s->d_soff.as<int64_t>(), (size_t)m + 1));
     hipLaunchKernelGGL(k_bam_gather, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, c->stream, w->d_rec.as<const uint8_t>(), s->d_so.as<const int64_t>(),
                        s->d_soff.as<const int64_t>(), (int64_t)0, s->d_out.as<uint8_t>(), m);
     VMX_TRY(w->pin.reserve((size_t)nr));
@@ -506,7 +471,7 @@ int vm_bam_sorter_plan(vm_bam_sorter* s, const char* const* run_paths, int64_t n
     VMX_TRY(prim_sort64(c, s->d_tmp, s->d_k0.as<const uint64_t>(), s->d_k1.as<uint64_t>(), s->d_v0.as<const uint64_t>(), s->d_gval.as<uint64_t>(), (size_t)n));
     hipLaunchKernelGGL(k_bam_merge_sizes, dim3(grid256(n + 1)), dim3(256), 0, c->stream, s->d_gval.as<const uint64_t>(), s->d_roff_all.as<const int64_t>(),
                        s->d_rstart.as<const int64_t>(), n, s->d_ssz.as<int64_t>());
-    VMX_TRY(prim_scan64(c, s->d_tmp, s->d_ssz.as<const int64_t>(), s->d_goff.as<int64_t>(), (size_t)n + 1));
+    VMX_TRY(vmx_scan64(c, s->d_tmp, s->d_ssz.as<const int64_t>(), s->d_goff.as<int64_t>(), (size_t)n + 1));
     VMX_HIP(hipMemcpyAsync(&s->total, s->d_goff.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, c->stream));
     VMX_TRY(sync(c));                                                // (also: K, R and rstart have been read)
     const int64_t nch = s->n_chunks = (s->total + s->chunk_bytes - 1) / s->chunk_bytes;
@@ -592,7 +557,7 @@ int vm_bam_sorter_index(vm_bam_sorter* s, char** out, int64_t* n_out) {
         VMX_TRY(prim_sort64(c, s->d_tmp, s->e_key.as<const uint64_t>(), s->d_k1.as<uint64_t>(), s->d_v0.as<const uint64_t>(), s->d_v1.as<uint64_t>(), (size_t)n));
         hipLaunchKernelGGL(k_csi_flags, dim3(grid256(n + 1)), dim3(256), 0, c->stream, s->d_k1.as<const uint64_t>(), s->d_v1.as<const uint64_t>(),
                            s->e_vbeg.as<const uint64_t>(), s->e_vend.as<const uint64_t>(), n, s->d_ssz.as<int64_t>());
-        VMX_TRY(prim_scan64(c, s->d_tmp, s->d_ssz.as<const int64_t>(), s->d_soff.as<int64_t>(), (size_t)n + 1));
+        VMX_TRY(vmx_scan64(c, s->d_tmp, s->d_ssz.as<const int64_t>(), s->d_soff.as<int64_t>(), (size_t)n + 1));
         int64_t nc = 0;
         VMX_HIP(hipMemcpyAsync(&nc, s->d_soff.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, c->stream));
         VMX_TRY(sync(c));
@@ -848,16 +813,6 @@ int parse_bam_header(const uint8_t* h, int64_t n, int64_t* end) {
     return 1;
 }
 
-int prim_scan64_in(vm_ctx* c, DevBuf& tmp, const int64_t* in, int64_t* out, size_t n) {
-    size_t tb = 0;
-    int e = vmx_prim_excl_scan_i64(nullptr, &tb, in, out, n, c->stream);
-    if (e != 0) return vmx::hip_fail((hipError_t)e, "scan", __FILE__, __LINE__);
-    VMX_TRY(tmp.reserve(tb ? tb : 8));
-    e = vmx_prim_excl_scan_i64(tmp.p, &tb, in, out, n, c->stream);
-    if (e != 0) return vmx::hip_fail((hipError_t)e, "scan", __FILE__, __LINE__);
-    return 0;
-}
-
 // the next window into win[slot]: 1 (its records decoded, possibly none), 0 at the end of the file, or a negative status
 int bam_in_window(vm_bam_reader* r, int slot) {
     vm_ctx* c = r->c;
@@ -929,7 +884,7 @@ int bam_in_window(vm_bam_reader* r, int slot) {
     VMX_TRY(r->d_sz.reserve(col * 8 * 4)); VMX_TRY(r->d_off.reserve(col * 8 * 4)); VMX_TRY(r->d_ooff.reserve(col * 8 * 3));
     int64_t* sz = r->d_sz.as<int64_t>(); int64_t* off = r->d_off.as<int64_t>(); int64_t* oo = r->d_ooff.as<int64_t>();
     hipLaunchKernelGGL(k_bam_in_sizes, dim3(grid256(n + 1)), dim3(256), 0, c->stream, dst.as<const uint8_t>(), r->d_roff.as<const int64_t>(), n, sz, sz + col, sz + 2 * col, sz + 3 * col);
-    for (int j = 0; j < 4; ++j) VMX_TRY(prim_scan64_in(c, r->d_tmp, sz + j * col, off + j * col, col));
+    for (int j = 0; j < 4; ++j) VMX_TRY(vmx_scan64(c, r->d_tmp, sz + j * col, off + j * col, col));
     int64_t* tot = (int64_t*)r->pin.p;
     for (int j = 0; j < 4; ++j) VMX_HIP(hipMemcpyAsync(tot + j, off + j * col + n, 8, hipMemcpyDeviceToHost, c->stream));
     const unsigned aux_grid = (unsigned)((n + 1 + 3) / 4);
@@ -939,7 +894,7 @@ int bam_in_window(vm_bam_reader* r, int slot) {
         VMX_HIP(hipMemsetAsync(r->d_aux.as<uint8_t>() + 8, 0, 8, c->stream));
         hipLaunchKernelGGL(k_bam_in_aux_size, dim3(aux_grid), dim3(256), 0, c->stream, dst.as<const uint8_t>(), r->d_roff.as<const int64_t>(), n, r->d_sel.as<const uint16_t>(),
                            (int)r->tags.size(), r->tags_all, r->d_csz.as<int64_t>(), r->d_aux.as<unsigned long long>(), r->d_aux.as<unsigned long long>() + 1);
-        VMX_TRY(prim_scan64_in(c, r->d_tmp, r->d_csz.as<const int64_t>(), r->d_coff.as<int64_t>(), col));
+        VMX_TRY(vmx_scan64(c, r->d_tmp, r->d_csz.as<const int64_t>(), r->d_coff.as<int64_t>(), col));
         VMX_HIP(hipMemcpyAsync(tot + 4, r->d_coff.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, c->stream));
         VMX_HIP(hipMemcpyAsync(tot + 5, r->d_aux.p, 16, hipMemcpyDeviceToHost, c->stream));
     }
@@ -1028,8 +983,6 @@ int vm_bgzf_decompress(vm_ctx* c, const void* in, int64_t n, char** out, int64_t
     if (rc == 0 && !(res = (char*)malloc((size_t)T.inflated + 1))) { set_error("out of host memory"); rc = VM_ERR_OOM; }
     if (rc == 0 && T.inflated && hipMemcpy(res, d_out.p, (size_t)T.inflated, hipMemcpyDeviceToHost) != hipSuccess) { set_error("vm_bgzf_decompress: download failed"); rc = VM_ERR_HIP; }
     (void)hipStreamSynchronize(c->stream);
-    DevBuf* bufs[] = {&d_out, &z.comp, &z.tab, &z.key};
-    for (DevBuf* b : bufs) b->release();
     if (rc < 0) { free(res); return rc; }
     *out = res; *n_out = T.inflated;
     return 0;
@@ -1041,8 +994,6 @@ void vm_bam_reader_close(vm_bam_reader* r) {
     if (r->pre_on) r->pre.get();
     (void)hipStreamSynchronize(r->c->stream);
     if (r->fd >= 0) close(r->fd);
-    DevBuf* bufs[] = {&r->z.comp, &r->z.tab, &r->z.key, &r->d_inf[0], &r->d_inf[1], &r->d_roff, &r->d_walk, &r->d_sz, &r->d_off, &r->d_tmp, &r->d_names, &r->d_seqs, &r->d_quals, &r->d_ooff, &r->d_sel, &r->d_csz, &r->d_coff, &r->d_comments, &r->d_ocoff, &r->d_aux};
-    for (DevBuf* b : bufs) b->release();
     delete r;
 }
 

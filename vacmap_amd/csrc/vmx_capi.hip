@@ -4,6 +4,7 @@
 #include <time.h>
 #include "vmx_select.h"
 #include "vmx_stage.h"
+#include "vmx_sam_dev.h"
 #include "vmx_round.h"
 #include <algorithm>
 #include <cmath>
@@ -21,9 +22,6 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line) {
 }  // namespace vmx
 using namespace vmx;
 
-void vmx_ctx_free_local_bufs(vm_ctx* c);    // vmx_stage_local.hip
-void vmx_ctx_free_batch_bufs(vm_ctx* c);    // vmx_align.hip
-void vmx_ctx_free_sam_bufs(vm_ctx* c);      // vmx_sam_dev.hip
 
 static inline int grid_for(const vm_ctx* c, int64_t n_items, int per_cu = 8) {
     int64_t g = std::min<int64_t>(n_items, (int64_t)c->num_cu * per_cu);
@@ -138,6 +136,29 @@ static void mailbox_destroy(vm_ctx* c) {
     if (m.big) (void)hipHostFree(m.big);
     if (m.done_ctr) (void)hipFree(m.done_ctr);
     m = vmx_mailbox();
+}
+#ifdef VMX_CF_TICKS
+extern "C" void vmx_cf_ticks_dump();
+#endif
+// The one way a context ends (vm_ctx_destroy, and vm_ctx_create when it fails half way: what was not created yet is null), in this order: the stream is drained,
+// every buffer of the context goes back, the parked allocations follow, and only then the events, the streams and the mailbox go.
+static void ctx_teardown(vm_ctx* c) {
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+#ifdef VMX_CF_TICKS
+    vmx_cf_ticks_dump();
+#endif
+    delete c->xbufs; delete c->lbufs; delete c->bbufs; delete c->sbufs;
+    c->tab_buf.release();
+    vmx::devbuf_retired().flush();
+    for (hipEvent_t e : c->ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->gev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->kev) if (e) (void)hipEventDestroy(e);
+    for (int i = 0; i < 4; ++i) { if (c->aux[i]) { (void)hipStreamSynchronize(c->aux[i]); (void)hipStreamDestroy(c->aux[i]); } if (c->join_ev[i]) (void)hipEventDestroy(c->join_ev[i]); }
+    if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
+    if (c->low) { (void)hipStreamSynchronize(c->low); (void)hipStreamDestroy(c->low); (void)hipEventDestroy(c->low_ev[0]); (void)hipEventDestroy(c->low_ev[1]); }
+    if (c->stream) (void)hipStreamDestroy(c->stream);
+    mailbox_destroy(c);
+    delete c;
 }
 int vmx_mailbox_wait(vm_ctx* c) {
     vmx_mailbox& m = c->mb;
@@ -256,7 +277,7 @@ int vm_ctx_create(int device_id, vm_ctx** out) {
     if (hipGetDeviceProperties(&prop, device_id) == hipSuccess && prop.multiProcessorCount > 0) c->num_cu = prop.multiProcessorCount;
     int prio_least = 0, prio_greatest = 0;
     const bool prio = vmx_stream_prio_on() && hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) == hipSuccess && prio_least != prio_greatest;
-    if ((prio ? hipStreamCreateWithPriority(&c->stream, hipStreamDefault, prio_greatest) : hipStreamCreate(&c->stream)) != hipSuccess) { delete c; set_error("hipStreamCreate failed"); return VM_ERR_HIP; }
+    if ((prio ? hipStreamCreateWithPriority(&c->stream, hipStreamDefault, prio_greatest) : hipStreamCreate(&c->stream)) != hipSuccess) { ctx_teardown(c); set_error("hipStreamCreate failed"); return VM_ERR_HIP; }
     if (prio && hipStreamCreateWithPriority(&c->low, hipStreamDefault, prio_least) == hipSuccess) { (void)hipEventCreateWithFlags(&c->low_ev[0], hipEventDisableTiming); (void)hipEventCreateWithFlags(&c->low_ev[1], hipEventDisableTiming); }
     else c->low = nullptr;
     for (int i = 0; i < 24; ++i) (void)hipEventCreate(&c->ev[i]);
@@ -273,8 +294,8 @@ int vm_ctx_create(int device_id, vm_ctx** out) {
     memcpy(&blob[o_extra], T.extra.data(), T.extra.size() * 4);
     memcpy(&blob[o_rh], T.readgap_h.data(), 400); memcpy(&blob[o_rr], T.readgap_r.data(), 400); memcpy(&blob[o_lr], T.large_readgap.data(), 400);
     memcpy(&blob[o_l2c], T.log2cache.data(), T.log2cache.size() * 8); memcpy(&blob[o_l2i], T.log2int.data(), T.log2int.size() * 8);
-    if (c->tab_buf.reserve(tot) < 0) { delete c; return VM_ERR_OOM; }
-    if (hipMemcpy(c->tab_buf.p, blob.data(), tot, hipMemcpyHostToDevice) != hipSuccess) { delete c; set_error("table upload failed"); return VM_ERR_HIP; }
+    if (c->tab_buf.reserve(tot) < 0) { ctx_teardown(c); return VM_ERR_OOM; }
+    if (hipMemcpy(c->tab_buf.p, blob.data(), tot, hipMemcpyHostToDevice) != hipSuccess) { ctx_teardown(c); set_error("table upload failed"); return VM_ERR_HIP; }
     char* base = (char*)c->tab_buf.p;
     c->tables.extra = (const float*)(base + o_extra); c->tables.extra_n = (int)T.extra.size();
     c->tables.readgap_h = (const float*)(base + o_rh); c->tables.readgap_r = (const float*)(base + o_rr);
@@ -290,38 +311,16 @@ int vm_ctx_create(int device_id, vm_ctx** out) {
             if (memcmp(&v, &T.extra[an], 4) != 0) break;
         }
         c->tables.extra_arith_n = an;
-        if (T.extra.back() != 36.0f) { delete c; set_error("cost table `extra` does not end at 36.0"); return VM_ERR_UNSUPPORTED; }
+        if (T.extra.back() != 36.0f) { ctx_teardown(c); set_error("cost table `extra` does not end at 36.0"); return VM_ERR_UNSUPPORTED; }
     }
     *out = c;
     return VM_OK;
 }
 
-#ifdef VMX_CF_TICKS
-extern "C" void vmx_cf_ticks_dump();
-#endif
 void vm_ctx_destroy(vm_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-#ifdef VMX_CF_TICKS
-    vmx_cf_ticks_dump();
-#endif
-    for (int i = 0; i < VMX_NBUF; ++i) c->b[i].release();
-    vmx_ctx_free_local_bufs(c);
-    vmx_ctx_free_batch_bufs(c);
-    vmx_ctx_free_sam_bufs(c);
-    c->tab_buf.release();
-    vmx::devbuf_retired().flush();
-    for (int i = 0; i < 24; ++i) (void)hipEventDestroy(c->ev[i]);
-    for (int i = 0; i < 48; ++i) (void)hipEventDestroy(c->gev[i]);
-    for (int i = 0; i < 4; ++i) (void)hipEventDestroy(c->kev[i]);
-    for (int i = 0; i < 4; ++i) { (void)hipStreamSynchronize(c->aux[i]); (void)hipStreamDestroy(c->aux[i]); (void)hipEventDestroy(c->join_ev[i]); }
-    (void)hipEventDestroy(c->fork_ev);
-    if (c->sync_ev) (void)hipEventDestroy(c->sync_ev);
-    if (c->low) { (void)hipStreamSynchronize(c->low); (void)hipStreamDestroy(c->low); (void)hipEventDestroy(c->low_ev[0]); (void)hipEventDestroy(c->low_ev[1]); }
-    (void)hipStreamDestroy(c->stream);
-    mailbox_destroy(c);
-    delete c;
+    ctx_teardown(c);
 }
 
 int vm_ctx_set_inflight(vm_ctx* c, int n_contexts) {
@@ -372,6 +371,8 @@ int64_t vm_table(vm_ctx* c, int which, void** data) {
 
 }  // extern "C"
 
+vmx_entry_bufs* vmx_ctx_entry_bufs(vm_ctx* c) { if (!c->xbufs) c->xbufs = new vmx_entry_bufs(); return c->xbufs; }
+
 // upload concatenated ASCII + encode to codes in buf_codes; offsets uploaded to buf_off
 static int upload_encode(vm_ctx* c, const char* s, const int64_t* off, int64_t n, DevBuf& raw, DevBuf& codes, DevBuf& doff) {
     const int64_t tot = off[n];
@@ -388,27 +389,28 @@ int vm_edit_distance_batch(vm_ctx* c, int64_t n, const char* q, const int64_t* q
     if (!c) { set_error("no context"); return VM_ERR_NO_CTX; }
     *dist = nullptr;
     VMX_HIP(hipSetDevice(c->device));
-    VMX_TRY(upload_encode(c, q, q_off, n, c->b[0], c->b[1], c->b[2]));
-    VMX_TRY(upload_encode(c, t, t_off, n, c->b[3], c->b[4], c->b[5]));
-    VMX_TRY(c->b[6].reserve((size_t)VMX_ED_WAVES * (size_t)t_off[n] + 64));     // carry ring: VMX_ED_WAVES x one int8 per text column
-    VMX_TRY(c->b[7].reserve(sizeof(int64_t) * (size_t)(n + 1)));
+    vmx_entry_bufs& X = *vmx_ctx_entry_bufs(c);
+    VMX_TRY(upload_encode(c, q, q_off, n, X.a.raw, X.a.codes, X.a.off));
+    VMX_TRY(upload_encode(c, t, t_off, n, X.b.raw, X.b.codes, X.b.off));
+    VMX_TRY(X.pool.reserve((size_t)VMX_ED_WAVES * (size_t)t_off[n] + 64));     // carry ring: VMX_ED_WAVES x one int8 per text column
+    VMX_TRY(X.out.reserve(sizeof(int64_t) * (size_t)(n + 1)));
     if (n) {
         // longest-first device work queue; long patterns (> 4 passes) on 16-wave workgroups, the rest on 4-wave workgroups
         std::vector<int64_t> sz((size_t)n); for (int64_t i = 0; i < n; ++i) sz[i] = q_off[i + 1] - q_off[i];
         int32_t nn = (int32_t)n;
-        VMX_TRY(upload(c->b[8], sz.data(), (size_t)n, c->stream)); VMX_TRY(upload(c->b[9], &nn, 1, c->stream));
-        VMX_TRY(c->b[10].reserve(4 * (size_t)(n + 1))); VMX_TRY(c->b[11].reserve(64));
-        int32_t* d_range = c->b[11].as<int32_t>(); int32_t* d_cnt = d_range + 4;
+        VMX_TRY(upload(X.sizes, sz.data(), (size_t)n, c->stream)); VMX_TRY(upload(X.count, &nn, 1, c->stream));
+        VMX_TRY(X.order.reserve(4 * (size_t)(n + 1))); VMX_TRY(X.range.reserve(64));
+        int32_t* d_range = X.range.as<int32_t>(); int32_t* d_cnt = d_range + 4;
         int64_t thresh = VMX_ED_LONG;
         if (const char* e = getenv("VMX_ED_LONG")) thresh = atoll(e);      // test knob: exercise the 16-wave launch with short patterns
-        hipLaunchKernelGGL(k_size_order, dim3(1), dim3(1024), 0, c->stream, c->b[8].as<int64_t>(), c->b[9].as<int32_t>(), thresh, c->b[10].as<int32_t>(), d_range, d_cnt);
+        hipLaunchKernelGGL(k_size_order, dim3(1), dim3(1024), 0, c->stream, X.sizes.as<int64_t>(), X.count.as<int32_t>(), thresh, X.order.as<int32_t>(), d_range, d_cnt);
         for (int which = 0; which < 2; ++which)
-            hipLaunchKernelGGL(k_edit_distance, dim3(grid_for(c, n, which == 0 ? 2 : 8)), dim3(which == 0 ? 64 * VMX_ED_WAVES : 256), 0, c->stream, c->b[1].as<uint8_t>(),
-                               c->b[2].as<int64_t>(), c->b[4].as<uint8_t>(), c->b[5].as<int64_t>(), c->b[6].as<int8_t>(), c->b[10].as<int32_t>(), d_range, d_cnt, which,
-                               c->b[7].as<int64_t>(), (int64_t)0, (int32_t*)nullptr);
+            hipLaunchKernelGGL(k_edit_distance, dim3(grid_for(c, n, which == 0 ? 2 : 8)), dim3(which == 0 ? 64 * VMX_ED_WAVES : 256), 0, c->stream, X.a.codes.as<uint8_t>(),
+                               X.a.off.as<int64_t>(), X.b.codes.as<uint8_t>(), X.b.off.as<int64_t>(), X.pool.as<int8_t>(), X.order.as<int32_t>(), d_range, d_cnt, which,
+                               X.out.as<int64_t>(), (int64_t)0, (int32_t*)nullptr);
     }
     *dist = host_alloc<int64_t>((size_t)n);
-    VMX_TRY(download(*dist, c->b[7].p, (size_t)n, c->stream));
+    VMX_TRY(download(*dist, X.out.p, (size_t)n, c->stream));
     VMX_HIP(hipStreamSynchronize(c->stream));
     VMX_HIP(hipGetLastError());
     return VM_OK;
@@ -418,25 +420,26 @@ int vm_edit_distance_bound_batch(vm_ctx* c, int tier, int64_t n, const char* q, 
     if (!c) { set_error("no context"); return VM_ERR_NO_CTX; }
     *bound = nullptr;
     VMX_HIP(hipSetDevice(c->device));
-    VMX_TRY(upload_encode(c, q, q_off, n, c->b[0], c->b[1], c->b[2]));
-    VMX_TRY(upload_encode(c, t, t_off, n, c->b[3], c->b[4], c->b[5]));
-    VMX_TRY(c->b[7].reserve(sizeof(int64_t) * (size_t)(n + 1)));
+    vmx_entry_bufs& X = *vmx_ctx_entry_bufs(c);
+    VMX_TRY(upload_encode(c, q, q_off, n, X.a.raw, X.a.codes, X.a.off));
+    VMX_TRY(upload_encode(c, t, t_off, n, X.b.raw, X.b.codes, X.b.off));
+    VMX_TRY(X.out.reserve(sizeof(int64_t) * (size_t)(n + 1)));
     if (n) {
         std::vector<int64_t> sz((size_t)n); for (int64_t i = 0; i < n; ++i) sz[i] = q_off[i + 1] - q_off[i];
         int32_t nn = (int32_t)n;
-        VMX_TRY(upload(c->b[8], sz.data(), (size_t)n, c->stream)); VMX_TRY(upload(c->b[9], &nn, 1, c->stream));
-        VMX_TRY(c->b[10].reserve(4 * (size_t)(n + 1))); VMX_TRY(c->b[11].reserve(64));
-        int32_t* d_range = c->b[11].as<int32_t>(); int32_t* d_cnt = d_range + 4;
-        hipLaunchKernelGGL(k_size_order, dim3(1), dim3(1024), 0, c->stream, c->b[8].as<int64_t>(), c->b[9].as<int32_t>(), (int64_t)0, c->b[10].as<int32_t>(), d_range, d_cnt);
+        VMX_TRY(upload(X.sizes, sz.data(), (size_t)n, c->stream)); VMX_TRY(upload(X.count, &nn, 1, c->stream));
+        VMX_TRY(X.order.reserve(4 * (size_t)(n + 1))); VMX_TRY(X.range.reserve(64));
+        int32_t* d_range = X.range.as<int32_t>(); int32_t* d_cnt = d_range + 4;
+        hipLaunchKernelGGL(k_size_order, dim3(1), dim3(1024), 0, c->stream, X.sizes.as<int64_t>(), X.count.as<int32_t>(), (int64_t)0, X.order.as<int32_t>(), d_range, d_cnt);
         if (tier == 1)
-            hipLaunchKernelGGL(k_ed_banded4, dim3(grid_for(c, (n + 3) / 4, 16)), dim3(64), 0, c->stream, c->b[1].as<uint8_t>(), c->b[2].as<int64_t>(), c->b[4].as<uint8_t>(),
-                               c->b[5].as<int64_t>(), c->b[10].as<int32_t>(), d_range, d_cnt, c->b[7].as<int64_t>());
+            hipLaunchKernelGGL(k_ed_banded4, dim3(grid_for(c, (n + 3) / 4, 16)), dim3(64), 0, c->stream, X.a.codes.as<uint8_t>(), X.a.off.as<int64_t>(), X.b.codes.as<uint8_t>(),
+                               X.b.off.as<int64_t>(), X.order.as<int32_t>(), d_range, d_cnt, X.out.as<int64_t>());
         else
-            hipLaunchKernelGGL(k_ed_banded, dim3(grid_for(c, n, 16)), dim3(64), 0, c->stream, c->b[1].as<uint8_t>(), c->b[2].as<int64_t>(), c->b[4].as<uint8_t>(), c->b[5].as<int64_t>(),
-                               c->b[10].as<int32_t>(), d_range, d_cnt, c->b[7].as<int64_t>());
+            hipLaunchKernelGGL(k_ed_banded, dim3(grid_for(c, n, 16)), dim3(64), 0, c->stream, X.a.codes.as<uint8_t>(), X.a.off.as<int64_t>(), X.b.codes.as<uint8_t>(), X.b.off.as<int64_t>(),
+                               X.order.as<int32_t>(), d_range, d_cnt, X.out.as<int64_t>());
     }
     *bound = host_alloc<int64_t>((size_t)n);
-    VMX_TRY(download(*bound, c->b[7].p, (size_t)n, c->stream));
+    VMX_TRY(download(*bound, X.out.p, (size_t)n, c->stream));
     VMX_HIP(hipStreamSynchronize(c->stream));
     VMX_HIP(hipGetLastError());
     return VM_OK;
@@ -461,12 +464,13 @@ int vm_k_extend_batch(vm_ctx* c, int match, int mismatch, int o, int e, int bw, 
                 set_error("vm_k_extend_batch: no band (bw < 0) with both sides longer than 496 unsupported"); return VM_ERR_UNSUPPORTED;
             }
     VMX_HIP(hipSetDevice(c->device));
-    VMX_TRY(upload_encode(c, t, t_off, n, c->b[0], c->b[1], c->b[2]));
-    VMX_TRY(upload_encode(c, q, q_off, n, c->b[3], c->b[4], c->b[5]));
-    VMX_TRY(c->b[6].reserve(sizeof(int32_t) * 3 * (size_t)(n + 1)));
-    int32_t* d_te = c->b[6].as<int32_t>(); int32_t* d_qe = d_te + n; int32_t* d_sc = d_qe + n;
-    if (n) hipLaunchKernelGGL(k_extend, dim3(grid_for(c, n, 16)), dim3(64), 0, c->stream, c->b[1].as<uint8_t>(), c->b[2].as<int64_t>(),
-                              c->b[4].as<uint8_t>(), c->b[5].as<int64_t>(), (int)n, match, mismatch, o, e, bw, zdrop, d_te, d_qe, d_sc, (const int32_t*)nullptr);
+    vmx_entry_bufs& X = *vmx_ctx_entry_bufs(c);
+    VMX_TRY(upload_encode(c, t, t_off, n, X.a.raw, X.a.codes, X.a.off));
+    VMX_TRY(upload_encode(c, q, q_off, n, X.b.raw, X.b.codes, X.b.off));
+    VMX_TRY(X.out.reserve(sizeof(int32_t) * 3 * (size_t)(n + 1)));
+    int32_t* d_te = X.out.as<int32_t>(); int32_t* d_qe = d_te + n; int32_t* d_sc = d_qe + n;
+    if (n) hipLaunchKernelGGL(k_extend, dim3(grid_for(c, n, 16)), dim3(64), 0, c->stream, X.a.codes.as<uint8_t>(), X.a.off.as<int64_t>(),
+                              X.b.codes.as<uint8_t>(), X.b.off.as<int64_t>(), (int)n, match, mismatch, o, e, bw, zdrop, d_te, d_qe, d_sc, (const int32_t*)nullptr);
     *t_e = host_alloc<int32_t>((size_t)n); *q_e = host_alloc<int32_t>((size_t)n); *score = host_alloc<int32_t>((size_t)n);
     VMX_TRY(download(*t_e, d_te, (size_t)n, c->stream)); VMX_TRY(download(*q_e, d_qe, (size_t)n, c->stream));
     VMX_TRY(download(*score, d_sc, (size_t)n, c->stream));
@@ -491,8 +495,9 @@ int vm_k_cigar_batch(vm_ctx* c, const vm_score* sc, int eqx, int64_t n, const ch
     if (!c) { set_error("no context"); return VM_ERR_NO_CTX; }
     if (n > 0x7fffffff) { set_error("too many problems"); return VM_ERR_ARG; }
     VMX_HIP(hipSetDevice(c->device));
-    VMX_TRY(upload_encode(c, t, t_off, n, c->b[0], c->b[1], c->b[2]));
-    VMX_TRY(upload_encode(c, q, q_off, n, c->b[3], c->b[4], c->b[5]));
+    vmx_entry_bufs& X = *vmx_ctx_entry_bufs(c);
+    VMX_TRY(upload_encode(c, t, t_off, n, X.a.raw, X.a.codes, X.a.off));
+    VMX_TRY(upload_encode(c, q, q_off, n, X.b.raw, X.b.codes, X.b.off));
     std::vector<vmx_dp_prob> probs((size_t)n);
     int64_t tb = 0, bnd = 0, run = 0, cig = 0;
     for (int64_t i = 0; i < n; ++i) {
@@ -503,21 +508,21 @@ int vm_k_cigar_batch(vm_ctx* c, const vm_score* sc, int eqx, int64_t n, const ch
         const vmx_gf_pool_sizes ps = vmx_gf_pools(p.tl, p.ql);
         bnd += ps.bnd; run += ps.run; cig += ps.cig;
     }
-    VMX_TRY(upload(c->b[6], probs.data(), (size_t)n, c->stream));
-    VMX_TRY(c->b[7].reserve((size_t)tb + 64)); VMX_TRY(c->b[8].reserve(sizeof(int32_t) * (size_t)(bnd + 4)));
-    VMX_TRY(c->b[9].reserve(sizeof(uint32_t) * (size_t)(run + 4))); VMX_TRY(c->b[10].reserve((size_t)cig + 16));
-    VMX_TRY(c->b[11].reserve(sizeof(int32_t) * 2 * (size_t)(n + 1)));
-    int32_t* d_score = c->b[11].as<int32_t>(); int32_t* d_len = d_score + n;
+    VMX_TRY(upload(X.probs, probs.data(), (size_t)n, c->stream));
+    VMX_TRY(X.pool.reserve((size_t)tb + 64)); VMX_TRY(X.bnd.reserve(sizeof(int32_t) * (size_t)(bnd + 4)));
+    VMX_TRY(X.run.reserve(sizeof(uint32_t) * (size_t)(run + 4))); VMX_TRY(X.cig.reserve((size_t)cig + 16));
+    VMX_TRY(X.out.reserve(sizeof(int32_t) * 2 * (size_t)(n + 1)));
+    int32_t* d_score = X.out.as<int32_t>(); int32_t* d_len = d_score + n;
     if (n) {
-        hipLaunchKernelGGL(k_gapfill_fill, dim3(grid_for(c, n, 16)), dim3(64), 0, c->stream, c->b[1].as<uint8_t>(), c->b[4].as<uint8_t>(),
-                           c->b[6].as<vmx_dp_prob>(), (int)n, sc->match, sc->mismatch, sc->o1, sc->e1, sc->o2, sc->e2, c->b[7].as<uint8_t>(),
-                           c->b[8].as<int32_t>(), d_score, (const int32_t*)nullptr, (int32_t*)nullptr);
-        hipLaunchKernelGGL(k_gapfill_trace, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, c->b[1].as<uint8_t>(), c->b[4].as<uint8_t>(),
-                           c->b[6].as<vmx_dp_prob>(), (int)n, eqx, c->b[7].as<uint8_t>(), c->b[9].as<uint32_t>(), c->b[10].as<char>(), d_len, (const int32_t*)nullptr, (const uint8_t*)nullptr, 1, (int32_t*)nullptr);
+        hipLaunchKernelGGL(k_gapfill_fill, dim3(grid_for(c, n, 16)), dim3(64), 0, c->stream, X.a.codes.as<uint8_t>(), X.b.codes.as<uint8_t>(),
+                           X.probs.as<vmx_dp_prob>(), (int)n, sc->match, sc->mismatch, sc->o1, sc->e1, sc->o2, sc->e2, X.pool.as<uint8_t>(),
+                           X.bnd.as<int32_t>(), d_score, (const int32_t*)nullptr, (int32_t*)nullptr);
+        hipLaunchKernelGGL(k_gapfill_trace, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, X.a.codes.as<uint8_t>(), X.b.codes.as<uint8_t>(),
+                           X.probs.as<vmx_dp_prob>(), (int)n, eqx, X.pool.as<uint8_t>(), X.run.as<uint32_t>(), X.cig.as<char>(), d_len, (const int32_t*)nullptr, (const uint8_t*)nullptr, 1, (int32_t*)nullptr);
     }
     std::vector<char> hc((size_t)cig + 16); std::vector<int32_t> hl((size_t)n);
     *scores = host_alloc<int32_t>((size_t)n);
-    VMX_TRY(download(hc.data(), c->b[10].p, (size_t)cig, c->stream));
+    VMX_TRY(download(hc.data(), X.cig.p, (size_t)cig, c->stream));
     VMX_TRY(download(hl.data(), d_len, (size_t)n, c->stream));
     VMX_TRY(download(*scores, d_score, (size_t)n, c->stream));
     VMX_HIP(hipStreamSynchronize(c->stream));
@@ -537,8 +542,9 @@ int vm_k_cigar_batch_banded(vm_ctx* c, const vm_score* sc, int eqx, int64_t n, c
     VMX_HIP(hipSetDevice(c->device));
     vmx_fetch_scope fetch_scope(c);
     vmx_batch_bufs& B = *vmx_ctx_batch_bufs(c);
-    VMX_TRY(upload_encode(c, t, t_off, n, c->b[0], B.tpool, c->b[2]));
-    VMX_TRY(upload_encode(c, q, q_off, n, c->b[3], B.qpool, c->b[5]));
+    vmx_entry_bufs& X = *vmx_ctx_entry_bufs(c);
+    VMX_TRY(upload_encode(c, t, t_off, n, X.a.raw, B.tpool, X.a.off));
+    VMX_TRY(upload_encode(c, q, q_off, n, X.b.raw, B.qpool, X.b.off));
     const int ad_pct = vmx_ad_pct_env();
     vmx_round_args R; memset(&R, 0, sizeof R);
     R.ad_on = 1; R.ad_match = sc->match; R.ad_o1 = sc->o1; R.ad_e1 = sc->e1; R.ad_o2 = sc->o2; R.ad_e2 = sc->e2; R.ad_pct = ad_pct;
@@ -629,7 +635,7 @@ int vm_chain_global_batch(vm_ctx* c, const vm_params* prm, int kmersize, int64_t
     for (int64_t r = 0; r < n; ++r) h_roff[(size_t)r + 1] = h_roff[(size_t)r] + readlens[r];
     VMX_TRY(upload(B.rows, anchors, (size_t)tot * 4, c->stream)); VMX_TRY(upload(B.aoff, aoff, (size_t)n + 1, c->stream));
     VMX_TRY(upload(B.lens, readlens, (size_t)n, c->stream)); VMX_TRY(upload(B.off, h_roff.data(), (size_t)n + 1, c->stream));
-    DevBuf& d_ran = c->b[0];                                          // GC-fast's flags: fast_used
+    DevBuf& d_ran = vmx_ctx_entry_bufs(c)->out;                       // GC-fast's flags: fast_used
     VMX_TRY(d_ran.reserve(4 * (size_t)(n + 1))); VMX_HIP(hipMemsetAsync(d_ran.p, 0, 4 * (size_t)n, c->stream));
     const int rmode = prm->mode == VM_MODE_R ? 1 : (prm->mode == VM_MODE_ASM ? 2 : 0);
     double* d_score = nullptr; int32_t* d_mapq = nullptr; int32_t* d_np = nullptr;

@@ -5,6 +5,10 @@
 #ifdef VMX_EMU
 #include "hip_emu.h"
 #define VMX_DYN_SHARED(type, name) type* name = (type*)hipemu::cur()->dynshared
+// the emulator's launch copies every object its argument expressions name (whole buffer bundles, which do not copy): as on the device, evaluate them once and hand on their values
+template <class K, class... A> inline void vmx_emu_launch(dim3 g, dim3 b, size_t sh, K k, A... a) { hipemu::run_grid(g, b, sh, [=]() { k(a...); }); }
+#undef hipLaunchKernelGGL
+#define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) vmx_emu_launch(dim3(grid), dim3(block), (size_t)(shmem), [](auto... a) { kernel(a...); }, __VA_ARGS__)
 #else
 #include <hip/hip_runtime.h>
 #define VMX_DYN_SHARED(type, name) extern __shared__ __attribute__((aligned(16))) type name[]

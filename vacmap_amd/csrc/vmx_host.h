@@ -5,6 +5,7 @@
 #include "vmx_kernels.h"
 #include "../../include/vacmapx.h"
 #include "vmx_batch_policy.h"
+#include "vmx_devbuf.h"
 #include <algorithm>
 #include <map>
 #include <cstring>
@@ -13,12 +14,8 @@
 #include <chrono>
 #include <atomic>
 #include <mutex>
-#include <execinfo.h>
 
 namespace vmx {
-
-void set_error(const std::string& s);
-int hip_fail(hipError_t e, const char* what, const char* file, int line);
 
 #define VMX_HIP(expr)                                                              \
     do {                                                                           \
@@ -26,55 +23,6 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line);
         if (_e != hipSuccess) return vmx::hip_fail(_e, #expr, __FILE__, __LINE__);  \
     } while (0)
 #define VMX_TRY(expr) do { int _rc = (expr); if (_rc < 0) return _rc; } while (0)
-
-// grow-only device buffer
-// growth statistics of the grow-only pools (tuning aid, printed with VMX_DBG_POOLS): a growth is a hipFree — which waits for the whole
-// device, every other context's batch included — plus a hipMalloc
-struct DevBufStats { std::atomic<long long> grows{0}, first{0}, ns{0}; };
-inline DevBufStats& devbuf_stats() { static DevBufStats s; return s; }
-
-// A buffer that has to grow is not freed on the spot: hipFree waits for the WHOLE device — every other context's batch in flight — and a
-// run's first windows grow a few hundred buffers (each new longest read resizes the per-slot pools). The outgrown allocations are parked
-// here and freed together once they add up to VMX_RETIRE_BYTES (one device-wide wait instead of hundreds), when an allocation fails, or
-// when a context is destroyed.
-struct DevBufRetired {
-    std::mutex m; std::vector<void*> v; size_t bytes = 0;
-    void flush_locked() { for (void* q : v) (void)hipFree(q); v.clear(); bytes = 0; }
-    void flush() { std::lock_guard<std::mutex> g(m); flush_locked(); }
-    void park(void* q, size_t cap) {
-        std::lock_guard<std::mutex> g(m);
-        v.push_back(q); bytes += cap;
-        if (bytes > ((size_t)6 << 30) || v.size() >= 512) flush_locked();
-    }
-};
-inline DevBufRetired& devbuf_retired() { static DevBufRetired r; return r; }
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    // grows with head-room so that slightly larger batches do not reallocate: 1/8 on the first allocation, 1/2 (at most 2 GB) when the
-    // buffer has to grow again — the input has shown that it varies
-    int reserve(size_t bytes) {
-        if (bytes <= cap && p) return 0;
-        const auto t0 = std::chrono::steady_clock::now();
-        const bool regrow = p != nullptr;
-        if (p) { devbuf_retired().park(p, cap); p = nullptr; cap = 0; }
-        size_t want = bytes + (regrow ? std::min<size_t>(bytes / 2, (size_t)2 << 30) : std::min<size_t>(bytes / 8, (size_t)1 << 30)) + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) { (void)hipGetLastError(); devbuf_retired().flush(); e = hipMalloc(&p, want); }                // give the parked memory back first
-        if (e != hipSuccess && regrow) { (void)hipGetLastError(); want = bytes + 256; e = hipMalloc(&p, want); }          // no room for the head-room: exact size
-        if (e != hipSuccess) { p = nullptr; if (getenv("VMX_DBG_POOLS")) { fprintf(stderr, "[pools] hipMalloc of %.3f GB (asked: %.3f GB) failed\n", want / 1e9, bytes / 1e9); void* bt[24]; const int nb = backtrace(bt, 24); backtrace_symbols_fd(bt, nb, 2); } return hip_fail(e, "hipMalloc", __FILE__, __LINE__); }
-        cap = want;
-        DevBufStats& st = devbuf_stats(); (regrow ? st.grows : st.first)++;
-        const long long ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-        st.ns += ns;
-        static const bool verbose = getenv("VMX_DBG_POOLS") && atoi(getenv("VMX_DBG_POOLS")) >= 2;
-        if (verbose && ns > 2000000) fprintf(stderr, "[pools] %s of %.3f GB took %.1f ms\n", regrow ? "re-allocation" : "allocation", want / 1e9, ns * 1e-6);
-        return 0;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <class T> T* as() const { return (T*)p; }
-};
 
 struct HostTables {
     std::vector<float> extra, readgap_h, readgap_r, large_readgap;
@@ -140,16 +88,13 @@ __global__ void k_signal(unsigned long long* word, unsigned long long v);
 struct vmx_export_args { const char* src[VMX_EXPORT_MAX]; char* dst[VMX_EXPORT_MAX]; unsigned long long bytes[VMX_EXPORT_MAX]; int n; unsigned long long* word; unsigned long long seq; unsigned long long* done; };
 __global__ void k_export(vmx_export_args A);
 
-enum { VMX_NBUF = 64 };
 struct vm_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     vmx_tables tables{};
     vmx::DevBuf tab_buf;
-    vmx::DevBuf b[VMX_NBUF];     // scratch buffers reused by the entry points (grow-only)
     int num_cu = 256;
     int inflight = 1;                            // contexts sharing the GPU (vm_ctx_set_inflight)
-    hipEvent_t sync_ev = nullptr;                // (legacy, unused since round 6: a blocking event's wait spins on this runtime)
     vmx_mailbox mb;                              // sleeping waits + page-locked exchange of the small data (above)
     hipEvent_t ev[24];
     hipEvent_t gev[48];                          // gap-fill chunk events: [redo][chunk 0..7][before fill, after fill, after trace]
@@ -172,8 +117,8 @@ struct vm_ctx {
     hipStream_t low = nullptr;                   // low-priority stream for the long VALU-bound launches (the gap fill's first launch): see vmx_lowprio_begin
     hipEvent_t low_ev[2] = {nullptr, nullptr};
     int64_t last_n_minimizers = 0;               // of the last seed stage (stats)
-    struct vmx_local_bufs* lbufs = nullptr;      // vmx_stage.h
-    struct vmx_extend_bufs* ebufs = nullptr;
+    struct vmx_entry_bufs* xbufs = nullptr;      // vmx_stage.h: scratch of the stage entry points
+    struct vmx_local_bufs* lbufs = nullptr;
     struct vmx_batch_bufs* bbufs = nullptr;
     struct vmx_sam_bufs* sbufs = nullptr;        // vmx_sam_dev.h: the device SAM emitter's buffers
 };

@@ -24,6 +24,7 @@
 using namespace vmx;
 
 #include "vmx_index_priv.h"
+#include "vmx_stage.h"
 
 __global__ void k_sketch32(const uint8_t* codes, const int64_t* roff, int n_reads, int k, int w, uint64_t* mz_hash, uint32_t* mz_ps, const int64_t* mz_off, int32_t* mz_cnt);
 __global__ void k_sketch(const uint8_t* codes, const int64_t* roff, int n_reads, int k, int w, uint64_t* mz_hash, uint32_t* mz_ps,
@@ -205,7 +206,6 @@ int vmx_index_finish_device(vm_index* mi, DevBuf& d_keys, int64_t n) {
     mi->n_min = n;
     if (n >= (1LL << 32)) { set_error("index: 2^32 or more minimizers (slot start is 32 bits)"); return VM_ERR_UNSUPPORTED; }
     DevBuf d_uniq, d_counts, d_starts, d_nruns, d_tmp, d_hist;
-    struct Rel { DevBuf* b[6]; ~Rel() { for (auto* x : b) x->release(); } } rel{{&d_uniq, &d_counts, &d_starts, &d_nruns, &d_tmp, &d_hist}};
     uint64_t nd = 0;
     if (n > 0) {
         VMX_TRY(d_uniq.reserve(8 * (size_t)n)); VMX_TRY(d_counts.reserve(4 * (size_t)n)); VMX_TRY(d_nruns.reserve(64));
@@ -216,7 +216,7 @@ int vmx_index_finish_device(vm_index* mi, DevBuf& d_keys, int64_t n) {
         VMX_TRY(download(&nd, d_nruns.p, 1, st));
         VMX_HIP(hipStreamSynchronize(st));
     }
-    d_keys.release();
+    d_keys.release();              // early: the sorted keys (8 bytes per minimizer) make room for the hash table allocated below
     mi->n_distinct = (int64_t)nd;
     // occurrence cap: max(10, count at the (1 - 2e-4) quantile of the distinct minimizers + 1)  [spec VMX-S1]
     int occ = 10;
@@ -268,7 +268,6 @@ static int index_build_device(vm_index* mi) {
     }
     const int64_t nj = (int64_t)jobs.size();
     DevBuf d_jobs, d_cnt, d_off, d_tmp, d_k0, d_v0, d_k1;
-    struct Rel { DevBuf* b[7]; ~Rel() { for (auto* x : b) x->release(); } } rel{{&d_jobs, &d_cnt, &d_off, &d_tmp, &d_k0, &d_v0, &d_k1}};
     int64_t n = 0;
     if (nj > 0) {
         VMX_TRY(upload(d_jobs, jobs.data(), (size_t)nj, st));
@@ -292,7 +291,7 @@ static int index_build_device(vm_index* mi) {
             VMX_TRY(d_tmp.reserve(tb + 256));
             VMX_PRIM(vmx_prim_sort_pairs_u64(d_tmp.p, &tb, d_k0.as<uint64_t>(), d_k1.as<uint64_t>(), d_v0.as<uint64_t>(), mi->d_pos.as<uint64_t>(), (size_t)n, 2 * k, st));
             VMX_HIP(hipStreamSynchronize(st));
-            d_k0.release(); d_v0.release(); d_tmp.release();
+            d_k0.release(); d_v0.release(); d_tmp.release();      // early: the sort's inputs and scratch (the build's peak) make room for the grouping and the table
         }
     }
     if (n == 0) VMX_TRY(mi->d_pos.reserve(8));
@@ -304,10 +303,10 @@ int vmx_index_upload_codes(vm_index* mi, const char* const* seqs) {
     vm_ctx* c = mi->ctx; hipStream_t st = c->stream;
     const int64_t tot = mi->offsets.back();
     VMX_TRY(mi->d_codes.reserve((size_t)tot + 64));
-    DevBuf stage; struct Rel { DevBuf* b; ~Rel() { b->release(); } } rel{&stage};
+    DevBuf stage;
     const int64_t CH = (int64_t)256 << 20;
     VMX_TRY(stage.reserve((size_t)std::min<int64_t>(std::max<int64_t>(tot, 1), CH)));
-    DevBuf other; struct Rel2 { DevBuf* b; ~Rel2() { b->release(); } } rel2{&other};      // letters that become code 4 without being N (the device SAM emitter cannot print them)
+    DevBuf other;      // letters that become code 4 without being N (the device SAM emitter cannot print them)
     VMX_TRY(other.reserve(8)); VMX_HIP(hipMemsetAsync(other.p, 0, 8, st));
     for (size_t i = 0; i < mi->lens.size(); ++i)
         for (int64_t s = 0; s < mi->lens[i]; s += CH) {
@@ -396,11 +395,7 @@ int vm_index_build_fasta(vm_ctx* c, const char* path, int k, int w, vm_index** o
     catch (const std::exception& e) { set_error(std::string("index build: ") + e.what()); return VM_ERR_IO; }
 }
 
-void vm_index_free(vm_index* mi) {
-    if (!mi) return;
-    mi->d_codes.release(); mi->d_pos.release(); mi->d_table.release(); mi->d_off.release();
-    delete mi;
-}
+void vm_index_free(vm_index* mi) { delete mi; }
 int vm_index_k(const vm_index* mi) { return mi->k; }
 int vm_index_w(const vm_index* mi) { return mi->w; }
 int vm_index_nseq(const vm_index* mi) { return (int)mi->names.size(); }
@@ -425,7 +420,6 @@ int64_t vm_index_seq(const vm_index* mi, int i, int64_t st, int64_t en, char* ou
     hipLaunchKernelGGL(k_decode, dim3(grid1d(en - st, 8192)), dim3(256), 0, c->stream, mi->d_codes.as<uint8_t>() + mi->offsets[i] + st, tmp.as<char>(), en - st);
     const hipError_t e = hipMemcpyAsync(out, tmp.p, (size_t)(en - st), hipMemcpyDeviceToHost, c->stream);
     const hipError_t e2 = hipStreamSynchronize(c->stream);
-    tmp.release();
     return (e == hipSuccess && e2 == hipSuccess) ? en - st : (int64_t)VM_ERR_HIP;
 }
 // tests: the sorted (hash, position) columns as the kernels see them, read back FROM THE DEVICE (hashes are recovered from the table)
@@ -442,7 +436,6 @@ int vm_index_minimizers(const vm_index* mi, uint64_t** hashes, uint64_t** positi
     int rc = download(*hashes, d_h.p, (size_t)*n, c->stream);
     if (rc == 0) rc = download(*positions, mi->d_pos.p, (size_t)*n, c->stream);
     const hipError_t e = hipStreamSynchronize(c->stream);
-    d_h.release();
     if (rc < 0) return rc;
     VMX_HIP(e);
     return VM_OK;
@@ -514,7 +507,7 @@ static int index_load_impl(vm_ctx* c, const char* path, vm_index** out) {
     VMX_TRY(vmx_index_upload_codes(mi, sp.data()));
     VMX_TRY(upload(mi->d_pos, pos.data(), (size_t)nmin, c->stream));
     VMX_TRY(upload(mi->d_off, mi->offsets.data(), mi->offsets.size(), c->stream));
-    DevBuf d_keys, d_err; struct Rel { DevBuf* b[2]; ~Rel() { for (auto* x : b) x->release(); } } rel{{&d_keys, &d_err}};
+    DevBuf d_keys, d_err;
     VMX_TRY(d_keys.reserve(8 * (size_t)std::max<int64_t>(nmin, 1))); VMX_TRY(d_err.reserve(64)); VMX_HIP(hipMemsetAsync(d_err.p, 0, 8, c->stream));
     if (nmin) {
         hipLaunchKernelGGL(k_idx_pos_keys, dim3(grid1d(nmin)), dim3(256), 0, c->stream, mi->d_codes.as<uint8_t>(), mi->d_off.as<int64_t>(), (int)nseq, mi->d_pos.as<uint64_t>(), nmin, (int)k,
@@ -604,14 +597,15 @@ int vm_sketch_batch(vm_ctx* c, int k, int w, int64_t n, const char* seqs, const 
     if (!c) { set_error("no context"); return VM_ERR_NO_CTX; }
     if (k < 1 || k > 28 || w < 1 || w > 255) { set_error("bad k/w"); return VM_ERR_ARG; }
     VMX_HIP(hipSetDevice(c->device));
-    VMX_TRY(upload_reads(c, n, seqs, off, c->b[0], c->b[1], c->b[2]));
+    vmx_entry_bufs& X = *vmx_ctx_entry_bufs(c);
+    VMX_TRY(upload_reads(c, n, seqs, off, X.a.raw, X.a.codes, X.a.off));
     const int64_t tot = off[n];
-    VMX_TRY(c->b[3].reserve(8 * (size_t)(tot + 1))); VMX_TRY(c->b[4].reserve(4 * (size_t)(tot + 1))); VMX_TRY(c->b[5].reserve(4 * (size_t)(n + 1)));
-    if (n) hipLaunchKernelGGL(k_sketch, dim3((unsigned)std::min<int64_t>(n, c->num_cu * 4)), dim3(256), 0, c->stream, c->b[1].as<uint8_t>(), c->b[2].as<int64_t>(),
-                              (int)n, k, w, c->b[3].as<uint64_t>(), c->b[4].as<uint32_t>(), c->b[2].as<int64_t>(), c->b[5].as<int32_t>());
+    VMX_TRY(X.hash.reserve(8 * (size_t)(tot + 1))); VMX_TRY(X.pos.reserve(4 * (size_t)(tot + 1))); VMX_TRY(X.out.reserve(4 * (size_t)(n + 1)));
+    if (n) hipLaunchKernelGGL(k_sketch, dim3((unsigned)std::min<int64_t>(n, c->num_cu * 4)), dim3(256), 0, c->stream, X.a.codes.as<uint8_t>(), X.a.off.as<int64_t>(),
+                              (int)n, k, w, X.hash.as<uint64_t>(), X.pos.as<uint32_t>(), X.a.off.as<int64_t>(), X.out.as<int32_t>());
     std::vector<int32_t> cnt((size_t)n); std::vector<uint64_t> hh((size_t)tot); std::vector<uint32_t> ps((size_t)tot);
-    VMX_TRY(download(cnt.data(), c->b[5].p, (size_t)n, c->stream)); VMX_TRY(download(hh.data(), c->b[3].p, (size_t)tot, c->stream));
-    VMX_TRY(download(ps.data(), c->b[4].p, (size_t)tot, c->stream));
+    VMX_TRY(download(cnt.data(), X.out.p, (size_t)n, c->stream)); VMX_TRY(download(hh.data(), X.hash.p, (size_t)tot, c->stream));
+    VMX_TRY(download(ps.data(), X.pos.p, (size_t)tot, c->stream));
     VMX_HIP(hipStreamSynchronize(c->stream)); VMX_HIP(hipGetLastError());
     int64_t m = 0; for (int64_t r = 0; r < n; ++r) m += cnt[r];
     *hash = (uint64_t*)malloc(8 * (size_t)std::max<int64_t>(m, 1)); *pos = (int32_t*)malloc(4 * (size_t)std::max<int64_t>(m, 1));
@@ -625,14 +619,13 @@ int vm_sketch_batch(vm_ctx* c, int k, int w, int64_t n, const char* seqs, const 
 // device-side seed stage shared by vm_map_batch and vm_align_batch: codes/roff already on the device.
 // leaves rows (int64 x4) at key_off[r] with n_anchors[r] valid rows; returns host copies of key_off / nhits totals
 int vmx_seed_stage(vm_ctx* c, const vm_index* mi, int check_num, int mid_occ, int64_t n, const uint8_t* d_codes, const int64_t* d_roff, int64_t total_bases,
-                   DevBuf* B /* >= 13 buffers */, std::vector<int64_t>& h_koff, std::vector<int64_t>& h_nhits, DevBuf* arena, int64_t** rows_out) {
+                   vmx_seed_bufs& B, std::vector<int64_t>& h_koff, std::vector<int64_t>& h_nhits, DevBuf* arena, int64_t** rows_out) {
     if (mid_occ <= 0) mid_occ = mi->mid_occ;
     // arena: a pool of the caller that is idle during this stage (the align path hands in its traceback pool, which only the gap fill uses, long
     // after the rows were compacted): the hit keys, their scratch copy and the row slots (48 B per hit: 8.4 GB for a batch of 35 kb reads) are views
     // into it instead of three pools of their own. *rows_out = where the rows are.
-    DevBuf vk, vc, vr;
-    DevBuf &mzh = B[0], &mzp = B[1], &mzc = B[2], &mst = B[3], &mcn = B[4], &mho = B[5], &nh = B[6], &koff = B[7], &keys = arena ? vk : B[8], &ckeys = arena ? vc : B[9],
-           &rows = arena ? vr : B[10], &nanc = B[11];
+    DevBuf &mzh = B.mzh, &mzp = B.mzp, &mzc = B.mzc, &mst = B.mst, &mcn = B.mcn, &mho = B.mho, &nh = B.nh, &koff = B.koff, &nanc = B.nanc;
+    DevView keys, ckeys, rows;
     VMX_TRY(mzh.reserve(8 * (size_t)(total_bases + 1))); VMX_TRY(mzp.reserve(4 * (size_t)(total_bases + 1))); VMX_TRY(mzc.reserve(4 * (size_t)(n + 1)));
     VMX_TRY(mst.reserve(4 * (size_t)(total_bases + 1))); VMX_TRY(mcn.reserve(4 * (size_t)(total_bases + 1))); VMX_TRY(mho.reserve(4 * (size_t)(total_bases + 1)));
     VMX_TRY(nh.reserve(8 * (size_t)(n + 2))); VMX_TRY(koff.reserve(8 * (size_t)(n + 2))); VMX_TRY(nanc.reserve(4 * (size_t)(n + 1)));
@@ -652,9 +645,10 @@ int vmx_seed_stage(vm_ctx* c, const vm_index* mi, int check_num, int mid_occ, in
     if (arena) {
         const size_t kb = (8 * (size_t)(ktot + 1) + 255) & ~(size_t)255;
         VMX_TRY(arena->reserve(2 * kb + 32 * (size_t)(ktot + 1)));
-        vk.p = arena->p; vk.cap = kb; vc.p = (char*)arena->p + kb; vc.cap = kb; vr.p = (char*)arena->p + 2 * kb; vr.cap = 32 * (size_t)(ktot + 1);
+        keys = DevView(arena->p, kb); ckeys = DevView((char*)arena->p + kb, kb); rows = DevView((char*)arena->p + 2 * kb, 32 * (size_t)(ktot + 1));
     } else {
-        VMX_TRY(keys.reserve(8 * (size_t)(ktot + 1))); VMX_TRY(ckeys.reserve(8 * (size_t)(ktot + 1))); VMX_TRY(rows.reserve(32 * (size_t)(ktot + 1)));
+        VMX_TRY(B.keys.reserve(8 * (size_t)(ktot + 1))); VMX_TRY(B.ckeys.reserve(8 * (size_t)(ktot + 1))); VMX_TRY(B.rows.reserve(32 * (size_t)(ktot + 1)));
+        keys = B.keys; ckeys = B.ckeys; rows = B.rows;
     }
     if (rows_out) *rows_out = rows.as<int64_t>();
     hipLaunchKernelGGL(k_fill_hits, dim3(grid), dim3(256), 0, c->stream, mzp.as<uint32_t>(), d_roff, mzc.as<int32_t>(), (int)n, mst.as<uint32_t>(), mcn.as<uint32_t>(),
@@ -675,9 +669,9 @@ int vmx_seed_stage(vm_ctx* c, const vm_index* mi, int check_num, int mid_occ, in
         std::vector<int32_t> rl(small); rl.insert(rl.end(), big.begin(), big.end());
         const size_t decl_at = rl.size();
         rl.resize(decl_at + 2 * (big.size() + 1), 0);
-        VMX_TRY(vmx_push(c, B[12], rl.data(), rl.size()));
-        const int32_t* d_rl = B[12].as<int32_t>();
-        int32_t* d_decl = B[12].as<int32_t>() + decl_at; int32_t* d_ndecl = d_decl + big.size();
+        VMX_TRY(vmx_push(c, B.rlist, rl.data(), rl.size()));
+        const int32_t* d_rl = B.rlist.as<int32_t>();
+        int32_t* d_decl = B.rlist.as<int32_t>() + decl_at; int32_t* d_ndecl = d_decl + big.size();
         int32_t* d_decl2 = d_ndecl + 1; int32_t* d_ndecl2 = d_decl2 + big.size();
         (void)hipEventRecord(c->kev[2], c->stream);
         if (!big.empty()) {
@@ -720,14 +714,15 @@ int vmx_seed_stage(vm_ctx* c, const vm_index* mi, int check_num, int mid_occ, in
 int vm_map_batch(vm_ctx* c, const vm_index* mi, int check_num, int mid_occ, int64_t n, const char* seqs, const int64_t* off, int64_t** anchors, int64_t** anchor_off) {
     if (!c) { set_error("no context"); return VM_ERR_NO_CTX; }
     VMX_HIP(hipSetDevice(c->device));
-    VMX_TRY(upload_reads(c, n, seqs, off, c->b[0], c->b[1], c->b[2]));
+    vmx_entry_bufs& X = *vmx_ctx_entry_bufs(c);
+    VMX_TRY(upload_reads(c, n, seqs, off, X.a.raw, X.a.codes, X.a.off));
     std::vector<int64_t> koff, nhits;
-    if (n) VMX_TRY(vmx_seed_stage(c, mi, check_num, mid_occ, n, c->b[1].as<uint8_t>(), c->b[2].as<int64_t>(), off[n], &c->b[3], koff, nhits, nullptr, nullptr));
+    if (n) VMX_TRY(vmx_seed_stage(c, mi, check_num, mid_occ, n, X.a.codes.as<uint8_t>(), X.a.off.as<int64_t>(), off[n], X.seed, koff, nhits, nullptr, nullptr));
     else koff.assign(1, 0);
     std::vector<int32_t> nanc((size_t)n);
     std::vector<int64_t> rows((size_t)koff[n] * 4);
-    VMX_TRY(download(nanc.data(), c->b[14].p, (size_t)n, c->stream));
-    VMX_TRY(download(rows.data(), c->b[13].p, rows.size(), c->stream));
+    VMX_TRY(download(nanc.data(), X.seed.nanc.p, (size_t)n, c->stream));
+    VMX_TRY(download(rows.data(), X.seed.rows.p, rows.size(), c->stream));
     VMX_HIP(hipStreamSynchronize(c->stream)); VMX_HIP(hipGetLastError());
     int64_t tot = 0; for (int64_t r = 0; r < n; ++r) tot += nanc[r];
     *anchors = (int64_t*)malloc(32 * (size_t)std::max<int64_t>(tot, 1)); *anchor_off = (int64_t*)malloc(8 * (size_t)(n + 1));
@@ -747,7 +742,6 @@ int vm_map(vm_ctx* c, const vm_index* mi, const char* seq, int64_t len, int chec
 
 }  // extern "C"
 
-#include "vmx_stage.h"
 void vmx_index_view(const vm_index* mi, vm_index_view* v) {
     v->codes = mi->d_codes.as<uint8_t>(); v->coff = mi->d_off.as<int64_t>(); v->nseq = (int)mi->names.size(); v->total_len = mi->offsets.back();
     v->pos = mi->d_pos.as<uint64_t>(); v->table = mi->d_table.as<vmx_slot>(); v->table_bits = mi->table_bits; v->k = mi->k; v->w = mi->w; v->mid_occ = mi->mid_occ;

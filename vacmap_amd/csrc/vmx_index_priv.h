@@ -25,6 +25,14 @@ struct vm_index {
 
 static inline unsigned grid1d(int64_t n, int64_t cap = 65536) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, cap)); }
 #define VMX_PRIM(expr) do { int _e = (expr); if (_e != 0) return vmx::hip_fail((hipError_t)_e, #expr, __FILE__, __LINE__); } while (0)
+// exclusive scan of n int64 on the context's stream; tmp: the caller's scratch buffer (grows as the primitive asks)
+static inline int vmx_scan64(vm_ctx* c, vmx::DevBuf& tmp, const int64_t* in, int64_t* out, size_t n) {
+    size_t tb = 0;
+    VMX_PRIM(vmx_prim_excl_scan_i64(nullptr, &tb, in, out, n, c->stream));
+    VMX_TRY(tmp.reserve(tb ? tb : 8));
+    VMX_PRIM(vmx_prim_excl_scan_i64(tmp.p, &tb, in, out, n, c->stream));
+    return 0;
+}
 
 // host bases (ASCII, one pointer per contig) -> mi->d_codes
 int vmx_index_upload_codes(vm_index* mi, const char* const* seqs);

@@ -107,7 +107,6 @@ static int load_mmi_impl(vm_ctx* c, const char* path, vm_index** out) {
     VMX_TRY(vmx_index_upload_codes(mi, sp.data()));
     VMX_TRY(upload(mi->d_off, mi->offsets.data(), mi->offsets.size(), st));
     DevBuf d_h0, d_v0, d_h1, d_v1, d_tmp, d_keys, d_err;
-    struct Rel { DevBuf* b[7]; ~Rel() { for (auto* q : b) q->release(); } } rel{{&d_h0, &d_v0, &d_h1, &d_v1, &d_tmp, &d_keys, &d_err}};
     VMX_TRY(mi->d_pos.reserve(8 * (size_t)n + 8));
     VMX_TRY(d_h1.reserve(8 * (size_t)std::max<int64_t>(n, 1)));
     if (n) {

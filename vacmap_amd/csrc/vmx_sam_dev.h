@@ -49,12 +49,6 @@ struct vmx_sam_bufs {
     vmx::DevBuf cnames, cname_off; uint64_t names_of = 0;                           // the contig-name blob and the serial of the index it was made for (vm_index.serial: never 0)
     std::string h_cnames; std::vector<int64_t> h_cname_off;
     double s_upload = 0, s_kernel = 0, s_download = 0;                              // wall seconds of the last call by phase
-    void release() {
-        vmx::DevBuf* all[] = {&names, &name_off, &seqs, &seq_off, &quals, &qual_off, &comments, &com_off, &recs, &cigars, &status, &rg, &cnt, &first, &keep, &ord, &mq, &flag, &rflag, &ri, &tsz, &toff,
-                              &scratch, &lsz, &loff, &res, &tmp, &text, &text_off, &cnames, &cname_off};
-        for (vmx::DevBuf* b : all) b->release();
-        names_of = 0;
-    }
 };
 struct vmx_sam_totals { int64_t text_bytes, n_lines, n_skipped; };
 
@@ -62,5 +56,4 @@ struct vmx_sam_totals { int64_t text_bytes, n_lines, n_skipped; };
 // (tot->text_bytes bytes), the per-read offsets in S->text_off (n_reads + 1). Two host waits; the caller fetches what it wants and waits once more.
 int vmx_sam_emit_dev(vm_ctx* c, const struct vm_index* mi, vmx_sam_in in, vmx_sam_totals* tot);
 vmx_sam_bufs* vmx_ctx_sam_bufs(vm_ctx* c);
-void vmx_ctx_free_sam_bufs(vm_ctx* c);
 #endif

@@ -10,9 +10,6 @@ vmx_sam_bufs* vmx_ctx_sam_bufs(vm_ctx* c) {
     if (!c->sbufs) c->sbufs = new vmx_sam_bufs();
     return c->sbufs;
 }
-void vmx_ctx_free_sam_bufs(vm_ctx* c) {
-    if (c->sbufs) { c->sbufs->release(); delete c->sbufs; c->sbufs = nullptr; }
-}
 
 namespace {
 
@@ -26,13 +23,6 @@ int wait(vm_ctx* c) {
 int launched(const char* what) {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
-    return 0;
-}
-int scan64(vm_ctx* c, DevBuf& tmp, const int64_t* in, int64_t* out, size_t n) {
-    size_t tb = 0;
-    VMX_PRIM(vmx_prim_excl_scan_i64(nullptr, &tb, in, out, n, c->stream));
-    VMX_TRY(tmp.reserve(tb ? tb : 8));
-    VMX_PRIM(vmx_prim_excl_scan_i64(tmp.p, &tb, in, out, n, c->stream));
     return 0;
 }
 
@@ -69,13 +59,13 @@ int vmx_sam_emit_dev(vm_ctx* c, const vm_index* mi, vmx_sam_in A, vmx_sam_totals
     VMX_HIP(hipMemsetAsync(K.cnt, 0, 8 * (size_t)(n + 1), st)); VMX_HIP(hipMemsetAsync(K.rflag, 0, 4 * (size_t)(n + 1), st)); VMX_HIP(hipMemsetAsync(K.res, 0, 64, st));
     VMX_HIP(hipMemsetAsync(K.tsz, 0, 8 * (size_t)(m + 1), st)); VMX_HIP(hipMemsetAsync(K.lsz, 0, 8 * (size_t)(m + 1), st));
     if (m) hipLaunchKernelGGL(k_sam_count, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, A, K);
-    VMX_TRY(scan64(c, S->tmp, K.cnt, K.first, (size_t)n + 1));
+    VMX_TRY(vmx_scan64(c, S->tmp, K.cnt, K.first, (size_t)n + 1));
     unsigned long long h_res[3] = {0, 0, 0}; int64_t h_tot = 0;
     // (a record that names no read or no contig is found by k_sam_count; the kernels below see its flag and do nothing)
     if (m) hipLaunchKernelGGL(k_sam_order, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A, K);
     if (m) hipLaunchKernelGGL(k_sam_ops, dim3((unsigned)m), dim3(64), 0, st, A, K, 0);
     VMX_TRY(launched("k_sam_ops (sizes)"));
-    VMX_TRY(scan64(c, S->tmp, K.tsz, K.toff, (size_t)m + 1));
+    VMX_TRY(vmx_scan64(c, S->tmp, K.tsz, K.toff, (size_t)m + 1));
     VMX_TRY(vmx_fetch(c, &h_tot, K.toff + m, 1)); VMX_TRY(vmx_fetch(c, h_res, K.res, 1));
     VMX_TRY(wait(c));                                                    // wait 1: the operator pass's sizes
     if (h_res[0] & VMX_SAM_E_RECORD) { set_error("vm_sam_emit_device: a record names no read or no contig, lies outside the CIGAR blob, or the records are not ordered by read"); return VM_ERR_ARG; }
@@ -85,7 +75,7 @@ int vmx_sam_emit_dev(vm_ctx* c, const vm_index* mi, vmx_sam_in A, vmx_sam_totals
     if (m) hipLaunchKernelGGL(k_sam_ops, dim3((unsigned)m), dim3(64), 0, st, A, K, 1);
     if (m) hipLaunchKernelGGL(k_sam_lines, dim3((unsigned)m), dim3(64), 0, st, A, K, (char*)nullptr, 0);
     VMX_TRY(launched("k_sam_lines (sizes)"));
-    VMX_TRY(scan64(c, S->tmp, K.lsz, K.loff, (size_t)m + 1));
+    VMX_TRY(vmx_scan64(c, S->tmp, K.lsz, K.loff, (size_t)m + 1));
     hipLaunchKernelGGL(k_sam_text_off, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, st, A, K, S->text_off.as<int64_t>());
     VMX_TRY(vmx_fetch(c, &h_tot, K.loff + m, 1)); VMX_TRY(vmx_fetch(c, h_res, K.res, 3));
     VMX_TRY(wait(c));                                                    // wait 2: the lines' sizes

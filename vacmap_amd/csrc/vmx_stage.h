@@ -22,23 +22,35 @@ struct vmx_local_bufs {
     int64_t la_pool_rows = 0;            // rows of the local-anchor pools (regular slots + overflow area)
     std::vector<int64_t> h_la_off;
     std::vector<int32_t> h_la_cnt;
-    void release() {
-        vmx::DevBuf* all[] = {&prep_ws, &sq, &dst, &rorder, &pc2, &stg, &si, &tg, &cntp, &fp, &pp, &dbg, &epoch, &hkey2, &guide_rows, &guide_len, &ng_used, &ng_total, &cnt, &cur, &tpos, &hkey, &hval, &hq, &goff, &pcnt, &gkey, &gq, &gr,
-                              &la_rows, &la_ekey, &la_sorted, &la_off, &la_cnt, &status, &gap, &rlist, &S, &P, &SA, &chain, &chain_len, &score, &variant};
-        for (auto* b : all) b->release();
-    }
 };
 vmx_local_bufs* vmx_ctx_local_bufs(vm_ctx* c);
 
+// the seed stage's buffers (vmx_seed_stage), named as it names them; rlist: the read lists of the clustering launches
+struct vmx_seed_bufs { vmx::DevBuf mzh, mzp, mzc, mst, mcn, mho, nh, koff, keys, ckeys, rows, nanc, rlist; };
+
+// scratch of the stage entry points (vm_edit_distance_batch ... vm_local_chain_batch), grow-only, one set per context. Entries share the members of a
+// role: every entry encodes its sequences into `a` (and `b`) and leaves its per-problem results in `out`.
+struct vmx_read_set { vmx::DevBuf raw, codes, off; };       // ASCII as uploaded, 2-bit codes (+ 64 bytes), n + 1 offsets
+struct vmx_entry_bufs {
+    vmx_read_set a, b;                                      // the entry's first / second sequence set (the reads of the seed and chain entries are `a`)
+    vmx::DevBuf out;                                        // distances or bounds; (t_e, q_e, score); (score, CIGAR length); minimizers per read; GC-fast's flags
+    vmx::DevBuf pool;                                       // the edit distance's carry ring; the full-matrix gap fill's traceback
+    vmx::DevBuf sizes, count, order, range;                 // edit distance entries: the device work queue (pattern sizes, their number, order, ranges + counters)
+    vmx::DevBuf probs, bnd, run, cig;                       // vm_k_cigar_batch: problem table, boundary / run / CIGAR pools
+    vmx::DevBuf hash, pos;                                  // vm_sketch_batch: minimizer columns
+    vmx_seed_bufs seed;                                     // vm_map_batch
+    vmx::DevBuf rows, plen, npaths, aoff, gscore;           // vm_local_chain_batch: the global paths it is given
+};
+vmx_entry_bufs* vmx_ctx_entry_bufs(vm_ctx* c);
+
 // the buffers of the batched path (vmx_align.hip), grow-only, one set per context
 struct vmx_batch_bufs {
-    vmx::DevBuf seed[13];
+    vmx_seed_bufs seed;
     vmx::DevBuf nanc64, aoff, rows, lens, keys, koff, sorted, flip, S, P, SA, cov, gmax, opc, rl, gap, scr, soff, res, plen, prow, ocodes;
     // extend stage
     vmx::DevBuf er, coff3, soff2, segA, st, en, segA_s, st_s, en_s, segprob, dup, desc[2], rcount, oflow, probread, tl, ql, toff, qoff, tpool, qpool;
     vmx::DevBuf edout, carry, ext3, dpsz[4], dpoff[4], dptab, tb, tbredo, bnd, run, cig, ciglen, dpscore, rec, blob, bloboff, reccoff, recclen, dupd, totals;
     vmx::DevBuf raw, codes, off, order, qrange, si, tg, cntp, fp, pp, chunkn, sellist, cigq, statblk, szh, side_codes, side_off, roundpart, gfctl, geotot;
-    void release() { vmx::DevBuf* p = (vmx::DevBuf*)this; for (size_t i = 0; i < sizeof(*this) / sizeof(vmx::DevBuf); ++i) p[i].release(); }
 };
 vmx_batch_bufs* vmx_ctx_batch_bufs(vm_ctx* c);
 
@@ -61,7 +73,7 @@ void vmx_gapfill_chunk(vm_ctx* c, vmx_batch_bufs& B, const vm_score& sc, int ad_
                        vmx_gf_ctl* ctl, int32_t* redo_list, int64_t redo_cap, hipEvent_t* ke);
 
 extern "C" int vmx_seed_stage(vm_ctx* c, const vm_index* mi, int check_num, int mid_occ, int64_t n, const uint8_t* d_codes, const int64_t* d_roff, int64_t total_bases,
-                   vmx::DevBuf* B, std::vector<int64_t>& h_koff, std::vector<int64_t>& h_nhits, vmx::DevBuf* arena = nullptr, int64_t** rows_out = nullptr);
+                   vmx_seed_bufs& B, std::vector<int64_t>& h_koff, std::vector<int64_t>& h_nhits, vmx::DevBuf* arena = nullptr, int64_t** rows_out = nullptr);
 int vmx_local_stage(vm_ctx* c, const vm_index_view& ix, const vm_params* prm, int64_t n, const uint8_t* d_ocodes, const int64_t* d_roff,
                     const std::vector<int64_t>& h_roff, const vmx_anchor* d_path_rows, const int32_t* d_path_len, const int32_t* d_npaths,
                     const int64_t* d_aoff, const std::vector<int64_t>& h_aoff, const double* d_gscore, vmx_local_bufs& L, bool fast = false);

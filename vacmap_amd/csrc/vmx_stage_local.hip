@@ -325,7 +325,8 @@ int vm_local_chain_batch(vm_ctx* c, const vm_index* mi, const vm_params* prm, in
     vmx_fetch_scope fetch_scope(c);
     vm_index_view ix; vmx_index_view(mi, &ix);
     // reads
-    DevBuf &raw = c->b[0], &codes = c->b[1], &roff = c->b[2];
+    vmx_entry_bufs& X = *vmx_ctx_entry_bufs(c);
+    DevBuf &raw = X.a.raw, &codes = X.a.codes, &roff = X.a.off;
     const int64_t tot = offsets[n];
     VMX_TRY(upload(raw, seqs, (size_t)tot, c->stream)); VMX_TRY(codes.reserve((size_t)tot + 64)); VMX_TRY(upload(roff, offsets, (size_t)n + 1, c->stream));
     if (tot) hipLaunchKernelGGL(k_encode, dim3((unsigned)std::min<int64_t>((tot + 255) / 256, 4096)), dim3(256), 0, c->stream, raw.as<char>(), codes.as<uint8_t>(), tot);
@@ -343,7 +344,7 @@ int vm_local_chain_batch(vm_ctx* c, const vm_index* mi, const vm_params* prm, in
             for (int64_t x = path_off[p]; x < path_off[p + 1]; ++x) { vmx_anchor a; a.q = (int32_t)path_anchors[4 * x]; a.r = path_anchors[4 * x + 1]; a.s = (int16_t)path_anchors[4 * x + 2]; a.l = (int16_t)path_anchors[4 * x + 3]; rows[w++] = a; }
         }
     }
-    DevBuf &d_rows = c->b[3], &d_plen = c->b[4], &d_np = c->b[5], &d_aoff = c->b[6], &d_gs = c->b[7];
+    DevBuf &d_rows = X.rows, &d_plen = X.plen, &d_np = X.npaths, &d_aoff = X.aoff, &d_gs = X.gscore;
     VMX_TRY(upload(d_rows, rows.data(), (size_t)ta + 1, c->stream)); VMX_TRY(upload(d_plen, plen.data(), (size_t)ta + 1, c->stream));
     VMX_TRY(upload(d_np, npaths.data(), (size_t)n, c->stream)); VMX_TRY(upload(d_aoff, h_aoff.data(), (size_t)n + 1, c->stream));
     VMX_TRY(upload(d_gs, gscore.data(), (size_t)n, c->stream));
@@ -378,7 +379,4 @@ int vm_local_chain_batch(vm_ctx* c, const vm_index* mi, const vm_params* prm, in
 vmx_local_bufs* vmx_ctx_local_bufs(vm_ctx* c) {
     if (!c->lbufs) c->lbufs = new vmx_local_bufs();
     return c->lbufs;
-}
-void vmx_ctx_free_local_bufs(vm_ctx* c) {
-    if (c->lbufs) { c->lbufs->release(); delete c->lbufs; c->lbufs = nullptr; }
 }
