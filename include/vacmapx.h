@@ -307,19 +307,28 @@ typedef struct vm_sam_opts {
     int32_t asm_mode;            /* 1: the emitter of -mode asm, iterator_get_bam_dict_str / _comments (mammap_asm.py:22757, :22942): NM = the CIGAR's X / D / I
                                   * counts as mergecigar_nm_ takes them (:23125), MAPQ written as 60 (1 for 0) in the column and in SA, the second record
                                   * primary when the first has MAPQ 1 and it has not (:22847-22850) */
+    int32_t keep_unmapped;       /* 1: a read that emits no record line emits one unmapped line instead (FLAG 4, see vm_sam_emit). Lies in what was the
+                                  * struct's tail padding: its size is unchanged, and a caller that zeroes the struct has the option off */
 } vm_sam_opts;
 /* reads as blobs with offsets[n + 1] (quals / comments and their offsets may be NULL; a read whose quality string is empty or of another
  * length than its sequence gets '*'); recs / cigar_blob / status as returned by vm_align_batch for these reads. text: the lines
  * ('\n'-terminated) of all reads in read order, text_off[n + 1] delimits every read's lines (both vm_free). A read whose emission raises in
- * the reference (index past a sequence end) or whose status is not 0 emits nothing and counts in n_skipped, like the worker's except
- * (:24127-24134). */
+ * the reference (index past a sequence end) or whose status is not 0 emits no record line and counts in n_skipped, like the worker's except
+ * (:24127-24134); a read without records emits none either.
+ * keep_unmapped = 0: such a read emits nothing (the reference's behaviour). keep_unmapped = 1: it emits exactly one line, at its place in the text,
+ *   QNAME 4 * 0 0 * * 0 0 SEQ QUAL [RG:Z:rg_id] [comment fields]
+ * MAPQ 0 (the SAM specification's recommended practice for an unmapped read); SEQ the read as given, whole and in its own orientation whatever
+ * hardclip says, '*' for an empty read; QUAL by the record lines' rule; the comment fields by the record lines' filter (:20686), the line's own tags
+ * being SA, NM, MD, cs (never copied) and RG under rg_id; no NM, SA, MD, cs; asm_mode changes nothing on it. n_lines counts these lines; n_skipped
+ * keeps its meaning (status not 0, or the emission raised). A read that emits record lines emits them unchanged. */
 int vm_sam_emit(const vm_index*, const vm_sam_opts*, int64_t n_reads, const char* names, const int64_t* name_off, const char* seqs, const int64_t* seq_off,
                 const char* quals, const int64_t* qual_off, const char* comments, const int64_t* com_off, const vm_record* recs, int64_t n_recs,
                 const char* cigar_blob, const int32_t* status, int nthreads, char** text, int64_t** text_off, int64_t* n_lines, int64_t* n_skipped);
 /* The same lines made on the GPU (k_sam.hip: merged CIGAR, NM, MD / cs, SA and the line text are device work; the host validates, uploads and
  * fetches the text): vm_sam_emit's arguments without comments and nthreads, plus the context whose stream and buffers the call uses (one call at a
  * time per context; any number of contexts may share an index). Returns what vm_sam_emit returns for the same inputs byte for byte, text_off, n_lines
- * and n_skipped included (text and text_off: vm_free). VM_ERR_UNSUPPORTED when the index keeps a host copy of a reference with letters other than
+ * and n_skipped included (text and text_off: vm_free), under keep_unmapped too: the unmapped lines are made by a wave per read (k_sam_unmapped), also in
+ * a batch without any record. VM_ERR_UNSUPPORTED when the index keeps a host copy of a reference with letters other than
  * ACGTN (the device holds N for them, vm_sam_emit prints them); comments are copied by vm_sam_emit_device_comments below. VM_ERR_ARG for what vm_sam_emit refuses, for
  * a record of an unknown contig and for a CIGAR operator count of 2^31 or more. Three host waits per call.
  * vm_sam_emit_device_times: wall seconds of the context's latest call (either entry): upload, passes, the text's way back. */
@@ -329,7 +338,7 @@ int vm_sam_emit_device(vm_ctx*, const vm_index*, const vm_sam_opts*, int64_t n_r
 /* vm_sam_emit_device that also copies the reads' comments (emit_read()'s rule of :20686, applied by k_sam_lines): comments / com_off as vm_sam_emit
  * takes them, after qual_off. comments == NULL or com_off == NULL: no comments, exactly vm_sam_emit_device. The blob is uploaded from its first to its
  * last used byte. VM_ERR_ARG also for decreasing com_off and for a NULL blob under offsets that span bytes. Returns vm_sam_emit's bytes, text_off,
- * n_lines and n_skipped for the same inputs. */
+ * n_lines and n_skipped for the same inputs; under keep_unmapped the unmapped lines carry their reads' comment fields as vm_sam_emit's do. */
 int vm_sam_emit_device_comments(vm_ctx*, const vm_index*, const vm_sam_opts*, int64_t n_reads, const char* names, const int64_t* name_off, const char* seqs,
                                 const int64_t* seq_off, const char* quals, const int64_t* qual_off, const char* comments, const int64_t* com_off,
                                 const vm_record* recs, int64_t n_recs, const char* cigar_blob, const int32_t* status, char** text, int64_t** text_off,

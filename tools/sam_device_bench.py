@@ -8,6 +8,8 @@
         --only device: the device calls alone, for a run under `rocprofv3 --kernel-trace --stats -d DIR -- python tools/sam_device_bench.py ...`.
         --comments: every read carries its uBAM tags as a comment of about 10 KB (MM:Z:, ML:B:C with one value per 8 bases, MN:i:, the shape of
         profiles/bam_tags_reader.json), copied by both emitters (k_sam_lines' comment stage on the device).
+        --drop-every N: the records of every N-th read are taken out of the batch before the emitters see it (reads that emit no record line);
+        --keep-unmapped: vm_sam_opts.keep_unmapped = 1, those reads stay as FLAG 4 lines (k_sam_unmapped on the device; profiles/sam_keep_unmapped.json).
     python tools/sam_device_bench.py kernels --set default|eqx_md --stats DIR/.../*_kernel_stats.csv --calls N [--out profiles/sam_device_kernels.json]
         sums the k_sam_* rows of the statistics of an `emitter --only device --set ...` run per batch (N = device calls of the run: --calls + 1
         warm-up; k_sam_count_other, part of the index build, left out), copies the rows to profiles/sam_device_kernel_stats_<set>.csv, compares
@@ -21,6 +23,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
 import numpy as np
+
+
+class _Records:
+    """a batch's records without those of every n-th read: what sam_emit / sam_emit_device read of a RawBatch"""
+
+    def __init__(self, VL, raw, n):
+        keep = [i for i in range(raw.nrec) if raw.recs[i].read_idx % n != n - 1]
+        self.recs = (VL.Record * max(len(keep), 1))(*[raw.recs[i] for i in keep])
+        self.nrec, self.blob, self.status, self.whole = len(keep), raw.blob, raw.status, raw
+
+    def close(self):
+        self.whole.close()
+
 
 STEP_MS, TARGET_MS = 15.3, 1.5            # the project's 4096-read step (BENCH_r06.json) and a tenth of it
 
@@ -59,10 +74,14 @@ def emitter(args):
         cb = np.frombuffer(b''.join(coms), np.uint8); co = np.concatenate([[0], np.cumsum([len(x) for x in coms])]).astype(np.int64)
         del coms
     res = {'reads': args.reads, 'bases': int(so[-1]), 'host_threads': args.threads, 'calls': args.calls, 'comment_bytes': int(co[-1]) if co is not None else 0, 'sets': {}}
-    for tag, eqx, opts in (('default', 0, VL.SamOpts(0, 1, 0, 0, 0, 0, b'1', 0)), ('eqx_md', 1, VL.SamOpts(1, 1, 0, 0, 0, 0, b'1', 0))):
+    ku = int(args.keep_unmapped)
+    res.update({'keep_unmapped': ku, 'drop_every': args.drop_every})
+    for tag, eqx, opts in (('default', 0, VL.SamOpts(0, 1, 0, 0, 0, 0, b'1', 0, ku)), ('eqx_md', 1, VL.SamOpts(1, 1, 0, 0, 0, 0, b'1', 0, ku))):
         if args.set not in ('both', tag):
             continue
         raw = VL.align_batch_raw(ctx, idx, ctx.lib.params('H', eqx=eqx), sb, so)
+        if args.drop_every:
+            raw = _Records(VL, raw, args.drop_every)
         blob_bytes = int(max((raw.recs[i].cigar_off + raw.recs[i].cigar_len for i in range(raw.nrec)), default=0))
 
         def host():
@@ -197,6 +216,8 @@ if __name__ == '__main__':
     ap.add_argument('--reads', type=int, default=None); ap.add_argument('--calls', type=int, default=5); ap.add_argument('--threads', type=int, default=16)
     ap.add_argument('--set', choices=['both', 'default', 'eqx_md'], default='both', help='emitter: the option set(s) to run; kernels: the set the statistics belong to')
     ap.add_argument('--comments', action='store_true', help='emitter: a 10 KB uBAM-tag comment on every read')
+    ap.add_argument('--keep-unmapped', action='store_true', help='emitter: vm_sam_opts.keep_unmapped = 1')
+    ap.add_argument('--drop-every', type=int, default=0, help='emitter: take the records of every N-th read out of the batch')
     ap.add_argument('--only', choices=['both', 'device'], default='both'); ap.add_argument('--stats'); ap.add_argument('--out')
     ap.add_argument('--replicate', type=int, default=8); ap.add_argument('--ref-mb', type=float, default=100); ap.add_argument('--rounds', type=int, default=3)
     ap.add_argument('--tmp', default='/dev/shm/sam_device_bench'); ap.add_argument('-t', type=int, default=16)

@@ -5,8 +5,10 @@
 //   k_sam_ops                   one wavefront per record, run twice (sizes, then bytes): the raw CIGAR text is tokenised 64 bytes per step, equal
 //                               neighbours are merged by a segmented sum that carries from step to step, and every batch of up to 64 merged operators
 //                               is handled by the wave at once: merged text, query / reference prefix sums, NM, MD and cs.
-//   k_sam_lines                 one wavefront per output line, run twice (sizes, then bytes), with the scan of the line sizes in between. The
+//   k_sam_lines                 one wavefront per record line, run twice (sizes, then bytes), with the scan of the line sizes in between. The
 //                               read's comment (FASTA / FASTQ comment, uBAM tags as text) is filtered and appended by the same wave (sam_comment).
+//   k_sam_unmapped              vm_sam_opts.keep_unmapped only: one wavefront per read, run twice beside k_sam_lines; the FLAG 4 line of a read that
+//                               emits no record line, in the read's own line slot, so that one scan lays out both kinds of line in read order.
 //
 // ORDERING. Lanes hand data to one another through ballots, shuffles and LDS (vmx_wave_lds_fence between an LDS store and another lane's load:
 // workgroups are one wavefront). No kernel here loads a global byte that the same launch stored: the merged text, MD and cs that k_sam_lines
@@ -383,7 +385,8 @@ template <bool W>
 __device__ __forceinline__ void sam_line(const vmx_sam_in& A, const vmx_sam_work& K, int64_t p, int lane, char* text) {
     const vm_record rec = A.recs[K.ord[p]];
     const int64_t r = rec.read_idx;
-    if ((A.status && A.status[r] != 0) || K.rflag[r]) { if (!W && lane == 0) K.lsz[p] = 0; return; }
+    const int64_t sl = vmx_sam_slot(A, p, r);
+    if ((A.status && A.status[r] != 0) || K.rflag[r]) { if (!W && lane == 0) K.lsz[sl] = 0; return; }
     const int64_t f = K.first[r], nr = K.first[r + 1] - f;
     const int64_t qlen = A.seq_off[r + 1] - A.seq_off[r];
     const char* seq = A.seqs + (A.seq_off[r] - A.seq_base);
@@ -395,7 +398,7 @@ __device__ __forceinline__ void sam_line(const vmx_sam_in& A, const vmx_sam_work
     const bool cg = 2 * ri.n_ops > 65535 && A.cigar2cg;
     const bool rev = rec.strand != 1;
     const char clip = A.hardclip ? 'H' : 'S';
-    SamOut<W> O{W ? text + K.loff[p] : nullptr, 0, lane};
+    SamOut<W> O{W ? text + K.loff[sl] : nullptr, 0, lane};
     O.bytes(A.names + (A.name_off[r] - A.name_base), A.name_off[r + 1] - A.name_off[r]); O.ch('\t');
     O.num(K.flag[p]); O.ch('\t');
     O.bytes(A.cnames + A.cname_off[rec.contig], A.cname_off[rec.contig + 1] - A.cname_off[rec.contig]); O.ch('\t');
@@ -435,7 +438,7 @@ __device__ __forceinline__ void sam_line(const vmx_sam_in& A, const vmx_sam_work
         if (cl > 0) sam_comment<W>(O, A.comments + (A.com_off[r] - A.com_base), cl, A.rg != nullptr, cg, lane);
     }
     O.ch('\n');
-    if (!W && lane == 0) K.lsz[p] = O.pos;
+    if (!W && lane == 0) K.lsz[sl] = O.pos;
 }
 
 __global__ void __launch_bounds__(64) k_sam_lines(vmx_sam_in A, vmx_sam_work K, char* text, int write) {
@@ -445,17 +448,67 @@ __global__ void __launch_bounds__(64) k_sam_lines(vmx_sam_in A, vmx_sam_work K, 
     if (write) sam_line<true>(A, K, p, lane, text); else sam_line<false>(A, K, p, lane, text);
 }
 
+// ---- keep_unmapped: the line of a read that emits no record line (no record, a status other than 0, or a raise: rflag, stored by the size pass
+// of k_sam_ops, an earlier launch). One wavefront per read, run twice like k_sam_lines; the line lives in the read's own slot (vmx_sam_dev.h).
+// FLAG 4, MAPQ 0, the read whole and in its own orientation whatever hardclip and asm_mode say; RG and the comment as on a record line without CG.
+
+// n bytes of a and (b != nullptr) of b to da and db, 64 bytes of each per step, four steps in flight: the eight loads are issued before the
+// first store waits for its byte (few waves run here, one per unmapped read, so a copy is as long as its chain of load latencies)
+__device__ __forceinline__ void sam_copy2(char* da, const char* a, char* db, const char* b, int64_t n, int lane) {
+    for (int64_t x = lane; x < n; x += 256) {
+        char ca[4], cb[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { const bool in = x + 64 * k < n; ca[k] = in ? a[x + 64 * k] : 0; cb[k] = (in && b) ? b[x + 64 * k] : 0; }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) if (x + 64 * k < n) { da[x + 64 * k] = ca[k]; if (b) db[x + 64 * k] = cb[k]; }
+    }
+}
+#define SAM_UNMAPPED_COLS "\t4\t*\t0\t0\t*\t*\t0\t0\t"
+template <bool W>
+__device__ __forceinline__ void sam_unmapped(const vmx_sam_in& A, const vmx_sam_work& K, int64_t r, int lane, char* text) {
+    const int64_t sl = vmx_sam_slot(A, K.first[r + 1], r);
+    const bool none = (A.status && A.status[r] != 0) || K.first[r + 1] == K.first[r] || K.rflag[r];
+    if (!none) { if (!W && lane == 0) K.lsz[sl] = 0; return; }
+    const int64_t qlen = A.seq_off[r + 1] - A.seq_off[r];
+    const int64_t qual_len = (A.quals && A.qual_off) ? A.qual_off[r + 1] - A.qual_off[r] : 0;
+    const bool has_qual = qual_len > 0 && qual_len == qlen;
+    SamOut<W> O{W ? text + K.loff[sl] : nullptr, 0, lane};
+    O.bytes(A.names + (A.name_off[r] - A.name_base), A.name_off[r + 1] - A.name_off[r]);
+    O.bytes(SAM_UNMAPPED_COLS, (int64_t)sizeof(SAM_UNMAPPED_COLS) - 1);
+    if (qlen > 0) {                                                      // SEQ and QUAL, 64 bytes per step
+        if (W) sam_copy2(O.p + O.pos, A.seqs + (A.seq_off[r] - A.seq_base), O.p + O.pos + qlen + 1, has_qual ? A.quals + (A.qual_off[r] - A.qual_base) : nullptr, qlen, lane);
+        O.pos += qlen;
+    } else O.ch('*');
+    O.ch('\t');
+    if (has_qual) O.pos += qlen; else O.ch('*');
+    if (A.rg) { O.bytes("\tRG:Z:", 6); O.bytes(A.rg, A.rg_len); }
+    if (A.comments) {
+        const int64_t cl = A.com_off[r + 1] - A.com_off[r];
+        if (cl > 0) sam_comment<W>(O, A.comments + (A.com_off[r] - A.com_base), cl, A.rg != nullptr, false, lane);
+    }
+    O.ch('\n');
+    if (!W && lane == 0) K.lsz[sl] = O.pos;
+}
+
+__global__ void __launch_bounds__(64) k_sam_unmapped(vmx_sam_in A, vmx_sam_work K, char* text, int write) {
+    const int lane = (int)threadIdx.x;
+    const int64_t r = blockIdx.x;
+    if (!A.keep_unmapped || r >= A.n_reads || (K.res[0] & VMX_SAM_E_RECORD)) return;
+    if (write) sam_unmapped<true>(A, K, r, lane, text); else sam_unmapped<false>(A, K, r, lane, text);
+}
+
 // text_off[r] = where read r's lines begin (text_off[n_reads] = all bytes); lines and skipped reads counted as vm_sam_emit counts them
 __global__ void __launch_bounds__(256) k_sam_text_off(vmx_sam_in A, vmx_sam_work K, int64_t* text_off) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r > A.n_reads) return;
     if (K.res[0] & VMX_SAM_E_RECORD) { text_off[r] = 0; return; }
-    text_off[r] = K.loff[K.first[r]];
+    text_off[r] = K.loff[vmx_sam_slot(A, K.first[r], r)];
     if (r == A.n_reads) return;
-    if (A.status && A.status[r] != 0) { atomicAdd(&K.res[2], 1ull); return; }
     const int64_t nr = K.first[r + 1] - K.first[r];
-    if (nr == 0) return;
-    if (K.rflag[r]) atomicAdd(&K.res[2], 1ull); else atomicAdd(&K.res[1], (unsigned long long)nr);
+    const bool skipped = (A.status && A.status[r] != 0) || (nr > 0 && K.rflag[r]);
+    if (skipped) atomicAdd(&K.res[2], 1ull);
+    if (!skipped && nr > 0) atomicAdd(&K.res[1], (unsigned long long)nr);
+    else if (A.keep_unmapped) atomicAdd(&K.res[1], 1ull);               // its unmapped line
 }
 
 __global__ void __launch_bounds__(256) k_sam_count_other(const char* in, int64_t n, unsigned long long* count) {

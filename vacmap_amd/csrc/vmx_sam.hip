@@ -6,7 +6,8 @@
 // get_bam_dict_str / _comments output, tests/golden/sam.json): reassign_mapq (/root/reference/src/vacmap/mammap_clrnano.py:11661),
 // record order (:20855-20856), mergecigar_ (:4773), nm_from_cigar (output_functions.py:300), MD / cs (:19012, :19062), approximate SA
 // CIGARs (--fakecigar), CG tag switch (:20962, Q4), P_alignmentstring (:5391) with comment copying (:20686). A read whose emission would
-// raise in the reference (an index past a sequence end) produces no line and is counted as skipped, like the worker's except (:24127-24134).
+// raise in the reference (an index past a sequence end) produces no line and is counted as skipped, like the worker's except (:24127-24134);
+// under vm_sam_opts.keep_unmapped it, a read whose status is not 0 and a read without records each produce one FLAG 4 line (unmapped_line).
 // No device code in this file.
 #include "vmx_index_priv.h"
 #include <atomic>
@@ -208,6 +209,45 @@ static void revcomp_into(const char* s, int64_t n, std::string& out) {
     for (int64_t i = 0; i < n; ++i) out[(size_t)i] = (char)tab.v[(unsigned char)s[n - 1 - i]];
 }
 
+// :20686 — the tab-separated XX:T:value fields of the FASTA/Q comment whose tag is not on the line yet (t_rg / t_cg: the line carries RG / CG;
+// SA, NM, MD and cs count as on it always), each appended behind a tab
+static void append_comments(std::string& out, const char* com, int64_t com_len, bool t_rg, bool t_cg) {
+    std::vector<std::string> seen;
+    auto present = [&](const std::string& tg) {
+        static const char* fixed[] = {"QNAME", "FLAG", "RNAME", "POS", "MAPQ", "CIGAR", "RNEXT", "PNEXT", "TLEN", "SEQ", "QUAL", "SA", "NM", "MD", "cs"};
+        for (const char* f : fixed) if (tg == f) return true;
+        if ((tg == "RG" && t_rg) || (tg == "CG" && t_cg)) return true;
+        for (auto& s : seen) if (s == tg) return true;
+        return false;
+    };
+    int64_t p = 0;
+    while (p <= com_len) {
+        int64_t e = p; while (e < com_len && com[e] != '\t') ++e;
+        // one.split(':') must give exactly three parts: two colons
+        int colons = 0; int64_t c1 = -1, c2 = -1;
+        for (int64_t x = p; x < e; ++x) if (com[x] == ':') { ++colons; if (c1 < 0) c1 = x; else if (c2 < 0) c2 = x; }
+        if (colons == 2 && c1 - p == 2 && c2 - c1 == 2) {
+            const std::string tg(com + p, 2); const char ty = com[c1 + 1];
+            if (!present(tg) && (ty == 'A' || ty == 'i' || ty == 'f' || ty == 'Z' || ty == 'H' || ty == 'B')) { out.push_back('\t'); out.append(com + p, (size_t)(e - p)); seen.push_back(tg); }
+        }
+        p = e + 1;
+    }
+}
+
+// the line of a read that emits no record line, under vm_sam_opts.keep_unmapped (vacmapx.h states the rule; sam.py: unmapped_line): FLAG 4,
+// MAPQ 0, the read whole and in its own orientation
+static void unmapped_line(const vm_sam_opts* o, const char* name, int64_t name_len, const char* query, int64_t qlen, const char* qual, int64_t qual_len, const char* com,
+                          int64_t com_len, std::string& out) {
+    out.append(name, (size_t)name_len);
+    out.append("\t4\t*\t0\t0\t*\t*\t0\t0\t");
+    if (qlen > 0) out.append(query, (size_t)qlen); else out.push_back('*');
+    out.push_back('\t');
+    if (qual != nullptr && qual_len == qlen && qlen > 0) out.append(qual, (size_t)qlen); else out.push_back('*');
+    if (o->rg_id) { out.append("\tRG:Z:"); out.append(o->rg_id); }
+    if (com && com_len > 0) append_comments(out, com, com_len, o->rg_id != nullptr, false);
+    out.push_back('\n');
+}
+
 struct Scratch { std::vector<Rec> recs; std::vector<Ops> ops; std::vector<std::string> cig, md, cs, fake; std::vector<int64_t> nm, nops; std::string rcq, rcqual; };
 
 // SAM lines of one read appended to `out`; returns the number of lines, or -1 when the reference's emitter would raise
@@ -272,11 +312,11 @@ static int emit_read(const vm_index* mi, const std::string& bases, const vm_sam_
             if (o->hardclip) { a = r.q_st < 0 ? 0 : (r.q_st > qlen ? qlen : r.q_st); b = r.q_en < 0 ? 0 : (r.q_en > qlen ? qlen : r.q_en); if (b < a) b = a; }
             out.append(sq + a, (size_t)(b - a)); out.push_back('\t');
             if (has_qual) out.append(ql_ + a, (size_t)(b - a)); else out.push_back('*');
-            bool t_rg = false, t_cg = false, t_sa = false, t_md = false;
+            bool t_rg = false, t_cg = false;
             if (o->rg_id) { out.append("\tRG:Z:"); out.append(o->rg_id); t_rg = true; }
             if (cg) { out.append("\tCG:Z:"); out.append(S.cig[i]); t_cg = true; }
             if (n > 1) {
-                out.append("\tSA:Z:"); t_sa = true;
+                out.append("\tSA:Z:");
                 for (size_t x = 0; x < n; ++x) {
                     if (x == i) continue;
                     const Rec& y = S.recs[x];
@@ -285,31 +325,8 @@ static int emit_read(const vm_index* mi, const std::string& bases, const vm_sam_
                 }
             }
             out.append("\tNM:i:"); put_int(out, S.nm[i]);
-            if (o->md) { out.append("\tMD:Z:"); out.append(S.md[i]); out.append("\tcs:Z:"); out.append(S.cs[i]); t_md = true; }
-            if (com && com_len > 0) {
-                // :20686 — tab-separated XX:T:value fields of the FASTA/Q comment whose tag is not on the line yet
-                std::vector<std::string> seen;
-                auto present = [&](const std::string& tg) {
-                    static const char* fixed[] = {"QNAME", "FLAG", "RNAME", "POS", "MAPQ", "CIGAR", "RNEXT", "PNEXT", "TLEN", "SEQ", "QUAL", "SA", "NM", "MD", "cs"};
-                    for (const char* f : fixed) if (tg == f) return true;
-                    if ((tg == "RG" && t_rg) || (tg == "CG" && t_cg)) return true;
-                    (void)t_sa; (void)t_md;
-                    for (auto& s : seen) if (s == tg) return true;
-                    return false;
-                };
-                int64_t p = 0;
-                while (p <= com_len) {
-                    int64_t e = p; while (e < com_len && com[e] != '\t') ++e;
-                    // one.split(':') must give exactly three parts: two colons
-                    int colons = 0; int64_t c1 = -1, c2 = -1;
-                    for (int64_t x = p; x < e; ++x) if (com[x] == ':') { ++colons; if (c1 < 0) c1 = x; else if (c2 < 0) c2 = x; }
-                    if (colons == 2 && c1 - p == 2 && c2 - c1 == 2) {
-                        const std::string tg(com + p, 2); const char ty = com[c1 + 1];
-                        if (!present(tg) && (ty == 'A' || ty == 'i' || ty == 'f' || ty == 'Z' || ty == 'H' || ty == 'B')) { out.push_back('\t'); out.append(com + p, (size_t)(e - p)); seen.push_back(tg); }
-                    }
-                    p = e + 1;
-                }
-            }
+            if (o->md) { out.append("\tMD:Z:"); out.append(S.md[i]); out.append("\tcs:Z:"); out.append(S.cs[i]); }
+            if (com && com_len > 0) append_comments(out, com, com_len, t_rg, t_cg);
             out.push_back('\n');
             ++lines;
         }
@@ -350,15 +367,21 @@ int vm_sam_emit(const vm_index* mi, const vm_sam_opts* o, int64_t n_reads, const
                 { int64_t est = 0; for (int64_t r = c * CH; r < std::min(n_reads, (c + 1) * CH); ++r) est += 2 * (seq_off[r + 1] - seq_off[r]) + (seq_off[r + 1] - seq_off[r]) / 2 + 512; out.reserve((size_t)est); }
                 for (int64_t r = c * CH; r < std::min(n_reads, (c + 1) * CH); ++r) {
                     const size_t before = out.size();
-                    if (status && status[r] != 0) { skipped.fetch_add(1); continue; }
                     const int64_t nr = first[(size_t)r + 1] - first[(size_t)r];
-                    if (nr == 0) continue;
                     const int64_t ql = qual_off ? qual_off[r + 1] - qual_off[r] : 0;
                     const int64_t cl = com_off ? com_off[r + 1] - com_off[r] : 0;
-                    const int rc = emit_read(mi, bases, o, names + name_off[r], name_off[r + 1] - name_off[r], seqs + seq_off[r], seq_off[r + 1] - seq_off[r],
-                                             (quals && ql > 0) ? quals + qual_off[r] : nullptr, ql, (comments && cl > 0) ? comments + com_off[r] : nullptr, cl,
-                                             recs + first[(size_t)r], nr, cigar_blob, S, out);
-                    if (rc < 0) skipped.fetch_add(1); else lines.fetch_add(rc);
+                    const char* qual = (quals && ql > 0) ? quals + qual_off[r] : nullptr; const char* com = (comments && cl > 0) ? comments + com_off[r] : nullptr;
+                    bool none = true;                            // the read emits no record line
+                    if (status && status[r] != 0) skipped.fetch_add(1);
+                    else if (nr > 0) {
+                        const int rc = emit_read(mi, bases, o, names + name_off[r], name_off[r + 1] - name_off[r], seqs + seq_off[r], seq_off[r + 1] - seq_off[r], qual, ql, com, cl,
+                                                 recs + first[(size_t)r], nr, cigar_blob, S, out);
+                        if (rc < 0) skipped.fetch_add(1); else { lines.fetch_add(rc); none = false; }
+                    }
+                    if (none && o->keep_unmapped) {
+                        unmapped_line(o, names + name_off[r], name_off[r + 1] - name_off[r], seqs + seq_off[r], seq_off[r + 1] - seq_off[r], qual, ql, com, cl, out);
+                        lines.fetch_add(1);
+                    }
                     rlen[(size_t)r] = (int64_t)(out.size() - before);
                 }
             }

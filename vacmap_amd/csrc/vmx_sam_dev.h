@@ -15,11 +15,14 @@ struct vmx_sam_in {
     const int32_t* status;                                              // nullptr: every read has status 0
     const uint8_t* codes; const int64_t* coff; int32_t nseq;            // the index's reference codes (0..3 = ACGT, 4 = N) and contig offsets[nseq + 1]
     const char* cnames; const int64_t* cname_off;                       // contig names back to back, offsets[nseq + 1]
-    int32_t md, shortcs, cigar2cg, markunbalancetra, hardclip, fakecigar, asm_mode;
+    int32_t md, shortcs, cigar2cg, markunbalancetra, hardclip, fakecigar, asm_mode, keep_unmapped;
     const char* rg; int32_t rg_len;                                     // rg == nullptr: no RG:Z: tag
 };
 
 // per emitted record (position p = first[read] + rank in the emitted order)
+// LINE SLOTS. Without keep_unmapped a line is a record: slot = p, n_recs slots. With it every read has one slot more, behind its records' slots, for
+// its unmapped line (size 0 when the read emits record lines): the slot of position p of read r is p + r, the read's own slot first[r + 1] + r,
+// n_recs + n_reads slots in read order. vmx_sam_slot / vmx_sam_slots say so; read r's lines begin at loff[vmx_sam_slot(A, first[r], r)].
 struct vmx_sam_rinfo { int64_t cig_len, md_len, cs_len, n_ops, nm; int32_t flags, pad; };
 enum { VMX_SAM_F_RAISED = 1, VMX_SAM_F_ABORTED = 2 };                   // the read raises / MD and cs are empty (an operator outside =XIDSH)
 enum { VMX_SAM_E_COUNT = 1, VMX_SAM_E_RECORD = 2 };                     // res[0] bits: an operator count >= 2^31 / a record that names no read or no contig
@@ -31,14 +34,18 @@ struct vmx_sam_work {
     int32_t* rflag;                               // per read: 1 = the read raises
     vmx_sam_rinfo* ri;
     int64_t* tsz; int64_t* toff; char* scratch;   // merged CIGAR + MD + cs text per emitted record: sizes, offsets (n_recs + 1), bytes
-    int64_t* lsz; int64_t* loff;                  // line sizes and offsets (n_recs + 1)
+    int64_t* lsz; int64_t* loff;                  // line sizes and offsets by line slot (vmx_sam_slots + 1)
     unsigned long long* res;                      // [0] VMX_SAM_E_* bits, [1] lines, [2] skipped reads
 };
+
+__host__ __device__ inline int64_t vmx_sam_slot(const vmx_sam_in& A, int64_t p, int64_t r) { return A.keep_unmapped ? p + r : p; }
+__host__ __device__ inline int64_t vmx_sam_slots(const vmx_sam_in& A) { return A.n_recs + (A.keep_unmapped ? A.n_reads : 0); }
 
 __global__ void k_sam_count(vmx_sam_in A, vmx_sam_work K);
 __global__ void k_sam_order(vmx_sam_in A, vmx_sam_work K);
 __global__ void k_sam_ops(vmx_sam_in A, vmx_sam_work K, int write);
 __global__ void k_sam_lines(vmx_sam_in A, vmx_sam_work K, char* text, int write);
+__global__ void k_sam_unmapped(vmx_sam_in A, vmx_sam_work K, char* text, int write);
 __global__ void k_sam_text_off(vmx_sam_in A, vmx_sam_work K, int64_t* text_off);
 
 // grow-only buffers of a context's device emitter

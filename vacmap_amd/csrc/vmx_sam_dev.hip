@@ -1,6 +1,7 @@
 // vmx_sam_dev.hip — host side of the device SAM emitter (kernels: k_sam.hip): vmx_sam_emit_dev works on device pointers only, vm_sam_emit_device_comments
 // (and vm_sam_emit_device, the same without comments) is the C-ABI around it (validation, uploads through the context's upload helpers, the text's way back through the mailbox's page-locked landing
-// block). Three host waits per call: the operator pass's sizes, the lines' sizes, the text.
+// block). Three host waits per call: the operator pass's sizes, the lines' sizes, the text. Under vm_sam_opts.keep_unmapped the per-read pass
+// (k_sam_unmapped) runs beside k_sam_lines on both sides of wait 2 and adds no wait; it runs in a batch without records too.
 #include "vmx_sam_dev.h"
 #include "vmx_index_priv.h"
 
@@ -42,14 +43,15 @@ int contig_names(vm_ctx* c, vmx_sam_bufs* S, const vm_index* mi) {
 int vmx_sam_emit_dev(vm_ctx* c, const vm_index* mi, vmx_sam_in A, vmx_sam_totals* tot) {
     vmx_sam_bufs* S = vmx_ctx_sam_bufs(c);
     tot->text_bytes = 0; tot->n_lines = 0; tot->n_skipped = 0;
-    const int64_t n = A.n_reads, m = A.n_recs;
+    const int64_t n = A.n_reads, m = A.n_recs, ns = vmx_sam_slots(A);    // reads, records, line slots
+    const bool unm = A.keep_unmapped && n > 0;
     VMX_TRY(contig_names(c, S, mi));
     A.codes = mi->d_codes.as<const uint8_t>(); A.coff = mi->d_off.as<const int64_t>(); A.nseq = (int32_t)mi->names.size();
     A.cnames = S->cnames.as<const char>(); A.cname_off = S->cname_off.as<const int64_t>();
     VMX_TRY(S->cnt.reserve(8 * (size_t)(n + 1))); VMX_TRY(S->first.reserve(8 * (size_t)(n + 1))); VMX_TRY(S->rflag.reserve(4 * (size_t)(n + 1)));
     VMX_TRY(S->keep.reserve(4 * (size_t)(m + 1))); VMX_TRY(S->ord.reserve(4 * (size_t)(m + 1))); VMX_TRY(S->mq.reserve(4 * (size_t)(m + 1))); VMX_TRY(S->flag.reserve(4 * (size_t)(m + 1)));
     VMX_TRY(S->ri.reserve(sizeof(vmx_sam_rinfo) * (size_t)(m + 1)));
-    VMX_TRY(S->tsz.reserve(8 * (size_t)(m + 1))); VMX_TRY(S->toff.reserve(8 * (size_t)(m + 1))); VMX_TRY(S->lsz.reserve(8 * (size_t)(m + 1))); VMX_TRY(S->loff.reserve(8 * (size_t)(m + 1)));
+    VMX_TRY(S->tsz.reserve(8 * (size_t)(m + 1))); VMX_TRY(S->toff.reserve(8 * (size_t)(m + 1))); VMX_TRY(S->lsz.reserve(8 * (size_t)(ns + 1))); VMX_TRY(S->loff.reserve(8 * (size_t)(ns + 1)));
     VMX_TRY(S->res.reserve(64)); VMX_TRY(S->text_off.reserve(8 * (size_t)(n + 1))); VMX_TRY(S->scratch.reserve(16));
     vmx_sam_work K{};
     K.cnt = S->cnt.as<int64_t>(); K.first = S->first.as<int64_t>(); K.keep = S->keep.as<int32_t>(); K.ord = S->ord.as<int32_t>(); K.mq = S->mq.as<int32_t>();
@@ -57,7 +59,7 @@ int vmx_sam_emit_dev(vm_ctx* c, const vm_index* mi, vmx_sam_in A, vmx_sam_totals
     K.scratch = S->scratch.as<char>(); K.lsz = S->lsz.as<int64_t>(); K.loff = S->loff.as<int64_t>(); K.res = S->res.as<unsigned long long>();
     hipStream_t st = c->stream;
     VMX_HIP(hipMemsetAsync(K.cnt, 0, 8 * (size_t)(n + 1), st)); VMX_HIP(hipMemsetAsync(K.rflag, 0, 4 * (size_t)(n + 1), st)); VMX_HIP(hipMemsetAsync(K.res, 0, 64, st));
-    VMX_HIP(hipMemsetAsync(K.tsz, 0, 8 * (size_t)(m + 1), st)); VMX_HIP(hipMemsetAsync(K.lsz, 0, 8 * (size_t)(m + 1), st));
+    VMX_HIP(hipMemsetAsync(K.tsz, 0, 8 * (size_t)(m + 1), st)); VMX_HIP(hipMemsetAsync(K.lsz, 0, 8 * (size_t)(ns + 1), st));
     if (m) hipLaunchKernelGGL(k_sam_count, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, A, K);
     VMX_TRY(vmx_scan64(c, S->tmp, K.cnt, K.first, (size_t)n + 1));
     unsigned long long h_res[3] = {0, 0, 0}; int64_t h_tot = 0;
@@ -74,13 +76,15 @@ int vmx_sam_emit_dev(vm_ctx* c, const vm_index* mi, vmx_sam_in A, vmx_sam_totals
     K.scratch = S->scratch.as<char>();
     if (m) hipLaunchKernelGGL(k_sam_ops, dim3((unsigned)m), dim3(64), 0, st, A, K, 1);
     if (m) hipLaunchKernelGGL(k_sam_lines, dim3((unsigned)m), dim3(64), 0, st, A, K, (char*)nullptr, 0);
+    if (unm) hipLaunchKernelGGL(k_sam_unmapped, dim3((unsigned)n), dim3(64), 0, st, A, K, (char*)nullptr, 0);      // (rflag: the size pass of k_sam_ops, before wait 1)
     VMX_TRY(launched("k_sam_lines (sizes)"));
-    VMX_TRY(vmx_scan64(c, S->tmp, K.lsz, K.loff, (size_t)m + 1));
+    VMX_TRY(vmx_scan64(c, S->tmp, K.lsz, K.loff, (size_t)ns + 1));
     hipLaunchKernelGGL(k_sam_text_off, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, st, A, K, S->text_off.as<int64_t>());
-    VMX_TRY(vmx_fetch(c, &h_tot, K.loff + m, 1)); VMX_TRY(vmx_fetch(c, h_res, K.res, 3));
+    VMX_TRY(vmx_fetch(c, &h_tot, K.loff + ns, 1)); VMX_TRY(vmx_fetch(c, h_res, K.res, 3));
     VMX_TRY(wait(c));                                                    // wait 2: the lines' sizes
     VMX_TRY(S->text.reserve((size_t)h_tot + 16));
     if (m) hipLaunchKernelGGL(k_sam_lines, dim3((unsigned)m), dim3(64), 0, st, A, K, S->text.as<char>(), 1);
+    if (unm) hipLaunchKernelGGL(k_sam_unmapped, dim3((unsigned)n), dim3(64), 0, st, A, K, S->text.as<char>(), 1);
     VMX_TRY(launched("k_sam_lines"));
     tot->text_bytes = h_tot; tot->n_lines = (int64_t)h_res[1]; tot->n_skipped = (int64_t)h_res[2];
     return 0;
@@ -148,7 +152,7 @@ int vm_sam_emit_device_comments(vm_ctx* c, const vm_index* mi, const vm_sam_opts
     A.comments = with_c ? S->comments.as<const char>() : nullptr; A.com_off = with_c ? S->com_off.as<const int64_t>() : nullptr; A.com_base = clo;
     A.recs = S->recs.as<const vm_record>(); A.cigars = S->cigars.as<const char>(); A.cigars_len = cig_len;
     A.status = status ? S->status.as<const int32_t>() : nullptr;
-    A.md = o->md; A.shortcs = o->shortcs; A.cigar2cg = o->cigar2cg; A.markunbalancetra = o->markunbalancetra; A.hardclip = o->hardclip; A.fakecigar = o->fakecigar; A.asm_mode = o->asm_mode;
+    A.md = o->md; A.shortcs = o->shortcs; A.cigar2cg = o->cigar2cg; A.markunbalancetra = o->markunbalancetra; A.hardclip = o->hardclip; A.fakecigar = o->fakecigar; A.asm_mode = o->asm_mode; A.keep_unmapped = o->keep_unmapped ? 1 : 0;
     A.rg = o->rg_id ? S->rg.as<const char>() : nullptr; A.rg_len = (int32_t)rg_len;
     const double t1 = now_s();
     vmx_sam_totals tot;

@@ -508,6 +508,11 @@ def build_parser():
                    help='who makes the SAM text of a batch: -t host threads (default) or the GPU (merged CIGAR, NM, MD / cs, SA and the lines themselves, on '
                         'VMX_EMIT_CONTEXTS contexts of their own); with --copycomments, --bam-tags, or a reference that holds letters other than ACGTN, the host '
                         'emitter is used. device-comments: the GPU also copies the comments (--copycomments, --bam-tags), so only such a reference falls back')
+    p.add_argument('--keep-unmapped', action='store_true',
+                   help='modes H, L, S and R: a read that aligns nowhere, that the aligner skipped or whose SAM emission fails stays in the output as one '
+                        'unmapped record (FLAG 4, MAPQ 0, the read and its qualities as given, RG and its comment fields) at its input position, so that '
+                        'every input read occurs once; the reference, and the default, drop such reads. Every emitter and writer takes it; with '
+                        '--bam-writer native-sort the unmapped records come last')
     return p
 
 
@@ -545,6 +550,8 @@ def _parse_args(argv, comm, sw):
         sys.exit(str(e))
     if args.o != '-' and not (args.o.endswith('.sam') or args.o.endswith('.bam')):
         sys.exit("Output path must end with .sam, .bam, .sorted.bam, or be '-' for stdout.")
+    if args.keep_unmapped and args.mode == 'asm':
+        sys.exit('--keep-unmapped is for the read modes H, L, S and R: -mode asm takes whole contigs, which nobody wants as unmapped records')
     args.native_bam = args.bam_writer in ('native', 'native-sort') and args.o.endswith('.bam')
     args.native_sort = args.bam_writer == 'native-sort' and args.o.endswith('sorted.bam')
     if args.native_bam and args.o.endswith('sorted.bam') and not args.native_sort:
@@ -630,7 +637,7 @@ def _alignment_options(args, lib):
         rg = {'ID': '1', 'SM': 'sample'}
     mark = args.markunbalancetra or args.mode in ('H', 'L')          # mode defaults of vacmap:286-296 (False for asm unless asked)
     opts = SamOpts(int(bool(args.MD)), int(args.cs != 'long'), int(bool(args.L)), int(bool(mark)), int(bool(args.H)), int(bool(args.fakecigar)), rg['ID'].encode(),
-                   int(args.mode == 'asm'))
+                   int(args.mode == 'asm'), int(bool(args.keep_unmapped)))
     return prm, rg, opts
 
 

@@ -202,6 +202,23 @@ def format_line(d, comments=None):
     return '\t'.join(cols)
 
 
+def unmapped_line(name, query, qual, rg_id=None, comments=None):
+    """The line of a read that emits no record line, kept under --keep-unmapped (the reference drops such reads): FLAG 4, RNAME and CIGAR *,
+    POS 0 and MAPQ 0 (the SAM specification's recommended practice for an unmapped read, not format_line's default 255), the read whole and in
+    its own orientation ('*' when empty), QUAL when its length is the read's and not 0, RG:Z: under rg_id, the comment fields by format_line's
+    own filter. No NM, SA, MD or cs. vm_sam_emit and the device emitter state the same rule (vm_sam_opts.keep_unmapped)."""
+    d = {}
+    if rg_id is not None:
+        d['RG'] = rg_id
+    d['QNAME'] = name
+    d['MAPQ'] = '0'
+    if query:
+        d['SEQ'] = query
+        if qual is not None and len(qual) == len(query):
+            d['QUAL'] = qual
+    return format_line(d, comments)
+
+
 def _fake_cigar(r, qlen, clip):
     top = '%d%s' % (r[3], clip) if r[3] > 0 else ''
     tail = '%d%s' % (qlen - r[4], clip) if qlen - r[4] > 0 else ''
