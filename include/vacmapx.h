@@ -420,6 +420,35 @@ int64_t vm_bam_reader_read(vm_bam_reader*, int64_t max_reads, int64_t max_bases,
 int vm_bam_reader_stats(const vm_bam_reader*, double* out, int n);
 void vm_bam_reader_close(vm_bam_reader*);
 
+/* Bgzipped FASTQ on the GPU (driver: --fastx-reader native): the BGZF members of x.fastq.gz are inflated as for BAM input and the text is parsed on
+ * the device into the four blobs of vm_fastx_read, by vm_fastx_read's own rule for four-line FASTQ:
+ *   lines     a line ends at '\n', one trailing '\r' is dropped; the bytes after the file's last '\n' form a line if there are any.
+ *   blank     a line is blank when, after that drop, every byte is a space, a tab or '\r' (an empty line is blank).
+ *   states    0 expects a header, 1 the bases, 2 the '+' line, 3 the qualities. In state 0 a blank line is skipped and any other line is a
+ *             header; in states 1, 2 and 3 every line, blank or not, is taken and leads to the next state (3 leads to 0). So blank lines are
+ *             skipped between records only, an empty bases or quality line is an empty field, the '+' line is not looked at, and a quality
+ *             line may begin with '@'.
+ *   header    byte 0 is '@'; the name is what follows up to the first space or tab, the comment everything behind that one separator
+ *             (empty without one): "@ x" has an empty name and the comment "x".
+ *   fields    in the bases a-z become upper case, every other byte stays; qualities are copied as they are; the two lengths are not compared.
+ * Errors: the file ends in state 1, 2 or 3: VM_ERR_IO, "truncated FASTQ record". A header whose byte 0 is neither '@' nor '>': VM_ERR_IO,
+ * "not FASTA/FASTQ: " and the line's first 40 bytes. A header that begins with '>': VM_ERR_UNSUPPORTED (vm_fastx_read would read a multi-line
+ * FASTA record there; this reader is FASTQ only), the message names the 1-based record. A header is judged as soon as its line is complete, whether or not
+ * the record's other lines exist. As with vm_fastx_read, the call that meets an error returns only the error: the records in front of a bad
+ * header have been handed out by earlier calls as far as those calls reached, and what the failing call had gathered is dropped. A truncated, non-BGZF or corrupt member (CRC32, ISIZE) later in the file: VM_ERR_IO, the message names its file offset.
+ * vm_fastq_reader_open reads up to the first record: VM_ERR_UNSUPPORTED when the file is not gzip, is gzip without the BGZF BC subfield, or its
+ * first record begins with '>' (use vm_fastx_open then); VM_ERR_IO for an empty or unreadable file. vm_fastq_reader_read has vm_fastx_read's
+ * signature and return convention. vm_fastq_reader_stats: seconds of I/O thread work, waiting for it, upload + inflate, newlines + states +
+ * records, sizes + scans + copy, download, handing out; then windows, file bytes, inflated bytes, records (11 numbers), as of the latest window
+ * the caller has begun to take.
+ * An open reader owns its context (it parses ahead on a thread of its own): close it before other calls use the context or destroy it. */
+typedef struct vm_fastq_reader vm_fastq_reader;
+int vm_fastq_reader_open(vm_ctx*, const char* path, vm_fastq_reader** out);
+int64_t vm_fastq_reader_read(vm_fastq_reader*, int64_t max_reads, int64_t max_bases, char** names, int64_t** name_off, char** seqs, int64_t** seq_off, char** quals,
+                             int64_t** qual_off, char** comments, int64_t** com_off);
+int vm_fastq_reader_stats(const vm_fastq_reader*, double* out, int n);
+void vm_fastq_reader_close(vm_fastq_reader*);
+
 /* Coordinate-sorted BAM and its CSI index (driver: --bam-writer native-sort). Order: ascending uint32(refID) << 32 | uint32(pos + 1) << 1 | reverse
  * strand, ties in the order the lines arrived; refID -1 last. An external sort: every vm_bam_sorter_add_parts call encodes its lines and returns
  * their records in sorted order, uncompressed (a run; the caller writes it to a file of its own, an empty call leaves no run); the sorter keeps

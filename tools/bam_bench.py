@@ -252,6 +252,52 @@ def input_bench(args):
     _save(res, args.out)
 
 
+def fastq_input_bench(args):
+    """lib.FastqReader against lib.Fastx on the same bgzipped FASTQ and against Fastx on the plain text: args.rounds alternated rounds, each
+    reader's second pass over its file timed (the first grows pools and warms the page cache) -> profiles/fastq_input_reader.json"""
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import bam_input_cases as K
+    import fastq_input_cases as F
+    from vacmap_amd.lib import Context, FastqReader, Fastx
+    os.makedirs(args.tmp, exist_ok=True)
+    ctx = Context(0)
+    t0 = time.time()
+    pieces, _ = F.scale_text(int(args.gb * (1 << 30)))
+    total = sum(len(x) for x in pieces)
+    gz, plain = os.path.join(args.tmp, 'in.fastq.gz'), os.path.join(args.tmp, 'in.fastq')
+    K.write_bgzf_zlib(gz, pieces)
+    with open(plain, 'wb') as f:
+        for x in pieces:
+            f.write(x)
+    res = {'reads': len(pieces), 'text_bytes': total, 'gz_bytes': os.path.getsize(gz), 'generate_s': time.time() - t0, 'rounds': []}
+    del pieces
+
+    def run(make):
+        out = None
+        for _ in range(2):                                  # the second pass counts
+            t0 = time.time()
+            rd = make()
+            n = 0
+            for ch in iter(lambda: rd.read(4096), None):
+                n += len(ch['seqs_off']) - 1
+            dt = time.time() - t0
+            out = {'reads': n, 'wall_s': dt, 'reads_per_s': n / dt, 'inflated_GBps': total / dt / 1e9}
+            if hasattr(rd, 'stats'):
+                out['phases'] = rd.stats()
+            rd.close()
+        return out
+    for _ in range(args.rounds):
+        rnd = {'device_gz': run(lambda: FastqReader(ctx, gz)), 'host_gz': run(lambda: Fastx(gz, lib=ctx.lib)), 'host_plain': run(lambda: Fastx(plain, lib=ctx.lib))}
+        rnd['device_over_host_gz'] = rnd['device_gz']['reads_per_s'] / rnd['host_gz']['reads_per_s']
+        res['rounds'].append(rnd)
+        print(json.dumps({k: v if isinstance(v, float) else v['reads_per_s'] for k, v in rnd.items()}), flush=True)
+    res['device_faster_in_every_pair'] = all(r['device_over_host_gz'] > 1.0 for r in res['rounds'])
+    res['pipeline_wants_GBps_of_text'] = 8.0
+    ctx.close()
+    os.remove(gz); os.remove(plain)
+    _save(res, args.out)
+
+
 def tags_bench(args):
     """lib.BamReader on 15 kb reads that carry MM / ML / MN, with and without tags"""
     import struct
@@ -373,7 +419,7 @@ def input_driver(args):
 
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
-    ap.add_argument('what', choices=['kernels', 'driver', 'sorted', 'input', 'input-driver'])
+    ap.add_argument('what', choices=['kernels', 'driver', 'sorted', 'input', 'input-driver', 'fastq-input'])
     ap.add_argument('--only', default=None); ap.add_argument('--tags', action='store_true'); ap.add_argument('--run-timeout', type=float, default=600.0); ap.add_argument('--bench-steps', type=int, default=12)
     ap.add_argument('--gb', type=float, default=2.0); ap.add_argument('--reads', type=int, default=40960); ap.add_argument('--replicate', type=int, default=8); ap.add_argument('--ref-mb', type=float, default=100.0)
     ap.add_argument('--rounds', type=int, default=3); ap.add_argument('--t', type=int, default=16); ap.add_argument('--tmp', default='/tmp/vmx_bam_bench')
@@ -381,6 +427,8 @@ if __name__ == '__main__':
     a = ap.parse_args()
     if a.what == 'input':
         tags_bench(a) if a.tags else input_bench(a)
+    elif a.what == 'fastq-input':
+        fastq_input_bench(a)
     elif a.what == 'input-driver':
         input_driver(a)
     else:

@@ -99,6 +99,29 @@ __global__ void k_bam_in_aux_size(const uint8_t* buf, const int64_t* roff, int64
 __global__ void k_bam_in_aux_write(const uint8_t* buf, const int64_t* roff, int64_t n, const uint16_t* sel, int n_sel, int all, const int64_t* coff, const int64_t* kidx,
                                    char* out, int64_t* out_coff);
 
+// FASTQ input on the device (k_fastx_in.hip): newlines, line states, records, field sizes, field copy over one window of inflated text
+#define VMX_FQ_CHUNK 4096               // text bytes per wavefront of the newline kernels: 4 steps of 64 lanes x 16 bytes
+#define VMX_FQ_LTILE 256                // lines per workgroup of the state kernels
+// a line's effect on the parser state (0 header, 1 sequence, 2 '+', 3 qualities) as a map of 4 states packed 2 bits each, state s in bits 2s
+#define VMX_FQ_MAP_LINE 0x39u           // [1, 2, 3, 0]: a line that is not blank
+#define VMX_FQ_MAP_BLANK 0x38u          // [0, 2, 3, 0]: a blank line is skipped in state 0 only
+#define VMX_FQ_MAP_IDENT 0xe4u          // [0, 1, 2, 3]
+enum { VMX_FQ_E_FASTA = 1, VMX_FQ_E_HEADER = 2 };
+// what the parse leaves: complete records, the offset behind them (the rest is carried), the first bad header (record << 8 | code, all ones: none),
+// the state after the window's last line, whether the window's last byte is something else than a newline
+struct vmx_fq_result { int64_t n_rec, end; uint64_t err_key; int32_t end_state, tail_open; };
+__global__ void k_fq_nl_count(const uint8_t* buf, int64_t len, int64_t n_chunks, int64_t* cnt, vmx_fq_result* res);
+__global__ void k_fq_nl_pos(const uint8_t* buf, int64_t len, int64_t n_chunks, const int64_t* coff, int64_t n_lines, int closing, int64_t* ls);
+__global__ void k_fq_line_maps(const uint8_t* buf, const int64_t* ls, int64_t n_lines, uint8_t* map, uint8_t* tile_tot);
+__global__ void k_fq_tile_scan(uint8_t* tile, int64_t n_tiles);
+__global__ void k_fq_line_states(const uint8_t* map, const uint8_t* tile_pre, int64_t n_lines, int64_t* start);
+__global__ void k_fq_records(const int64_t* start, const int64_t* ridx, int64_t n_lines, int64_t* rline);
+__global__ void k_fq_result(const uint8_t* buf, const int64_t* ls, const int64_t* ridx, const int64_t* rline, int64_t n_lines, int64_t len, vmx_fq_result* res);
+__global__ void k_fq_sizes(const uint8_t* buf, const int64_t* ls, const int64_t* rline, int64_t n_rec, int64_t* nsz, int64_t* csz, int64_t* ssz, int64_t* qsz,
+                           unsigned long long* err_key);
+__global__ void k_fq_copy(const uint8_t* buf, const int64_t* ls, const int64_t* rline, int64_t n_rec, const int64_t* noff, const int64_t* coff, const int64_t* soff,
+                          const int64_t* qoff, uint8_t* names, uint8_t* comments, uint8_t* seqs, uint8_t* quals);
+
 // coordinate sort, merge and CSI (k_bam_sort.hip)
 #define VMX_BAM_RUN_SHIFT 40            // value of the merge sort: run << 40 | index in run
 #define VMX_BAM_RUN_MASK ((1ULL << VMX_BAM_RUN_SHIFT) - 1)

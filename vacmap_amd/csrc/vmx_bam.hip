@@ -1,5 +1,6 @@
 // vmx_bam.hip — C-ABI of the BAM writer (include/vacmapx.h): SAM text -> BAM records -> BGZF members, on the device (kernels: k_bam.hip), and, at the
-// end of the file, of the BAM reader (BGZF members -> records -> read blobs; kernels: k_bam_in.hip).
+// end of the file, of the BAM reader (BGZF members -> records -> read blobs; kernels: k_bam_in.hip) and of the reader of bgzipped FASTQ, which
+// shares the BAM reader's file / inflate half (BgzfIn) and its hand-out (HandOut) (kernels: k_fastx_in.hip).
 // A writer owns grow-only device buffers and one page-locked staging buffer: after the first windows, a call allocates nothing but its
 // malloc'ed result. Host work per call: gathering the text into the staging buffer, three small waits (line count, record sizes and
 // errors, compressed size) and the few float tokens the device cannot convert exactly (vmx_bam_patch).
@@ -747,9 +748,8 @@ struct DecodedWin { HostPinned names, seqs, quals, comments, off; int64_t n = 0;
 
 struct BamInChunk { HostPinned stage; MemberTab T; int64_t fpos = 0, got = 0; int rc = 0; std::string err; bool not_bgzf = false; double busy = 0; };
 
-}  // namespace
-
-struct vm_bam_reader {
+// The file and inflate half of a reader of BGZF input (vm_bam_reader, vm_fastq_reader): the file read ahead in chunks, the windows inflated behind the carried tail
+struct BgzfIn {
     vm_ctx* c = nullptr;
     int fd = -1;
     int64_t fsize = 0, chunk_bytes = 0, max_inf = 0;
@@ -758,23 +758,46 @@ struct vm_bam_reader {
     std::future<void> pre; bool pre_on = false; bool file_done = false; int64_t next_fpos = 0;
     InflateBufs z;
     DevBuf d_inf[2]; int which = 0; int64_t tail_off = 0, carry = 0;     // the bytes of d_inf[which] from tail_off on go in front of the next window
+    HostPinned pin;
+};
+
+// The hand-out half: two decoded windows, the one the caller takes records from and the one a producer thread fills
+struct HandOut {
+    DecodedWin win[2]; int cur = 0; int64_t at = 0;     // records [at, win[cur].n) are not handed out yet; the other slot is being produced
+    std::future<int> prod; bool prod_on = false; std::string prod_err;      // the next window, decoded ahead on a thread of its own
+    double handout_s = 0;
+};
+
+}  // namespace
+
+struct vm_bam_reader {
+    vm_ctx* c = nullptr;
+    BgzfIn in;
     bool hdr_done = false;
     DevBuf d_roff, d_walk, d_sz, d_off, d_tmp, d_names, d_seqs, d_quals, d_ooff;
     // tags asked for (vm_bam_reader_open_tags): the selection on the device, per-record comment bytes, their scan, the blob, the kept records' offsets, error key + drop counter
     bool tags_on = false; int tags_all = 0; std::vector<uint16_t> tags;
     DevBuf d_sel, d_csz, d_coff, d_comments, d_ocoff, d_aux;
     int64_t n_aux_dropped = 0;
-    HostPinned pin;
-    DecodedWin win[2]; int cur = 0; int64_t at = 0;     // records [at, win[cur].n) are not handed out yet; the other slot is being produced
-    std::future<int> prod; bool prod_on = false; std::string prod_err;      // the next window, decoded ahead on a thread of its own
+    HandOut h;
     int64_t n_seen = 0, n_dropped = 0;                  // records walked / without bases
     double st[13] = {0};                                // written by whoever produces a window
-    double pub[13] = {0}; double handout_s = 0;         // what vm_bam_reader_stats reads: st as of the latest window the caller's thread has taken over
+    double pub[13] = {0};                               // what vm_bam_reader_stats reads: st as of the latest window the caller's thread has taken over
+};
+
+struct vm_fastq_reader {
+    vm_ctx* c = nullptr;
+    BgzfIn in;
+    DevBuf d_cnt, d_coff, d_ls, d_map, d_tile, d_start, d_ridx, d_rline, d_res, d_sz, d_off, d_tmp, d_names, d_seqs, d_quals, d_comments;
+    HandOut h;
+    int64_t n_seen = 0;                                 // complete records of the windows so far
+    int fail_rc = 0; std::string fail_msg;              // a bad header ends the input behind the records in front of it: the next window is this error
+    double st[13] = {0}, pub[13] = {0};                 // as the BAM reader's, the first 11
 };
 
 namespace {
 
-void read_chunk_in(vm_bam_reader* r, int slot, int64_t fpos) {
+void read_chunk_in(BgzfIn* r, int slot, int64_t fpos) {
     BamInChunk& k = r->ch[slot];
     const double t0 = now_s();
     k.fpos = fpos; k.got = 0; k.rc = 0; k.err.clear(); k.T.m.clear(); k.T.foff.clear(); k.T.consumed = 0; k.T.inflated = 0;
@@ -813,27 +836,24 @@ int parse_bam_header(const uint8_t* h, int64_t n, int64_t* end) {
     return 1;
 }
 
-// the next window into win[slot]: 1 (its records decoded, possibly none), 0 at the end of the file, or a negative status
-int bam_in_window(vm_bam_reader* r, int slot) {
+// The next chunk's members inflated behind the carried tail: 1 (d_inf[which] holds *avail bytes, 64 more are reserved behind them; the caller sets
+// tail_off and carry anew), 0 when the file has been read to its end, or a negative status. st: the reader's statistics (I/O busy 0, I/O wait 1,
+// inflate 2, windows 7, file bytes 8, inflated bytes 9)
+int bgzf_in_window(BgzfIn* r, double* st, int64_t* avail_out) {
     vm_ctx* c = r->c;
-    DecodedWin& D = r->win[slot];
-    D.n = 0;
-    if (r->file_done) {
-        if (r->carry > 0) { set_error(r->hdr_done ? "truncated file: BAM record " + std::to_string((long long)r->n_seen + 1) + " is not complete" : "truncated file: the BAM header is not complete"); return VM_ERR_IO; }
-        return 0;
-    }
+    if (r->file_done) return 0;
     double t0 = now_s();
     if (r->pre_on) { r->pre.get(); r->pre_on = false; }
     else read_chunk_in(r, r->slot, r->next_fpos);
-    r->st[1] += now_s() - t0;
+    st[1] += now_s() - t0;
     BamInChunk& k = r->ch[r->slot];
-    r->st[0] += k.busy;
+    st[0] += k.busy;
     if (k.rc < 0) { set_error(k.err); return k.rc; }
     r->next_fpos = k.fpos + k.T.consumed;
     if (k.T.m.empty() || r->next_fpos >= r->fsize) r->file_done = true;
     else { r->pre_on = true; r->pre = std::async(std::launch::async, read_chunk_in, r, r->slot ^ 1, r->next_fpos); }
     r->slot ^= 1;
-    if (k.T.m.empty()) return bam_in_window(r, slot);                         // (an empty file tail: the end-of-file checks above)
+    if (k.T.m.empty()) return 0;                                              // (an empty file tail: the caller's end-of-file checks)
     // inflate behind the carried tail
     t0 = now_s();
     DevBuf& dst = r->d_inf[r->which ^ 1];
@@ -842,7 +862,50 @@ int bam_in_window(vm_bam_reader* r, int slot) {
     if (r->carry) VMX_HIP(hipMemcpyAsync(dst.p, r->d_inf[r->which].as<uint8_t>() + r->tail_off, (size_t)r->carry, hipMemcpyDeviceToDevice, c->stream));
     VMX_TRY(inflate_run(c, r->z, r->pin, (const uint8_t*)k.stage.p, k.T.consumed, k.T, dst.as<uint8_t>() + r->carry));
     r->which ^= 1;
-    r->st[2] += now_s() - t0; r->st[7] += 1; r->st[8] += (double)k.T.consumed; r->st[9] += (double)k.T.inflated;
+    st[2] += now_s() - t0; st[7] += 1; st[8] += (double)k.T.consumed; st[9] += (double)k.T.inflated;
+    *avail_out = avail;
+    return 1;
+}
+
+// the file opened, its size, the chunk and window sizes, both staging buffers
+int bgzf_in_open(BgzfIn* r, vm_ctx* c, const char* path) {
+    r->c = c;
+    r->fd = open(path, O_RDONLY);
+    if (r->fd < 0) { set_error(std::string("cannot open ") + path); return VM_ERR_IO; }
+    r->fsize = (int64_t)lseek(r->fd, 0, SEEK_END);
+    // VMX_BAM_IN_CHUNK / VMX_BAM_IN_MAXINF: compressed bytes per read and inflated bytes per window (tests cross many windows with small files)
+    r->chunk_bytes = 64 << 20; r->max_inf = (int64_t)512 << 20;
+    if (const char* e = getenv("VMX_BAM_IN_CHUNK")) r->chunk_bytes = std::max<int64_t>(atoll(e), 1 << 17);
+    if (const char* e = getenv("VMX_BAM_IN_MAXINF")) r->max_inf = std::max<int64_t>(atoll(e), 1 << 16);
+    if (r->fsize < 0) { set_error(std::string("cannot seek in ") + path); return VM_ERR_IO; }
+    const size_t stage = (size_t)std::min<int64_t>(r->chunk_bytes, std::max<int64_t>(r->fsize, 1));
+    VMX_TRY(r->ch[0].stage.reserve(stage));
+    VMX_TRY(r->ch[1].stage.reserve(stage));
+    VMX_TRY(r->pin.reserve(256));
+    return 0;
+}
+
+void bgzf_in_close(BgzfIn* r) {
+    if (r->pre_on) { r->pre.get(); r->pre_on = false; }
+    if (r->c) (void)hipStreamSynchronize(r->c->stream);
+    if (r->fd >= 0) { close(r->fd); r->fd = -1; }
+}
+
+// the next window into win[slot]: 1 (its records decoded, possibly none), 0 at the end of the file, or a negative status
+int reader_window(vm_bam_reader* r, int slot) {
+    vm_ctx* c = r->c;
+    DecodedWin& D = r->h.win[slot];
+    D.n = 0;
+    int64_t avail = 0;
+    const int irc = bgzf_in_window(&r->in, r->st, &avail);
+    if (irc < 0) return irc;
+    if (irc == 0) {
+        if (r->in.carry > 0) { set_error(r->hdr_done ? "truncated file: BAM record " + std::to_string((long long)r->n_seen + 1) + " is not complete" : "truncated file: the BAM header is not complete"); return VM_ERR_IO; }
+        return 0;
+    }
+    BgzfIn& in = r->in;
+    DevBuf& dst = in.d_inf[in.which];
+    double t0;
     int64_t begin = 0;
     if (!r->hdr_done) {
         std::vector<uint8_t> H;
@@ -855,8 +918,8 @@ int bam_in_window(vm_bam_reader* r, int slot) {
             if (pr < 0) { set_error("not a BAM file: the inflated stream does not begin with BAM\\1"); return VM_ERR_ARG; }
             if (pr > 0) break;
             if (have == avail) {
-                if (r->file_done && avail < 4) { set_error("not a BAM file: the inflated stream does not begin with BAM\\1"); return VM_ERR_ARG; }
-                r->tail_off = 0; r->carry = avail; return 1;
+                if (in.file_done && avail < 4) { set_error("not a BAM file: the inflated stream does not begin with BAM\\1"); return VM_ERR_ARG; }
+                in.tail_off = 0; in.carry = avail; return 1;
             }
         }
         r->hdr_done = true;
@@ -867,9 +930,9 @@ int bam_in_window(vm_bam_reader* r, int slot) {
     VMX_TRY(r->d_roff.reserve((size_t)(max_rec + 1) * 8));
     VMX_TRY(r->d_walk.reserve(sizeof(vmx_bam_in_walk)));
     hipLaunchKernelGGL(k_bam_in_walk, dim3(1), dim3(64), 0, c->stream, dst.as<const uint8_t>(), begin, avail, max_rec, r->d_roff.as<int64_t>(), r->d_walk.as<vmx_bam_in_walk>());
-    VMX_HIP(hipMemcpyAsync(r->pin.p, r->d_walk.p, sizeof(vmx_bam_in_walk), hipMemcpyDeviceToHost, c->stream));
+    VMX_HIP(hipMemcpyAsync(in.pin.p, r->d_walk.p, sizeof(vmx_bam_in_walk), hipMemcpyDeviceToHost, c->stream));
     VMX_TRY(sync(c));
-    vmx_bam_in_walk W; memcpy(&W, r->pin.p, sizeof W);
+    vmx_bam_in_walk W; memcpy(&W, in.pin.p, sizeof W);
     r->st[3] += now_s() - t0;
     if (W.err_key != ~0ull) {
         set_error("BAM record " + std::to_string((long long)(r->n_seen + (int64_t)(W.err_key >> 8)) + 1) + ": block_size is below 32, smaller than its name, CIGAR and bases, or above 512 MB");
@@ -877,7 +940,7 @@ int bam_in_window(vm_bam_reader* r, int slot) {
     }
     const int64_t n = W.n_rec, rec0 = r->n_seen;
     r->n_seen += n;
-    r->tail_off = W.end; r->carry = avail - W.end;
+    in.tail_off = W.end; in.carry = avail - W.end;
     if (n == 0) return 1;
     t0 = now_s();
     const size_t col = (size_t)(n + 1);
@@ -885,7 +948,7 @@ int bam_in_window(vm_bam_reader* r, int slot) {
     int64_t* sz = r->d_sz.as<int64_t>(); int64_t* off = r->d_off.as<int64_t>(); int64_t* oo = r->d_ooff.as<int64_t>();
     hipLaunchKernelGGL(k_bam_in_sizes, dim3(grid256(n + 1)), dim3(256), 0, c->stream, dst.as<const uint8_t>(), r->d_roff.as<const int64_t>(), n, sz, sz + col, sz + 2 * col, sz + 3 * col);
     for (int j = 0; j < 4; ++j) VMX_TRY(vmx_scan64(c, r->d_tmp, sz + j * col, off + j * col, col));
-    int64_t* tot = (int64_t*)r->pin.p;
+    int64_t* tot = (int64_t*)in.pin.p;
     for (int j = 0; j < 4; ++j) VMX_HIP(hipMemcpyAsync(tot + j, off + j * col + n, 8, hipMemcpyDeviceToHost, c->stream));
     const unsigned aux_grid = (unsigned)((n + 1 + 3) / 4);
     if (r->tags_on) {                                                   // the comment text's size pass, its scan, the first malformed record and the dropped fields
@@ -940,27 +1003,211 @@ int bam_in_window(vm_bam_reader* r, int slot) {
     return 1;
 }
 
+// ------------------------------------------------------------------------------------------------ FASTQ windows (kernels: k_fastx_in.hip)
+
+// the first 40 bytes of the header line of the window's record `rec`, as vm_fastx_read quotes them (the stream is idle)
+int fq_header_text(vm_fastq_reader* r, const uint8_t* buf, int64_t rec, std::string* out) {
+    int64_t k = 0, ab[2] = {0, 0};
+    VMX_HIP(hipMemcpy(&k, r->d_rline.as<int64_t>() + rec, 8, hipMemcpyDeviceToHost));
+    VMX_HIP(hipMemcpy(ab, r->d_ls.as<int64_t>() + k, 16, hipMemcpyDeviceToHost));
+    char line[48];
+    const int64_t raw = std::min<int64_t>(ab[1] - 1 - ab[0], 41);
+    if (raw > 0) VMX_HIP(hipMemcpy(line, buf + ab[0], (size_t)raw, hipMemcpyDeviceToHost));
+    int64_t len = raw;
+    if (len > 0 && len < 41 && line[len - 1] == '\r') --len;              // (the line's last byte: its '\r' is not part of it)
+    out->assign(line, (size_t)std::min<int64_t>(len, 40));
+    return 0;
+}
+
+// the next window into win[slot]: 1 (its complete records parsed, possibly none), 0 at the end of the file, or a negative status
+int reader_window(vm_fastq_reader* r, int slot) {
+    vm_ctx* c = r->c;
+    BgzfIn& in = r->in;
+    DecodedWin& D = r->h.win[slot];
+    D.n = 0;
+    if (r->fail_rc < 0) { set_error(r->fail_msg); return r->fail_rc; }
+    int64_t avail = 0;
+    const int irc = bgzf_in_window(&in, r->st, &avail);
+    if (irc < 0) return irc;
+    if (irc == 0) {
+        if (in.carry > 0) { set_error("truncated FASTQ record: the file ends inside record " + std::to_string((long long)r->n_seen + 1)); return VM_ERR_IO; }
+        return 0;
+    }
+    const bool last = in.file_done;                                         // the bytes behind the last newline are a line only here
+    const uint8_t* buf = in.d_inf[in.which].as<const uint8_t>();
+    if (avail == 0) { in.tail_off = 0; in.carry = 0; return 1; }
+    // newlines
+    double t0 = now_s();
+    const int64_t nch = (avail + VMX_FQ_CHUNK - 1) / VMX_FQ_CHUNK;
+    VMX_TRY(r->d_cnt.reserve((size_t)(nch + 1) * 8)); VMX_TRY(r->d_coff.reserve((size_t)(nch + 1) * 8)); VMX_TRY(r->d_res.reserve(sizeof(vmx_fq_result)));
+    vmx_fq_result* res = r->d_res.as<vmx_fq_result>();
+    VMX_HIP(hipMemsetAsync(res, 0xff, sizeof(vmx_fq_result), c->stream));
+    const unsigned gch = (unsigned)((nch + 3) / 4);
+    hipLaunchKernelGGL(k_fq_nl_count, dim3(gch), dim3(256), 0, c->stream, buf, avail, nch, r->d_cnt.as<int64_t>(), res);
+    VMX_TRY(vmx_scan64(c, r->d_tmp, r->d_cnt.as<const int64_t>(), r->d_coff.as<int64_t>(), (size_t)nch + 1));
+    VMX_HIP(hipMemcpyAsync(in.pin.p, r->d_coff.as<int64_t>() + nch, 8, hipMemcpyDeviceToHost, c->stream));
+    VMX_HIP(hipMemcpyAsync(in.pin.p + 8, res, sizeof(vmx_fq_result), hipMemcpyDeviceToHost, c->stream));
+    VMX_TRY(sync(c));
+    int64_t n_nl; memcpy(&n_nl, in.pin.p, 8);
+    vmx_fq_result R; memcpy(&R, in.pin.p + 8, sizeof R);
+    const int closing = last && R.tail_open ? 1 : 0;
+    const int64_t n_lines = n_nl + closing;
+    if (n_lines == 0) { in.tail_off = 0; in.carry = avail; r->st[3] += now_s() - t0; return 1; }      // (a line longer than the window so far)
+    VMX_TRY(r->d_ls.reserve((size_t)(n_lines + 1) * 8));
+    hipLaunchKernelGGL(k_fq_nl_pos, dim3(gch), dim3(256), 0, c->stream, buf, avail, nch, r->d_coff.as<const int64_t>(), n_lines, closing, r->d_ls.as<int64_t>());
+    // states and records
+    const int64_t ntile = (n_lines + VMX_FQ_LTILE) / VMX_FQ_LTILE;           // (covers line index n_lines, the scan's total slot)
+    VMX_TRY(r->d_map.reserve((size_t)n_lines)); VMX_TRY(r->d_tile.reserve((size_t)ntile));
+    VMX_TRY(r->d_start.reserve((size_t)(n_lines + 1) * 8)); VMX_TRY(r->d_ridx.reserve((size_t)(n_lines + 1) * 8)); VMX_TRY(r->d_rline.reserve((size_t)(n_lines + 1) * 8));
+    const int64_t* ls = r->d_ls.as<const int64_t>();
+    hipLaunchKernelGGL(k_fq_line_maps, dim3((unsigned)ntile), dim3(VMX_FQ_LTILE), 0, c->stream, buf, ls, n_lines, r->d_map.as<uint8_t>(), r->d_tile.as<uint8_t>());
+    hipLaunchKernelGGL(k_fq_tile_scan, dim3(1), dim3(1024), 0, c->stream, r->d_tile.as<uint8_t>(), ntile);
+    hipLaunchKernelGGL(k_fq_line_states, dim3((unsigned)ntile), dim3(VMX_FQ_LTILE), 0, c->stream, r->d_map.as<const uint8_t>(), r->d_tile.as<const uint8_t>(), n_lines, r->d_start.as<int64_t>());
+    VMX_TRY(vmx_scan64(c, r->d_tmp, r->d_start.as<const int64_t>(), r->d_ridx.as<int64_t>(), (size_t)n_lines + 1));
+    hipLaunchKernelGGL(k_fq_records, dim3(grid256(n_lines)), dim3(256), 0, c->stream, r->d_start.as<const int64_t>(), r->d_ridx.as<const int64_t>(), n_lines, r->d_rline.as<int64_t>());
+    hipLaunchKernelGGL(k_fq_result, dim3(1), dim3(64), 0, c->stream, buf, ls, r->d_ridx.as<const int64_t>(), r->d_rline.as<const int64_t>(), n_lines, avail, res);
+    VMX_HIP(hipMemcpyAsync(in.pin.p, res, sizeof(vmx_fq_result), hipMemcpyDeviceToHost, c->stream));
+    VMX_TRY(sync(c));
+    memcpy(&R, in.pin.p, sizeof R);
+    r->st[3] += now_s() - t0;
+    if (R.n_rec < 0 || R.end < 0 || R.end > avail) { set_error("vm_fastq_reader: the record pass left an offset outside the window"); return VM_ERR_HIP; }
+    in.tail_off = R.end; in.carry = avail - R.end;
+    int64_t n = R.n_rec;
+    const int64_t rec0 = r->n_seen;
+    // sizes, offsets, the first bad header (k_fq_result has looked at the header of the record that lacks lines, k_fq_sizes looks at the complete ones), the copy
+    t0 = now_s();
+    const size_t col = (size_t)(n + 1);
+    VMX_TRY(r->d_sz.reserve(col * 8 * 4)); VMX_TRY(r->d_off.reserve(col * 8 * 4));
+    int64_t* sz = r->d_sz.as<int64_t>(); int64_t* off = r->d_off.as<int64_t>();
+    const int64_t* rline = r->d_rline.as<const int64_t>();
+    uint64_t key = R.err_key;
+    if (n > 0) {
+        hipLaunchKernelGGL(k_fq_sizes, dim3((unsigned)((n + 1 + 3) / 4)), dim3(256), 0, c->stream, buf, ls, rline, n, sz, sz + col, sz + 2 * col, sz + 3 * col, (unsigned long long*)&res->err_key);
+        for (int j = 0; j < 4; ++j) VMX_TRY(vmx_scan64(c, r->d_tmp, sz + j * col, off + j * col, col));
+        VMX_HIP(hipMemcpyAsync(in.pin.p, &res->err_key, 8, hipMemcpyDeviceToHost, c->stream));
+        VMX_TRY(sync(c));
+        memcpy(&key, in.pin.p, 8);
+    }
+    if (key != ~0ull) {                                                     // the records in front of the bad header are good; the input ends there
+        const int64_t bad = (int64_t)(key >> 8);
+        const std::string num = std::to_string((long long)(rec0 + bad) + 1);
+        if ((int)(key & 0xff) == VMX_FQ_E_FASTA) {
+            r->fail_rc = VM_ERR_UNSUPPORTED;
+            r->fail_msg = "record " + num + " begins with '>': FASTA is not read on the device, use the host reader (vm_fastx_read; driver: --fastx-reader host)";
+        } else {
+            std::string text;
+            VMX_TRY(fq_header_text(r, buf, bad, &text));
+            r->fail_rc = VM_ERR_IO;
+            r->fail_msg = "not FASTA/FASTQ: " + text;
+        }
+        n = bad;
+        if (n == 0) { set_error(r->fail_msg); return r->fail_rc; }
+    }
+    if (n == 0) return 1;
+    r->n_seen += n;
+    int64_t* tot = (int64_t*)in.pin.p;
+    for (int j = 0; j < 4; ++j) VMX_HIP(hipMemcpyAsync(tot + j, off + j * col + n, 8, hipMemcpyDeviceToHost, c->stream));
+    VMX_TRY(sync(c));
+    const int64_t tn = tot[0], tc = tot[1], ts = tot[2], tq = tot[3];
+    VMX_TRY(r->d_names.reserve((size_t)tn + 16)); VMX_TRY(r->d_comments.reserve((size_t)tc + 16)); VMX_TRY(r->d_seqs.reserve((size_t)ts + 16)); VMX_TRY(r->d_quals.reserve((size_t)tq + 16));
+    hipLaunchKernelGGL(k_fq_copy, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, buf, ls, rline, n, off, off + col, off + 2 * col, off + 3 * col, r->d_names.as<uint8_t>(),
+                       r->d_comments.as<uint8_t>(), r->d_seqs.as<uint8_t>(), r->d_quals.as<uint8_t>());
+    VMX_TRY(sync(c));
+    r->st[4] += now_s() - t0;
+    // download: names, bases, qualities, comments and their offsets, in the order the hand-out reads them
+    t0 = now_s();
+    VMX_TRY(D.names.reserve((size_t)tn + 8)); VMX_TRY(D.seqs.reserve((size_t)ts + 8)); VMX_TRY(D.quals.reserve((size_t)tq + 8)); VMX_TRY(D.comments.reserve((size_t)tc + 8));
+    VMX_TRY(D.off.reserve((size_t)(n + 1) * 8 * 4));
+    if (tn) VMX_HIP(hipMemcpyAsync(D.names.p, r->d_names.p, (size_t)tn, hipMemcpyDeviceToHost, c->stream));
+    if (ts) VMX_HIP(hipMemcpyAsync(D.seqs.p, r->d_seqs.p, (size_t)ts, hipMemcpyDeviceToHost, c->stream));
+    if (tq) VMX_HIP(hipMemcpyAsync(D.quals.p, r->d_quals.p, (size_t)tq, hipMemcpyDeviceToHost, c->stream));
+    if (tc) VMX_HIP(hipMemcpyAsync(D.comments.p, r->d_comments.p, (size_t)tc, hipMemcpyDeviceToHost, c->stream));
+    static const int col_of[4] = {0, 2, 3, 1};                              // host order names, bases, qualities, comments <- device columns name, comment, bases, qualities
+    for (int j = 0; j < 4; ++j) VMX_HIP(hipMemcpyAsync((int64_t*)D.off.p + j * (n + 1), off + col_of[j] * col, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    VMX_TRY(sync(c));
+    r->st[5] += now_s() - t0;
+    D.n = n; r->st[10] += (double)n;
+    return 1;
+}
+
+// ------------------------------------------------------------------------------------------------ hand-out, shared by both readers
+
 // the producer thread: the device belongs to the reader's context, the message to the thread that asks for it
-int bam_in_produce(vm_bam_reader* r, int slot) {
+template <class R> int reader_produce(R* r, int slot) {
     (void)hipSetDevice(r->c->device);
-    const int rc = bam_in_window(r, slot);
-    if (rc < 0) r->prod_err = vm_last_error();
+    const int rc = reader_window(r, slot);
+    if (rc < 0) r->h.prod_err = vm_last_error();
     return rc;
 }
 
 // win[cur] is drained: the window produced ahead becomes the current one and the next is started in the drained slot
-int bam_in_next(vm_bam_reader* r) {
-    const int nxt = r->cur ^ 1;
+template <class R> int reader_next(R* r) {
+    HandOut& h = r->h;
+    const int nxt = h.cur ^ 1;
     int rc;
-    if (r->prod_on) { rc = r->prod.get(); r->prod_on = false; if (rc < 0) set_error(r->prod_err); }
-    else rc = bam_in_window(r, nxt);
+    if (h.prod_on) { rc = h.prod.get(); h.prod_on = false; if (rc < 0) set_error(h.prod_err); }
+    else rc = reader_window(r, nxt);
     memcpy(r->pub, r->st, sizeof r->pub);                               // (no window is in production here)
     if (rc < 0) return rc;
-    r->cur = nxt; r->at = 0;
-    if (rc == 0) { r->win[nxt].n = 0; return 0; }
-    r->prod_on = true; r->prod_err.clear();
-    r->prod = std::async(std::launch::async, bam_in_produce, r, nxt ^ 1);
+    h.cur = nxt; h.at = 0;
+    if (rc == 0) { h.win[nxt].n = 0; return 0; }
+    h.prod_on = true; h.prod_err.clear();
+    h.prod = std::async(std::launch::async, reader_produce<R>, r, nxt ^ 1);
     return 1;
+}
+
+// up to max_reads records, cut where max_bases is reached as vm_fastx_read cuts; what is not handed out stays for the next call.
+// with_comments: the windows hold a fourth blob and offset column
+template <class R> int64_t reader_read(R* r, bool with_comments, const char* who, int64_t max_reads, int64_t max_bases, char** names, int64_t** name_off, char** seqs,
+                                       int64_t** seq_off, char** quals, int64_t** qual_off, char** comments, int64_t** com_off) {
+    const std::string oom = std::string(who) + ": out of host memory";
+    HandOut& h = r->h;
+    try {
+        Grow nb, sb, qb, cb;
+        std::vector<int64_t> no(1, 0), so(1, 0), qo(1, 0), co(1, 0);
+        int64_t n = 0;
+        bool end = false;
+        while (n < max_reads && (int64_t)sb.n < max_bases && !end) {
+            if (h.at >= h.win[h.cur].n) {
+                const int rc = reader_next(r);
+                if (rc < 0) return rc;
+                if (rc == 0) end = true;
+                continue;
+            }
+            const double t0 = now_s();
+            const DecodedWin& D = h.win[h.cur];
+            const int64_t nk = D.n;
+            const int64_t* hn = (const int64_t*)D.off.p; const int64_t* hs = hn + (nk + 1); const int64_t* hq = hs + (nk + 1);
+            const int64_t a = h.at;
+            int64_t m = 0;
+            while (a + m < nk && n + m < max_reads && (int64_t)sb.n + (hs[a + m] - hs[a]) < max_bases) ++m;
+            if (!nb.append(D.names.p + hn[a], (size_t)(hn[a + m] - hn[a])) || !sb.append(D.seqs.p + hs[a], (size_t)(hs[a + m] - hs[a])) ||
+                !qb.append(D.quals.p + hq[a], (size_t)(hq[a + m] - hq[a]))) { set_error(oom); return VM_ERR_OOM; }
+            const int64_t n0 = no.back() - hn[a], s0 = so.back() - hs[a], q0 = qo.back() - hq[a];
+            for (int64_t j = 1; j <= m; ++j) { no.push_back(n0 + hn[a + j]); so.push_back(s0 + hs[a + j]); qo.push_back(q0 + hq[a + j]); }
+            if (with_comments) {                                        // the comments are cut where the records are
+                const int64_t* hc = hq + (nk + 1);
+                if (!cb.append(D.comments.p + hc[a], (size_t)(hc[a + m] - hc[a]))) { set_error(oom); return VM_ERR_OOM; }
+                const int64_t c0 = co.back() - hc[a];
+                for (int64_t j = 1; j <= m; ++j) co.push_back(c0 + hc[a + j]);
+            }
+            h.at += m; n += m;
+            h.handout_s += now_s() - t0;
+        }
+        auto giveo = [](const std::vector<int64_t>& v, int64_t** p) { *p = (int64_t*)malloc(8 * v.size()); memcpy(*p, v.data(), 8 * v.size()); };
+        *names = nb.release(); *seqs = sb.release(); *quals = qb.release(); *comments = cb.release();
+        giveo(no, name_off); giveo(so, seq_off); giveo(qo, qual_off);
+        if (!with_comments) co.assign((size_t)n + 1, 0);
+        giveo(co, com_off);
+        return n;
+    }
+    catch (const std::bad_alloc&) { set_error(oom); return VM_ERR_OOM; }
+}
+
+template <class R> void reader_close(R* r) {
+    if (r->h.prod_on) (void)r->h.prod.get();
+    bgzf_in_close(&r->in);
+    delete r;
 }
 
 }  // namespace
@@ -990,11 +1237,7 @@ int vm_bgzf_decompress(vm_ctx* c, const void* in, int64_t n, char** out, int64_t
 
 void vm_bam_reader_close(vm_bam_reader* r) {
     if (!r) return;
-    if (r->prod_on) (void)r->prod.get();
-    if (r->pre_on) r->pre.get();
-    (void)hipStreamSynchronize(r->c->stream);
-    if (r->fd >= 0) close(r->fd);
-    delete r;
+    reader_close(r);
 }
 
 int vm_bam_reader_open(vm_ctx* c, const char* path, vm_bam_reader** out) { return vm_bam_reader_open_tags(c, path, nullptr, out); }
@@ -1013,35 +1256,23 @@ int vm_bam_reader_open_tags(vm_ctx* c, const char* path, const char* tags, vm_ba
             if (q[2] == 0) break;
         }
     }
-    const int fd = open(path, O_RDONLY);
-    if (fd < 0) { set_error(std::string("cannot open ") + path); return VM_ERR_IO; }
     vm_bam_reader* r = new vm_bam_reader();
-    r->c = c; r->fd = fd;
+    r->c = c;
     r->tags_on = all || !sel.empty(); r->tags_all = all ? 1 : 0; r->tags = sel;
-    r->fsize = (int64_t)lseek(fd, 0, SEEK_END);
-    // VMX_BAM_IN_CHUNK / VMX_BAM_IN_MAXINF: compressed bytes per read and inflated bytes per window (tests cross many windows with small files)
-    r->chunk_bytes = 64 << 20; r->max_inf = (int64_t)512 << 20;
-    if (const char* e = getenv("VMX_BAM_IN_CHUNK")) r->chunk_bytes = std::max<int64_t>(atoll(e), 1 << 17);
-    if (const char* e = getenv("VMX_BAM_IN_MAXINF")) r->max_inf = std::max<int64_t>(atoll(e), 1 << 16);
-    int rc = r->fsize < 0 ? (int)VM_ERR_IO : 0;
-    if (rc < 0) set_error(std::string("cannot seek in ") + path);
-    const size_t stage = (size_t)std::min<int64_t>(r->chunk_bytes, std::max<int64_t>(r->fsize, 1));
-    if (rc == 0) rc = r->ch[0].stage.reserve(stage);
-    if (rc == 0) rc = r->ch[1].stage.reserve(stage);
-    if (rc == 0) rc = r->pin.reserve(256);
+    int rc = bgzf_in_open(&r->in, c, path);
     if (rc == 0 && r->tags_on) rc = r->d_sel.reserve(sel.size() * 2 + 8);
     if (rc == 0 && !sel.empty() && hipMemcpy(r->d_sel.p, sel.data(), sel.size() * 2, hipMemcpyHostToDevice) != hipSuccess) { set_error("vm_bam_reader_open_tags: upload failed"); rc = VM_ERR_HIP; }
-    if (rc == 0 && r->fsize == 0) { set_error(std::string("empty file: ") + path); rc = VM_ERR_IO; }
+    if (rc == 0 && r->in.fsize == 0) { set_error(std::string("empty file: ") + path); rc = VM_ERR_IO; }
     while (rc == 0 && !r->hdr_done) {
-        rc = bam_in_window(r, 0);
+        rc = reader_window(r, 0);
         if (rc == 0) { set_error("truncated file: the BAM header is not complete"); rc = VM_ERR_IO; }
         else if (rc > 0) rc = 0;
     }
     if (rc < 0) { vm_bam_reader_close(r); return rc; }
-    r->cur = 0; r->at = 0;
+    r->h.cur = 0; r->h.at = 0;
     memcpy(r->pub, r->st, sizeof r->pub);
-    r->prod_on = true;                                                  // the second window is decoded while the caller takes the first
-    r->prod = std::async(std::launch::async, bam_in_produce, r, 1);
+    r->h.prod_on = true;                                                // the second window is decoded while the caller takes the first
+    r->h.prod = std::async(std::launch::async, reader_produce<vm_bam_reader>, r, 1);
     *out = r;
     return 0;
 }
@@ -1050,51 +1281,60 @@ int64_t vm_bam_reader_read(vm_bam_reader* r, int64_t max_reads, int64_t max_base
                            int64_t** qual_off, char** comments, int64_t** com_off) {
     if (!r || !r->c) return VM_ERR_NO_CTX;
     if (!names || !name_off || !seqs || !seq_off || !quals || !qual_off || !comments || !com_off) return VM_ERR_ARG;
-    try {
-        Grow nb, sb, qb, cb;
-        std::vector<int64_t> no(1, 0), so(1, 0), qo(1, 0), co(1, 0);
-        int64_t n = 0;
-        bool end = false;
-        while (n < max_reads && (int64_t)sb.n < max_bases && !end) {
-            if (r->at >= r->win[r->cur].n) {
-                const int rc = bam_in_next(r);
-                if (rc < 0) return rc;
-                if (rc == 0) end = true;
-                continue;
-            }
-            const double t0 = now_s();
-            const DecodedWin& D = r->win[r->cur];
-            const int64_t nk = D.n;
-            const int64_t* hn = (const int64_t*)D.off.p; const int64_t* hs = hn + (nk + 1); const int64_t* hq = hs + (nk + 1);
-            const int64_t a = r->at;
-            int64_t m = 0;
-            while (a + m < nk && n + m < max_reads && (int64_t)sb.n + (hs[a + m] - hs[a]) < max_bases) ++m;
-            if (!nb.append(D.names.p + hn[a], (size_t)(hn[a + m] - hn[a])) || !sb.append(D.seqs.p + hs[a], (size_t)(hs[a + m] - hs[a])) ||
-                !qb.append(D.quals.p + hq[a], (size_t)(hq[a + m] - hq[a]))) { set_error("vm_bam_reader_read: out of host memory"); return VM_ERR_OOM; }
-            const int64_t n0 = no.back() - hn[a], s0 = so.back() - hs[a], q0 = qo.back() - hq[a];
-            for (int64_t j = 1; j <= m; ++j) { no.push_back(n0 + hn[a + j]); so.push_back(s0 + hs[a + j]); qo.push_back(q0 + hq[a + j]); }
-            if (r->tags_on) {                                           // the comments are cut where the records are
-                const int64_t* hc = hq + (nk + 1);
-                if (!cb.append(D.comments.p + hc[a], (size_t)(hc[a + m] - hc[a]))) { set_error("vm_bam_reader_read: out of host memory"); return VM_ERR_OOM; }
-                const int64_t c0 = co.back() - hc[a];
-                for (int64_t j = 1; j <= m; ++j) co.push_back(c0 + hc[a + j]);
-            }
-            r->at += m; n += m;
-            r->handout_s += now_s() - t0;
-        }
-        auto giveo = [](const std::vector<int64_t>& v, int64_t** p) { *p = (int64_t*)malloc(8 * v.size()); memcpy(*p, v.data(), 8 * v.size()); };
-        *names = nb.release(); *seqs = sb.release(); *quals = qb.release(); *comments = cb.release();
-        giveo(no, name_off); giveo(so, seq_off); giveo(qo, qual_off);
-        if (!r->tags_on) co.assign((size_t)n + 1, 0);
-        giveo(co, com_off);
-        return n;
-    }
-    catch (const std::bad_alloc&) { set_error("vm_bam_reader_read: out of host memory"); return VM_ERR_OOM; }
+    return reader_read(r, r->tags_on, "vm_bam_reader_read", max_reads, max_bases, names, name_off, seqs, seq_off, quals, qual_off, comments, com_off);
 }
 
 int vm_bam_reader_stats(const vm_bam_reader* r, double* out, int n) {
     if (!r || !out) return VM_ERR_ARG;
-    for (int i = 0; i < n; ++i) out[i] = i == 6 ? r->handout_s : i < 13 ? r->pub[i] : 0.0;         // (both written by the caller's own thread)
+    for (int i = 0; i < n; ++i) out[i] = i == 6 ? r->h.handout_s : i < 13 ? r->pub[i] : 0.0;       // (both written by the caller's own thread)
+    return 0;
+}
+
+/* ---- bgzipped FASTQ (include/vacmapx.h) ---- */
+
+void vm_fastq_reader_close(vm_fastq_reader* r) {
+    if (!r) return;
+    reader_close(r);
+}
+
+int vm_fastq_reader_open(vm_ctx* c, const char* path, vm_fastq_reader** out) {
+    if (out) *out = nullptr;
+    if (!c) return VM_ERR_NO_CTX;
+    if (!out || !path) return VM_ERR_ARG;
+    vm_fastq_reader* r = new vm_fastq_reader();
+    r->c = c;
+    int rc = bgzf_in_open(&r->in, c, path);
+    if (rc == 0 && r->in.fsize == 0) { set_error(std::string("empty file: ") + path); rc = VM_ERR_IO; }
+    if (rc == 0) {
+        unsigned char magic[2] = {0, 0};
+        const ssize_t got = pread(r->in.fd, magic, 2, 0);
+        if (got < 0) { set_error(std::string("cannot read ") + path); rc = VM_ERR_IO; }
+        else if (got < 2 || magic[0] != 0x1f || magic[1] != 0x8b) { set_error(std::string("not a gzip file (the device reader takes bgzipped FASTQ): ") + path); rc = VM_ERR_UNSUPPORTED; }
+    }
+    // windows until one holds a record: the first record's header decides at once whether this is FASTQ
+    int w = 1;
+    while (rc == 0 && w == 1 && r->h.win[0].n == 0) { w = reader_window(r, 0); if (w < 0) rc = w; }
+    if (rc < 0) { vm_fastq_reader_close(r); return rc; }
+    r->h.cur = 0; r->h.at = 0;
+    memcpy(r->pub, r->st, sizeof r->pub);
+    if (w == 1) {                                                       // the second window is parsed while the caller takes the first
+        r->h.prod_on = true;
+        r->h.prod = std::async(std::launch::async, reader_produce<vm_fastq_reader>, r, 1);
+    }
+    *out = r;
+    return 0;
+}
+
+int64_t vm_fastq_reader_read(vm_fastq_reader* r, int64_t max_reads, int64_t max_bases, char** names, int64_t** name_off, char** seqs, int64_t** seq_off, char** quals,
+                             int64_t** qual_off, char** comments, int64_t** com_off) {
+    if (!r || !r->c) return VM_ERR_NO_CTX;
+    if (!names || !name_off || !seqs || !seq_off || !quals || !qual_off || !comments || !com_off) return VM_ERR_ARG;
+    return reader_read(r, true, "vm_fastq_reader_read", max_reads, max_bases, names, name_off, seqs, seq_off, quals, qual_off, comments, com_off);
+}
+
+int vm_fastq_reader_stats(const vm_fastq_reader* r, double* out, int n) {
+    if (!r || !out) return VM_ERR_ARG;
+    for (int i = 0; i < n; ++i) out[i] = i == 6 ? r->h.handout_s : i < 11 ? r->pub[i] : 0.0;
     return 0;
 }
 

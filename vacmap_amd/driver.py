@@ -261,6 +261,58 @@ def _native_bam_chunks(path, n_max, lib, device, tags=None):
         ctx.close()
 
 
+def _gzip_is_bgzf(path):
+    """the first gzip member carries the BGZF extra subfield BC (SAMv1 4.1): what the device inflate needs to find the member boundaries"""
+    with open(path, 'rb') as f:
+        h = f.read(12)
+        if len(h) < 12 or h[:3] != b'\x1f\x8b\x08' or not h[3] & 4:
+            return False
+        extra = f.read(h[10] | h[11] << 8)
+    q = 0
+    while q + 4 <= len(extra):
+        if extra[q:q + 2] == b'BC':
+            return True
+        q += 4 + (extra[q + 2] | extra[q + 3] << 8)
+    return False
+
+
+def _native_fastq_chunks(path, n_max, lib, device):
+    """--fastx-reader native: the chunks of lib.Fastx from lib.FastqReader (BGZF inflate and the FASTQ parse on the GPU) on a context of its own.
+    What the device reader does not take (plain gzip: no member boundaries to inflate side by side; FASTA) goes to the host reader, with one
+    line on stderr; the context is released before the host reader starts."""
+    from .lib import FastqReader, Fastx, Context, VmxError
+    ctx = Context(device, lib=lib)
+    rd = None
+    try:
+        try:
+            rd = FastqReader(ctx, path)
+        except VmxError as e:
+            if e.code != -7:                               # VM_ERR_UNSUPPORTED
+                raise
+        if rd is not None:
+            try:
+                yield from iter(lambda: rd.read(n_max), None)
+            finally:
+                rd.close()
+            return
+    finally:
+        ctx.close()
+    why = 'is FASTA' if _gzip_is_bgzf(path) else 'is gzip but not BGZF'       # (the two things vm_fastq_reader_open refuses in a gzip file)
+    sys.stderr.write('[vacmap_amd] --fastx-reader native: %s %s, reading it with the host reader\n' % (path, why))
+    rd = Fastx(path, lib=lib)
+    try:
+        yield from iter(lambda: rd.read(n_max), None)
+    finally:
+        rd.close()
+
+
+def _is_gzip(path):
+    if not os.path.isfile(path):
+        return False
+    with open(path, 'rb') as f:
+        return f.read(2) == b'\x1f\x8b'
+
+
 def _is_plain_fastx(path):
     """an uncompressed FASTA / FASTQ file (byte ranges of it can be parsed independently)"""
     if path.endswith('.bam') or not os.path.isfile(path):
@@ -278,7 +330,7 @@ def _parse_slice(path, lib, a, b, n_max):
         rd.close()
 
 
-def _input_chunks(path, n_max, lib, device=0, bam_reader='python', parse_threads=0, share=(0, 1), slice_bytes=1 << 30, bam_tags=None):
+def _input_chunks(path, n_max, lib, device=0, bam_reader='python', parse_threads=0, share=(0, 1), slice_bytes=1 << 30, bam_tags=None, fastx_reader='host'):
     """blob chunks (names, upper-cased sequences, qualities, comments; at most n_max records each) of one input in file order: a .bam through
     the native or the Python reader, a compressed FASTA / FASTQ file through one library reader. parse_threads > 0: a plain file is cut into
     record-aligned slices of about slice_bytes (vm_fastx_open_range) which that many threads parse ahead of the consumer, and share = (i, n)
@@ -287,6 +339,9 @@ def _input_chunks(path, n_max, lib, device=0, bam_reader='python', parse_threads
     from .lib import Fastx
     if path.endswith('.bam'):
         yield from (_native_bam_chunks(path, n_max, lib, device, bam_tags) if bam_reader == 'native' else _bam_chunks(path, n_max, bam_tags))
+        return
+    if fastx_reader == 'native' and _is_gzip(path):
+        yield from _native_fastq_chunks(path, n_max, lib, device)
         return
     if not parse_threads or not _is_plain_fastx(path):
         rd = Fastx(path, lib=lib)
@@ -500,6 +555,9 @@ def build_parser():
     p.add_argument('--bam-reader', choices=['python', 'native'], default='python',
                    help='how -read x.bam is read: the Python reader on one host thread (default) or BGZF inflate and record decoding on the GPU '
                         '(lib.BamReader, on a context of its own); a .bam that is gzip but not BGZF falls back to the Python reader')
+    p.add_argument('--fastx-reader', choices=['host', 'native'], default='host',
+                   help='how a compressed -read x.fastq.gz is read: zlib and the parser on one host thread (default) or BGZF inflate and the FASTQ parse on '
+                        'the GPU (lib.FastqReader, on a context of its own); plain gzip and FASTA fall back to the host reader, plain files keep the threaded parser')
     p.add_argument('--bam-tags', metavar='LIST|all', default=None,
                    help='carry auxiliary fields of -read x.bam records to the output as optional fields (the reference drops them): a comma-separated list '
                         'of two-character tags (MM,ML,MN) or `all`; with --bam-reader native they are turned into SAM text on the GPU. They travel as the '
@@ -873,7 +931,7 @@ def _run_asm(args, net, lib, ctx, index, prm, opts, out, device, t_start):
     group, gbases = [], 0
     for path in (p for grp in args.read for p in grp):
         # (.bam input like every other mode: vacmap:452-470)
-        with contextlib.closing(_input_chunks(path, 64, lib, device, args.bam_reader, bam_tags=args.bam_tags)) as chunks:
+        with contextlib.closing(_input_chunks(path, 64, lib, device, args.bam_reader, bam_tags=args.bam_tags, fastx_reader=args.fastx_reader)) as chunks:
             for ch in _first_of_each_name(chunks, seen, lib):
                 if not _carries_comments(args, path):
                     import numpy as np
@@ -1017,7 +1075,7 @@ class ReadStream:
         share = (self.rank, self.world) if self.range_mode else (0, 1)
         slice_bytes = max(1 << 20, int(sw['VMX_SLICE_MB'] * (1 << 20)))
         for file_no, path in enumerate(p for grp in args.read for p in grp):
-            with contextlib.closing(_input_chunks(path, win_reads, self.lib, self.device, args.bam_reader, parse_threads, share, slice_bytes, args.bam_tags)) as chunks:
+            with contextlib.closing(_input_chunks(path, win_reads, self.lib, self.device, args.bam_reader, parse_threads, share, slice_bytes, args.bam_tags, args.fastx_reader)) as chunks:
                 for ch in _first_of_each_name(chunks, seen, self.lib):
                     n = len(ch['seqs_off']) - 1
                     if self.range_mode and n:

@@ -197,6 +197,9 @@ class VmxLib:
         L.vm_bam_reader_open.argtypes = [vp, cp, P(vp)]; L.vm_bam_reader_open_tags.argtypes = [vp, cp, cp, P(vp)]; L.vm_bam_reader_close.argtypes = [vp]; L.vm_bam_reader_close.restype = None
         L.vm_bam_reader_read.argtypes = [vp, i64, i64] + [P(vp), P(P(i64))] * 4; L.vm_bam_reader_read.restype = i64
         L.vm_bam_reader_stats.argtypes = [vp, P(C.c_double), C.c_int]
+        L.vm_fastq_reader_open.argtypes = [vp, cp, P(vp)]; L.vm_fastq_reader_close.argtypes = [vp]; L.vm_fastq_reader_close.restype = None
+        L.vm_fastq_reader_read.argtypes = [vp, i64, i64] + [P(vp), P(P(i64))] * 4; L.vm_fastq_reader_read.restype = i64
+        L.vm_fastq_reader_stats.argtypes = [vp, P(C.c_double), C.c_int]
 
     def err(self):
         return self.L.vm_last_error().decode()
@@ -699,22 +702,11 @@ def bgzf_decompress(ctx, data):
     return _take_bytes(ctx.lib, p, n)
 
 
-class BamReader:
-    """BAM reader into blobs (vm_bam_reader_*): BGZF inflate and record decoding on the device; read() as Fastx.read().
-    tags: None (comments stay empty), '*' or 'all' (every auxiliary field), or a list / comma-separated string of two-character tags: the
-    selected fields become each read's comment, `XX:T:value` joined by tabs, made on the device (vm_bam_reader_open_tags)"""
-    STATS = ('io_busy_s', 'io_wait_s', 'inflate_s', 'walk_s', 'decode_s', 'download_s', 'handout_s', 'windows', 'file_bytes', 'inflated_bytes', 'records', 'dropped',
-             'fields_dropped')
-
-    def __init__(self, ctx, path, tags=None):
-        self.ctx, self.lib = ctx, ctx.lib
-        h = C.c_void_p()
-        if tags is None:
-            self.lib.check(self.lib.L.vm_bam_reader_open(ctx.h, _b(path), C.byref(h)))
-        else:
-            spec = '*' if tags in ('*', 'all') else tags if isinstance(tags, str) else ','.join(tags)
-            self.lib.check(self.lib.L.vm_bam_reader_open_tags(ctx.h, _b(path), _b(spec), C.byref(h)))
-        self.h = h
+class _BlobReader:
+    """what the device readers share: read() as Fastx.read(), stats() as a dict of the STATS names, close(). A subclass names its three
+    C-ABI entries (_READ, _STATS_FN, _CLOSE), whose signatures are the same, and sets self.ctx, self.lib and self.h"""
+    STATS = ()
+    _READ = _STATS_FN = _CLOSE = None
 
     def read(self, max_reads, max_bases=1 << 62):
         """next chunk: dict of uint8 blobs and int64 offsets (names, seqs, quals, comments), or None at the end of the input"""
@@ -722,7 +714,7 @@ class BamReader:
         args = []
         for p, o in zip(ptrs, offs):
             args += [C.byref(p), C.byref(o)]
-        n = self.lib.L.vm_bam_reader_read(self.h, int(max_reads), int(max_bases), *args)
+        n = getattr(self.lib.L, self._READ)(self.h, int(max_reads), int(max_bases), *args)
         if n < 0:
             raise VmxError(int(n), self.lib.err())
         out = {}
@@ -734,14 +726,14 @@ class BamReader:
         return out if n > 0 else None
 
     def stats(self):
-        v = (C.c_double * 13)()
-        self.lib.check(self.lib.L.vm_bam_reader_stats(self.h, v, 13))
+        v = (C.c_double * len(self.STATS))()
+        self.lib.check(getattr(self.lib.L, self._STATS_FN)(self.h, v, len(self.STATS)))
         return dict(zip(self.STATS, list(v)))
 
     def close(self):
         if getattr(self, 'h', None):
             if self.ctx.h:                                   # (a reader outlives its context only by mistake: then its memory is left to the process)
-                self.lib.L.vm_bam_reader_close(self.h)
+                getattr(self.lib.L, self._CLOSE)(self.h)
             self.h = None
 
     def __del__(self):
@@ -749,6 +741,38 @@ class BamReader:
             self.close()
         except Exception:
             pass
+
+
+class BamReader(_BlobReader):
+    """BAM reader into blobs (vm_bam_reader_*): BGZF inflate and record decoding on the device; read() as Fastx.read().
+    tags: None (comments stay empty), '*' or 'all' (every auxiliary field), or a list / comma-separated string of two-character tags: the
+    selected fields become each read's comment, `XX:T:value` joined by tabs, made on the device (vm_bam_reader_open_tags)"""
+    STATS = ('io_busy_s', 'io_wait_s', 'inflate_s', 'walk_s', 'decode_s', 'download_s', 'handout_s', 'windows', 'file_bytes', 'inflated_bytes', 'records', 'dropped',
+             'fields_dropped')
+    _READ, _STATS_FN, _CLOSE = 'vm_bam_reader_read', 'vm_bam_reader_stats', 'vm_bam_reader_close'
+
+    def __init__(self, ctx, path, tags=None):
+        self.ctx, self.lib = ctx, ctx.lib
+        h = C.c_void_p()
+        if tags is None:
+            self.lib.check(self.lib.L.vm_bam_reader_open(ctx.h, _b(path), C.byref(h)))
+        else:
+            spec = '*' if tags in ('*', 'all') else tags if isinstance(tags, str) else ','.join(tags)
+            self.lib.check(self.lib.L.vm_bam_reader_open_tags(ctx.h, _b(path), _b(spec), C.byref(h)))
+        self.h = h
+
+
+class FastqReader(_BlobReader):
+    """Reader of bgzipped FASTQ into blobs (vm_fastq_reader_*): BGZF inflate and the four-line parse on the device, by Fastx's own rule
+    (include/vacmapx.h); read() as Fastx.read(). VmxError -7 at open: plain gzip, not gzip, or FASTA (Fastx reads those)"""
+    STATS = ('io_busy_s', 'io_wait_s', 'inflate_s', 'parse_s', 'copy_s', 'download_s', 'handout_s', 'windows', 'file_bytes', 'inflated_bytes', 'records')
+    _READ, _STATS_FN, _CLOSE = 'vm_fastq_reader_read', 'vm_fastq_reader_stats', 'vm_fastq_reader_close'
+
+    def __init__(self, ctx, path):
+        self.ctx, self.lib = ctx, ctx.lib
+        h = C.c_void_p()
+        self.lib.check(self.lib.L.vm_fastq_reader_open(ctx.h, _b(path), C.byref(h)))
+        self.h = h
 
 
 class BamCodec:
