@@ -87,6 +87,19 @@ int vm_ctx_mem_info(vm_ctx*, int64_t* free_bytes, int64_t* total_bytes);
 /* build the minimizer index of a FASTA file / in-memory contigs ON THE GPU and keep it resident in HBM
  * (replaces `mp.Aligner(path, w=, k=)`, src/vacmap/vacmap:344; index.py:26) */
 int vm_index_build_fasta(vm_ctx*, const char* fasta_path, int k, int w, vm_index** out);
+/* The rule of a reference FASTA, for both entries. A line is the bytes between newlines; the bytes behind the last newline are a line as well.
+ * All trailing '\r' of a line are removed; an empty line is skipped. A line whose first byte is '>' starts a contig: its name is the bytes
+ * behind '>' up to the first blank or tab (it may be empty), and a header without sequence lines gives a contig of length 0. Any other line
+ * is appended whole to the current contig (interior blanks and '\r' stay and become "other letters"), or dropped when no header has been
+ * seen. The host copy of the bases has a-z upper-cased; the device codes are A C G T -> 0 1 2 3 in either case, everything else 4.
+ * A file that begins with the gzip magic 1f 8b is read as a gzip stream of any number of members (plain gzip and BGZF): vm_index_build_fasta
+ * through zlib. vm_index_build_fasta_device parses the text on the GPU (csrc/k_fasta_in.hip) window by window: plain files are read into
+ * page-locked memory, BGZF members are inflated on the GPU, plain gzip is inflated by zlib on a host thread. The index is the one
+ * vm_index_build_fasta builds, byte for byte (.vmx file, device codes, count of other letters). A header line that does not fit in one window
+ * (256 MB of text; BGZF: 512 MB) returns VM_ERR_UNSUPPORTED: the caller falls back to vm_index_build_fasta. stats (may be NULL; n_stats
+ * doubles are written, 8 are defined): seconds of [0] file read and upload, [1] inflate, [2] parse kernels, [3] download of the bases,
+ * [4] index build, then [5] bytes of text, [6] windows, [7] contigs. */
+int vm_index_build_fasta_device(vm_ctx*, const char* fasta_path, int k, int w, vm_index** out, double* stats, int n_stats);
 int vm_index_build_mem(vm_ctx*, int nseq, const char* const* names, const char* const* seqs, const int64_t* lens,
                        int k, int w, vm_index** out);
 /* own on-disk format `<ref>.w<w>_k<k>.vmx` (the reference's naming rule `<ref>.w<w>_k<k>.mmi`, vacmap:326): contig table, bases and the

@@ -122,6 +122,20 @@ __global__ void k_fq_sizes(const uint8_t* buf, const int64_t* ls, const int64_t*
 __global__ void k_fq_copy(const uint8_t* buf, const int64_t* ls, const int64_t* rline, int64_t n_rec, const int64_t* noff, const int64_t* coff, const int64_t* soff,
                           const int64_t* qoff, uint8_t* names, uint8_t* comments, uint8_t* seqs, uint8_t* quals);
 
+// The reference FASTA on the device (k_fasta_in.hip): per chunk of VMX_FQ_CHUNK bytes, state = in a header line | a header has been seen << 1; a
+// chunk's map has the format of the FASTQ line maps (k_fq_tile_scan scans the tiles of both)
+// what the passes over a window leave: 1 + its last header start (0: none), where it is cut, whether a newline stands in front of the cut
+struct vmx_fa_result { uint64_t last_hs; int64_t end; int32_t end_ls, pad; };
+__global__ void k_fa_maps(const uint8_t* buf, int64_t len, int64_t n_chunks, int ls0, uint8_t* map, vmx_fa_result* res);
+__global__ void k_fa_tile_tot(const uint8_t* map, int64_t n_chunks, uint8_t* tile_tot);
+__global__ void k_fa_states(const uint8_t* map, const uint8_t* tile_pre, int64_t n_chunks, int s_in, uint8_t* state);
+__global__ void k_fa_result(const uint8_t* buf, int64_t len, int64_t n_chunks, const uint8_t* state, int ls0, int closing, vmx_fa_result* res);
+__global__ void k_fa_count(const uint8_t* buf, int64_t end, int64_t n_chunks, const uint8_t* state, int ls0, int64_t* cnt);
+__global__ void k_fa_write(const uint8_t* buf, int64_t end, int64_t n_chunks, const uint8_t* state, int ls0, const int64_t* coff, int64_t base0, uint8_t* letters,
+                           uint8_t* codes, int64_t* hpos, int64_t* hbase, unsigned long long* other);
+__global__ void k_fa_hdr_size(const uint8_t* buf, int64_t end, const int64_t* hpos, int64_t n, int64_t* hsz);
+__global__ void k_fa_hdr_copy(const uint8_t* buf, const int64_t* hpos, const int64_t* hoff, int64_t n, uint8_t* blob);
+
 // coordinate sort, merge and CSI (k_bam_sort.hip)
 #define VMX_BAM_RUN_SHIFT 40            // value of the merge sort: run << 40 | index in run
 #define VMX_BAM_RUN_MASK ((1ULL << VMX_BAM_RUN_SHIFT) - 1)

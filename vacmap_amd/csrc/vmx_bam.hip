@@ -7,7 +7,9 @@
 #include "vmx_host.h"
 #include "vmx_bam.h"
 #include "vmx_index_priv.h"
+#include "vmx_fasta_rule.h"
 #include <fcntl.h>
+#include <zlib.h>
 #include <unistd.h>
 #include <algorithm>
 #include <cctype>
@@ -1339,3 +1341,242 @@ int vm_fastq_reader_stats(const vm_fastq_reader* r, double* out, int n) {
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ the reference FASTA (kernels: k_fasta_in.hip)
+// The text of a reference goes through the device window by window: plain files by read(2) into page-locked staging (read ahead on a thread),
+// plain gzip through zlib on that thread into the same staging, BGZF through BgzfIn. What is carried from window to window: the bases so far,
+// "a header has been seen", "at a line start", and as bytes the incomplete header line or the '\r' run the window was cut in front of.
+
+namespace {
+
+struct RefRaw {                                         // plain or plain-gzip input: two staging buffers, the next one filled while the device parses
+    int fd = -1; gzFile gz = nullptr;
+    int64_t win = 0;
+    HostPinned stage[2]; int64_t got[2] = {0, 0}; int rc[2] = {0, 0}; bool eof[2] = {false, false}; std::string err[2]; double busy[2] = {0, 0};
+    std::future<void> pre; bool pre_on = false; int slot = 0;
+    ~RefRaw() { if (pre_on) pre.get(); if (gz) gzclose(gz); else if (fd >= 0) close(fd); }
+};
+
+void ref_raw_fill(RefRaw* s, int k) {
+    const double t0 = now_s();
+    s->got[k] = 0; s->rc[k] = 0; s->eof[k] = false; s->err[k].clear();
+    while (s->got[k] < s->win) {
+        const int64_t want = std::min<int64_t>(s->win - s->got[k], 1 << 30);
+        const int64_t q = s->gz ? (int64_t)gzread(s->gz, s->stage[k].p + s->got[k], (unsigned)want) : (int64_t)read(s->fd, s->stage[k].p + s->got[k], (size_t)want);
+        if (q < 0) { s->rc[k] = VM_ERR_IO; s->err[k] = s->gz ? std::string("gzip stream: ") + gzerror(s->gz, nullptr) : std::string("read error"); break; }
+        if (q == 0) {
+            s->eof[k] = true;
+            int en = Z_OK;
+            if (s->gz) { const char* msg = gzerror(s->gz, &en); if (en != Z_OK && en != Z_STREAM_END) { s->rc[k] = VM_ERR_IO; s->err[k] = std::string("gzip stream: ") + msg; } }
+            break;
+        }
+        s->got[k] += q;
+    }
+    s->busy[k] = now_s() - t0;
+}
+
+struct RefParse {
+    vm_ctx* c = nullptr; vm_index* mi = nullptr;
+    DevBuf d_map, d_tile, d_state, d_res, d_cnt, d_coff, d_tmp, d_wout, d_hpos, d_hbase, d_hsz, d_hoff, d_blob, d_other;
+    HostPinned pin;
+    int64_t base = 0; int seen = 0, ls0 = 1;             // carried: bases so far, a header has been seen, the window begins at a line start
+    std::vector<int64_t> starts;
+    int64_t win = 0; std::string path;
+    double* st = nullptr;
+};
+
+// the codes so far are kept when the buffer has to grow (compressed input: the total is not known in front)
+int ref_codes_room(RefParse& R, int64_t need) {
+    DevBuf& d = R.mi->d_codes;
+    if (d.p && (size_t)need + 64 <= d.cap) return 0;
+    if (!d.p || R.base == 0) return d.reserve((size_t)need + 64);
+    DevBuf nb;
+    VMX_TRY(nb.reserve(std::max((size_t)need + 64, d.cap + d.cap / 2)));
+    VMX_HIP(hipMemcpyAsync(nb.p, d.p, (size_t)R.base, hipMemcpyDeviceToDevice, R.c->stream));
+    VMX_TRY(sync(R.c));
+    d = std::move(nb);
+    return 0;
+}
+
+int ref_long_line(const RefParse& R) {
+    set_error("reference FASTA " + R.path + ": a header line (or a run of '\\r') does not fit in one window of " + std::to_string((long long)R.win) + " bytes");
+    return VM_ERR_UNSUPPORTED;
+}
+
+// one window buf[0, avail): its kept bytes to mi->bases and mi->d_codes, its headers to mi->names and R.starts; *end_out: where it was cut
+int ref_window(RefParse& R, const uint8_t* buf, int64_t avail, bool closing, int64_t* end_out) {
+    vm_ctx* c = R.c; vm_index* mi = R.mi;
+    *end_out = avail;
+    if (avail == 0) return 0;
+    double t0 = now_s();
+    const int64_t nch = (avail + VMX_FQ_CHUNK - 1) / VMX_FQ_CHUNK, ntile = (nch + VMX_FQ_LTILE) / VMX_FQ_LTILE;
+    VMX_TRY(R.d_map.reserve((size_t)nch + 1)); VMX_TRY(R.d_tile.reserve((size_t)ntile)); VMX_TRY(R.d_state.reserve((size_t)nch + 1));
+    VMX_TRY(R.d_res.reserve(sizeof(vmx_fa_result))); VMX_TRY(R.pin.reserve(256));
+    vmx_fa_result* res = R.d_res.as<vmx_fa_result>();
+    VMX_HIP(hipMemsetAsync(res, 0, sizeof(vmx_fa_result), c->stream));
+    const unsigned gch = (unsigned)((nch + 3) / 4);
+    hipLaunchKernelGGL(k_fa_maps, dim3(gch), dim3(256), 0, c->stream, buf, avail, nch, R.ls0, R.d_map.as<uint8_t>(), res);
+    hipLaunchKernelGGL(k_fa_tile_tot, dim3((unsigned)ntile), dim3(VMX_FQ_LTILE), 0, c->stream, R.d_map.as<const uint8_t>(), nch, R.d_tile.as<uint8_t>());
+    hipLaunchKernelGGL(k_fq_tile_scan, dim3(1), dim3(1024), 0, c->stream, R.d_tile.as<uint8_t>(), ntile);
+    hipLaunchKernelGGL(k_fa_states, dim3((unsigned)ntile), dim3(VMX_FQ_LTILE), 0, c->stream, R.d_map.as<const uint8_t>(), R.d_tile.as<const uint8_t>(), nch, R.seen << 1, R.d_state.as<uint8_t>());
+    hipLaunchKernelGGL(k_fa_result, dim3(1), dim3(64), 0, c->stream, buf, avail, nch, R.d_state.as<const uint8_t>(), R.ls0, closing ? 1 : 0, res);
+    VMX_HIP(hipMemcpyAsync(R.pin.p, res, sizeof(vmx_fa_result), hipMemcpyDeviceToHost, c->stream));
+    VMX_TRY(sync(c));
+    vmx_fa_result F; memcpy(&F, R.pin.p, sizeof F);
+    if (F.end < 0 || F.end > avail) { set_error("reference FASTA: the cut pass left an offset outside the window"); return VM_ERR_HIP; }
+    const int64_t end = F.end;
+    *end_out = end;
+    if (end == 0) { R.st[2] += now_s() - t0; return 0; }
+    const int64_t ne = (end + VMX_FQ_CHUNK - 1) / VMX_FQ_CHUNK;
+    const unsigned ge = (unsigned)((ne + 3) / 4);
+    VMX_TRY(R.d_cnt.reserve((size_t)(ne + 1) * 8)); VMX_TRY(R.d_coff.reserve((size_t)(ne + 1) * 8));
+    hipLaunchKernelGGL(k_fa_count, dim3(ge), dim3(256), 0, c->stream, buf, end, ne, R.d_state.as<const uint8_t>(), R.ls0, R.d_cnt.as<int64_t>());
+    VMX_TRY(vmx_scan64(c, R.d_tmp, R.d_cnt.as<const int64_t>(), R.d_coff.as<int64_t>(), (size_t)ne + 1));
+    VMX_HIP(hipMemcpyAsync(R.pin.p, R.d_coff.as<int64_t>() + ne, 8, hipMemcpyDeviceToHost, c->stream));
+    VMX_TRY(sync(c));
+    int64_t tot; memcpy(&tot, R.pin.p, 8);
+    const int64_t kept = tot & 0xffffffffll, nh = tot >> 32;
+    if (kept > end || nh > end) { set_error("reference FASTA: the count pass left a total larger than the window"); return VM_ERR_HIP; }
+    if (R.base + kept >= (1LL << 35)) { set_error("reference longer than 2^35 bases"); return VM_ERR_UNSUPPORTED; }
+    if ((int64_t)mi->names.size() + nh > (1 << 24)) { set_error("reference with more than 2^24 contigs"); return VM_ERR_UNSUPPORTED; }
+    VMX_TRY(ref_codes_room(R, R.base + kept));
+    VMX_TRY(R.d_wout.reserve((size_t)kept + 32)); VMX_TRY(R.d_hpos.reserve((size_t)(nh + 1) * 8)); VMX_TRY(R.d_hbase.reserve((size_t)(nh + 1) * 8));
+    hipLaunchKernelGGL(k_fa_write, dim3(ge), dim3(256), 0, c->stream, buf, end, ne, R.d_state.as<const uint8_t>(), R.ls0, R.d_coff.as<const int64_t>(), R.base, R.d_wout.as<uint8_t>(),
+                       mi->d_codes.as<uint8_t>(), R.d_hpos.as<int64_t>(), R.d_hbase.as<int64_t>(), R.d_other.as<unsigned long long>());
+    std::vector<int64_t> hoff, hbase; std::vector<char> blob;
+    if (nh > 0) {
+        VMX_TRY(R.d_hsz.reserve((size_t)(nh + 1) * 8)); VMX_TRY(R.d_hoff.reserve((size_t)(nh + 1) * 8));
+        hipLaunchKernelGGL(k_fa_hdr_size, dim3((unsigned)((nh + 1 + 3) / 4)), dim3(256), 0, c->stream, buf, end, R.d_hpos.as<const int64_t>(), nh, R.d_hsz.as<int64_t>());
+        VMX_TRY(vmx_scan64(c, R.d_tmp, R.d_hsz.as<const int64_t>(), R.d_hoff.as<int64_t>(), (size_t)nh + 1));
+        hoff.resize((size_t)nh + 1); hbase.resize((size_t)nh);
+        VMX_TRY(download(hoff.data(), R.d_hoff.p, (size_t)nh + 1, c->stream));
+        VMX_TRY(download(hbase.data(), R.d_hbase.p, (size_t)nh, c->stream));
+        VMX_TRY(sync(c));
+        const int64_t hb = hoff[(size_t)nh];
+        if (hb < 0 || hb > end) { set_error("reference FASTA: the header pass left a size larger than the window"); return VM_ERR_HIP; }
+        VMX_TRY(R.d_blob.reserve((size_t)hb + 32));
+        hipLaunchKernelGGL(k_fa_hdr_copy, dim3((unsigned)((nh + 3) / 4)), dim3(256), 0, c->stream, buf, R.d_hpos.as<const int64_t>(), R.d_hoff.as<const int64_t>(), nh, R.d_blob.as<uint8_t>());
+        blob.resize((size_t)hb + 1);
+        VMX_TRY(download(blob.data(), R.d_blob.p, (size_t)hb, c->stream));
+    }
+    VMX_TRY(sync(c));
+    R.st[2] += now_s() - t0;
+    for (int64_t h = 0; h < nh; ++h) {
+        if (hoff[(size_t)h + 1] - hoff[(size_t)h] + 1 >= R.win) return ref_long_line(R);    // (one rule, wherever the line falls in its window)
+        mi->names.push_back(fasta_header_name(blob.data() + hoff[(size_t)h], (size_t)(hoff[(size_t)h + 1] - hoff[(size_t)h])));
+        R.starts.push_back(hbase[(size_t)h]);
+    }
+    t0 = now_s();
+    if (kept > 0) {
+        if ((int64_t)mi->bases.size() < R.base + kept) mi->bases.resize((size_t)(R.base + kept));      // (compressed input: the string grows, geometrically past what was reserved)
+        VMX_HIP(hipMemcpyAsync(&mi->bases[(size_t)R.base], R.d_wout.as<uint8_t>() + (R.base & 15), (size_t)kept, hipMemcpyDeviceToHost, c->stream));
+        VMX_TRY(sync(c));
+    }
+    R.st[3] += now_s() - t0;
+    R.base += kept; R.seen |= nh > 0; R.ls0 = F.end_ls;
+    return 0;
+}
+
+int ref_fasta_device_impl(vm_ctx* c, const char* path, vm_index* mi, double* st) {
+    RefParse R; R.c = c; R.mi = mi; R.st = st;
+    VMX_TRY(R.d_other.reserve(8)); VMX_HIP(hipMemsetAsync(R.d_other.p, 0, 8, c->stream));
+    BgzfIn in;
+    struct CloseIn { BgzfIn* r; ~CloseIn() { bgzf_in_close(r); } } close_in{&in};
+    in.c = c;
+    unsigned char mg[18]; ssize_t ng;
+    {
+        const int fd = open(path, O_RDONLY);
+        if (fd < 0) { set_error(std::string("cannot open ") + path); return VM_ERR_IO; }
+        ng = pread(fd, mg, 18, 0);
+        close(fd);
+    }
+    const bool gz = ng >= 2 && mg[0] == 0x1f && mg[1] == 0x8b;
+    const bool bgzf = gz && ng >= 18 && mg[2] == 8 && mg[3] == 4 && mg[12] == 'B' && mg[13] == 'C';
+    int64_t win = (int64_t)256 << 20;
+    RefRaw raw;
+    if (bgzf) { VMX_TRY(bgzf_in_open(&in, c, path)); win = in.max_inf; mi->bases.reserve((size_t)std::min<int64_t>(in.fsize * 5, (1LL << 35) - 1)); }
+    else {
+        // VMX_REF_IN_WINDOW: text bytes per window of plain and plain-gzip input (tests cross many windows with small files)
+        if (const char* e = getenv("VMX_REF_IN_WINDOW")) win = std::min<int64_t>(std::max<int64_t>(atoll(e), 1 << 16), (int64_t)1 << 30);
+        raw.fd = open(path, O_RDONLY);
+        if (raw.fd < 0) { set_error(std::string("cannot open ") + path); return VM_ERR_IO; }
+        const int64_t fsize = (int64_t)lseek(raw.fd, 0, SEEK_END);
+        if (fsize < 0 || lseek(raw.fd, 0, SEEK_SET) != 0) { set_error(std::string("cannot seek in ") + path); return VM_ERR_IO; }
+        if (gz) {
+            mi->bases.reserve((size_t)std::min<int64_t>(fsize * 5, (1LL << 35) - 1));     // (address space for the usual 4 : 1 of DNA text: the string then grows in place)
+            raw.gz = gzdopen(raw.fd, "rb");
+            if (!raw.gz) { set_error(std::string("cannot open the gzip stream of ") + path); return VM_ERR_IO; }
+            gzbuffer(raw.gz, 1 << 20);
+        } else {
+            // the file size bounds the bases of a plain file: too long a reference is refused, and the codes and the host copy are sized, before the first window
+            win = std::min<int64_t>(win, std::max<int64_t>(fsize, 1 << 16));
+            const int64_t bound = std::min<int64_t>(fsize, (1LL << 35) - 1);
+            VMX_TRY(ref_codes_room(R, bound));
+            mi->bases.resize((size_t)bound);
+        }
+        VMX_TRY(raw.stage[0].reserve((size_t)win)); VMX_TRY(raw.stage[1].reserve((size_t)win));
+        raw.win = win;
+        VMX_TRY(in.pin.reserve(256));
+    }
+    R.win = win; R.path = path;
+    for (bool closing = false; !closing;) {
+        int64_t avail = 0;
+        if (bgzf) {
+            double bst[13] = {0};
+            const int irc = bgzf_in_window(&in, bst, &avail);
+            st[0] += bst[0]; st[1] += bst[2]; st[5] += bst[9];
+            if (irc < 0) return irc;
+            closing = in.file_done;
+            if (irc == 0) {                                                  // (the file ended behind a window that was not its last: what was carried closes it)
+                DevBuf& dst = in.d_inf[in.which ^ 1];
+                VMX_TRY(dst.reserve((size_t)in.carry + 64));
+                if (in.carry) VMX_HIP(hipMemcpyAsync(dst.p, in.d_inf[in.which].as<uint8_t>() + in.tail_off, (size_t)in.carry, hipMemcpyDeviceToDevice, c->stream));
+                in.which ^= 1; avail = in.carry; closing = true;
+            }
+        } else {
+            double t0;
+            if (raw.pre_on) { raw.pre.get(); raw.pre_on = false; } else ref_raw_fill(&raw, raw.slot);
+            const int k = raw.slot;
+            st[gz ? 1 : 0] += raw.busy[k];                                   // (zlib's time holds the file read of a gzip stream)
+            if (raw.rc[k] < 0) { set_error(raw.err[k] + " in " + path); return raw.rc[k]; }
+            closing = raw.eof[k];
+            if (!closing) { raw.pre_on = true; raw.pre = std::async(std::launch::async, ref_raw_fill, &raw, k ^ 1); }
+            raw.slot ^= 1;
+            t0 = now_s();
+            DevBuf& dst = in.d_inf[in.which ^ 1];
+            avail = in.carry + raw.got[k];
+            VMX_TRY(dst.reserve((size_t)avail + 64));
+            if (in.carry) VMX_HIP(hipMemcpyAsync(dst.p, in.d_inf[in.which].as<uint8_t>() + in.tail_off, (size_t)in.carry, hipMemcpyDeviceToDevice, c->stream));
+            if (raw.got[k]) VMX_HIP(hipMemcpyAsync(dst.as<uint8_t>() + in.carry, raw.stage[k].p, (size_t)raw.got[k], hipMemcpyHostToDevice, c->stream));
+            VMX_TRY(sync(c));
+            in.which ^= 1;
+            st[0] += now_s() - t0;                                           // (the upload counts as reading the file)
+            st[5] += (double)raw.got[k];
+        }
+        st[6] += 1;
+        int64_t end = avail;
+        VMX_TRY(ref_window(R, in.d_inf[in.which].as<const uint8_t>(), avail, closing, &end));
+        in.tail_off = end; in.carry = avail - end;
+        if (!closing && in.carry >= win) return ref_long_line(R);
+    }
+    mi->bases.resize((size_t)R.base);
+    const size_t n = mi->names.size();
+    for (size_t i = 0; i < n; ++i) { mi->offsets.push_back(R.starts[i]); mi->lens.push_back((i + 1 < n ? R.starts[i + 1] : R.base) - R.starts[i]); }
+    mi->offsets.push_back(R.base);
+    VMX_TRY(ref_codes_room(R, R.base));
+    unsigned long long n_other = 0;
+    VMX_HIP(hipMemcpyAsync(&n_other, R.d_other.p, 8, hipMemcpyDeviceToHost, c->stream));
+    VMX_TRY(sync(c));
+    mi->n_other_letters = (int64_t)n_other;
+    st[7] = (double)n;
+    return 0;
+}
+
+}  // namespace
+
+// path -> mi->names, lens, offsets, bases, d_codes (without the tail padding) and n_other_letters, parsed on the device. st[0 .. 8): seconds of file
+// read, inflate, parse kernels, download of the bases, (index build: the caller's), then text bytes, windows, contigs.
+int vmx_ref_fasta_device(vm_ctx* c, const char* path, vm_index* mi, double* st) {
+    try { return ref_fasta_device_impl(c, path, mi, st); }
+    catch (const std::bad_alloc&) { set_error("reference FASTA: out of host memory"); return VM_ERR_OOM; }
+}

@@ -24,6 +24,8 @@
 using namespace vmx;
 
 #include "vmx_index_priv.h"
+#include "vmx_fasta_rule.h"
+#include <zlib.h>
 #include "vmx_stage.h"
 
 __global__ void k_sketch32(const uint8_t* codes, const int64_t* roff, int n_reads, int k, int w, uint64_t* mz_hash, uint32_t* mz_ps, const int64_t* mz_off, int32_t* mz_cnt);
@@ -368,28 +370,67 @@ int vm_index_build_mem(vm_ctx* c, int nseq, const char* const* names, const char
     catch (const std::exception& e) { set_error(std::string("index build: ") + e.what()); return VM_ERR_ARG; }
 }
 
+// the host parser: a plain file by fread, a gzip stream (magic 1f 8b; concatenated members, hence BGZF, included) through zlib, both into the one line rule
+static int fasta_host_parse(const char* path, FastaRule& R) {
+    FILE* f = fopen(path, "rb");
+    if (!f) { set_error(std::string("cannot open ") + path); return VM_ERR_IO; }
+    unsigned char mg[2];
+    const bool gz = fread(mg, 1, 2, f) == 2 && mg[0] == 0x1f && mg[1] == 0x8b;
+    std::vector<char> buf((size_t)1 << 20);
+    if (!gz) {
+        rewind(f);
+        for (size_t n; (n = fread(buf.data(), 1, buf.size(), f)) > 0;) R.feed(buf.data(), n);
+        const bool bad = ferror(f) != 0;
+        fclose(f);
+        if (bad) { set_error(std::string("read error in ") + path); return VM_ERR_IO; }
+    } else {
+        fclose(f);
+        gzFile g = gzopen(path, "rb");
+        if (!g) { set_error(std::string("cannot open ") + path); return VM_ERR_IO; }
+        gzbuffer(g, 1 << 20);
+        int n, en = Z_OK;
+        while ((n = gzread(g, buf.data(), (unsigned)buf.size())) > 0) R.feed(buf.data(), (size_t)n);
+        const std::string msg = gzerror(g, &en);
+        gzclose(g);
+        if (n < 0 || (en != Z_OK && en != Z_STREAM_END)) { set_error("gzip stream: " + msg + " in " + path); return VM_ERR_IO; }
+    }
+    R.finish();
+    return 0;
+}
+
 int vm_index_build_fasta(vm_ctx* c, const char* path, int k, int w, vm_index** out) {
     *out = nullptr;
     if (!c) { set_error("no context"); return VM_ERR_NO_CTX; }
     try {
-        FILE* f = fopen(path, "rb");
-        if (!f) { set_error(std::string("cannot open ") + path); return VM_ERR_IO; }
-        std::vector<std::string> names, seqs; std::string cur; char buf[1 << 16];
-        auto flush_line = [&](const std::string& ln) {
-            if (ln.empty()) return;
-            if (ln[0] == '>') { std::string nm = ln.substr(1); size_t e = nm.find_first_of(" \t"); if (e != std::string::npos) nm.resize(e); names.push_back(nm); seqs.emplace_back(); }
-            else if (!seqs.empty()) seqs.back() += ln;
-        };
-        while (fgets(buf, sizeof buf, f)) {
-            size_t n = strlen(buf); bool eol = n && buf[n - 1] == '\n';
-            while (n && (buf[n - 1] == '\n' || buf[n - 1] == '\r')) --n;
-            cur.append(buf, n);
-            if (eol) { flush_line(cur); cur.clear(); }
-        }
-        flush_line(cur); fclose(f);
+        FastaRule R;
+        VMX_TRY(fasta_host_parse(path, R));
         std::vector<const char*> np, sp; std::vector<int64_t> ls;
-        for (size_t i = 0; i < names.size(); ++i) { np.push_back(names[i].c_str()); sp.push_back(seqs[i].data()); ls.push_back((int64_t)seqs[i].size()); }
-        return index_build_mem_impl(c, (int)names.size(), np.data(), sp.data(), ls.data(), k, w, out);
+        for (size_t i = 0; i < R.names.size(); ++i) { np.push_back(R.names[i].c_str()); sp.push_back(R.seqs[i].data()); ls.push_back((int64_t)R.seqs[i].size()); }
+        return index_build_mem_impl(c, (int)R.names.size(), np.data(), sp.data(), ls.data(), k, w, out);
+    }
+    catch (const std::bad_alloc&) { set_error("index build: out of host memory"); return VM_ERR_OOM; }
+    catch (const std::exception& e) { set_error(std::string("index build: ") + e.what()); return VM_ERR_IO; }
+}
+
+int vm_index_build_fasta_device(vm_ctx* c, const char* path, int k, int w, vm_index** out, double* stats, int n_stats) {
+    if (out) *out = nullptr;
+    if (!c) { set_error("no context"); return VM_ERR_NO_CTX; }
+    if (!out || !path) { set_error("vm_index_build_fasta_device: no path or no result pointer"); return VM_ERR_ARG; }
+    if (k < 1 || k > 28 || w < 1 || w > 255) { set_error("k must be in [1,28], w in [1,255]"); return VM_ERR_ARG; }
+    try {
+        VMX_HIP(hipSetDevice(c->device));
+        vm_index* mi = new vm_index();
+        struct Guard { vm_index* m; ~Guard() { if (m) vm_index_free(m); } } g{mi};
+        mi->ctx = c; mi->k = k; mi->w = w;
+        double st[8] = {0};
+        VMX_TRY(vmx_ref_fasta_device(c, path, mi, st));
+        const auto t0 = std::chrono::steady_clock::now();
+        hipLaunchKernelGGL(k_fill_u8, dim3(1), dim3(256), 0, c->stream, mi->d_codes.as<uint8_t>() + mi->offsets.back(), (int64_t)64, (uint8_t)4);
+        VMX_TRY(index_build_device(mi));
+        st[4] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        for (int i = 0; stats && i < n_stats; ++i) stats[i] = i < 8 ? st[i] : 0.0;
+        *out = mi; g.m = nullptr;
+        return VM_OK;
     }
     catch (const std::bad_alloc&) { set_error("index build: out of host memory"); return VM_ERR_OOM; }
     catch (const std::exception& e) { set_error(std::string("index build: ") + e.what()); return VM_ERR_IO; }

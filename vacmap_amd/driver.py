@@ -558,6 +558,9 @@ def build_parser():
     p.add_argument('--fastx-reader', choices=['host', 'native'], default='host',
                    help='how a compressed -read x.fastq.gz is read: zlib and the parser on one host thread (default) or BGZF inflate and the FASTQ parse on '
                         'the GPU (lib.FastqReader, on a context of its own); plain gzip and FASTA fall back to the host reader, plain files keep the threaded parser')
+    p.add_argument('--ref-reader', choices=['host', 'native'], default='host',
+                   help='how the FASTA of -ref is parsed when no cached index is found: on one host thread (default) or on the GPU (plain, gzip and bgzipped '
+                        'files; lib.Index.from_fasta(reader=\'native\')); a header line longer than a window falls back to the host parser')
     p.add_argument('--bam-tags', metavar='LIST|all', default=None,
                    help='carry auxiliary fields of -read x.bam records to the output as optional fields (the reference drops them): a comma-separated list '
                         'of two-character tags (MM,ML,MN) or `all`; with --bam-reader native they are turned into SAM text on the GPU. They travel as the '
@@ -655,7 +658,7 @@ def _context_and_index(args, net, device):
     try:
         if net.rank == 0:
             from .indexfile import find_index
-            index = find_index(ctx, args.ref, int(args.k), int(args.w), write=not args.nowriteindex)
+            index = find_index(ctx, args.ref, int(args.k), int(args.w), write=not args.nowriteindex, log=sys.stderr, reader=args.ref_reader)
         if net.world > 1 or net.force:
             import torch
             from .dist import broadcast_index

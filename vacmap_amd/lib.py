@@ -144,6 +144,7 @@ class VmxLib:
         L.vm_align_asm.argtypes = [vp, vp, P(Params), C.c_char_p, i64, i64, i64, i64, P(P(Record)), P(i64), P(vp), P(C.c_int32)]
         L.vm_chains_out_free.argtypes = [P(ChainsOut)]
         L.vm_index_build_fasta.argtypes = [vp, cp, C.c_int, C.c_int, P(vp)]
+        L.vm_index_build_fasta_device.argtypes = [vp, cp, C.c_int, C.c_int, P(vp), P(dbl), C.c_int]
         L.vm_index_build_mem.argtypes = [vp, C.c_int, P(cp), P(cp), P(i64), C.c_int, C.c_int, P(vp)]
         L.vm_index_save.argtypes = [vp, cp]; L.vm_index_load.argtypes = [vp, cp, P(vp)]
         L.vm_index_save_mmi.argtypes = [vp, cp, C.c_int]; L.vm_index_load_mmi.argtypes = [vp, cp, P(vp)]
@@ -989,6 +990,9 @@ def local_chain_batch(ctx, index, prm, seqs, paths_per_read):
     return res
 
 
+REF_BUILD_STATS = ('read_s', 'inflate_s', 'parse_s', 'download_s', 'index_s', 'text_bytes', 'windows', 'contigs')     # vm_index_build_fasta_device's stats
+
+
 class Index:
     """HBM-resident minimizer index (vm_index); mirrors what the reference reads from `mp.Aligner` (vacmap:344-367)."""
 
@@ -1005,10 +1009,23 @@ class Index:
             self.names.append(nm.value.decode()); self.lens.append(ln.value); self.offsets.append(of.value)
 
     @classmethod
-    def from_fasta(cls, ctx, path, k=15, w=10):
+    def from_fasta(cls, ctx, path, k=15, w=10, reader='host'):
+        """the index of a FASTA file, plain, gzip or bgzipped. reader='host': vm_index_build_fasta parses the text on one host thread;
+        reader='native': vm_index_build_fasta_device parses it on the GPU (the same index, byte for byte) and leaves its statistics in
+        idx.build_stats; a header line longer than a window raises VmxError(VM_ERR_UNSUPPORTED)"""
+        if reader not in ('host', 'native'):
+            raise ValueError("reader must be 'host' or 'native'")
         h = C.c_void_p()
-        ctx.lib.check(ctx.lib.L.vm_index_build_fasta(ctx.h, _b(path), k, w, C.byref(h)))
-        return cls(ctx, h)
+        if reader == 'host':
+            ctx.lib.check(ctx.lib.L.vm_index_build_fasta(ctx.h, _b(path), k, w, C.byref(h)))
+            return cls(ctx, h)
+        st = (C.c_double * 8)()
+        ctx.lib.check(ctx.lib.L.vm_index_build_fasta_device(ctx.h, _b(path), k, w, C.byref(h), st, 8))
+        idx = cls(ctx, h)
+        idx.build_stats = dict(zip(REF_BUILD_STATS, (float(x) for x in st)))
+        for key in ('text_bytes', 'windows', 'contigs'):
+            idx.build_stats[key] = int(idx.build_stats[key])
+        return idx
 
     @classmethod
     def from_seqs(cls, ctx, names, seqs, k=15, w=10):
