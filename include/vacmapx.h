@@ -100,6 +100,14 @@ int vm_index_build_fasta(vm_ctx*, const char* fasta_path, int k, int w, vm_index
  * doubles are written, 8 are defined): seconds of [0] file read and upload, [1] inflate, [2] parse kernels, [3] download of the bases,
  * [4] index build, then [5] bytes of text, [6] windows, [7] contigs. */
 int vm_index_build_fasta_device(vm_ctx*, const char* fasta_path, int k, int w, vm_index** out, double* stats, int n_stats);
+/* vm_index_build_fasta_device with options. flags 0: exactly vm_index_build_fasta_device. VM_READER_GZIP_DEVICE: a plain-gzip file (no BGZF BC
+ * subfield in its first member) is inflated on the GPU in parallel chunks, window after window (as vm_fastq_reader_open_opts describes), instead
+ * of by zlib on a host thread; stats[1] is then the seconds of that inflate. The index is the same, byte for byte. VM_ERR_UNSUPPORTED (a single
+ * deflate block that does not end inside one window of VMX_BAM_IN_CHUNK compressed bytes, a header line longer than a window): the caller falls back. */
+#ifndef VM_READER_GZIP_DEVICE
+#define VM_READER_GZIP_DEVICE 1
+#endif
+int vm_index_build_fasta_device_opts(vm_ctx*, const char* fasta_path, int k, int w, int flags, vm_index** out, double* stats, int n_stats);
 int vm_index_build_mem(vm_ctx*, int nseq, const char* const* names, const char* const* seqs, const int64_t* lens,
                        int k, int w, vm_index** out);
 /* own on-disk format `<ref>.w<w>_k<k>.vmx` (the reference's naming rule `<ref>.w<w>_k<k>.mmi`, vacmap:326): contig table, bases and the
@@ -433,6 +441,22 @@ int64_t vm_bam_reader_read(vm_bam_reader*, int64_t max_reads, int64_t max_bases,
 int vm_bam_reader_stats(const vm_bam_reader*, double* out, int n);
 void vm_bam_reader_close(vm_bam_reader*);
 
+/* Plain gzip on the GPU. vm_gzip_decompress: any series of complete gzip members (RFC 1952: any writer's, FEXTRA / FNAME / FCOMMENT / FHCRC
+ * headers, stored, fixed and dynamic blocks, empty members, zero bytes between members) -> their bytes (vm_free). A member's deflate stream has
+ * no index, so it is inflated in parallel chunks: block starts are searched for in every VMX_GZ_CHUNK compressed bytes (environment; default
+ * 32768, at least 1024), every start is decoded by a wavefront of its own with the unknown 32 KB in front of it kept as markers, the chain of
+ * chunks is linked (a start that the chain steps over was a false candidate and is dropped), the 32 KB windows are passed along, and the
+ * markers are replaced. Every member's CRC32 and ISIZE are checked. Errors: VM_ERR_IO for input that is truncated ("truncated"),
+ * for a bad code, distance or stored length (the message names the file offset of the block), for a member whose CRC32 or ISIZE does not match
+ * (its file offset) and for anything that is not a gzip member where one must begin; VM_ERR_UNSUPPORTED for more than 256 MB of compressed
+ * data or 4 GB of text in one call.
+ * vm_gzip_decompress_stats is the same call and also fills stats[0, n_stats), whether it succeeds or not: chunks started (waves that began
+ * decoding), candidates rejected by the link check, chunks decoded again after a rejection, text bytes decoded by the first chain (the wave
+ * that starts at the first member's header), then seconds in the search, the count and write passes with the link check, the window pass,
+ * the marker pass (8 numbers). Device memory of a call: 3 bytes per text byte, the compressed data, and 32 KB per chunk started. */
+int vm_gzip_decompress(vm_ctx*, const void* in, int64_t n, char** out, int64_t* n_out);
+int vm_gzip_decompress_stats(vm_ctx*, const void* in, int64_t n, char** out, int64_t* n_out, double* stats, int n_stats);
+
 /* Bgzipped FASTQ on the GPU (driver: --fastx-reader native): the BGZF members of x.fastq.gz are inflated as for BAM input and the text is parsed on
  * the device into the four blobs of vm_fastx_read, by vm_fastx_read's own rule for four-line FASTQ:
  *   lines     a line ends at '\n', one trailing '\r' is dropped; the bytes after the file's last '\n' form a line if there are any.
@@ -457,6 +481,21 @@ void vm_bam_reader_close(vm_bam_reader*);
  * An open reader owns its context (it parses ahead on a thread of its own): close it before other calls use the context or destroy it. */
 typedef struct vm_fastq_reader vm_fastq_reader;
 int vm_fastq_reader_open(vm_ctx*, const char* path, vm_fastq_reader** out);
+/* vm_fastq_reader_open with options. flags 0: exactly vm_fastq_reader_open. VM_READER_GZIP_DEVICE: a file whose first member lacks the BGZF BC
+ * subfield (plain gzip: gzip, pigz, a basecaller's output, concatenated .gz files) is inflated on the GPU in parallel chunks (vm_gzip_decompress's
+ * kernels) instead of being refused: the file is taken in windows of VMX_BAM_IN_CHUNK compressed bytes; carried from window to window are the bit
+ * position of the next block (always a verified block start or a member header), the 32 KB in front of it on the device, and the running CRC32 and size
+ * of the open member; of a window's chain the leading chunks whose text fits VMX_BAM_IN_MAXINF are taken (always one), the rest start the next
+ * window. The file is read ahead on a thread of its own while the device works on a window. A single block that does not end inside one window's
+ * compressed bytes: VM_ERR_UNSUPPORTED (use vm_fastx_open); from vm_fastq_reader_open the caller can fall back, from a later vm_fastq_reader_read
+ * records have been handed out and the refusal is fatal to the run (with the default VMX_BAM_IN_CHUNK of 64 MB no deflate writer makes such a block). Truncation, a bad code,
+ * distance or stored length, a CRC32 or ISIZE mismatch: VM_ERR_IO with the file offset of the block or member, from the read call that reaches it.
+ * vm_fastq_reader_stats then has 8 more numbers behind its 11, of the windows inflated so far: chunks started, candidates rejected, chunks decoded
+ * again, text bytes of the file's first chain, seconds in find / decode / window / resolve. */
+#ifndef VM_READER_GZIP_DEVICE
+#define VM_READER_GZIP_DEVICE 1
+#endif
+int vm_fastq_reader_open_opts(vm_ctx*, const char* path, int flags, vm_fastq_reader** out);
 int64_t vm_fastq_reader_read(vm_fastq_reader*, int64_t max_reads, int64_t max_bases, char** names, int64_t** name_off, char** seqs, int64_t** seq_off, char** quals,
                              int64_t** qual_off, char** comments, int64_t** com_off);
 int vm_fastq_reader_stats(const vm_fastq_reader*, double* out, int n);

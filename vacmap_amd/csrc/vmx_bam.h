@@ -99,6 +99,38 @@ __global__ void k_bam_in_aux_size(const uint8_t* buf, const int64_t* roff, int64
 __global__ void k_bam_in_aux_write(const uint8_t* buf, const int64_t* roff, int64_t n, const uint16_t* sel, int n_sel, int all, const int64_t* coff, const int64_t* kidx,
                                    char* out, int64_t* out_coff);
 
+// Plain gzip on the device (k_gzip_in.hip): one deflate stream inflated in parallel chunks. A decode wave begins at a block
+// start inside the compressed window (a gzip member header, or a candidate that k_gz_find judged a valid non-final dynamic block header) and
+// ends at the first block boundary at or after stop_bit. Its output is 16-bit symbols: 0 ... 255 a byte, VMX_GZ_MARK | j byte j of the
+// 32 KB in front of the wave's first output byte.
+#define VMX_GZ_WIN 32768
+#define VMX_GZ_MARK 0x8000u
+#define VMX_GZ_NONE 0xffffffffu          // no candidate in the chunk / no stop: decode to the end of the window
+#define VMX_GZ_F_HEADER 1u              // (vmx_gz_wave.flags) a gzip member header stands at start_bit: what is in front is known to be nothing
+#define VMX_GZ_R_END 1u                 // (vmx_gz_res.flags) the wave met the end of the compressed window behind a member's trailer
+#define VMX_GZ_R_HEADER 4u              // (vmx_gz_res.flags) the wave ended at a member header (or the padding in front of one), not at a block
+#define VMX_GZ_R_RESUME_HDR 8u          // (vmx_gz_res.flags) resume_bit is a member header
+#define VMX_GZ_R_MEMBER 2u              // (vmx_gz_res.flags) a member began inside the wave (or at its start): `open` counts from the last such start
+#define VMX_GZ_TILE 16384               // text bytes per workgroup of k_gz_resolve: 256 lanes x 64 bytes
+struct vmx_gz_wave {
+    uint32_t start_bit, stop_bit, flags;
+    uint32_t hist;          // k_gz_resolve: bytes of the open member in front of the wave's first byte, at most VMX_GZ_WIN: a marker below VMX_GZ_WIN - hist reaches before the member
+    int64_t ooff, eoff;     // write pass: the wave's first symbol and its first member entry
+    uint32_t n_sym, n_ev;   // what the count pass counted: the write pass stores no more
+};
+// err: 0 or VMX_BGZF_E_* / VMX_GZ_E_*; err_bit: where the block (or header) with the error begins; open: text bytes behind the last member start (all of n_sym without one)
+// resume_bit: the latest place in front of the error (or the end) where a wave can begin: a block's first bit, or a member header (R_RESUME_HDR)
+struct vmx_gz_res { uint32_t end_bit, err, err_bit, flags, n_sym, n_ev, open, resume_bit; };
+// a member's end as the wave that decoded its final block met it: text position (from the wave's first symbol), the trailer, the file byte behind the trailer
+struct vmx_gz_member { uint32_t opos, crc, isize, next_byte; };
+enum { VMX_GZ_E_MAGIC = 20, VMX_GZ_E_METHOD = 21, VMX_GZ_E_BIG = 22, VMX_GZ_E_MARK = 23 };
+__global__ void k_gz_find(const uint8_t* comp, uint32_t n_bytes, uint32_t chunk_bytes, uint32_t first_chunk, uint32_t min_bit, uint32_t* cand);
+__global__ void k_gz_count(const uint8_t* comp, uint32_t n_bytes, const vmx_gz_wave* tab, const uint32_t* todo, vmx_gz_res* res);
+__global__ void k_gz_decode(const uint8_t* comp, uint32_t n_bytes, const vmx_gz_wave* tab, vmx_gz_res* res, uint16_t* sym, vmx_gz_member* ev);
+__global__ void k_gz_window(const uint16_t* sym, const vmx_gz_wave* tab, int64_t n_waves, const uint8_t* win0, uint8_t* win_in, uint8_t* win_out);
+__global__ void k_gz_resolve(const uint16_t* sym, const vmx_gz_wave* tab, int64_t n_waves, const uint8_t* win_in, const uint64_t* ev_end, int64_t n_ev, int64_t total,
+                             vmx_crc_x2n x2n, uint8_t* out, uint32_t* crc_acc, unsigned long long* err_key);
+
 // FASTQ input on the device (k_fastx_in.hip): newlines, line states, records, field sizes, field copy over one window of inflated text
 #define VMX_FQ_CHUNK 4096               // text bytes per wavefront of the newline kernels: 4 steps of 64 lanes x 16 bytes
 #define VMX_FQ_LTILE 256                // lines per workgroup of the state kernels

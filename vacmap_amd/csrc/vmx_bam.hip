@@ -787,9 +787,20 @@ struct vm_bam_reader {
     double pub[13] = {0};                               // what vm_bam_reader_stats reads: st as of the latest window the caller's thread has taken over
 };
 
+namespace {
+// the plain-gzip file half (defined with the gzip host code below); null in a reader of BGZF
+struct GzipIn;
+int gzip_in_window(BgzfIn* r, GzipIn* g, double* st, int64_t* avail_out);
+void gzip_in_free(GzipIn* g);
+GzipIn* gzip_in_new();
+double gzip_in_stat(const GzipIn* g, int i);
+}
+
 struct vm_fastq_reader {
     vm_ctx* c = nullptr;
     BgzfIn in;
+    GzipIn* gz = nullptr;
+    ~vm_fastq_reader() { gzip_in_free(gz); }
     DevBuf d_cnt, d_coff, d_ls, d_map, d_tile, d_start, d_ridx, d_rline, d_res, d_sz, d_off, d_tmp, d_names, d_seqs, d_quals, d_comments;
     HandOut h;
     int64_t n_seen = 0;                                 // complete records of the windows so far
@@ -1029,7 +1040,7 @@ int reader_window(vm_fastq_reader* r, int slot) {
     D.n = 0;
     if (r->fail_rc < 0) { set_error(r->fail_msg); return r->fail_rc; }
     int64_t avail = 0;
-    const int irc = bgzf_in_window(&in, r->st, &avail);
+    const int irc = r->gz ? gzip_in_window(&in, r->gz, r->st, &avail) : bgzf_in_window(&in, r->st, &avail);
     if (irc < 0) return irc;
     if (irc == 0) {
         if (in.carry > 0) { set_error("truncated FASTQ record: the file ends inside record " + std::to_string((long long)r->n_seen + 1)); return VM_ERR_IO; }
@@ -1212,9 +1223,358 @@ template <class R> void reader_close(R* r) {
     delete r;
 }
 
+// ---- plain gzip (kernels: k_gzip_in.hip) ----
+// One compressed window (vm_gzip_decompress: the whole input; a reader: VMX_BAM_IN_CHUNK bytes of the file) is searched for block starts per chunk of VMX_GZ_CHUNK bytes, every start is decoded by a
+// wave of its own in a count pass, and the host links the chain on the small table that pass leaves: wave k is verified when wave k - 1 is
+// and ended exactly at k's first bit. A start the chain steps over was false: it is dropped, and its verified predecessor is counted again
+// up to the next start that remains. Only an error of a verified wave is the file's error. The verified waves are then written at their
+// final offsets, the windows are passed along, markers are replaced and the members' CRC32 and ISIZE are compared.
+struct GzipBufs { DevBuf comp, cand, tab, todo, res, sym, ev, win_in, win_out, ev_end, acc, key, out; };
+// chunks started, candidates rejected, chunks decoded again, text bytes of the first chain, seconds in find / decode / window / resolve
+struct GzipStats { double v[8] = {0, 0, 0, 0, 0, 0, 0, 0}; };
+
+const char* gzip_reason(int code) {
+    switch (code) {
+        case VMX_GZ_E_MAGIC: return "not a gzip member (bad magic)";
+        case VMX_GZ_E_METHOD: return "gzip member with an unknown compression method";
+        case VMX_GZ_E_BIG: return "more than 2 GB of text behind one block start";
+        case VMX_BGZF_E_LONG: return "the write pass met more text than the count pass";
+        default: return bgzf_reason(code);
+    }
+}
+
+int gzip_wave_error(const vmx_gz_res& R, int64_t base_foff) {
+    const std::string at = std::to_string((long long)(base_foff + (R.err_bit >> 3)));
+    if (R.err == VMX_BGZF_E_INPUT) { set_error("truncated gzip input: what begins at file offset " + at + " is not complete"); return VM_ERR_IO; }
+    if (R.err == VMX_GZ_E_BIG) { set_error(std::string("gzip: ") + gzip_reason((int)R.err) + " (file offset " + at + ")"); return VM_ERR_UNSUPPORTED; }
+    if (R.err == VMX_GZ_E_MAGIC || R.err == VMX_GZ_E_METHOD) { set_error(std::string(gzip_reason((int)R.err)) + " at file offset " + at); return VM_ERR_IO; }
+    set_error(std::string("gzip: ") + gzip_reason((int)R.err) + " in the block at file offset " + at);
+    return R.err == VMX_BGZF_E_LONG ? VM_ERR_HIP : VM_ERR_IO;
+}
+
+// x^(8 n) modulo the CRC polynomial, and crc(A B) from crc(A), crc(B) and |B| (zlib's crc32_combine), on the host
+uint32_t crc_x8n_host(uint64_t n) {
+    const vmx_crc_x2n& t = crc_x2n_table();
+    uint32_t mul = 1u << 31, k = 3;
+    for (uint64_t r = n; r; r >>= 1, ++k) if (r & 1) mul = crc_multmodp(t.v[k & 31], mul);
+    return mul;
+}
+uint32_t crc_combine_host(uint32_t a, uint32_t b, uint64_t len_b) { return crc_multmodp(crc_x8n_host(len_b), a) ^ b; }
+
+// What is carried from one compressed window of a file to the next (GzipIn): where the next window begins (a verified block start or a member
+// header), the 32 KB in front of it on the device, and of the member that is open there its text bytes so far, their CRC32 and its file offset
+struct GzipCarry {
+    uint32_t start_bit = 0; bool at_header = true;
+    DevBuf win; bool have_win = false;
+    uint64_t open = 0; uint32_t crc = 0; int64_t member_foff = 0;
+};
+
+// One compressed window: comp[0, n) (host), whose byte 0 is byte base_foff of the file; K says where in it the first wave begins and is
+// left saying where the next window begins: *consumed_bits from comp[0]. last: the file ends with comp[n - 1], so input that runs out is
+// truncation; otherwise the chain is cut at the last place in the window where a wave can begin. Of the linked waves the leading ones whose
+// text fits max_text are taken (always one). The text -> z.out[0, *n_text). *done: the stream ended with the window. Waits for the result.
+int gzip_window_run(vm_ctx* c, GzipBufs& z, HostPinned& pin, const uint8_t* comp, int64_t n, int64_t base_foff, bool last, int64_t max_text, GzipCarry& K, GzipStats& S,
+                    int64_t* n_text, int64_t* consumed_bits, bool* done) {
+    *n_text = 0; *consumed_bits = K.start_bit; *done = false;
+    if (n > ((int64_t)1 << 28)) { set_error("gzip: more than 256 MB of compressed data in one window"); return VM_ERR_UNSUPPORTED; }
+    int64_t chunk = 32768;                                              // (the best of 16, 32, 64 and 128 KB for FastqReader: profiles/gzip_input_reader.json)
+    if (const char* e = getenv("VMX_GZ_CHUNK")) chunk = std::min<int64_t>(std::max<int64_t>(atoll(e), 1024), 1 << 26);
+    const int64_t n_chunks = (n + chunk - 1) / chunk;
+    const uint32_t nb = (uint32_t)n;
+    auto wave_error = [&](const vmx_gz_res& r) { return gzip_wave_error(r, base_foff); };
+    int64_t cut_wave = -1;
+    double t0 = now_s();
+    VMX_TRY(z.comp.reserve((size_t)n + 64));
+    VMX_TRY(z.cand.reserve((size_t)n_chunks * 4));
+    VMX_HIP(hipMemsetAsync(z.comp.as<uint8_t>() + (n & ~(int64_t)3), 0, 32, c->stream));        // the last word's bytes behind the data are zeros
+    VMX_HIP(hipMemcpyAsync(z.comp.p, comp, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    VMX_HIP(hipMemsetAsync(z.cand.p, 0xff, (size_t)n_chunks * 4, c->stream));
+    if (n_chunks > 1)
+        hipLaunchKernelGGL(k_gz_find, dim3((unsigned)(n_chunks - 1)), dim3(64), 0, c->stream, z.comp.as<const uint8_t>(), nb, (uint32_t)chunk, 1u, K.start_bit + 1u, z.cand.as<uint32_t>());
+    VMX_TRY(pin.reserve((size_t)n_chunks * 4));
+    VMX_HIP(hipMemcpyAsync(pin.p, z.cand.p, (size_t)n_chunks * 4, hipMemcpyDeviceToHost, c->stream));
+    VMX_TRY(sync(c));
+    S.v[4] += now_s() - t0;
+    // the waves: where the window begins, then every candidate
+    std::vector<vmx_gz_wave> W;
+    W.push_back(vmx_gz_wave{K.start_bit, VMX_GZ_NONE, K.at_header ? VMX_GZ_F_HEADER : 0u, 0, 0, 0, 0, 0});
+    for (int64_t k = 1; k < n_chunks; ++k) {
+        uint32_t b; memcpy(&b, pin.p + 4 * k, 4);
+        if (b != VMX_GZ_NONE) W.push_back(vmx_gz_wave{b, VMX_GZ_NONE, 0, 0, 0, 0, 0, 0});
+    }
+    const int64_t nw = (int64_t)W.size();
+    for (int64_t k = 0; k + 1 < nw; ++k) W[k].stop_bit = W[k + 1].start_bit;
+    S.v[0] += (double)nw;
+    // count passes and the link check
+    t0 = now_s();
+    std::vector<vmx_gz_res> R((size_t)nw);
+    std::vector<uint32_t> todo((size_t)nw), chain{0};
+    std::vector<char> alive((size_t)nw, 1);
+    for (int64_t k = 0; k < nw; ++k) todo[k] = (uint32_t)k;
+    VMX_TRY(z.tab.reserve((size_t)nw * sizeof(vmx_gz_wave)));
+    VMX_TRY(z.todo.reserve((size_t)nw * 4));
+    VMX_TRY(z.res.reserve((size_t)nw * sizeof(vmx_gz_res)));
+    VMX_TRY(pin.reserve((size_t)nw * sizeof(vmx_gz_res)));
+    int64_t cur = 0, sum_before = 0;
+    bool linked = false;
+    while (!linked) {
+        VMX_HIP(hipMemcpyAsync(z.tab.p, W.data(), (size_t)nw * sizeof(vmx_gz_wave), hipMemcpyHostToDevice, c->stream));
+        VMX_HIP(hipMemcpyAsync(z.todo.p, todo.data(), todo.size() * 4, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_gz_count, dim3((unsigned)todo.size()), dim3(64), 0, c->stream, z.comp.as<const uint8_t>(), nb, z.tab.as<const vmx_gz_wave>(),
+                           z.todo.as<const uint32_t>(), z.res.as<vmx_gz_res>());
+        VMX_HIP(hipMemcpyAsync(pin.p, z.res.p, (size_t)nw * sizeof(vmx_gz_res), hipMemcpyDeviceToHost, c->stream));
+        VMX_TRY(sync(c));
+        for (uint32_t k : todo) memcpy(&R[k], pin.p + (size_t)k * sizeof(vmx_gz_res), sizeof(vmx_gz_res));
+        todo.clear();
+        for (;;) {
+            const vmx_gz_res& r = R[cur];
+            if (cur > 0 && sum_before >= max_text) {
+                // the waves in front fill the window's text: this one and what follows start the next window, and whatever is wrong with them is
+                // that window's error, behind the records of this one
+                chain.pop_back();
+                for (int64_t k = cur; k < nw; ++k) alive[k] = 0;
+                linked = true;
+                break;
+            }
+            if (r.err == VMX_BGZF_E_INPUT && !last) {
+                // the window ends inside this wave: it is cut at the last place where a wave can begin, or, where that is its own start, left out
+                if (r.resume_bit > W[cur].start_bit) { W[cur].stop_bit = r.resume_bit; cut_wave = cur; todo.push_back((uint32_t)cur); break; }
+                if (cur == 0) { set_error("gzip: the block at file offset " + std::to_string((long long)(base_foff + (W[0].start_bit >> 3))) + " does not end inside one chunk of the reader"); return VM_ERR_UNSUPPORTED; }
+                chain.pop_back();
+                for (int64_t k = cur; k < nw; ++k) alive[k] = 0;
+                linked = true;
+                break;
+            }
+            if (r.err) return wave_error(r);
+            int64_t nx = cur + 1;
+            const bool at_end = (r.flags & VMX_GZ_R_END) != 0 || cur == cut_wave;       // (what lies behind a cut wave belongs to the next window)
+            while (nx < nw && (!alive[nx] || at_end || W[nx].start_bit < r.end_bit)) { if (alive[nx]) { alive[nx] = 0; if (cur != cut_wave) S.v[1] += 1; } ++nx; }
+            if (at_end) { linked = true; break; }
+            if (nx < nw && W[nx].start_bit == r.end_bit) { chain.push_back((uint32_t)nx); sum_before += r.n_sym; cur = nx; continue; }
+            const uint32_t stop = nx < nw ? W[nx].start_bit : VMX_GZ_NONE;
+            if (stop == W[cur].stop_bit) { set_error("gzip: the block chain does not advance"); return VM_ERR_HIP; }
+            W[cur].stop_bit = stop; todo.push_back((uint32_t)cur); S.v[2] += 1;
+            break;
+        }
+    }
+    if (K.at_header && K.start_bit == 0 && base_foff == 0) S.v[3] = (double)R[0].n_sym;
+    // the leading verified waves whose text fits, at their final offsets
+    int64_t nv = 0, total = 0, n_ev = 0;
+    uint64_t open = K.open;
+    std::vector<vmx_gz_wave> V;
+    for (size_t i = 0; i < chain.size(); ++i) {
+        const vmx_gz_res& r = R[chain[i]];
+        if (i > 0 && total + (int64_t)r.n_sym > max_text) break;
+        vmx_gz_wave v = W[chain[i]];
+        v.hist = (uint32_t)std::min<uint64_t>(open, VMX_GZ_WIN); v.ooff = total; v.eoff = n_ev; v.n_sym = r.n_sym; v.n_ev = r.n_ev;
+        V.push_back(v);
+        open = r.flags & VMX_GZ_R_MEMBER ? (uint64_t)r.open : open + r.n_sym;
+        total += r.n_sym; n_ev += r.n_ev; ++nv;
+    }
+    const bool all = nv == (int64_t)chain.size();
+    const vmx_gz_res& rl = R[chain[nv - 1]];
+    const bool next_hdr = all ? (rl.flags & (VMX_GZ_R_END | VMX_GZ_R_HEADER)) != 0 : false;
+    *consumed_bits = all ? (int64_t)rl.end_bit : (int64_t)W[chain[nv]].start_bit;
+    *done = all && last && (rl.flags & VMX_GZ_R_END) != 0;
+    if (nv == 0) return 0;                                              // (cannot be: wave 0 is verified by definition or the call has returned)
+    if (total >= ((int64_t)1 << 32)) { set_error("gzip: 4 GB of text or more in one window"); return VM_ERR_UNSUPPORTED; }
+    VMX_TRY(z.sym.reserve((size_t)(total + 64) * 2));
+    VMX_TRY(z.out.reserve((size_t)total + 128));
+    VMX_TRY(z.ev.reserve((size_t)(n_ev + 1) * sizeof(vmx_gz_member)));
+    VMX_TRY(z.ev_end.reserve((size_t)(n_ev + 1) * 8));
+    VMX_TRY(z.acc.reserve((size_t)(n_ev + 1) * 4));
+    VMX_TRY(z.win_in.reserve((size_t)nv * VMX_GZ_WIN));
+    VMX_TRY(z.win_out.reserve(VMX_GZ_WIN));
+    VMX_TRY(z.key.reserve(8));
+    VMX_TRY(pin.reserve((size_t)nv * sizeof(vmx_gz_res) + (size_t)(n_ev + 1) * sizeof(vmx_gz_member) + 64));
+    VMX_HIP(hipMemcpyAsync(z.tab.p, V.data(), (size_t)nv * sizeof(vmx_gz_wave), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_gz_decode, dim3((unsigned)nv), dim3(64), 0, c->stream, z.comp.as<const uint8_t>(), nb, z.tab.as<const vmx_gz_wave>(), z.res.as<vmx_gz_res>(),
+                       z.sym.as<uint16_t>(), z.ev.as<vmx_gz_member>());
+    char* p_ev = pin.p + (size_t)nv * sizeof(vmx_gz_res);
+    VMX_HIP(hipMemcpyAsync(pin.p, z.res.p, (size_t)nv * sizeof(vmx_gz_res), hipMemcpyDeviceToHost, c->stream));
+    if (n_ev) VMX_HIP(hipMemcpyAsync(p_ev, z.ev.p, (size_t)n_ev * sizeof(vmx_gz_member), hipMemcpyDeviceToHost, c->stream));
+    VMX_TRY(sync(c));
+    for (int64_t i = 0; i < nv; ++i) {
+        vmx_gz_res r; memcpy(&r, pin.p + (size_t)i * sizeof(vmx_gz_res), sizeof r);
+        const vmx_gz_res& q = R[chain[i]];
+        if (r.err) return wave_error(r);
+        if (r.n_sym != q.n_sym || r.n_ev != q.n_ev || r.end_bit != q.end_bit) { set_error("gzip: the write pass and the count pass disagree"); return VM_ERR_HIP; }
+    }
+    std::vector<vmx_gz_member> M((size_t)n_ev);
+    std::vector<uint64_t> ev_end((size_t)n_ev + 1);
+    if (n_ev) memcpy(M.data(), p_ev, (size_t)n_ev * sizeof(vmx_gz_member));
+    for (int64_t i = 0; i < nv; ++i) for (int64_t e = V[i].eoff; e < V[i].eoff + V[i].n_ev; ++e) ev_end[e] = (uint64_t)(V[i].ooff + M[e].opos);
+    ev_end[n_ev] = (uint64_t)total;                                     // the member that is open where the text ends: its piece's CRC32 is carried
+    S.v[5] += now_s() - t0;
+    if (total) {
+        t0 = now_s();
+        hipLaunchKernelGGL(k_gz_window, dim3(1), dim3(1024), 0, c->stream, z.sym.as<const uint16_t>(), z.tab.as<const vmx_gz_wave>(), nv,
+                           K.have_win ? K.win.as<const uint8_t>() : (const uint8_t*)nullptr, z.win_in.as<uint8_t>(), z.win_out.as<uint8_t>());
+        VMX_TRY(sync(c));
+        S.v[6] += now_s() - t0;
+        t0 = now_s();
+        VMX_HIP(hipMemcpyAsync(z.ev_end.p, ev_end.data(), (size_t)(n_ev + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        VMX_HIP(hipMemsetAsync(z.acc.p, 0, (size_t)(n_ev + 1) * 4, c->stream));
+        VMX_HIP(hipMemsetAsync(z.key.p, 0xff, 8, c->stream));
+        hipLaunchKernelGGL(k_gz_resolve, dim3((unsigned)((total + VMX_GZ_TILE - 1) / VMX_GZ_TILE)), dim3(256), 0, c->stream, z.sym.as<const uint16_t>(),
+                           z.tab.as<const vmx_gz_wave>(), nv, z.win_in.as<const uint8_t>(), z.ev_end.as<const uint64_t>(), n_ev + 1, total, crc_x2n_table(), z.out.as<uint8_t>(),
+                           z.acc.as<uint32_t>(), z.key.as<unsigned long long>());
+        VMX_HIP(hipMemcpyAsync(pin.p, z.key.p, 8, hipMemcpyDeviceToHost, c->stream));
+        VMX_HIP(hipMemcpyAsync(pin.p + 64, z.acc.p, (size_t)(n_ev + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+        VMX_TRY(sync(c));
+        S.v[7] += now_s() - t0;
+        uint64_t key; memcpy(&key, pin.p, 8);
+        if (key != ~0ull) {
+            int64_t i = 0;
+            while (i + 1 < nv && V[i + 1].ooff <= (int64_t)key) ++i;
+            set_error("gzip: " + std::string(bgzf_reason(VMX_BGZF_E_DIST)) + " in the blocks from file offset " + std::to_string((long long)(base_foff + (V[i].start_bit >> 3))));
+            return VM_ERR_IO;
+        }
+    }
+    // every member that ends in this window: its CRC32 and ISIZE, with what was carried for the one that was open; then the new carry
+    uint64_t begin = 0;
+    for (int64_t e = 0; e <= n_ev; ++e) {
+        uint32_t piece = 0;
+        if (total) memcpy(&piece, pin.p + 64 + 4 * e, 4);
+        const uint64_t len = ev_end[e] - begin;
+        const uint32_t crc = e == 0 ? crc_combine_host(K.crc, piece, len) : piece;
+        const uint64_t size = e == 0 ? K.open + len : len;
+        if (e == n_ev) { K.crc = crc; K.open = size; break; }
+        const std::string where = "gzip member at file offset " + std::to_string((long long)K.member_foff) + ": ";
+        if ((uint32_t)size != M[e].isize) { set_error(where + "ISIZE mismatch"); return VM_ERR_IO; }
+        if (crc != M[e].crc) { set_error(where + "CRC32 mismatch"); return VM_ERR_IO; }
+        begin = ev_end[e]; K.member_foff = base_foff + (int64_t)M[e].next_byte;
+        if (e == 0) { K.crc = 0; K.open = 0; }
+    }
+    if (total) {
+        VMX_TRY(K.win.reserve(VMX_GZ_WIN));
+        VMX_HIP(hipMemcpyAsync(K.win.p, z.win_out.p, VMX_GZ_WIN, hipMemcpyDeviceToDevice, c->stream));
+        VMX_TRY(sync(c));
+        K.have_win = true;
+    }
+    K.start_bit = (uint32_t)(*consumed_bits & 7); K.at_header = next_hdr;
+    *n_text = total;
+    return 0;
+}
+
+// comp[0, n) (host): a series of complete gzip members -> z.out[0, *n_text) on the device; waits for the result
+int gzip_inflate_buffer(vm_ctx* c, GzipBufs& z, HostPinned& pin, const uint8_t* comp, int64_t n, GzipStats& S, int64_t* n_text) {
+    S = GzipStats();
+    *n_text = 0;
+    if (n < 2 || comp[0] != 0x1f || comp[1] != 0x8b) { set_error("not a gzip member (bad magic) at file offset 0"); return VM_ERR_IO; }
+    GzipCarry K;
+    int64_t used = 0; bool done = false;
+    return gzip_window_run(c, z, pin, comp, n, 0, true, INT64_MAX, K, S, n_text, &used, &done);
+}
+
+// The file half of a reader of plain gzip: beside BgzfIn, whose file, staging buffer, inflate buffers and carried tail it uses, with
+// bgzf_in_window's contract: "d_inf[which] holds *avail bytes of text behind the carried tail". A window is the VMX_BAM_IN_CHUNK bytes of the
+// file from the byte of the next block on; what links the windows is GzipCarry. READ-AHEAD: ch[0].stage (two chunks of room) holds the
+// file's bytes [fpos, fpos + have). The next window begins somewhere inside this one, so what it needs beyond these bytes is known before this
+// window's chain is linked: the chunk_bytes behind fpos + have. They are read into ch[1].stage on a thread of its own while the device
+// works on this window, and appended when the next window is asked for; what this window consumed is then dropped from the front.
+struct GzipIn { GzipBufs z; GzipCarry K; GzipStats S; int64_t fpos = 0, have = 0; bool eof = false; int64_t pre_want = 0; };
+
+void gzip_in_free(GzipIn* g) { delete g; }
+
+// bytes [at, at + want) of the file into k.stage; k.got: how many there were; k.rc / k.err on a read error
+void gzip_read_into(BgzfIn* r, int slot, int64_t off_in_stage, int64_t at, int64_t want) {
+    BamInChunk& k = r->ch[slot];
+    const double t0 = now_s();
+    k.got = 0; k.rc = 0; k.err.clear();
+    while (k.got < want) {
+        const ssize_t q = pread(r->fd, k.stage.p + off_in_stage + k.got, (size_t)(want - k.got), (off_t)(at + k.got));
+        if (q < 0) { k.rc = VM_ERR_IO; k.err = "read error at file offset " + std::to_string((long long)(at + k.got)); break; }
+        if (q == 0) break;
+        k.got += q;
+    }
+    k.busy = now_s() - t0;
+}
+
+int gzip_in_window(BgzfIn* r, GzipIn* g, double* st, int64_t* avail_out) {
+    vm_ctx* c = r->c;
+    if (r->file_done) return 0;
+    BamInChunk& k = r->ch[0];
+    double t0 = now_s();
+    VMX_TRY(k.stage.reserve((size_t)std::min<int64_t>(2 * r->chunk_bytes, std::max<int64_t>(r->fsize, 1))));      // (reserved once: the size does not change)
+    if (r->pre_on) {                                                    // what was read ahead goes behind the bytes in hand
+        r->pre.get(); r->pre_on = false;
+        BamInChunk& a = r->ch[1];
+        st[0] += a.busy;
+        if (a.rc < 0) { set_error(a.err); return a.rc; }
+        memcpy(k.stage.p + g->have, a.stage.p, (size_t)a.got);
+        g->have += a.got;
+        if (a.got < g->pre_want) g->eof = true;
+    }
+    if (g->have < r->chunk_bytes && !g->eof) {                          // the first window (nothing was read ahead yet)
+        const int64_t want = r->chunk_bytes - g->have;
+        gzip_read_into(r, 0, g->have, g->fpos + g->have, want);
+        if (k.rc < 0) { set_error(k.err); return k.rc; }
+        st[0] += k.busy;
+        g->have += k.got;
+        if (k.got < want) g->eof = true;
+    }
+    st[1] += now_s() - t0;
+    if (g->have == 0) {                                                 // the file ended at a window's edge
+        if (!g->K.at_header) { set_error("truncated gzip input: what begins at file offset " + std::to_string((long long)g->fpos) + " is not complete"); return VM_ERR_IO; }
+        r->file_done = true;
+        return 0;
+    }
+    k.got = std::min<int64_t>(g->have, r->chunk_bytes);
+    const bool last = g->eof && k.got == g->have;
+    if (!g->eof && g->have <= r->chunk_bytes) {                         // read ahead while the device works
+        VMX_TRY(r->ch[1].stage.reserve((size_t)std::min<int64_t>(r->chunk_bytes, std::max<int64_t>(r->fsize, 1))));
+        g->pre_want = r->chunk_bytes;
+        r->pre_on = true;
+        r->pre = std::async(std::launch::async, gzip_read_into, r, 1, (int64_t)0, g->fpos + g->have, g->pre_want);
+    }
+    t0 = now_s();
+    int64_t text = 0, used = 0; bool done = false;
+    VMX_TRY(gzip_window_run(c, g->z, r->pin, (const uint8_t*)k.stage.p, k.got, g->fpos, last, r->max_inf, g->K, g->S, &text, &used, &done));
+    DevBuf& dst = r->d_inf[r->which ^ 1];
+    const int64_t avail = r->carry + text;
+    VMX_TRY(dst.reserve((size_t)avail + 64));
+    if (r->carry) VMX_HIP(hipMemcpyAsync(dst.p, r->d_inf[r->which].as<uint8_t>() + r->tail_off, (size_t)r->carry, hipMemcpyDeviceToDevice, c->stream));
+    if (text) VMX_HIP(hipMemcpyAsync(dst.as<uint8_t>() + r->carry, g->z.out.p, (size_t)text, hipMemcpyDeviceToDevice, c->stream));
+    VMX_TRY(sync(c));
+    r->which ^= 1;
+    const int64_t eaten = used >> 3;                                    // whole bytes in front of the next window's first bit
+    memmove(k.stage.p, k.stage.p + eaten, (size_t)(g->have - eaten));
+    g->have -= eaten; g->fpos += eaten;
+    if (done) r->file_done = true;
+    st[2] += now_s() - t0; st[7] += 1; st[8] += (double)(used >> 3); st[9] += (double)text;
+    *avail_out = avail;
+    return 1;
+}
+
+double gzip_in_stat(const GzipIn* g, int i) { return g && i >= 0 && i < 8 ? g->S.v[i] : 0.0; }
+
+GzipIn* gzip_in_new() { return new GzipIn(); }
+
 }  // namespace
 
 extern "C" {
+
+int vm_gzip_decompress_stats(vm_ctx* c, const void* in, int64_t n, char** out, int64_t* n_out, double* stats, int n_stats) {
+    if (out) *out = nullptr;
+    if (n_out) *n_out = 0;
+    if (!c) return VM_ERR_NO_CTX;
+    if (!out || !n_out || n < 0 || (n > 0 && !in) || (n_stats > 0 && !stats)) return VM_ERR_ARG;
+    GzipBufs z; HostPinned pin; GzipStats S;
+    int64_t total = 0;
+    int rc = 0;
+    if (n > 0) rc = gzip_inflate_buffer(c, z, pin, (const uint8_t*)in, n, S, &total);
+    for (int i = 0; i < n_stats; ++i) stats[i] = i < 8 ? S.v[i] : 0.0;
+    char* res = nullptr;
+    if (rc == 0 && !(res = (char*)malloc((size_t)total + 1))) { set_error("out of host memory"); rc = VM_ERR_OOM; }
+    if (rc == 0 && total && hipMemcpy(res, z.out.p, (size_t)total, hipMemcpyDeviceToHost) != hipSuccess) { set_error("vm_gzip_decompress: download failed"); rc = VM_ERR_HIP; }
+    (void)hipStreamSynchronize(c->stream);
+    if (rc < 0) { free(res); return rc; }
+    *out = res; *n_out = total;
+    return 0;
+}
+
+int vm_gzip_decompress(vm_ctx* c, const void* in, int64_t n, char** out, int64_t* n_out) { return vm_gzip_decompress_stats(c, in, n, out, n_out, nullptr, 0); }
 
 int vm_bgzf_decompress(vm_ctx* c, const void* in, int64_t n, char** out, int64_t* n_out) {
     if (out) *out = nullptr;
@@ -1299,7 +1659,9 @@ void vm_fastq_reader_close(vm_fastq_reader* r) {
     reader_close(r);
 }
 
-int vm_fastq_reader_open(vm_ctx* c, const char* path, vm_fastq_reader** out) {
+int vm_fastq_reader_open(vm_ctx* c, const char* path, vm_fastq_reader** out) { return vm_fastq_reader_open_opts(c, path, 0, out); }
+
+int vm_fastq_reader_open_opts(vm_ctx* c, const char* path, int flags, vm_fastq_reader** out) {
     if (out) *out = nullptr;
     if (!c) return VM_ERR_NO_CTX;
     if (!out || !path) return VM_ERR_ARG;
@@ -1312,6 +1674,12 @@ int vm_fastq_reader_open(vm_ctx* c, const char* path, vm_fastq_reader** out) {
         const ssize_t got = pread(r->in.fd, magic, 2, 0);
         if (got < 0) { set_error(std::string("cannot read ") + path); rc = VM_ERR_IO; }
         else if (got < 2 || magic[0] != 0x1f || magic[1] != 0x8b) { set_error(std::string("not a gzip file (the device reader takes bgzipped FASTQ): ") + path); rc = VM_ERR_UNSUPPORTED; }
+    }
+    if (rc == 0 && (flags & VM_READER_GZIP_DEVICE)) {                   // plain gzip (no BGZF BC subfield in the first member) goes through GzipIn
+        unsigned char h[18] = {0};
+        const ssize_t got = pread(r->in.fd, h, 18, 0);
+        const bool bgzf = got == 18 && h[3] == 4 && h[12] == 'B' && h[13] == 'C';
+        if (!bgzf) r->gz = gzip_in_new();
     }
     // windows until one holds a record: the first record's header decides at once whether this is FASTQ
     int w = 1;
@@ -1336,7 +1704,7 @@ int64_t vm_fastq_reader_read(vm_fastq_reader* r, int64_t max_reads, int64_t max_
 
 int vm_fastq_reader_stats(const vm_fastq_reader* r, double* out, int n) {
     if (!r || !out) return VM_ERR_ARG;
-    for (int i = 0; i < n; ++i) out[i] = i == 6 ? r->h.handout_s : i < 11 ? r->pub[i] : 0.0;
+    for (int i = 0; i < n; ++i) out[i] = i == 6 ? r->h.handout_s : i < 11 ? r->pub[i] : i < 19 ? gzip_in_stat(r->gz, i - 11) : 0.0;
     return 0;
 }
 
@@ -1477,7 +1845,7 @@ int ref_window(RefParse& R, const uint8_t* buf, int64_t avail, bool closing, int
     return 0;
 }
 
-int ref_fasta_device_impl(vm_ctx* c, const char* path, vm_index* mi, double* st) {
+int ref_fasta_device_impl(vm_ctx* c, const char* path, vm_index* mi, double* st, int flags) {
     RefParse R; R.c = c; R.mi = mi; R.st = st;
     VMX_TRY(R.d_other.reserve(8)); VMX_HIP(hipMemsetAsync(R.d_other.p, 0, 8, c->stream));
     BgzfIn in;
@@ -1492,9 +1860,12 @@ int ref_fasta_device_impl(vm_ctx* c, const char* path, vm_index* mi, double* st)
     }
     const bool gz = ng >= 2 && mg[0] == 0x1f && mg[1] == 0x8b;
     const bool bgzf = gz && ng >= 18 && mg[2] == 8 && mg[3] == 4 && mg[12] == 'B' && mg[13] == 'C';
+    // VM_READER_GZIP_DEVICE: plain gzip through GzipIn (inflated on the device in parallel chunks) in BgzfIn's place, window for window
+    struct FreeGz { GzipIn* g; ~FreeGz() { gzip_in_free(g); } } gzdev{gz && !bgzf && (flags & VM_READER_GZIP_DEVICE) ? gzip_in_new() : nullptr};
+    const bool dev_in = bgzf || gzdev.g;
     int64_t win = (int64_t)256 << 20;
     RefRaw raw;
-    if (bgzf) { VMX_TRY(bgzf_in_open(&in, c, path)); win = in.max_inf; mi->bases.reserve((size_t)std::min<int64_t>(in.fsize * 5, (1LL << 35) - 1)); }
+    if (dev_in) { VMX_TRY(bgzf_in_open(&in, c, path)); win = in.max_inf; mi->bases.reserve((size_t)std::min<int64_t>(in.fsize * 5, (1LL << 35) - 1)); }
     else {
         // VMX_REF_IN_WINDOW: text bytes per window of plain and plain-gzip input (tests cross many windows with small files)
         if (const char* e = getenv("VMX_REF_IN_WINDOW")) win = std::min<int64_t>(std::max<int64_t>(atoll(e), 1 << 16), (int64_t)1 << 30);
@@ -1521,9 +1892,9 @@ int ref_fasta_device_impl(vm_ctx* c, const char* path, vm_index* mi, double* st)
     R.win = win; R.path = path;
     for (bool closing = false; !closing;) {
         int64_t avail = 0;
-        if (bgzf) {
+        if (dev_in) {
             double bst[13] = {0};
-            const int irc = bgzf_in_window(&in, bst, &avail);
+            const int irc = gzdev.g ? gzip_in_window(&in, gzdev.g, bst, &avail) : bgzf_in_window(&in, bst, &avail);
             st[0] += bst[0]; st[1] += bst[2]; st[5] += bst[9];
             if (irc < 0) return irc;
             closing = in.file_done;
@@ -1576,7 +1947,7 @@ int ref_fasta_device_impl(vm_ctx* c, const char* path, vm_index* mi, double* st)
 
 // path -> mi->names, lens, offsets, bases, d_codes (without the tail padding) and n_other_letters, parsed on the device. st[0 .. 8): seconds of file
 // read, inflate, parse kernels, download of the bases, (index build: the caller's), then text bytes, windows, contigs.
-int vmx_ref_fasta_device(vm_ctx* c, const char* path, vm_index* mi, double* st) {
-    try { return ref_fasta_device_impl(c, path, mi, st); }
+int vmx_ref_fasta_device(vm_ctx* c, const char* path, vm_index* mi, double* st, int flags) {
+    try { return ref_fasta_device_impl(c, path, mi, st, flags); }
     catch (const std::bad_alloc&) { set_error("reference FASTA: out of host memory"); return VM_ERR_OOM; }
 }

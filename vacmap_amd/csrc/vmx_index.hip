@@ -413,6 +413,10 @@ int vm_index_build_fasta(vm_ctx* c, const char* path, int k, int w, vm_index** o
 }
 
 int vm_index_build_fasta_device(vm_ctx* c, const char* path, int k, int w, vm_index** out, double* stats, int n_stats) {
+    return vm_index_build_fasta_device_opts(c, path, k, w, 0, out, stats, n_stats);
+}
+
+int vm_index_build_fasta_device_opts(vm_ctx* c, const char* path, int k, int w, int flags, vm_index** out, double* stats, int n_stats) {
     if (out) *out = nullptr;
     if (!c) { set_error("no context"); return VM_ERR_NO_CTX; }
     if (!out || !path) { set_error("vm_index_build_fasta_device: no path or no result pointer"); return VM_ERR_ARG; }
@@ -423,7 +427,7 @@ int vm_index_build_fasta_device(vm_ctx* c, const char* path, int k, int w, vm_in
         struct Guard { vm_index* m; ~Guard() { if (m) vm_index_free(m); } } g{mi};
         mi->ctx = c; mi->k = k; mi->w = w;
         double st[8] = {0};
-        VMX_TRY(vmx_ref_fasta_device(c, path, mi, st));
+        VMX_TRY(vmx_ref_fasta_device(c, path, mi, st, flags));
         const auto t0 = std::chrono::steady_clock::now();
         hipLaunchKernelGGL(k_fill_u8, dim3(1), dim3(256), 0, c->stream, mi->d_codes.as<uint8_t>() + mi->offsets.back(), (int64_t)64, (uint8_t)4);
         VMX_TRY(index_build_device(mi));

@@ -38,7 +38,7 @@ static inline int vmx_scan64(vm_ctx* c, vmx::DevBuf& tmp, const int64_t* in, int
 int vmx_index_upload_codes(vm_index* mi, const char* const* seqs);
 // the reference FASTA at path parsed on the device (vmx_bam.hip, kernels: k_fasta_in.hip) -> mi->names, lens, offsets, bases, d_codes (without the 64
 // bytes of padding) and n_other_letters. st[0 .. 8): seconds of file read, inflate, parse kernels, download of the bases, [4] the caller's, text bytes, windows, contigs
-int vmx_ref_fasta_device(vm_ctx* c, const char* path, vm_index* mi, double* st);
+int vmx_ref_fasta_device(vm_ctx* c, const char* path, vm_index* mi, double* st, int flags = 0);      // flags: VM_READER_GZIP_DEVICE
 // sorted (hash, position) pairs on the device (positions in mi->d_pos) -> distinct keys, occurrence cap, hash table, contig offsets.
 // d_keys is consumed (released).
 int vmx_index_finish_device(vm_index* mi, vmx::DevBuf& d_keys, int64_t n);

@@ -16,7 +16,7 @@ def index_paths(ref, k, w):
     return base + '.vmx', base + '.mmi'
 
 
-def find_index(ctx, ref, k, w, write=True, log=sys.stderr, reader='host'):
+def find_index(ctx, ref, k, w, write=True, log=sys.stderr, reader='host', gzip='host'):
     vmx, mmi = index_paths(ref, k, w)
     ref_m = os.path.getmtime(ref)
     for path, loader in ((vmx, Index.load), (mmi, Index.load_mmi)):
@@ -34,7 +34,8 @@ def find_index(ctx, ref, k, w, write=True, log=sys.stderr, reader='host'):
     idx = None
     if reader == 'native':                                  # the FASTA parsed on the GPU; what it does not take goes to the host parser, with one line
         try:
-            idx = Index.from_fasta(ctx, ref, k=k, w=w, reader='native')
+            opt = {'gzip': 'device'} if gzip == 'device' else {}          # (--gzip-inflate device: plain gzip inflated on the GPU)
+            idx = Index.from_fasta(ctx, ref, k=k, w=w, reader='native', **opt)
         except VmxError as e:
             if e.code != -7:                                # VM_ERR_UNSUPPORTED
                 raise

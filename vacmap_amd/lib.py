@@ -145,6 +145,7 @@ class VmxLib:
         L.vm_chains_out_free.argtypes = [P(ChainsOut)]
         L.vm_index_build_fasta.argtypes = [vp, cp, C.c_int, C.c_int, P(vp)]
         L.vm_index_build_fasta_device.argtypes = [vp, cp, C.c_int, C.c_int, P(vp), P(dbl), C.c_int]
+        L.vm_index_build_fasta_device_opts.argtypes = [vp, cp, C.c_int, C.c_int, C.c_int, P(vp), P(dbl), C.c_int]
         L.vm_index_build_mem.argtypes = [vp, C.c_int, P(cp), P(cp), P(i64), C.c_int, C.c_int, P(vp)]
         L.vm_index_save.argtypes = [vp, cp]; L.vm_index_load.argtypes = [vp, cp, P(vp)]
         L.vm_index_save_mmi.argtypes = [vp, cp, C.c_int]; L.vm_index_load_mmi.argtypes = [vp, cp, P(vp)]
@@ -195,6 +196,9 @@ class VmxLib:
         L.vm_bam_sorter_index.argtypes = [vp, P(vp), P(i64)]
         L.vm_bgzf_compress.argtypes = [vp, vp, i64, P(vp), P(i64)]
         L.vm_bgzf_decompress.argtypes = [vp, vp, i64, P(vp), P(i64)]
+        L.vm_gzip_decompress.argtypes = [vp, vp, i64, P(vp), P(i64)]
+        L.vm_gzip_decompress_stats.argtypes = [vp, vp, i64, P(vp), P(i64), P(C.c_double), C.c_int]
+        L.vm_fastq_reader_open_opts.argtypes = [vp, cp, C.c_int, P(vp)]
         L.vm_bam_reader_open.argtypes = [vp, cp, P(vp)]; L.vm_bam_reader_open_tags.argtypes = [vp, cp, cp, P(vp)]; L.vm_bam_reader_close.argtypes = [vp]; L.vm_bam_reader_close.restype = None
         L.vm_bam_reader_read.argtypes = [vp, i64, i64] + [P(vp), P(P(i64))] * 4; L.vm_bam_reader_read.restype = i64
         L.vm_bam_reader_stats.argtypes = [vp, P(C.c_double), C.c_int]
@@ -703,6 +707,22 @@ def bgzf_decompress(ctx, data):
     return _take_bytes(ctx.lib, p, n)
 
 
+GZIP_STATS = ('chunks_started', 'candidates_rejected', 'chunks_redone', 'first_chain_bytes', 'find_s', 'decode_s', 'window_s', 'resolve_s')
+
+
+def gzip_decompress(ctx, data, stats=None):
+    """gzip members (plain gzip: any writer's, one member or many) -> their bytes, inflated on the device in parallel chunks
+    (vm_gzip_decompress_stats). stats: a dict that receives the call's GZIP_STATS, also when the call raises"""
+    data = bytes(data)
+    p = C.c_void_p(); n = C.c_int64()
+    v = (C.c_double * len(GZIP_STATS))()
+    rc = ctx.lib.L.vm_gzip_decompress_stats(ctx.h, data, len(data), C.byref(p), C.byref(n), v, len(GZIP_STATS))
+    if stats is not None:
+        stats.update(zip(GZIP_STATS, v))
+    ctx.lib.check(rc)
+    return _take_bytes(ctx.lib, p, n)
+
+
 class _BlobReader:
     """what the device readers share: read() as Fastx.read(), stats() as a dict of the STATS names, close(). A subclass names its three
     C-ABI entries (_READ, _STATS_FN, _CLOSE), whose signatures are the same, and sets self.ctx, self.lib and self.h"""
@@ -769,10 +789,18 @@ class FastqReader(_BlobReader):
     STATS = ('io_busy_s', 'io_wait_s', 'inflate_s', 'parse_s', 'copy_s', 'download_s', 'handout_s', 'windows', 'file_bytes', 'inflated_bytes', 'records')
     _READ, _STATS_FN, _CLOSE = 'vm_fastq_reader_read', 'vm_fastq_reader_stats', 'vm_fastq_reader_close'
 
-    def __init__(self, ctx, path):
+    def __init__(self, ctx, path, gzip='host'):
+        """gzip='device': a plain-gzip file is inflated on the device in parallel chunks (vm_fastq_reader_open_opts, VM_READER_GZIP_DEVICE)
+        instead of being refused; stats() then has GZIP_STATS too"""
+        if gzip not in ('host', 'device'):
+            raise ValueError("gzip must be 'host' or 'device'")
         self.ctx, self.lib = ctx, ctx.lib
         h = C.c_void_p()
-        self.lib.check(self.lib.L.vm_fastq_reader_open(ctx.h, _b(path), C.byref(h)))
+        if gzip == 'device':
+            self.STATS = FastqReader.STATS + GZIP_STATS
+            self.lib.check(self.lib.L.vm_fastq_reader_open_opts(ctx.h, _b(path), 1, C.byref(h)))
+        else:
+            self.lib.check(self.lib.L.vm_fastq_reader_open(ctx.h, _b(path), C.byref(h)))
         self.h = h
 
 
@@ -1009,18 +1037,24 @@ class Index:
             self.names.append(nm.value.decode()); self.lens.append(ln.value); self.offsets.append(of.value)
 
     @classmethod
-    def from_fasta(cls, ctx, path, k=15, w=10, reader='host'):
+    def from_fasta(cls, ctx, path, k=15, w=10, reader='host', gzip='host'):
         """the index of a FASTA file, plain, gzip or bgzipped. reader='host': vm_index_build_fasta parses the text on one host thread;
         reader='native': vm_index_build_fasta_device parses it on the GPU (the same index, byte for byte) and leaves its statistics in
-        idx.build_stats; a header line longer than a window raises VmxError(VM_ERR_UNSUPPORTED)"""
+        idx.build_stats; a header line longer than a window raises VmxError(VM_ERR_UNSUPPORTED). gzip='device' (with reader='native'): a
+        plain-gzip file is inflated on the GPU in parallel chunks instead of by zlib on a host thread (vm_index_build_fasta_device_opts)"""
         if reader not in ('host', 'native'):
             raise ValueError("reader must be 'host' or 'native'")
+        if gzip not in ('host', 'device'):
+            raise ValueError("gzip must be 'host' or 'device'")
         h = C.c_void_p()
         if reader == 'host':
             ctx.lib.check(ctx.lib.L.vm_index_build_fasta(ctx.h, _b(path), k, w, C.byref(h)))
             return cls(ctx, h)
         st = (C.c_double * 8)()
-        ctx.lib.check(ctx.lib.L.vm_index_build_fasta_device(ctx.h, _b(path), k, w, C.byref(h), st, 8))
+        if gzip == 'device':
+            ctx.lib.check(ctx.lib.L.vm_index_build_fasta_device_opts(ctx.h, _b(path), k, w, 1, C.byref(h), st, 8))       # VM_READER_GZIP_DEVICE
+        else:
+            ctx.lib.check(ctx.lib.L.vm_index_build_fasta_device(ctx.h, _b(path), k, w, C.byref(h), st, 8))
         idx = cls(ctx, h)
         idx.build_stats = dict(zip(REF_BUILD_STATS, (float(x) for x in st)))
         for key in ('text_bytes', 'windows', 'contigs'):
