@@ -491,10 +491,22 @@ int vm_fastq_reader_open(vm_ctx*, const char* path, vm_fastq_reader** out);
  * records have been handed out and the refusal is fatal to the run (with the default VMX_BAM_IN_CHUNK of 64 MB no deflate writer makes such a block). Truncation, a bad code,
  * distance or stored length, a CRC32 or ISIZE mismatch: VM_ERR_IO with the file offset of the block or member, from the read call that reaches it.
  * vm_fastq_reader_stats then has 8 more numbers behind its 11, of the windows inflated so far: chunks started, candidates rejected, chunks decoded
- * again, text bytes of the file's first chain, seconds in find / decode / window / resolve. */
+ * again, text bytes of the file's first chain, seconds in find / decode / window / resolve.
+ * VM_READER_FASTA (alone or with VM_READER_GZIP_DEVICE): the reader parses by vm_fastx_read's whole rule, FASTA records included, and hands out its
+ * four blobs. Lines and blank lines as above; a line whose byte 0 is '>' is class G, any other line that is not blank class O. States: 0 between
+ * records, 1 - 3 the FASTQ states, 4 inside a FASTA record. State 0: a blank line is skipped, G starts a FASTA record (-> 4), O starts a FASTQ
+ * record (-> 1; byte 0 must be '@', else VM_ERR_IO "not FASTA/FASTQ: " and the line's first 40 bytes). States 1, 2, 3 take any line (-> 2, 3, 0).
+ * State 4: G starts the next FASTA record, every other line, blank or not, '@...' and '+' lines too, is body (-> 4). Header of both kinds: the
+ * name is bytes 1 to the first space or tab, the comment everything behind that one separator. A FASTA body line, after the '\r' drop, is
+ * stripped of spaces and tabs (not '\r') at both ends, upper-cased and appended; interior bytes stay. FASTQ lines are whole. A FASTA record has
+ * empty qualities, and one without body lines empty bases. The file may end in state 4 (the last record is complete); ending in state 1, 2 or 3
+ * is "truncated FASTQ record". VM_ERR_UNSUPPORTED for '>' does not occur. A record is carried from window to window until the line that starts
+ * the next record (or the file's end) is in the window: device memory alone bounds its length. Without this flag the reader is exactly the
+ * FASTQ-only one, the same kernels included. Flag bits other than these two: VM_ERR_ARG. */
 #ifndef VM_READER_GZIP_DEVICE
 #define VM_READER_GZIP_DEVICE 1
 #endif
+#define VM_READER_FASTA 2
 int vm_fastq_reader_open_opts(vm_ctx*, const char* path, int flags, vm_fastq_reader** out);
 int64_t vm_fastq_reader_read(vm_fastq_reader*, int64_t max_reads, int64_t max_bases, char** names, int64_t** name_off, char** seqs, int64_t** seq_off, char** quals,
                              int64_t** qual_off, char** comments, int64_t** com_off);

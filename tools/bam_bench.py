@@ -23,6 +23,11 @@
         it is without tags) and with tags='*' (the auxiliary fields turned into comment text on the device), two passes each: reads/s, the
         producer's per-step clocks and the comment bytes per read of the second passes. Run it under `rocprofv3 --kernel-trace --stats` with a
         smaller --gb for the aux kernels' own time next to k_bgzf_inflate's.
+    python tools/bam_bench.py fasta-input [--gb 2] [--asm-gb 3.1] [--rounds 3] [--only hifi_line,hifi_wrapped,assembly,fastq] [--out profiles/fasta_reads_reader.json]
+        FASTA reads on the device (lib.FastqReader(fasta=True)) against lib.Fastx on the same bgzipped files: 15 kb reads on one line and
+        wrapped at 60, an hg38-shape assembly of 24 contigs, and the FASTQ file of fastq-input through fasta=True against fasta=False.
+        Every step is a child process under --run-timeout. For the kernels' own time run it under `rocprofv3 --kernel-trace --stats` with
+        --gb 0.5 --rounds 1.
     python tools/bam_bench.py input-driver [--reads 40960] [--replicate 8] [--rounds 3] [--out profiles/bam_input_driver.json]
         the driver on the same reads as plain FASTQ and as unaligned BAM with --bam-reader native, alternated in fresh processes: the
         driver's own wait_input seconds and loop time per run.
@@ -298,6 +303,106 @@ def fastq_input_bench(args):
     _save(res, args.out)
 
 
+def _hifi_pieces(n_bytes, wrapped, seed=17, pool=64):
+    """FASTA text of at least n_bytes: 15 kb reads (2 ... 40 kb) on one line each, or wrapped at 60; read i is a rotation of pool read i mod pool"""
+    rng = np.random.default_rng(seed)
+    lens = np.clip(rng.normal(15000, 4000, pool), 2000, 40000).astype(np.int64)
+    seqs = [np.frombuffer(b'ACGT', np.uint8)[rng.integers(0, 4, int(n))] for n in lens]
+    pieces, tot, i = [], 0, 0
+    while tot < n_bytes:
+        k = i % pool
+        n = int(lens[k])
+        s = np.roll(seqs[k], (i * 131) % n)
+        if wrapped:
+            m = n // 60
+            body = np.empty((m, 61), np.uint8); body[:, :60] = s[:m * 60].reshape(m, 60); body[:, 60] = 10
+            body = body.tobytes() + (s[m * 60:].tobytes() + b'\n' if m * 60 < n else b'')
+        else:
+            body = s.tobytes() + b'\n'
+        pieces.append(b'>read%09d ch=%d\n' % (i, i % 512) + body)
+        tot += len(pieces[-1]); i += 1
+    return pieces
+
+
+def _fasta_input_step(args):
+    """child of fasta_input_bench: --only READER:PATH, two passes over the file, the second one reported"""
+    from vacmap_amd.lib import Context, FastqReader, Fastx
+    kind, path = args.only.split(':', 1)
+    ctx = Context(0)
+    out = None
+    for _ in range(2):                                      # the second pass counts (the first grows pools and warms the page cache)
+        t0 = time.time()
+        rd = Fastx(path, lib=ctx.lib) if kind == 'host' else FastqReader(ctx, path, fasta=(kind == 'device_fasta'))
+        n = bases = 0
+        for ch in iter(lambda: rd.read(4096), None):
+            n += len(ch['seqs_off']) - 1; bases += int(ch['seqs_off'][-1])
+        out = {'reads': n, 'bases': bases, 'wall_s': time.time() - t0}
+        if hasattr(rd, 'stats'):
+            out['phases'] = rd.stats()
+        rd.close()
+    ctx.close()
+    print('RESULT ' + json.dumps(out))
+
+
+def fasta_input_bench(args):
+    """lib.FastqReader(fasta=True) against lib.Fastx on the same bgzipped files -> profiles/fasta_reads_reader.json: (a) 15 kb reads as one-line
+    FASTA and wrapped at 60 (--gb of text each, zlib level 6 members), (b) the hg38-shape assembly of tools/ref_load_bench.py (--asm-gb of bases,
+    60 columns), (c) the FASTQ file of fastq-input through fasta=True against fasta=False: the price of the general parser. args.rounds
+    alternated rounds; every step is a child process under --run-timeout that reads its file twice and reports the second pass. A child that
+    fails or runs out of time ends the run: nothing more is started."""
+    if args.only and ':' in args.only:
+        return _fasta_input_step(args)
+    sys.path.insert(0, os.path.join(ROOT, 'tests')); sys.path.insert(0, os.path.join(ROOT, 'tools'))
+    import bam_input_cases as K
+    import fastq_input_cases as F
+    import ref_load_bench as RL
+    from vacmap_amd import synth
+    os.makedirs(args.tmp, exist_ok=True)
+    t0 = time.time()
+    files, text = {}, {}
+    want = [w for w in ('hifi_line', 'hifi_wrapped', 'assembly', 'fastq') if not args.only or w in args.only.split(',')]
+    for w in want:
+        files[w] = os.path.join(args.tmp, 'fa_%s.gz' % w)
+        if w == 'assembly':
+            lens = synth.hg38_like_lengths(int(args.asm_gb * 1e9))
+            plain = os.path.join(args.tmp, 'fa_assembly.fa')
+            text[w] = RL.write_fasta(plain, synth.make_reference_fast(lens, seed=5), [b'chr%d synthetic' % (i + 1) for i in range(len(lens))])
+            K.write_bgzf_zlib(files[w], RL.pieces_of(plain), level=6)
+            os.remove(plain)
+        else:
+            pieces = F.scale_text(int(args.gb * (1 << 30)))[0] if w == 'fastq' else _hifi_pieces(int(args.gb * (1 << 30)), w == 'hifi_wrapped')
+            text[w] = sum(len(x) for x in pieces)
+            K.write_bgzf_zlib(files[w], pieces)
+            del pieces
+    res = {'text_bytes': text, 'gz_bytes': {w: os.path.getsize(p) for w, p in files.items()}, 'generate_s': time.time() - t0, 'rounds': []}
+    print('generated in %.0f s' % res['generate_s'], flush=True)
+
+    def step(kind, w):
+        pr = subprocess.run([sys.executable, os.path.abspath(__file__), 'fasta-input', '--only', kind + ':' + files[w]], stdout=subprocess.PIPE, text=True, timeout=args.run_timeout)
+        line = [ln for ln in pr.stdout.splitlines() if ln.startswith('RESULT ')]
+        if pr.returncode != 0 or not line:
+            raise SystemExit('%s on %s failed with status %d: nothing more is started' % (kind, w, pr.returncode))
+        out = json.loads(line[-1][7:])
+        out['text_GBps'] = text[w] / out['wall_s'] / 1e9; out['reads_per_s'] = out['reads'] / out['wall_s']
+        return out
+    try:
+        for _ in range(args.rounds):
+            rnd = {}
+            for w in want:
+                kinds = ('device_fasta', 'device_fastq') if w == 'fastq' else ('device_fasta', 'host')
+                rnd[w] = {k: step(k, w) for k in kinds}
+                a, b = rnd[w][kinds[0]], rnd[w][kinds[1]]
+                assert a['reads'] == b['reads'] and a['bases'] == b['bases'], (w, a['reads'], b['reads'])
+                rnd[w]['fasta_over_' + kinds[1]] = b['wall_s'] / a['wall_s']
+                print(json.dumps({w: {k: round(rnd[w][k]['text_GBps'], 3) for k in kinds}}), flush=True)
+            res['rounds'].append(rnd)
+    finally:
+        for p in files.values():
+            if os.path.exists(p):
+                os.remove(p)
+    _save(res, args.out)
+
+
 def tags_bench(args):
     """lib.BamReader on 15 kb reads that carry MM / ML / MN, with and without tags"""
     import struct
@@ -419,16 +524,18 @@ def input_driver(args):
 
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
-    ap.add_argument('what', choices=['kernels', 'driver', 'sorted', 'input', 'input-driver', 'fastq-input'])
+    ap.add_argument('what', choices=['kernels', 'driver', 'sorted', 'input', 'input-driver', 'fastq-input', 'fasta-input'])
     ap.add_argument('--only', default=None); ap.add_argument('--tags', action='store_true'); ap.add_argument('--run-timeout', type=float, default=600.0); ap.add_argument('--bench-steps', type=int, default=12)
     ap.add_argument('--gb', type=float, default=2.0); ap.add_argument('--reads', type=int, default=40960); ap.add_argument('--replicate', type=int, default=8); ap.add_argument('--ref-mb', type=float, default=100.0)
     ap.add_argument('--rounds', type=int, default=3); ap.add_argument('--t', type=int, default=16); ap.add_argument('--tmp', default='/tmp/vmx_bam_bench')
-    ap.add_argument('--out', default=None)
+    ap.add_argument('--out', default=None); ap.add_argument('--asm-gb', type=float, default=3.1)
     a = ap.parse_args()
     if a.what == 'input':
         tags_bench(a) if a.tags else input_bench(a)
     elif a.what == 'fastq-input':
         fastq_input_bench(a)
+    elif a.what == 'fasta-input':
+        fasta_input_bench(a)
     elif a.what == 'input-driver':
         input_driver(a)
     else:

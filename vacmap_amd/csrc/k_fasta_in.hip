@@ -27,10 +27,6 @@
 
 struct fa_bits { uint32_t nl, cr, gt, valid; fq_v16 v; };
 
-__device__ __forceinline__ uint32_t fa_mask16(const fq_v16& v, uint32_t c4) {
-    return fq_nibble(fq_eq_bytes(v.x, c4)) | fq_nibble(fq_eq_bytes(v.y, c4)) << 4 | fq_nibble(fq_eq_bytes(v.z, c4)) << 8 | fq_nibble(fq_eq_bytes(v.w, c4)) << 12;
-}
-
 // the 16 bytes at off (a multiple of 16; buf is a device allocation's base) as bit masks; bytes at and beyond len are masked out, but the vector
 // that holds byte len - 1 is loaded whole: up to 15 bytes behind len, inside the 64 bytes of slack behind every window
 __device__ __forceinline__ fa_bits fa_load(const uint8_t* buf, int64_t off, int64_t len) {
@@ -40,9 +36,9 @@ __device__ __forceinline__ fa_bits fa_load(const uint8_t* buf, int64_t off, int6
     b.v = *(const fq_v16*)(buf + off);
     const int64_t left = len - off;
     b.valid = left < 16 ? (1u << (int)left) - 1u : 0xffffu;
-    b.nl = fa_mask16(b.v, 0x0a0a0a0au) & b.valid;
-    b.cr = fa_mask16(b.v, 0x0d0d0d0du) & b.valid;
-    b.gt = fa_mask16(b.v, 0x3e3e3e3eu) & b.valid;
+    b.nl = fq_mask16(b.v, 0x0a0a0a0au) & b.valid;
+    b.cr = fq_mask16(b.v, 0x0d0d0d0du) & b.valid;
+    b.gt = fq_mask16(b.v, 0x3e3e3e3eu) & b.valid;
     return b;
 }
 
@@ -204,8 +200,6 @@ __global__ void __launch_bounds__(64 * FA_WAVES) k_fa_count(const uint8_t* buf, 
     if (ch == 0 && lane == 0) cnt[n_chunks] = 0;
 }
 
-__device__ __forceinline__ uint32_t fa_byte(const fq_v16& v, int k) { const uint32_t w = k < 4 ? v.x : k < 8 ? v.y : k < 12 ? v.z : v.w; return w >> (8 * (k & 3)) & 0xffu; }
-
 // The kept bytes of chunk ch go to letters[lpad + i] (upper-cased) and codes[base0 + i] for i in [lo32(coff[ch]), lo32(coff[ch + 1])), where
 // lpad = base0 & 15: both destinations have the same residue modulo 16 (letters and codes are allocation bases). A wavefront compacts its
 // chunk in LDS at that residue, then stores whole 16-byte vectors to aligned addresses and the two ragged ends byte by byte. Header h =
@@ -243,7 +237,7 @@ __global__ void __launch_bounds__(64 * FA_WAVES) k_fa_write(const uint8_t* buf, 
 #pragma unroll
             for (int k = 0; k < 16; ++k)
                 if (keep >> k & 1u) {
-                    const uint8_t x = (uint8_t)fa_byte(b.v, k);
+                    const uint8_t x = (uint8_t)fq_byte16(b.v, k);
                     const uint8_t u = x & 0xDF;
                     oth += !(u == 'A' || u == 'C' || u == 'G' || u == 'T' || u == 'N');
                     sl[p] = fq_upper1(x); sc[p] = vmx_code(x); ++p;

@@ -15,6 +15,18 @@ __device__ __forceinline__ uint32_t fq_eq_bytes(uint32_t x, uint32_t c4) {
 }
 __device__ __forceinline__ uint32_t fq_nibble(uint32_t m) { return (m >> 7 & 1u) | (m >> 14 & 2u) | (m >> 21 & 4u) | (m >> 28 & 8u); }
 
+// bit i: byte i of the 16 in v equals the byte repeated in c4
+__device__ __forceinline__ uint32_t fq_mask16(const fq_v16& v, uint32_t c4) {
+    return fq_nibble(fq_eq_bytes(v.x, c4)) | fq_nibble(fq_eq_bytes(v.y, c4)) << 4 | fq_nibble(fq_eq_bytes(v.z, c4)) << 8 | fq_nibble(fq_eq_bytes(v.w, c4)) << 12;
+}
+__device__ __forceinline__ uint32_t fq_byte16(const fq_v16& v, int k) { const uint32_t w = k < 4 ? v.x : k < 8 ? v.y : k < 12 ? v.z : v.w; return w >> (8 * (k & 3)) & 0xffu; }
+
+// line k without its terminator and without one trailing '\r': buf[a, b), 0 <= a <= b <= len (ls[k + 1] - 1 is the newline's position, or len)
+__device__ __forceinline__ void fq_line(const uint8_t* buf, const int64_t* ls, int64_t k, int64_t& a, int64_t& b) {
+    a = ls[k]; b = ls[k + 1] - 1;
+    if (b > a && buf[b - 1] == '\r') --b;
+}
+
 // first f, then g
 __device__ __forceinline__ uint32_t fq_compose(uint32_t f, uint32_t g) {
     uint32_t h = 0;

@@ -31,12 +31,6 @@ __device__ __forceinline__ uint32_t fq_nl_bits(const uint8_t* buf, int64_t off, 
     return m;
 }
 
-// line k without its terminator and without one trailing '\r': buf[a, b), 0 <= a <= b <= len (ls[k + 1] - 1 is the newline's position, or len)
-__device__ __forceinline__ void fq_line(const uint8_t* buf, const int64_t* ls, int64_t k, int64_t& a, int64_t& b) {
-    a = ls[k]; b = ls[k + 1] - 1;
-    if (b > a && buf[b - 1] == '\r') --b;
-}
-
 // ------------------------------------------------------------------------------------------------ newlines
 
 // cnt[ch] = newlines of buf[ch * 4096, ...) (one wavefront each), cnt[n_chunks] = 0 (the scan's total slot); len > 0.

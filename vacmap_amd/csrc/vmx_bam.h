@@ -154,6 +154,30 @@ __global__ void k_fq_sizes(const uint8_t* buf, const int64_t* ls, const int64_t*
 __global__ void k_fq_copy(const uint8_t* buf, const int64_t* ls, const int64_t* rline, int64_t n_rec, const int64_t* noff, const int64_t* coff, const int64_t* soff,
                           const int64_t* qoff, uint8_t* names, uint8_t* comments, uint8_t* seqs, uint8_t* quals);
 
+// FASTA and FASTQ reads on the device (k_fasta_reads.hip): the general record rule of vm_fastx_read over the line table of k_fq_nl_pos. States 0 between
+// records, 1 - 3 the FASTQ states, 4 inside a FASTA record; a line's class (blank, '>' first, other) maps the state before it to the state behind
+// it, 5 states packed 3 bits each, state s in bits 3s
+#define VMX_FR_MAP_BLANK 0x40d0u        // [0, 2, 3, 0, 4]
+#define VMX_FR_MAP_GT 0x40d4u           // [4, 2, 3, 0, 4]: a '>' line starts a FASTA record between records and inside one
+#define VMX_FR_MAP_OTHER 0x40d1u        // [1, 2, 3, 0, 4]
+#define VMX_FR_MAP_IDENT 0x4688u        // [0, 1, 2, 3, 4]
+// what the record pass leaves: complete records, the offset behind them (the rest is carried), the line the cut stands in front of (n_lines: none), the
+// first bad header (record << 8 | VMX_FQ_E_HEADER, all ones: none), the state behind the window's last line
+struct vmx_fr_result { int64_t n_rec, end, cut_line; uint64_t err_key; int32_t end_state, pad; };
+__global__ void k_fr_line_maps(const uint8_t* buf, const int64_t* ls, int64_t n_lines, uint16_t* map, uint16_t* tile_tot);
+__global__ void k_fr_tile_scan(uint16_t* tile, int64_t n_tiles);
+__global__ void k_fr_line_states(const uint16_t* map, const uint16_t* tile_pre, int64_t n_lines, uint8_t* state, int64_t* start);
+__global__ void k_fr_result(const uint8_t* buf, const int64_t* ls, const uint8_t* state, const int64_t* ridx, const int64_t* rline, int64_t n_lines, int64_t len,
+                            int closing, vmx_fr_result* res);
+__global__ void k_fr_line_keep(const uint8_t* buf, const int64_t* ls, const uint16_t* map, const uint8_t* state, int64_t n_lines, int64_t cut_line, int64_t* ka,
+                               int64_t* ks, int64_t* kq);
+__global__ void k_fr_copy(const uint8_t* buf, int64_t len, int64_t n_chunks, const int64_t* coff, const int64_t* ka, const int64_t* ks, const int64_t* kq,
+                          const int64_t* so, const int64_t* qo, uint8_t* seqs, uint8_t* quals);
+__global__ void k_fr_hdr_sizes(const uint8_t* buf, const int64_t* ls, const int64_t* rline, int64_t n_rec, int64_t cut_line, const int64_t* so, const int64_t* qo,
+                               int64_t* nsz, int64_t* csz, int64_t* soff, int64_t* qoff, unsigned long long* err_key);
+__global__ void k_fr_hdr_copy(const uint8_t* buf, const int64_t* ls, const int64_t* rline, int64_t n_rec, const int64_t* noff, const int64_t* coff, uint8_t* names,
+                              uint8_t* comments);
+
 // The reference FASTA on the device (k_fasta_in.hip): per chunk of VMX_FQ_CHUNK bytes, state = in a header line | a header has been seen << 1; a
 // chunk's map has the format of the FASTQ line maps (k_fq_tile_scan scans the tiles of both)
 // what the passes over a window leave: 1 + its last header start (0: none), where it is cut, whether a newline stands in front of the cut

@@ -802,6 +802,8 @@ struct vm_fastq_reader {
     GzipIn* gz = nullptr;
     ~vm_fastq_reader() { gzip_in_free(gz); }
     DevBuf d_cnt, d_coff, d_ls, d_map, d_tile, d_start, d_ridx, d_rline, d_res, d_sz, d_off, d_tmp, d_names, d_seqs, d_quals, d_comments;
+    bool fasta = false;                                 // VM_READER_FASTA: reader_window_fasta parses the windows (kernels: k_fasta_reads.hip)
+    DevBuf d_state, d_ka, d_ks, d_kq, d_so, d_qo, d_fres;
     HandOut h;
     int64_t n_seen = 0;                                 // complete records of the windows so far
     int fail_rc = 0; std::string fail_msg;              // a bad header ends the input behind the records in front of it: the next window is this error
@@ -1032,8 +1034,56 @@ int fq_header_text(vm_fastq_reader* r, const uint8_t* buf, int64_t rec, std::str
     return 0;
 }
 
+// The line table of a window buf[0, avail): ls[0 .. *n_lines] (k_fq_nl_count, the scan of its counts in d_coff, k_fq_nl_pos). last: the bytes behind the
+// last newline are a line (*closing, when there are any). *n_lines == 0: the window holds no line yet and nothing more is launched. d_res is
+// reset (its error key to all ones). Waits for the counts.
+int fq_line_table(vm_fastq_reader* r, const uint8_t* buf, int64_t avail, bool last, int64_t* n_lines, int* closing) {
+    vm_ctx* c = r->c;
+    BgzfIn& in = r->in;
+    const int64_t nch = (avail + VMX_FQ_CHUNK - 1) / VMX_FQ_CHUNK;
+    VMX_TRY(r->d_cnt.reserve((size_t)(nch + 1) * 8)); VMX_TRY(r->d_coff.reserve((size_t)(nch + 1) * 8)); VMX_TRY(r->d_res.reserve(sizeof(vmx_fq_result)));
+    vmx_fq_result* res = r->d_res.as<vmx_fq_result>();
+    VMX_HIP(hipMemsetAsync(res, 0xff, sizeof(vmx_fq_result), c->stream));
+    const unsigned gch = (unsigned)((nch + 3) / 4);
+    hipLaunchKernelGGL(k_fq_nl_count, dim3(gch), dim3(256), 0, c->stream, buf, avail, nch, r->d_cnt.as<int64_t>(), res);
+    VMX_TRY(vmx_scan64(c, r->d_tmp, r->d_cnt.as<const int64_t>(), r->d_coff.as<int64_t>(), (size_t)nch + 1));
+    VMX_HIP(hipMemcpyAsync(in.pin.p, r->d_coff.as<int64_t>() + nch, 8, hipMemcpyDeviceToHost, c->stream));
+    VMX_HIP(hipMemcpyAsync(in.pin.p + 8, res, sizeof(vmx_fq_result), hipMemcpyDeviceToHost, c->stream));
+    VMX_TRY(sync(c));
+    int64_t n_nl; memcpy(&n_nl, in.pin.p, 8);
+    vmx_fq_result R; memcpy(&R, in.pin.p + 8, sizeof R);
+    *closing = last && R.tail_open ? 1 : 0;
+    *n_lines = n_nl + *closing;
+    if (*n_lines == 0) return 0;
+    VMX_TRY(r->d_ls.reserve((size_t)(*n_lines + 1) * 8));
+    hipLaunchKernelGGL(k_fq_nl_pos, dim3(gch), dim3(256), 0, c->stream, buf, avail, nch, r->d_coff.as<const int64_t>(), *n_lines, *closing, r->d_ls.as<int64_t>());
+    return 0;
+}
+
+// download of a parsed window's n records: names, bases, qualities, comments and their offsets, in the order the hand-out reads them. off: the device
+// columns name, comment, bases, qualities of `col` entries each; tn, tc, ts, tq: the blobs' bytes
+int fq_download(vm_fastq_reader* r, DecodedWin& D, int64_t n, const int64_t* off, size_t col, int64_t tn, int64_t tc, int64_t ts, int64_t tq) {
+    vm_ctx* c = r->c;
+    const double t0 = now_s();
+    VMX_TRY(D.names.reserve((size_t)tn + 8)); VMX_TRY(D.seqs.reserve((size_t)ts + 8)); VMX_TRY(D.quals.reserve((size_t)tq + 8)); VMX_TRY(D.comments.reserve((size_t)tc + 8));
+    VMX_TRY(D.off.reserve((size_t)(n + 1) * 8 * 4));
+    if (tn) VMX_HIP(hipMemcpyAsync(D.names.p, r->d_names.p, (size_t)tn, hipMemcpyDeviceToHost, c->stream));
+    if (ts) VMX_HIP(hipMemcpyAsync(D.seqs.p, r->d_seqs.p, (size_t)ts, hipMemcpyDeviceToHost, c->stream));
+    if (tq) VMX_HIP(hipMemcpyAsync(D.quals.p, r->d_quals.p, (size_t)tq, hipMemcpyDeviceToHost, c->stream));
+    if (tc) VMX_HIP(hipMemcpyAsync(D.comments.p, r->d_comments.p, (size_t)tc, hipMemcpyDeviceToHost, c->stream));
+    static const int col_of[4] = {0, 2, 3, 1};                              // host order names, bases, qualities, comments <- device columns name, comment, bases, qualities
+    for (int j = 0; j < 4; ++j) VMX_HIP(hipMemcpyAsync((int64_t*)D.off.p + j * (n + 1), off + col_of[j] * col, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    VMX_TRY(sync(c));
+    r->st[5] += now_s() - t0;
+    D.n = n; r->st[10] += (double)n;
+    return 1;
+}
+
+int reader_window_fasta(vm_fastq_reader* r, int slot);
+
 // the next window into win[slot]: 1 (its complete records parsed, possibly none), 0 at the end of the file, or a negative status
 int reader_window(vm_fastq_reader* r, int slot) {
+    if (r->fasta) return reader_window_fasta(r, slot);
     vm_ctx* c = r->c;
     BgzfIn& in = r->in;
     DecodedWin& D = r->h.win[slot];
@@ -1051,23 +1101,11 @@ int reader_window(vm_fastq_reader* r, int slot) {
     if (avail == 0) { in.tail_off = 0; in.carry = 0; return 1; }
     // newlines
     double t0 = now_s();
-    const int64_t nch = (avail + VMX_FQ_CHUNK - 1) / VMX_FQ_CHUNK;
-    VMX_TRY(r->d_cnt.reserve((size_t)(nch + 1) * 8)); VMX_TRY(r->d_coff.reserve((size_t)(nch + 1) * 8)); VMX_TRY(r->d_res.reserve(sizeof(vmx_fq_result)));
-    vmx_fq_result* res = r->d_res.as<vmx_fq_result>();
-    VMX_HIP(hipMemsetAsync(res, 0xff, sizeof(vmx_fq_result), c->stream));
-    const unsigned gch = (unsigned)((nch + 3) / 4);
-    hipLaunchKernelGGL(k_fq_nl_count, dim3(gch), dim3(256), 0, c->stream, buf, avail, nch, r->d_cnt.as<int64_t>(), res);
-    VMX_TRY(vmx_scan64(c, r->d_tmp, r->d_cnt.as<const int64_t>(), r->d_coff.as<int64_t>(), (size_t)nch + 1));
-    VMX_HIP(hipMemcpyAsync(in.pin.p, r->d_coff.as<int64_t>() + nch, 8, hipMemcpyDeviceToHost, c->stream));
-    VMX_HIP(hipMemcpyAsync(in.pin.p + 8, res, sizeof(vmx_fq_result), hipMemcpyDeviceToHost, c->stream));
-    VMX_TRY(sync(c));
-    int64_t n_nl; memcpy(&n_nl, in.pin.p, 8);
-    vmx_fq_result R; memcpy(&R, in.pin.p + 8, sizeof R);
-    const int closing = last && R.tail_open ? 1 : 0;
-    const int64_t n_lines = n_nl + closing;
+    int64_t n_lines = 0; int closing = 0;
+    VMX_TRY(fq_line_table(r, buf, avail, last, &n_lines, &closing));
     if (n_lines == 0) { in.tail_off = 0; in.carry = avail; r->st[3] += now_s() - t0; return 1; }      // (a line longer than the window so far)
-    VMX_TRY(r->d_ls.reserve((size_t)(n_lines + 1) * 8));
-    hipLaunchKernelGGL(k_fq_nl_pos, dim3(gch), dim3(256), 0, c->stream, buf, avail, nch, r->d_coff.as<const int64_t>(), n_lines, closing, r->d_ls.as<int64_t>());
+    vmx_fq_result* res = r->d_res.as<vmx_fq_result>();
+    vmx_fq_result R;
     // states and records
     const int64_t ntile = (n_lines + VMX_FQ_LTILE) / VMX_FQ_LTILE;           // (covers line index n_lines, the scan's total slot)
     VMX_TRY(r->d_map.reserve((size_t)n_lines)); VMX_TRY(r->d_tile.reserve((size_t)ntile));
@@ -1127,20 +1165,118 @@ int reader_window(vm_fastq_reader* r, int slot) {
                        r->d_comments.as<uint8_t>(), r->d_seqs.as<uint8_t>(), r->d_quals.as<uint8_t>());
     VMX_TRY(sync(c));
     r->st[4] += now_s() - t0;
-    // download: names, bases, qualities, comments and their offsets, in the order the hand-out reads them
-    t0 = now_s();
-    VMX_TRY(D.names.reserve((size_t)tn + 8)); VMX_TRY(D.seqs.reserve((size_t)ts + 8)); VMX_TRY(D.quals.reserve((size_t)tq + 8)); VMX_TRY(D.comments.reserve((size_t)tc + 8));
-    VMX_TRY(D.off.reserve((size_t)(n + 1) * 8 * 4));
-    if (tn) VMX_HIP(hipMemcpyAsync(D.names.p, r->d_names.p, (size_t)tn, hipMemcpyDeviceToHost, c->stream));
-    if (ts) VMX_HIP(hipMemcpyAsync(D.seqs.p, r->d_seqs.p, (size_t)ts, hipMemcpyDeviceToHost, c->stream));
-    if (tq) VMX_HIP(hipMemcpyAsync(D.quals.p, r->d_quals.p, (size_t)tq, hipMemcpyDeviceToHost, c->stream));
-    if (tc) VMX_HIP(hipMemcpyAsync(D.comments.p, r->d_comments.p, (size_t)tc, hipMemcpyDeviceToHost, c->stream));
-    static const int col_of[4] = {0, 2, 3, 1};                              // host order names, bases, qualities, comments <- device columns name, comment, bases, qualities
-    for (int j = 0; j < 4; ++j) VMX_HIP(hipMemcpyAsync((int64_t*)D.off.p + j * (n + 1), off + col_of[j] * col, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    return fq_download(r, D, n, off, col, tn, tc, ts, tq);
+}
+
+// ------------------------------------------------------------------------------------------------ FASTA and FASTQ windows (VM_READER_FASTA; kernels: k_fasta_reads.hip)
+
+// reader_window under VM_READER_FASTA: the same file half, line table, statistics and download; the record rule is vm_fastx_read's whole one.
+// A window is cut in front of its last record start unless it ends between records, or is the file's last and ends inside a FASTA record.
+int reader_window_fasta(vm_fastq_reader* r, int slot) {
+    vm_ctx* c = r->c;
+    BgzfIn& in = r->in;
+    DecodedWin& D = r->h.win[slot];
+    D.n = 0;
+    if (r->fail_rc < 0) { set_error(r->fail_msg); return r->fail_rc; }
+    int64_t avail = 0;
+    const int irc = r->gz ? gzip_in_window(&in, r->gz, r->st, &avail) : bgzf_in_window(&in, r->st, &avail);
+    if (irc < 0) return irc;
+    if (irc == 0) {
+        if (in.carry == 0) return 0;
+        // the file ended at a window's edge: the carried tail (a FASTA record waiting for its successor, or a FASTQ record that lacks lines) is the closing window
+        DevBuf& dst = in.d_inf[in.which ^ 1];
+        VMX_TRY(dst.reserve((size_t)in.carry + 64));
+        VMX_HIP(hipMemcpyAsync(dst.p, in.d_inf[in.which].as<uint8_t>() + in.tail_off, (size_t)in.carry, hipMemcpyDeviceToDevice, c->stream));
+        in.which ^= 1;
+        avail = in.carry;
+    }
+    const bool last = in.file_done;                                         // the bytes behind the last newline are a line only here
+    const uint8_t* buf = in.d_inf[in.which].as<const uint8_t>();
+    if (avail == 0) { in.tail_off = 0; in.carry = 0; return 1; }
+    // newlines
+    double t0 = now_s();
+    int64_t n_lines = 0; int closing = 0;
+    VMX_TRY(fq_line_table(r, buf, avail, last, &n_lines, &closing));
+    if (n_lines == 0) { in.tail_off = 0; in.carry = avail; r->st[3] += now_s() - t0; return 1; }      // (a line longer than the window so far)
+    VMX_TRY(r->d_fres.reserve(sizeof(vmx_fr_result)));
+    vmx_fr_result* fres = r->d_fres.as<vmx_fr_result>();
+    VMX_HIP(hipMemsetAsync(fres, 0xff, sizeof(vmx_fr_result), c->stream));
+    // states, records, the cut
+    const int64_t ntile = (n_lines + VMX_FQ_LTILE) / VMX_FQ_LTILE;           // (covers line index n_lines, the scans' total slot)
+    const size_t lcol = (size_t)(n_lines + 1);
+    VMX_TRY(r->d_map.reserve(lcol * 2)); VMX_TRY(r->d_tile.reserve((size_t)ntile * 2)); VMX_TRY(r->d_state.reserve(lcol));
+    VMX_TRY(r->d_start.reserve(lcol * 8)); VMX_TRY(r->d_ridx.reserve(lcol * 8)); VMX_TRY(r->d_rline.reserve(lcol * 8));
+    const int64_t* ls = r->d_ls.as<const int64_t>();
+    hipLaunchKernelGGL(k_fr_line_maps, dim3((unsigned)ntile), dim3(VMX_FQ_LTILE), 0, c->stream, buf, ls, n_lines, r->d_map.as<uint16_t>(), r->d_tile.as<uint16_t>());
+    hipLaunchKernelGGL(k_fr_tile_scan, dim3(1), dim3(1024), 0, c->stream, r->d_tile.as<uint16_t>(), ntile);
+    hipLaunchKernelGGL(k_fr_line_states, dim3((unsigned)ntile), dim3(VMX_FQ_LTILE), 0, c->stream, r->d_map.as<const uint16_t>(), r->d_tile.as<const uint16_t>(), n_lines,
+                       r->d_state.as<uint8_t>(), r->d_start.as<int64_t>());
+    VMX_TRY(vmx_scan64(c, r->d_tmp, r->d_start.as<const int64_t>(), r->d_ridx.as<int64_t>(), lcol));
+    hipLaunchKernelGGL(k_fq_records, dim3(grid256(n_lines)), dim3(256), 0, c->stream, r->d_start.as<const int64_t>(), r->d_ridx.as<const int64_t>(), n_lines, r->d_rline.as<int64_t>());
+    hipLaunchKernelGGL(k_fr_result, dim3(1), dim3(64), 0, c->stream, buf, ls, r->d_state.as<const uint8_t>(), r->d_ridx.as<const int64_t>(), r->d_rline.as<const int64_t>(), n_lines,
+                       avail, last ? 1 : 0, fres);
+    VMX_HIP(hipMemcpyAsync(in.pin.p, fres, sizeof(vmx_fr_result), hipMemcpyDeviceToHost, c->stream));
     VMX_TRY(sync(c));
-    r->st[5] += now_s() - t0;
-    D.n = n; r->st[10] += (double)n;
-    return 1;
+    vmx_fr_result R; memcpy(&R, in.pin.p, sizeof R);
+    r->st[3] += now_s() - t0;
+    if (R.n_rec < 0 || R.end < 0 || R.end > avail || R.cut_line < 0 || R.cut_line > n_lines) { set_error("vm_fastq_reader: the record pass left an offset outside the window"); return VM_ERR_HIP; }
+    in.tail_off = R.end; in.carry = avail - R.end;
+    const bool truncated = last && R.end_state >= 1 && R.end_state <= 3;      // the file ends inside a FASTQ record: the error of the call behind this window's records
+    if (last) in.carry = 0;
+    int64_t n = R.n_rec;
+    const int64_t rec0 = r->n_seen;
+    // keep ranges and their scans, header sizes, the first bad header (k_fr_result has looked at the header of the record the cut stands in front of)
+    t0 = now_s();
+    const size_t col = (size_t)(n + 1);
+    VMX_TRY(r->d_ka.reserve(lcol * 8)); VMX_TRY(r->d_ks.reserve(lcol * 8)); VMX_TRY(r->d_kq.reserve(lcol * 8)); VMX_TRY(r->d_so.reserve(lcol * 8)); VMX_TRY(r->d_qo.reserve(lcol * 8));
+    VMX_TRY(r->d_sz.reserve(col * 8 * 2)); VMX_TRY(r->d_off.reserve(col * 8 * 4));
+    int64_t* sz = r->d_sz.as<int64_t>(); int64_t* off = r->d_off.as<int64_t>();
+    const int64_t* rline = r->d_rline.as<const int64_t>();
+    uint64_t key = R.err_key;
+    if (n > 0) {
+        hipLaunchKernelGGL(k_fr_line_keep, dim3(grid256(n_lines + 1)), dim3(256), 0, c->stream, buf, ls, r->d_map.as<const uint16_t>(), r->d_state.as<const uint8_t>(), n_lines, R.cut_line,
+                           r->d_ka.as<int64_t>(), r->d_ks.as<int64_t>(), r->d_kq.as<int64_t>());
+        VMX_TRY(vmx_scan64(c, r->d_tmp, r->d_ks.as<const int64_t>(), r->d_so.as<int64_t>(), lcol));
+        VMX_TRY(vmx_scan64(c, r->d_tmp, r->d_kq.as<const int64_t>(), r->d_qo.as<int64_t>(), lcol));
+        hipLaunchKernelGGL(k_fr_hdr_sizes, dim3((unsigned)((n + 1 + 3) / 4)), dim3(256), 0, c->stream, buf, ls, rline, n, R.cut_line, r->d_so.as<const int64_t>(), r->d_qo.as<const int64_t>(),
+                           sz, sz + col, off + 2 * col, off + 3 * col, (unsigned long long*)&fres->err_key);
+        for (int j = 0; j < 2; ++j) VMX_TRY(vmx_scan64(c, r->d_tmp, sz + j * col, off + j * col, col));
+        VMX_HIP(hipMemcpyAsync(in.pin.p, &fres->err_key, 8, hipMemcpyDeviceToHost, c->stream));
+        VMX_TRY(sync(c));
+        memcpy(&key, in.pin.p, 8);
+    }
+    if (key != ~0ull) {                                                     // the records in front of the bad header are good; the input ends there
+        const int64_t bad = (int64_t)(key >> 8);
+        std::string text;
+        VMX_TRY(fq_header_text(r, buf, bad, &text));
+        r->fail_rc = VM_ERR_IO;
+        r->fail_msg = "not FASTA/FASTQ: " + text;
+        n = bad;
+        if (n == 0) { set_error(r->fail_msg); return r->fail_rc; }
+    }
+    else if (truncated) {
+        r->fail_rc = VM_ERR_IO;
+        r->fail_msg = "truncated FASTQ record: the file ends inside record " + std::to_string((long long)(rec0 + n) + 1);
+        if (n == 0) { set_error(r->fail_msg); return r->fail_rc; }
+    }
+    if (n == 0) return 1;
+    r->n_seen += n;
+    int64_t* tot = (int64_t*)in.pin.p;
+    for (int j = 0; j < 4; ++j) VMX_HIP(hipMemcpyAsync(tot + j, off + j * col + n, 8, hipMemcpyDeviceToHost, c->stream));
+    VMX_HIP(hipMemcpyAsync(tot + 4, r->d_so.as<int64_t>() + n_lines, 8, hipMemcpyDeviceToHost, c->stream));        // what k_fr_copy writes: every kept byte in front of the cut
+    VMX_HIP(hipMemcpyAsync(tot + 5, r->d_qo.as<int64_t>() + n_lines, 8, hipMemcpyDeviceToHost, c->stream));
+    VMX_TRY(sync(c));
+    const int64_t tn = tot[0], tc = tot[1], ts = tot[2], tq = tot[3], ws = tot[4], wq = tot[5];
+    if (ts > ws || tq > wq || ws > avail || wq > avail) { set_error("vm_fastq_reader: the keep ranges do not add up"); return VM_ERR_HIP; }
+    VMX_TRY(r->d_names.reserve((size_t)tn + 16)); VMX_TRY(r->d_comments.reserve((size_t)tc + 16)); VMX_TRY(r->d_seqs.reserve((size_t)ws + 16)); VMX_TRY(r->d_quals.reserve((size_t)wq + 16));
+    const int64_t cch = (R.end + VMX_FQ_CHUNK - 1) / VMX_FQ_CHUNK;             // (nothing is kept at or behind the cut)
+    if (cch > 0)
+        hipLaunchKernelGGL(k_fr_copy, dim3((unsigned)((cch + 3) / 4)), dim3(256), 0, c->stream, buf, avail, cch, r->d_coff.as<const int64_t>(), r->d_ka.as<const int64_t>(),
+                           r->d_ks.as<const int64_t>(), r->d_kq.as<const int64_t>(), r->d_so.as<const int64_t>(), r->d_qo.as<const int64_t>(), r->d_seqs.as<uint8_t>(), r->d_quals.as<uint8_t>());
+    hipLaunchKernelGGL(k_fr_hdr_copy, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, buf, ls, rline, n, off, off + col, r->d_names.as<uint8_t>(), r->d_comments.as<uint8_t>());
+    VMX_TRY(sync(c));
+    r->st[4] += now_s() - t0;
+    return fq_download(r, D, n, off, col, tn, tc, ts, tq);
 }
 
 // ------------------------------------------------------------------------------------------------ hand-out, shared by both readers
@@ -1665,8 +1801,10 @@ int vm_fastq_reader_open_opts(vm_ctx* c, const char* path, int flags, vm_fastq_r
     if (out) *out = nullptr;
     if (!c) return VM_ERR_NO_CTX;
     if (!out || !path) return VM_ERR_ARG;
+    if (flags & ~(VM_READER_GZIP_DEVICE | VM_READER_FASTA)) { set_error("vm_fastq_reader_open_opts: unknown flag bits " + std::to_string(flags & ~(VM_READER_GZIP_DEVICE | VM_READER_FASTA))); return VM_ERR_ARG; }
     vm_fastq_reader* r = new vm_fastq_reader();
     r->c = c;
+    r->fasta = (flags & VM_READER_FASTA) != 0;
     int rc = bgzf_in_open(&r->in, c, path);
     if (rc == 0 && r->in.fsize == 0) { set_error(std::string("empty file: ") + path); rc = VM_ERR_IO; }
     if (rc == 0) {

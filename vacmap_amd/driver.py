@@ -276,18 +276,22 @@ def _gzip_is_bgzf(path):
     return False
 
 
-def _native_fastq_chunks(path, n_max, lib, device, gzip_inflate='host'):
+def _native_fastq_chunks(path, n_max, lib, device, gzip_inflate='host', fasta_reads='host'):
     """--fastx-reader native: the chunks of lib.Fastx from lib.FastqReader (BGZF inflate and the FASTQ parse on the GPU) on a context of its own.
     What the device reader does not take (plain gzip: no member boundaries to inflate side by side; FASTA) goes to the host reader, with one
     line on stderr; the context is released before the host reader starts. gzip_inflate='device' (--gzip-inflate device): a plain-gzip file is
     inflated on the GPU in parallel chunks (FastqReader(gzip='device')) instead of falling back; what that reader refuses at open (FASTA, a
-    block larger than the reader's chunk) still falls back, the line naming the reason."""
+    block larger than the reader's chunk) still falls back, the line naming the reason. fasta_reads='device' (--fasta-reads device): the reader
+    is opened with fasta=True and parses FASTA records (and files that mix both kinds) on the GPU instead of falling back on them."""
     from .lib import FastqReader, Fastx, Context, VmxError
     ctx = Context(device, lib=lib)
     rd = None
     try:
         try:
-            rd = FastqReader(ctx, path, gzip='device') if gzip_inflate == 'device' else FastqReader(ctx, path)
+            if fasta_reads == 'device':
+                rd = FastqReader(ctx, path, gzip=gzip_inflate, fasta=True)
+            else:
+                rd = FastqReader(ctx, path, gzip='device') if gzip_inflate == 'device' else FastqReader(ctx, path)
         except VmxError as e:
             if e.code != -7:                               # VM_ERR_UNSUPPORTED
                 raise
@@ -301,6 +305,8 @@ def _native_fastq_chunks(path, n_max, lib, device, gzip_inflate='host'):
     finally:
         ctx.close()
     why = 'is FASTA' if _gzip_is_bgzf(path) else 'is gzip but not BGZF'       # (the two things vm_fastq_reader_open refuses in a gzip file)
+    if fasta_reads == 'device' and why == 'is FASTA':
+        why = 'was refused by the device reader (%s)' % refused
     if gzip_inflate == 'device' and why != 'is FASTA':
         why = 'was refused by the device inflate (%s)' % refused
     sys.stderr.write('[vacmap_amd] --fastx-reader native: %s %s, reading it with the host reader\n' % (path, why))
@@ -335,7 +341,7 @@ def _parse_slice(path, lib, a, b, n_max):
         rd.close()
 
 
-def _input_chunks(path, n_max, lib, device=0, bam_reader='python', parse_threads=0, share=(0, 1), slice_bytes=1 << 30, bam_tags=None, fastx_reader='host', gzip_inflate='host'):
+def _input_chunks(path, n_max, lib, device=0, bam_reader='python', parse_threads=0, share=(0, 1), slice_bytes=1 << 30, bam_tags=None, fastx_reader='host', gzip_inflate='host', fasta_reads='host'):
     """blob chunks (names, upper-cased sequences, qualities, comments; at most n_max records each) of one input in file order: a .bam through
     the native or the Python reader, a compressed FASTA / FASTQ file through one library reader. parse_threads > 0: a plain file is cut into
     record-aligned slices of about slice_bytes (vm_fastx_open_range) which that many threads parse ahead of the consumer, and share = (i, n)
@@ -346,7 +352,7 @@ def _input_chunks(path, n_max, lib, device=0, bam_reader='python', parse_threads
         yield from (_native_bam_chunks(path, n_max, lib, device, bam_tags) if bam_reader == 'native' else _bam_chunks(path, n_max, bam_tags))
         return
     if fastx_reader == 'native' and _is_gzip(path):
-        yield from _native_fastq_chunks(path, n_max, lib, device, gzip_inflate)
+        yield from _native_fastq_chunks(path, n_max, lib, device, gzip_inflate, fasta_reads)
         return
     if not parse_threads or not _is_plain_fastx(path):
         rd = Fastx(path, lib=lib)
@@ -564,6 +570,9 @@ def build_parser():
                    help='device: where --fastx-reader native or --ref-reader native meets a plain-gzip file (gzip, pigz, concatenated .gz: no BGZF members), '
                         'inflate it on the GPU in parallel chunks (lib.FastqReader / Index.from_fasta with gzip=\'device\') instead of falling back to the host '
                         'reader (reads) or inflating with zlib on a host thread (reference); what the device inflate refuses at open falls back with one stderr line')
+    p.add_argument('--fasta-reads', choices=['host', 'device'], default='host',
+                   help='device: where --fastx-reader native meets FASTA reads or contigs (x.fa.gz, bgzipped, or plain gzip with --gzip-inflate device), parse '
+                        'the multi-line records on the GPU (lib.FastqReader with fasta=True) instead of falling back to the host reader')
     p.add_argument('--fastx-reader', choices=['host', 'native'], default='host',
                    help='how a compressed -read x.fastq.gz is read: zlib and the parser on one host thread (default) or BGZF inflate and the FASTQ parse on '
                         'the GPU (lib.FastqReader, on a context of its own); plain gzip and FASTA fall back to the host reader, plain files keep the threaded parser')
@@ -943,7 +952,7 @@ def _run_asm(args, net, lib, ctx, index, prm, opts, out, device, t_start):
     group, gbases = [], 0
     for path in (p for grp in args.read for p in grp):
         # (.bam input like every other mode: vacmap:452-470)
-        with contextlib.closing(_input_chunks(path, 64, lib, device, args.bam_reader, bam_tags=args.bam_tags, fastx_reader=args.fastx_reader, gzip_inflate=args.gzip_inflate)) as chunks:
+        with contextlib.closing(_input_chunks(path, 64, lib, device, args.bam_reader, bam_tags=args.bam_tags, fastx_reader=args.fastx_reader, gzip_inflate=args.gzip_inflate, fasta_reads=args.fasta_reads)) as chunks:
             for ch in _first_of_each_name(chunks, seen, lib):
                 if not _carries_comments(args, path):
                     import numpy as np
@@ -1087,7 +1096,7 @@ class ReadStream:
         share = (self.rank, self.world) if self.range_mode else (0, 1)
         slice_bytes = max(1 << 20, int(sw['VMX_SLICE_MB'] * (1 << 20)))
         for file_no, path in enumerate(p for grp in args.read for p in grp):
-            with contextlib.closing(_input_chunks(path, win_reads, self.lib, self.device, args.bam_reader, parse_threads, share, slice_bytes, args.bam_tags, args.fastx_reader, args.gzip_inflate)) as chunks:
+            with contextlib.closing(_input_chunks(path, win_reads, self.lib, self.device, args.bam_reader, parse_threads, share, slice_bytes, args.bam_tags, args.fastx_reader, args.gzip_inflate, args.fasta_reads)) as chunks:
                 for ch in _first_of_each_name(chunks, seen, self.lib):
                     n = len(ch['seqs_off']) - 1
                     if self.range_mode and n:

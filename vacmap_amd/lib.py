@@ -785,20 +785,24 @@ class BamReader(_BlobReader):
 
 class FastqReader(_BlobReader):
     """Reader of bgzipped FASTQ into blobs (vm_fastq_reader_*): BGZF inflate and the four-line parse on the device, by Fastx's own rule
-    (include/vacmapx.h); read() as Fastx.read(). VmxError -7 at open: plain gzip, not gzip, or FASTA (Fastx reads those)"""
+    (include/vacmapx.h); read() as Fastx.read(). VmxError -7 at open: not gzip; plain gzip unless gzip='device'; FASTA unless fasta=True
+    (Fastx reads those)"""
     STATS = ('io_busy_s', 'io_wait_s', 'inflate_s', 'parse_s', 'copy_s', 'download_s', 'handout_s', 'windows', 'file_bytes', 'inflated_bytes', 'records')
     _READ, _STATS_FN, _CLOSE = 'vm_fastq_reader_read', 'vm_fastq_reader_stats', 'vm_fastq_reader_close'
 
-    def __init__(self, ctx, path, gzip='host'):
+    def __init__(self, ctx, path, gzip='host', fasta=False):
         """gzip='device': a plain-gzip file is inflated on the device in parallel chunks (vm_fastq_reader_open_opts, VM_READER_GZIP_DEVICE)
-        instead of being refused; stats() then has GZIP_STATS too"""
+        instead of being refused; stats() then has GZIP_STATS too. fasta=True (VM_READER_FASTA): the device parses by Fastx's whole rule,
+        multi-line FASTA records and files that mix both kinds included, instead of refusing a record that begins with '>'"""
         if gzip not in ('host', 'device'):
             raise ValueError("gzip must be 'host' or 'device'")
         self.ctx, self.lib = ctx, ctx.lib
         h = C.c_void_p()
+        flags = (1 if gzip == 'device' else 0) | (2 if fasta else 0)
         if gzip == 'device':
             self.STATS = FastqReader.STATS + GZIP_STATS
-            self.lib.check(self.lib.L.vm_fastq_reader_open_opts(ctx.h, _b(path), 1, C.byref(h)))
+        if flags:
+            self.lib.check(self.lib.L.vm_fastq_reader_open_opts(ctx.h, _b(path), flags, C.byref(h)))
         else:
             self.lib.check(self.lib.L.vm_fastq_reader_open(ctx.h, _b(path), C.byref(h)))
         self.h = h
