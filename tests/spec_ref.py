@@ -393,3 +393,222 @@ def map_read_brute(index_hashes, index_positions, k, w, read, check_num, mid_occ
         if 1 <= len(pvs) <= mid_occ:
             hits += [(q, pv >> 1, 1 if (pv & 1) == z else -1, k) for pv in pvs]
     return cluster_hits_brute(hits, check_num)
+
+
+# ------------------------------------------------------------------------------------------------ L1 / L2: local re-seeding
+LOCAL_SPANS = {'H': (7000, 7000), 'L': (7000, 7000), 'S': (7000, 7000), 'R': (2000, 500), 'asm': (2000, 500)}   # (look span, read span)
+LOCAL_BUDGET = {'H': 5, 'L': 3, 'S': None}                                   # guide chains re-seeded per read
+
+_RC = str.maketrans('ACGTN', 'TGCAN')
+
+
+def revcomp(s):
+    return s.translate(_RC)[::-1]
+
+
+def _rows(a):
+    return [tuple(int(v) for v in row) for row in np.asarray(a, dtype=np.int64).reshape(-1, 4)]
+
+
+def pos2contig(pos, contig2start):
+    """the last contig that starts at or before pos"""
+    c = 0
+    for i, st in enumerate(contig2start):
+        if pos < st:
+            break
+        c = i
+    return c
+
+
+def find_closest(arr, target):
+    """findClosest_1: (|arr[i0] - target|, |arr[i1] - target|, i0, i1) of the two neighbours of target in the ascending arr; both the same
+    one when target lies on an element, before the first or after the last"""
+    n = len(arr)
+    if target <= arr[0]:
+        return arr[0] - target, arr[0] - target, 0, 0
+    if target >= arr[n - 1]:
+        return target - arr[n - 1], target - arr[n - 1], n - 1, n - 1
+    i, j = 0, n
+    while i < j:
+        mid = (i + j) // 2
+        if arr[mid] == target:
+            return 0, 0, mid, mid
+        if target < arr[mid]:
+            j = mid
+        else:
+            i = mid + 1
+    return abs(arr[j - 1] - target), abs(arr[j] - target), j - 1, j
+
+
+def local_guides(paths, mode):
+    """L1: the guide chains that are re-seeded, in order, from the read's paths (primary first, each (m, 4) rows (q, r, s, l) in descending read
+    order). Modes R and asm: the paths as they are. Otherwise merge_chain over paths[1:] (sorted by start; chain j joins chain i when i's end
+    anchor ie and j's start anchor js have one strand, ie.q + ie.l <= js.q and |readgap - refgap| < 500), a stable sort by length, drop_somechains
+    (a chain goes when its strand majority does not agree with the primary's over its span and it comes within 500 of the primary, or when it
+    spans fewer than 100 read bases), a stable sort by length descending, and the budget. Returns (guides, n_total): n_total counts the list
+    before the budget."""
+    paths = [_rows(p) for p in paths]
+    if mode in ('R', 'asm'):
+        return paths, len(paths)
+    chains = sorted(paths[1:], key=lambda c: c[-1][0])
+    iloc = 0
+    while iloc < len(chains) - 1:
+        jloc = iloc + 1
+        while jloc < len(chains):
+            ie, js = chains[iloc][0], chains[jloc][-1]
+            if ie[0] + ie[3] <= js[0] and ie[2] == js[2]:
+                readgap = js[0] - ie[0] - ie[3]
+                refgap = js[1] - ie[1] - ie[3] if ie[2] == 1 else ie[1] - js[1] - js[3]
+                if abs(readgap - refgap) < 500:
+                    chains[iloc] = chains[jloc] + chains[iloc]
+                    chains.pop(jloc)
+                    continue
+            jloc += 1
+        iloc += 1
+    chains.sort(key=len)
+    lst = [paths[0]] + chains
+    kept = [lst[0]]
+    for chain in lst[1:]:
+        sc = [0, 0]; cc = [0, 0]
+        distance = None
+        cur = 0
+        for item in lst[0]:
+            if chain[-1][0] <= item[0] <= chain[0][0]:
+                sc[0 if item[2] == 1 else 1] += 1
+            while chain[cur][0] > item[0]:
+                if cur < len(chain) - 1:
+                    cur += 1
+                else:
+                    break
+            d = abs(item[1] - chain[cur][1])
+            if distance is None or d < distance:
+                distance = d
+        for item in chain:
+            cc[0 if item[2] == 1 else 1] += 1
+        keep = (sc[0] > sc[1] and cc[0] > cc[1]) or (sc[0] < sc[1] and cc[0] < cc[1])
+        if (not keep and distance < 500) or (chain[0][0] - chain[-1][0]) < 100:
+            continue
+        kept.append(chain)
+    kept.sort(key=lambda c: -len(c))
+    budget = LOCAL_BUDGET[mode]
+    return (kept if budget is None else kept[:budget]), len(kept)
+
+
+def local_seed(contigs, read, guide, k, mode, d1=True):
+    """L2: the run-merged local anchors of one guide chain, rows (q, r, s, l) in the order they are appended, and a trace
+    {'windows': [(lo, hi)] as widened and clipped, 'hits': [(q, strand, refloc, (diff clause, ref1 clause, ref2 clause))] of the accepted hits in
+    lookup order, 'per_q': {q: accepted hits}}. The tables _s (k-mers seen once) and _m (more than once) are keyed by the k-mer's text; d1: a
+    k-mer with a non-ACGT base enters no table (otherwise only the all-N k-mer is left out, and text equality decides)."""
+    look_span, read_span = LOCAL_SPANS[mode]
+    contigs = [c.upper() for c in contigs]; read = read.upper()
+    contig2start = [0]
+    for c in contigs[:-1]:
+        contig2start.append(contig2start[-1] + len(c))
+    g = _rows(guide)
+    readgap = 0
+    for pre, now in zip(g, g[1:]):
+        readgap = max(readgap, abs(now[0] - pre[0]))
+    readgap = max(readgap + 1000, 5000)
+    g.sort(key=lambda a: a[1])
+
+    def cut(split_contig):
+        se = [(g[0][1], g[0][1])]
+        cur = pos2contig(g[0][1], contig2start)
+        for item in g[1:]:
+            if item[1] - se[-1][1] < readgap and (not split_contig or cur == pos2contig(item[1], contig2start)):
+                se[-1] = (se[-1][0], item[1])
+            else:
+                if se[-1][0] == se[-1][1]:
+                    se.pop()
+                se.append((item[1], item[1]))
+                cur = pos2contig(item[1], contig2start)
+        if se[-1][0] == se[-1][1]:
+            se.pop()
+        return se
+
+    def tables(se):
+        _s, _m, multi, windows = {}, {}, [], []
+        for min_ref, max_ref in se:
+            c = pos2contig(min_ref, contig2start)
+            if c != pos2contig(max_ref, contig2start):
+                return None
+            min_ref -= min(look_span, min_ref - contig2start[c])
+            max_ref += look_span
+            seq = contigs[c][min_ref - contig2start[c]:max_ref - contig2start[c]]
+            windows.append((min_ref, min_ref + len(seq)))
+            for iloc in range(0, len(seq) - k + 1):
+                kmer = seq[iloc:iloc + k]
+                if kmer == 'N' * k or (d1 and kmer.strip('ACGT')):
+                    continue
+                if kmer not in _s:
+                    _s[kmer] = min_ref + iloc
+                elif kmer in _m:
+                    _m[kmer].append(min_ref + iloc)
+                else:
+                    _m[kmer] = [_s[kmer], min_ref + iloc]
+                    multi.append(kmer)
+        for kmer in multi:
+            _s.pop(kmer)
+        return _s, _m, windows
+
+    t = tables(cut(False))
+    if t is None:
+        t = tables(cut(True))
+        assert t is not None
+    _s, _m, windows = t
+    g.sort(key=lambda a: a[0])
+    assert len({a[0] for a in g}) == len(g), 'guide read positions must be distinct'
+    readstart = max(0, g[0][0] - read_span)
+    readend = min(len(read) - k + 1, g[-1][0] + read_span)
+    readposarr = [a[0] for a in g]
+    rc = revcomp(read)
+    out, pointdict, pointdict_key = [], {}, []
+    trace = {'windows': windows, 'hits': [], 'per_q': {}}
+
+    def on_hit(iloc, refloc, strand):
+        point = refloc - iloc if strand == 1 else -(refloc + iloc)
+        if point in pointdict:
+            c0, c1, c2, c3 = pointdict[point]
+            if c0 + c3 >= iloc:
+                bonus = iloc - (c0 + c3) + k
+                if bonus > 0:
+                    keep_r = c1 if strand == 1 else refloc
+                    if c3 + bonus < 20:
+                        pointdict[point] = (c0, keep_r, strand, c3 + bonus)
+                    else:
+                        out.append((c0, c1, c2, c3))
+                        pointdict[point] = (c0 + c3, c1 + c3 if strand == 1 else refloc, strand, bonus)
+            else:
+                out.append((c0, c1, c2, c3))
+                pointdict[point] = (iloc, refloc, strand, k)
+        else:
+            pointdict[point] = (iloc, refloc, strand, k)
+            pointdict_key.append(point)
+
+    for iloc in range(readstart, readend):
+        fwd, rev = read[iloc:iloc + k], rc[-(iloc + k):-iloc]
+        if fwd == rev:
+            continue
+        b0, b1, i0, i1 = find_closest(readposarr, iloc)
+        interval = min(b0 + b1 + 500, 2000)
+        ref1, ref2 = g[i0][1], g[i1][1]
+        rgap = abs(iloc - g[i0][0])
+        for kmer, strand in ((fwd, 1), (rev, -1)):
+            for refloc in ([_s[kmer]] if kmer in _s else _m.get(kmer, ())):
+                why = (abs(rgap - abs(refloc - ref1)) < 500, ref1 - interval <= refloc <= ref1 + interval, ref2 - interval <= refloc <= ref2 + interval)
+                if any(why):
+                    trace['hits'].append((iloc, strand, refloc, why))
+                    trace['per_q'][iloc] = trace['per_q'].get(iloc, 0) + 1
+                    on_hit(iloc, refloc, strand)
+    for key in pointdict_key:
+        out.append(pointdict[key])
+    return out, trace
+
+
+def local_raw(contigs, read, paths, k, mode):
+    """the read's raw local anchors: every guide of local_guides re-seeded, the rows concatenated and sorted (stable) by q + l, in mode R by q"""
+    rows = []
+    for g in local_guides(paths, mode)[0]:
+        rows += local_seed(contigs, read, g, k, mode)[0]
+    rows.sort(key=(lambda a: a[0]) if mode == 'R' else (lambda a: a[0] + a[3]))
+    return np.array(rows, dtype=np.int64).reshape(-1, 4)

@@ -295,3 +295,75 @@ def test_oracle_sketch_and_index_are_spec(oracle):
         oi = oracle.Index.from_seqs(['c%d' % i for i in range(len(contigs))], contigs, k=k, w=w)
         got, exp = oi.minimizers(), R.index_minimizers(contigs, k, w)
         assert all(np.array_equal(a, b) for a, b in zip(got, exp)), (k, w)
+
+
+# ------------------------------------------------------------------------------------------------ L1 / L2: local re-seeding
+def _planted(total, at, s):
+    return 'N' * at + s + 'N' * (total - at - len(s))
+
+
+def test_local_find_closest():
+    a = [10, 20, 30]
+    assert R.find_closest(a, 5) == (5, 5, 0, 0) and R.find_closest(a, 10) == (0, 0, 0, 0) and R.find_closest(a, 35) == (5, 5, 2, 2)
+    assert R.find_closest(a, 20) == (0, 0, 1, 1) and R.find_closest(a, 24) == (4, 6, 1, 2) and R.find_closest(a, 11) == (1, 9, 0, 1)
+    assert R.find_closest([7], 7) == (0, 0, 0, 0) and R.find_closest([7], 9) == (2, 2, 0, 0)
+
+
+def test_local_seed_by_hand():
+    P = 'ACGTTGCAAGTCC'                                        # 13 bases: five 9-mers
+    ref, read = _planted(20000, 10000, P), _planted(300, 100, P)
+    guide = [(200, 10100, 1, 15), (50, 9950, 1, 15)]
+    rows, tr = R.local_seed([ref], read, guide, 9, 'H')
+    assert tr['windows'] == [(2950, 17100)]                   # 9950 - 7000 .. 10100 + 7000
+    assert [h[:3] for h in tr['hits']] == [(100 + o, 1, 10000 + o) for o in range(5)] and tr['per_q'] == {100 + o: 1 for o in range(5)}
+    assert tr['hits'][0][3] == (True, True, True)             # q = 100: b0 = 50, b1 = 100, interval 650; refloc - ref1 = 50 = the read gap, refloc - ref2 = -100
+    assert rows == [(100, 10000, 1, 13)]                      # one run: l = 9, 10, ... 13
+    # text equality (the reference): the k-mers of Ns and the probe's ends match too, 92 .. 112; l + bonus reaches 20 at q = 103
+    assert R.local_seed([ref], read, guide, 9, 'H', d1=False)[0] == [(92, 9992, 1, 19), (111, 10011, 1, 10)]
+    # mode R: reference span 2000, read span 500
+    assert R.local_seed([ref], read, guide, 9, 'R')[1]['windows'] == [(7950, 12100)]
+    assert R.local_seed([ref], _planted(2000, 1200, P), [(600, 10600, 1, 15), (500, 10500, 1, 15)], 9, 'R')[0] == []      # read window ends at 600 + 500
+    assert R.local_seed([ref], _planted(2000, 1095, P), [(600, 9505, 1, 15), (500, 9405, 1, 15)], 9, 'R')[0] == [(1095, 10000, 1, 13)]
+    # the reverse strand: r follows the newest hit; no reverse look-up at read position 0
+    rows, tr = R.local_seed([ref], _planted(300, 0, R.revcomp(P)), [(150, 10150, 1, 15), (20, 10020, 1, 15)], 9, 'H')
+    assert [h[:3] for h in tr['hits']] == [(1, -1, 10003), (2, -1, 10002), (3, -1, 10001), (4, -1, 10000)] and rows == [(1, 10000, -1, 12)]
+    # a single-anchor guide, and two anchors readgap apart, have no window: nothing
+    assert R.local_seed([ref], read, [(100, 10000, 1, 15)], 9, 'H')[0] == []
+    assert R.local_seed([ref], read, [(200, 15000, 1, 15), (100, 10000, 1, 15)], 9, 'H')[0] == []
+    assert R.local_seed([ref], read, [(200, 14999, 1, 15), (100, 10000, 1, 15)], 9, 'H')[0] == [(100, 10000, 1, 13)]
+    # two copies in the reference: both diagonals, the leftovers in first-appearance order (ascending reference position here)
+    ref2 = ref[:10300] + P + ref[10313:]
+    assert R.local_seed([ref2], read, guide, 9, 'H')[0] == [(100, 10000, 1, 13), (100, 10300, 1, 13)]
+    # a guide across two contigs is cut at the contig change (the retry): with one anchor on either side nothing is left, with two there are two
+    # windows, each inside its contig, and the copy at the start of the second contig is found
+    two = [ref[:10020], P + ref[10033:]]
+    assert R.local_seed(two, read, guide, 9, 'H')[0] == []
+    rows, tr = R.local_seed(two, read, [(200, 10100, 1, 15), (150, 10050, 1, 15), (90, 9990, 1, 15), (50, 9950, 1, 15)], 9, 'H')
+    assert rows == [(100, 10000, 1, 13), (100, 10020, 1, 13)] and tr['windows'] == [(2950, 10020), (10020, 17100)]
+
+
+def test_local_guides_and_raw_by_hand():
+    P0 = [(q, 1000 + q, 1, 15) for q in range(900, 0, -100)]
+    short = [(360, 50360, 1, 15), (330, 50330, 1, 15), (300, 50300, 1, 15)]          # spans 60 read positions: dropped
+    longer = [(450, 50450, 1, 15), (375, 50375, 1, 15), (300, 50300, 1, 15)]
+    assert R.local_guides([P0, short], 'H') == ([P0], 1) and R.local_guides([P0, short], 'R') == ([P0, short], 2)
+    assert R.local_guides([P0, longer], 'H') == ([P0, longer], 2) and R.local_guides([longer, P0], 'H') == ([P0, longer], 2)      # by length, descending
+    # two short chains that merge (gap difference 499) are one guide of six anchors; at 500 they stay apart and are dropped
+    nxt = [(560, 50560 + 499, 1, 15), (530, 50530 + 499, 1, 15), (500, 50500 + 499, 1, 15)]
+    assert R.local_guides([P0, nxt, short], 'H') == ([P0, nxt + short], 2)
+    assert R.local_guides([P0, [(q, r + 1, s, l) for q, r, s, l in nxt], short], 'H') == ([P0], 1)
+    # the budget: 5 / 3 / all
+    many = [[(q, 60000 * (j + 1) + q, 1, 15) for q in (400, 300, 200)] for j in range(6)]
+    assert [len(R.local_guides([P0] + many, m)[0]) for m in ('H', 'L', 'S')] == [5, 3, 7] and R.local_guides([P0] + many, 'H')[1] == 7
+    # local_raw: the guides' rows in one list, sorted by q + l (stable), in mode R by q
+    A, B = 'ACGTTGCAAGTCC', 'TTGACCAGTAC'
+    ref = _planted(20000, 10000, A)
+    ref = ref[:10090] + B + ref[10101:]
+    read = _planted(300, 100, A)
+    read = read[:102] + B + read[113:]
+    guide = [(200, 10100, 1, 15), (50, 9950, 1, 15)]
+    assert R.local_raw([ref], read[:100] + A + read[113:], [guide], 9, 'H').tolist() == [[100, 10000, 1, 13]]
+    read2 = _planted(300, 100, A)[:120] + B + 'N' * 169
+    assert R.local_raw([ref], read2, [guide], 9, 'H').tolist() == [[100, 10000, 1, 13], [120, 10090, 1, 11]]
+    read3 = _planted(300, 104, B)[:130] + A[:9] + 'N' * 161                            # B ends at 115, A's first 9-mer at 139: q + l order is B, A; so is q order
+    assert R.local_raw([ref], read3, [guide], 9, 'H').tolist() == [[104, 10090, 1, 11], [130, 10000, 1, 9]]

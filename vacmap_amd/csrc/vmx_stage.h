@@ -20,6 +20,7 @@ struct vmx_local_bufs {
     vmx::DevBuf guide_rows, guide_len, ng_used, ng_total, cnt, cur, tpos, hkey, hkey2, dbg, hval, hq, goff, pcnt, gkey, gq, gr, epoch;
     vmx::DevBuf la_rows, la_ekey, la_sorted, la_off, la_cnt, status, gap, rlist, S, P, SA, chain, chain_len, score, variant;
     int64_t la_pool_rows = 0;            // rows of the local-anchor pools (regular slots + overflow area)
+    int64_t head_stride = 0;             // entries per slot of k_local_seed's head tables (cnt) as last filled: it depends on local_kmersize
     std::vector<int64_t> h_la_off;
     std::vector<int32_t> h_la_cnt;
 };

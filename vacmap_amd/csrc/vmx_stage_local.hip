@@ -100,15 +100,19 @@ int vmx_local_stage(vm_ctx* c, const vm_index_view& ix, const vm_params* prm, in
     A.rd_off = nullptr; A.rd_len = nullptr; A.r_st = nullptr; A.r_en = nullptr;
     static const bool dbg_on = getenv("VMX_DBG") != nullptr;
     // one launch over the reads listed in L.rorder[1 .. cnt] with `slots` workgroups and per-slot hit pools of `hcap` entries
-    auto run_seed = [&](int cnt, int slots, int64_t hcap, bool band) -> int {
+    auto run_seed = [&](int cnt, int slots, int64_t hcap, bool band, int64_t tcap) -> int {
         const int64_t hit_cap = hcap;
+        const int64_t tpos_cap = tcap;                                // (k_local_seed: window positions of one guide)
         const int G = slots;
         if (!band) {   // head tables: entries are tagged with the slot's epoch (k_local_seed), so only fresh memory is filled (0xff = epoch 511, never current)
             const size_t need = 4 * (size_t)G * (size_t)head_stride;
             const void* before = L.cnt.p; const size_t cap_before = L.cnt.cap;
             const void* ebefore = L.epoch.p;
             VMX_TRY(L.cnt.reserve(need)); VMX_TRY(L.epoch.reserve(4 * (size_t)G + 64));
-            if (L.cnt.p != before || L.cnt.cap != cap_before || L.epoch.p != ebefore) {
+            // (a slot's table starts at slot * head_stride: after a call with another local_kmersize the slots lie elsewhere, over entries that carry
+            // OTHER slots' epochs, and one of those may equal the slot's current epoch — a k-mer list that is not this read's)
+            if (L.cnt.p != before || L.cnt.cap != cap_before || L.epoch.p != ebefore || L.head_stride != head_stride) {
+                L.head_stride = head_stride;
                 VMX_HIP(hipMemsetAsync(L.cnt.p, 0xff, L.cnt.cap, c->stream)); VMX_HIP(hipMemsetAsync(L.epoch.p, 0, L.epoch.cap, c->stream));
             }
         }
@@ -155,7 +159,7 @@ int vmx_local_stage(vm_ctx* c, const vm_index_view& ix, const vm_params* prm, in
     (void)hipEventRecord(c->kev[0], c->stream);
     // (the banded form keeps no hits in HBM: its per-slot pools hold the chunk log and the anchors' sort keys only)
     int64_t hit_cap_b = 1; while (hit_cap_b < Lmax / 2 + 8192) hit_cap_b <<= 1;        // >= the read's anchor slot (len / 2 + 4096) and its chunk log (~0.25 records per base)
-    VMX_TRY(run_seed((int)n, band_on ? GB : G, band_on ? hit_cap_b : hit_cap, band_on));
+    VMX_TRY(run_seed((int)n, band_on ? GB : G, band_on ? hit_cap_b : hit_cap, band_on, tpos_cap));
     (void)hipEventRecord(c->kev[1], c->stream); c->kev_set |= 1;
     const bool rows_kernel = vmx_chain_rows_on() && prm->mode != VM_MODE_ASM;      // four reads per wavefront (k_chain_rows.hip); -mode asm keeps the one-wave kernel
     if (fast && !rows_kernel) { set_error("vmx_local_stage: the fast form needs the row chain kernels"); return VM_ERR_ARG; }
@@ -181,7 +185,7 @@ int vmx_local_stage(vm_ctx* c, const vm_index_view& ix, const vm_params* prm, in
         if (cnt) {
             std::stable_sort(ord.begin() + 1, ord.end(), [&](int32_t a, int32_t b) { return h_roff[a + 1] - h_roff[a] > h_roff[b + 1] - h_roff[b]; });
             VMX_TRY(vmx_push(c, L.rorder, ord.data(), ord.size()));
-            VMX_TRY(run_seed(cnt, std::min(cnt, G), hit_cap, false));
+            VMX_TRY(run_seed(cnt, std::min(cnt, G), hit_cap, false, tpos_cap));
             VMX_TRY(vmx_fetch(c, L.h_la_cnt.data(), L.la_cnt.p, (size_t)n));
             VMX_TRY(vmx_fetch(c, h_lstatus.data(), L.status.p, (size_t)n));
             VMX_HIP(vmx_stream_sync(c));
@@ -209,7 +213,8 @@ int vmx_local_stage(vm_ctx* c, const vm_index_view& ix, const vm_params* prm, in
             int64_t hcap = 1; while (hcap < mult * 4 * (lmax_f + 14000)) hcap <<= 1;
             if (hcap > ((int64_t)1 << 26)) hcap = (int64_t)1 << 26;          // stream indices are 26-bit
             A.la_slot_len = mult;                                            // slot length = mult * VMX_LA_SLOT(len) for the listed reads
-            VMX_TRY(run_seed(cnt, std::min(cnt, 8), hcap, false));
+            // (the table of window positions grows with the pools: a guide of many far-apart windows, 14 kb each, overflows the regular one)
+            VMX_TRY(run_seed(cnt, std::min(cnt, 8), hcap, false, std::min<int64_t>(mult * tpos_cap, ((int64_t)1 << 23) - 2)));
             VMX_TRY(vmx_fetch(c, L.h_la_cnt.data(), L.la_cnt.p, (size_t)n));
             VMX_TRY(vmx_fetch(c, h_lstatus.data(), L.status.p, (size_t)n));
             VMX_HIP(vmx_stream_sync(c));
