@@ -191,6 +191,36 @@ int vm_local_chain_batch(vm_ctx*, const vm_index*, const vm_params*, int64_t n, 
                          const int64_t* read_path_off, const int64_t* path_off, const int64_t* path_anchors, vm_local_out* out);
 void vm_local_out_free(vm_local_out*);
 
+/* The local chain DPs alone (L3 LC-exact :27305, L4 LC-mm :28250, L5 their `_fast` twins :26938 / :27891; mode R: `_scar`, mammap_noprefercloser.py:23419) on
+ * GIVEN anchor rows: the second half of vm_local_chain_batch, the same function with the same routing (four reads per wavefront or one wavefront per read,
+ * LDS-resident or not, the `_fast` launch behind them). rows: 4 int64 per row (q, r, s, l), read r's at row_off[r] ... row_off[r + 1], already in the DP's input
+ * order — stable by q + l, in mode R by q. n_guides_total[r]: the guide chains L1 would have kept for the read (1: LC-exact, more: LC-mm; mode R runs `_scar`
+ * whatever it says). readlens[r]: the read's length (the `_fast` twins size their score buckets from it); every row ends inside its read. flags:
+ * VM_LOCAL_DP_WANT_SP asks for S / P; VM_LOCAL_DP_DEVICE_LIST takes the read list built on the device (the route every batch after a context's first takes;
+ * it needs the row kernels). A batch with a row the device's fields cannot carry (l outside 0 ... 65535, q or q + l outside int32, s other than +1 / -1) is refused
+ * as a whole with VM_ERR_UNSUPPORTED, the message names the row; rows out of order, a negative q, a row that ends behind its read or a guide count below 1 are VM_ERR_ARG.
+ * (The order check is also what keeps the reference's non-terminating `continue` of the `_fast` twins, :27103, out of k_chain_local_fast: in order of read end only row 0
+ * can be a candidate that ends at or behind the current row, and only before the first advance, when its bucket holds one entry.)
+ * out per read: status (0, or VM_READ_RAISED where the reference's `_fast` twin would raise or never return), variant (0 LC-exact, 1 LC-mm, 2 `_scar`), fast_used
+ * (the opcount switch :27380 / :28333 was taken), score, the chain (descending read order, overlaps trimmed) and, with VM_LOCAL_DP_WANT_SP, S / P laid out like
+ * rows. sp_valid: bit 0 S, bit 1 P of the read are defined — P of every chained read, S unless the one-wavefront form kept it in LDS; a read without rows
+ * has status 0, score 0 and an empty chain. */
+#define VM_LOCAL_DP_WANT_SP 1
+#define VM_LOCAL_DP_DEVICE_LIST 2
+typedef struct vm_local_dp_out {
+    int32_t* status;         /* n */
+    int32_t* variant;        /* n */
+    int32_t* fast_used;      /* n */
+    int32_t* sp_valid;       /* n */
+    double* score;           /* n */
+    int64_t* chain_off;      /* n+1 */
+    int64_t* chain;          /* rows */
+    double* S; int64_t* P;   /* row_off[n] each; NULL without VM_LOCAL_DP_WANT_SP */
+} vm_local_dp_out;
+int vm_local_dp_batch(vm_ctx*, const vm_params*, int64_t n, const int64_t* rows, const int64_t* row_off, const int32_t* n_guides_total,
+                      const int64_t* readlens, int flags, vm_local_dp_out* out);
+void vm_local_dp_out_free(vm_local_dp_out*);
+
 /* One batch of -mode asm's LINKED chain DPs on the device (contigs of 500 kb and more, src/vacmap/mammap_asm.py:23228-23275 / :23328-23373):
  * which = 0 linked GC-exact (:21686), 2 linked LC (:21504). rows: n x 4 int64, the n_pre anchors carried from the previous batch first, the
  * new ones sorted by read position behind them; pre_S / pre_P, g_max_scores, g_max_index, prereadloc: the carried state (n_pre may be 0).

@@ -112,6 +112,11 @@ int vmo_local_chain(const vmo_index*, const char* read, int64_t readlen, int n_p
                     const int64_t* path_anchors, const vmo_params* p, double* score,
                     int64_t** chain, int64_t* n_chain, int64_t** raw, int64_t* n_raw, int32_t* variant);
 
+/* L3-L5 alone on given rows (n x (q, r, s, l) in the DP's input order): variant 0 LC-exact :27305, 1 LC-mm :28250 (either switches to its `_fast` twin by the
+ * reference's opcount rule), 2 `_scar` (mammap_noprefercloser.py:23419). S / P: n each. info[0]: 1 if the twin ran, info[1]: opcount at the switch or at the end. */
+int vmo_local_dp(const int64_t* rows, int64_t n, int variant, int mode, int kmersize, double skipcost, int maxdiff, int maxgap, double* score,
+                 int64_t** chain, int64_t* n_chain, double* S, int64_t* P, int64_t* info);
+
 /* ---- records ---- */
 typedef struct vmo_record {
     int32_t read_idx; int32_t contig; int32_t strand; /* +1 / -1 as labelled in the tuple */

@@ -255,7 +255,7 @@ int64_t chain_global_fast_asm(const std::vector<Anchor>& A, int kmersize, double
 
 // L5 :26938-27303 (mismatch = false) / :27891-28249 (mismatch = true). A sorted by q+l (stable).
 int local_chain_fast(const std::vector<Anchor>& A, int kmersize, double skipcost, int maxdiff, int maxgap, bool mismatch, int mode,
-                     double* score, Path& path) {
+                     double* score, Path& path, std::vector<double>* S_out, std::vector<int64_t>* P_out) {
     std::vector<double> S; std::vector<int64_t> P, SA;
     double gmax = 0.0;
     const int64_t g = fast_dp(A, mismatch ? 2 : 1, kmersize, skipcost, maxdiff, maxgap, mode, S, P, SA, &gmax);
@@ -277,6 +277,8 @@ int local_chain_fast(const std::vector<Anchor>& A, int kmersize, double skipcost
         preitem = now;
     }
     *score = gmax;
+    if (S_out) *S_out = S;
+    if (P_out) *P_out = P;
     return 0;
 }
 

@@ -210,11 +210,14 @@ static int64_t smallorequal2target_1d_point(const double* arr, double target, in
 }
 
 int local_chain_fast(const std::vector<Anchor>& A, int kmersize, double skipcost, int maxdiff, int maxgap, bool mismatch,
-                     int mode, double* score, Path& path);   // vmo_chain_fast.cc
+                     int mode, double* score, Path& path, std::vector<double>* S_out = nullptr, std::vector<int64_t>* P_out = nullptr);   // vmo_chain_fast.cc
+
+// what vmo_local_dp reports beside the chain (tests): whether the opcount switch (:27380 / :28333) was taken, and opcount where the DP stopped counting
+struct LocalDpInfo { bool switched = false; int64_t opcount = 0; };
 
 // LC-exact :27305-27528 (mismatch=false) and LC-mm :28250-28476 (mismatch=true). A sorted by q+l (stable).
 static int local_chain_dp(const std::vector<Anchor>& A, int kmersize, double skipcost, int maxdiff, int maxgap, bool mismatch,
-                          int mode, double* score, Path& path, std::vector<double>* S_out, std::vector<int64_t>* P_out) {
+                          int mode, double* score, Path& path, std::vector<double>* S_out, std::vector<int64_t>* P_out, LocalDpInfo* info = nullptr) {
     const Tables& T = tables();
     const int64_t extra_size = (int64_t)T.extra.size() - 1;
     const int64_t log2cache_size = (int64_t)T.log2cache.size() - 1;
@@ -236,8 +239,10 @@ static int local_chain_dp(const std::vector<Anchor>& A, int kmersize, double ski
         double max_scores = (double)A[i].l;
         int64_t pre_index = NOPRE;
         if (prereadloc < A[i].q + A[i].l) {
-            if (opcount > 100000 && ((double)opcount / (double)prereadloc) > 1000.0)      // :27380
-                return local_chain_fast(A, kmersize, skipcost, maxdiff, maxgap, mismatch, mode, score, path);
+            if (opcount > 100000 && ((double)opcount / (double)prereadloc) > 1000.0) {    // :27380
+                if (info) { info->switched = true; info->opcount = opcount; }
+                return local_chain_fast(A, kmersize, skipcost, maxdiff, maxgap, mismatch, mode, score, path, S_out, P_out);
+            }
             for (int64_t k = testspace_en; k < i; ++k) {
                 int64_t loc = smallorequal2target_1d_point(S.data(), S[k], k, S_arg.data()) + 1;
                 memmove(S_arg.data() + loc + 1, S_arg.data() + loc, sizeof(int64_t) * (size_t)(k - loc));
@@ -304,6 +309,7 @@ static int local_chain_dp(const std::vector<Anchor>& A, int kmersize, double ski
     *score = g_max_scores;
     if (S_out) *S_out = S;
     if (P_out) *P_out = P;
+    if (info) info->opcount = opcount;
     return 0;
 }
 
@@ -374,7 +380,8 @@ int local_chain_asm(const std::vector<Anchor>& A, int kmersize, double skipcost,
 // START (stable); the candidate window still advances on read ENDS (:23484). Co-linear gap cost 0.5*log2 for every size (:23432), read-gap
 // cost from the R table (:16534), a non-co-linear step costs the fixed skipcost, refunded after skipcost co-linear bases (fixed_penatly /
 // pre_penatly). No opcount switch.
-static int local_chain_scar(const std::vector<Anchor>& A, int kmersize, double skipcost, int maxdiff, int maxgap, double* score, Path& path) {
+static int local_chain_scar(const std::vector<Anchor>& A, int kmersize, double skipcost, int maxdiff, int maxgap, double* score, Path& path,
+                            std::vector<double>* S_out = nullptr, std::vector<int64_t>* P_out = nullptr) {
     const Tables& T = tables();
     const int64_t n = (int64_t)A.size();
     if (n == 0) return -1;
@@ -450,6 +457,8 @@ static int local_chain_scar(const std::vector<Anchor>& A, int kmersize, double s
         preitem = now;
     }
     *score = g_max_scores;
+    if (S_out) *S_out = S;
+    if (P_out) *P_out = P;
     return 0;
 }
 
@@ -559,6 +568,28 @@ int local_chain(const vmo_index* mi, const std::string& read, const std::string&
 }  // namespace vmo
 
 using namespace vmo;
+
+// The local chain DP alone on given rows (tests: vm_local_dp_batch's twin). rows: n x (q, r, s, l) in the DP's input order. variant: 0 LC-exact (:27305),
+// 1 LC-mm (:28250) — either switches to its `_fast` twin by the reference's opcount rule — 2 `_scar` (mammap_noprefercloser.py:23419). skipcost / maxgap: what
+// get_localmap_multi_all_forDP_inv_guide_list passes for the mode. S / P: n each (of the twin when it ran). info[0]: 1 if the twin ran, info[1]: opcount (at the
+// switch, else at the end; `_scar` does not count). Returns 0, or negative where the reference raises or does not return.
+extern "C" int vmo_local_dp(const int64_t* rows, int64_t n, int variant, int mode, int kmersize, double skipcost, int maxdiff, int maxgap, double* score,
+                            int64_t** chain, int64_t* n_chain, double* S, int64_t* P, int64_t* info) {
+    std::vector<Anchor> A((size_t)n);
+    for (int64_t i = 0; i < n; ++i) A[(size_t)i] = Anchor{rows[4 * i], rows[4 * i + 1], rows[4 * i + 2], rows[4 * i + 3]};
+    Path ch; double sc = 0; std::vector<double> Sv; std::vector<int64_t> Pv; LocalDpInfo li;
+    int rc;
+    if (variant == 2) rc = local_chain_scar(A, kmersize, skipcost, maxdiff, maxgap, &sc, ch, &Sv, &Pv);
+    else rc = local_chain_dp(A, kmersize, skipcost, maxdiff, maxgap, variant == 1, mode, &sc, ch, &Sv, &Pv, &li);
+    if (rc != 0) { ch.clear(); sc = 0; }
+    *chain = (int64_t*)malloc(sizeof(int64_t) * 4 * (ch.size() ? ch.size() : 1));
+    for (size_t i = 0; i < ch.size(); ++i) { (*chain)[4 * i] = ch[i].q; (*chain)[4 * i + 1] = ch[i].r; (*chain)[4 * i + 2] = ch[i].s; (*chain)[4 * i + 3] = ch[i].l; }
+    *n_chain = (int64_t)ch.size();
+    if (score) *score = sc;
+    if (rc == 0 && (int64_t)Sv.size() == n) { if (S) memcpy(S, Sv.data(), sizeof(double) * (size_t)n); if (P) memcpy(P, Pv.data(), sizeof(int64_t) * (size_t)n); }
+    if (info) { info[0] = li.switched ? 1 : 0; info[1] = li.opcount; }
+    return rc;
+}
 
 extern "C" int vmo_local_chain(const vmo_index* mi, const char* read, int64_t readlen, int n_paths, const int64_t* path_off,
                                const int64_t* pa, const vmo_params* p, double* score, int64_t** chain, int64_t* n_chain,

@@ -292,6 +292,14 @@ def bailout_cases(rng, mode):
     for n in (2002, 2003):
         a = np.array([(2 + t, 5 * FAR + 5000 * t, 1 if t % 9 else -1, 15) for t in range(n)], dtype=np.int64)
         out.append(Case('form/bailout/%d' % n, mode, n + 20, a[rng.permutation(n)]))
+    if mode == 'H':
+        # GC-fast on a length at the 16-bit edge (k_chain_fast.hip reads vmx_anchor.l through vmx_anchor_len): the bail-out set, a row of l = 32 768 chained
+        # co-linearly behind it and a last row far enough out that the scores stay inside the twin's score table (last q + 50). Oracle only.
+        n = 2003
+        rows = [(2 + t, 5 * FAR + 5000 * t, 1 if t % 9 else -1, 15) for t in range(n)]
+        rows += [(2100, 900 * FAR, 1, 15), (2117, 900 * FAR + 17, 1, 32768), (2117 + 32768 + 3, 900 * FAR + 17 + 32768 + 3, 1, 15), (40000, 950 * FAR, 1, 15)]
+        a = np.array(rows, dtype=np.int64)
+        out.append(Case('form/bailout/l32768', mode, 40040, a[np.random.default_rng(32768).permutation(len(a))], record=False))     # (its own stream: the recorded sets keep theirs)
     return out
 
 

@@ -95,6 +95,20 @@ class Rd:
         return bytes(self.buf)
 
 
+DP_ROWS = 2000
+DP_SKIP = {'H': 40., 'L': 59., 'S': 30., 'R': 30.}       # -localpenalty defaults (vacmap:257-296)
+_dp_tables = None
+
+
+def dp_tables():
+    """the cost tables tests/golden/tables.json pins (test_oracle_golden.py), as the oracle builds them"""
+    global _dp_tables
+    if _dp_tables is None:
+        import oracle_lib
+        _dp_tables = {n: oracle_lib.table(i) for i, n in enumerate(('extra', 'readgap_h', 'readgap_r', 'large_readgap', 'log2cache', 'log2int'))}
+    return _dp_tables
+
+
 def mirrored(rd):
     L = len(rd.buf)
     out = Rd(rd.label + '/rc', L, [[(L - q - l, r, -s, l) for q, r, s, l in p.tolist()[::-1]] for p in rd.paths], rd.expect)
@@ -129,6 +143,19 @@ class Case:
 
     def hits(self, i):
         return [h for _, t in self.traces(i) for h in t['hits']]
+
+    def dp(self, i):
+        """spec_ref.local_dp on the spec's raw rows of read i, with the variant and the parameters get_localmap_multi_all_forDP_inv_guide_list would take
+        (None: no rows, -mode asm's own DP, or more than DP_ROWS rows — the plain statement is quadratic in Python)"""
+        if ('dp', i) not in self._spec:
+            rows, e = self.rows(i), None
+            if self.mode != 'asm' and 0 < len(rows) <= DP_ROWS:
+                ng = R.local_guides(self.reads[i].paths, self.mode)[1]
+                variant = 2 if self.mode == 'R' else (1 if ng > 1 else 0)
+                skip = min(DP_SKIP[self.mode], 40.) if (self.mode == 'L' and variant == 1) else DP_SKIP[self.mode]
+                e = dict(R.local_dp(rows, variant, self.mode, self.k, skip, 30, 50 if self.mode == 'L' else 99, dp_tables()), variant=variant)
+            self._spec['dp', i] = e
+        return self._spec['dp', i]
 
 
 class Plan:
@@ -713,7 +740,8 @@ def parse_trace(text):
 
 def check_case(ctx, index, case, build, band, trace):
     """local_chain_batch on every read of the case in ONE call against spec_ref.local_raw: status 0 and the rows of `raw`, row for row (a read
-    without any local anchor has nothing to chain: raw is empty, the status stays 0). band: VMX_LSEED_BAND as the caller has
+    without any local anchor has nothing to chain: raw is empty, the status stays 0) — and against spec_ref.local_dp applied to those rows: variant, score
+    as bits and the chain (Case.dp: not -mode asm, whose DP is another one, and not the reads of more than DP_ROWS rows). band: VMX_LSEED_BAND as the caller has
     set it in the environment together with VMX_LSEED_TRACE; trace() returns what the process wrote to stderr since the last call. With the
     banded form on, the trace line's hand-backs must be exactly the case's expected ones, and the reads expected to stay, run again on their own,
     must all stay."""
@@ -728,6 +756,14 @@ def check_case(ctx, index, case, build, band, trace):
             exp = case.rows(i)
             assert g['status'] == 0, (what, case.label, case.reads[i].label, g['status'])
             same(g['raw'], exp, case, case.reads[i], what)
+            assert len(exp) == 0 or 0 < exp[:, 3].min() and exp[:, 3].max() <= max(19, case.k), (case.label, 'a run is flushed before it reaches 20 (:23240): the 16-bit length field is exact')
+            e = case.dp(i)
+            if e is not None and not e['switch']:
+                assert g['variant'] == e['variant'], (what, case.label, case.reads[i].label, 'variant', g['variant'], e['variant'])
+                assert np.float64(g['score']).view(np.uint64) == np.float64(e['score']).view(np.uint64), (what, case.label, case.reads[i].label, 'score', g['score'], e['score'])
+                same(g['chain'], e['chain'], case, case.reads[i], what + ', chain')
+            elif len(exp) == 0:
+                assert len(g['chain']) == 0, (what, case.label, case.reads[i].label, 'a chain without rows')
         return lines
 
     ids = list(range(len(case.reads)))

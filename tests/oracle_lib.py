@@ -78,6 +78,7 @@ def lib():
     L.vmo_decode_hit.argtypes = [vp, i64, i64, C.c_int, P(Params), P(Chains)]
     L.vmo_chains_free.argtypes = [P(Chains)]
     L.vmo_local_chain.argtypes = [vp, cp, i64, C.c_int, vp, vp, P(Params), P(dbl), P(P(i64)), P(i64), P(P(i64)), P(i64), P(i32)]
+    L.vmo_local_dp.argtypes = [vp, i64, C.c_int, C.c_int, C.c_int, dbl, C.c_int, C.c_int, P(dbl), P(P(i64)), P(i64), vp, vp, vp]
     L.vmo_extend.argtypes = [vp, cp, i64, vp, i64, C.c_int, C.c_int, C.c_int, P(Params), P(P(Record)), P(i64), P(vp), P(i32)]
     L.vmo_align_read.argtypes = [vp, cp, i64, P(Params), P(P(Record)), P(i64), P(vp)]
     L.vmo_align_batch.argtypes = [vp, P(Params), i64, cp, vp, C.c_int, P(P(Record)), P(i64), P(vp), vp]
@@ -261,6 +262,19 @@ def local_chain(index, read, paths, prm):
     rc = lib().vmo_local_chain(index.h, rd, len(rd), len(paths), off.ctypes.data, pa.ctypes.data, C.byref(prm), C.byref(sc),
                                C.byref(ch), C.byref(nch), C.byref(rw), C.byref(nrw), C.byref(var))
     return {'rc': rc, 'score': sc.value, 'chain': _take_rows(ch, nch.value), 'raw': _take_rows(rw, nrw.value), 'variant': var.value}
+
+
+def local_dp(rows, variant, mode, k, skipcost, maxdiff, maxgap):
+    """vmo_local_dp: the local chain DP alone on rows in the DP's input order. variant 0 LC-exact, 1 LC-mm, 2 `_scar`. Returns dict(rc, score, chain (descending),
+    S, P, fast_used, opcount); S / P are None when the read raised"""
+    a = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, 4)
+    n = len(a)
+    S = np.zeros(max(n, 1), np.float64); Pp = np.zeros(max(n, 1), np.int64); info = np.zeros(2, np.int64)
+    sc = C.c_double(); ch = C.POINTER(C.c_int64)(); nch = C.c_int64()
+    rc = lib().vmo_local_dp(a.ctypes.data, n, int(variant), MODES[mode], int(k), float(skipcost), int(maxdiff), int(maxgap), C.byref(sc), C.byref(ch), C.byref(nch),
+                            S.ctypes.data, Pp.ctypes.data, info.ctypes.data)
+    return {'rc': rc, 'score': sc.value, 'chain': _take_rows(ch, nch.value), 'S': S[:n] if rc == 0 else None, 'P': Pp[:n] if rc == 0 else None,
+            'fast_used': bool(info[0]), 'opcount': int(info[1])}
 
 
 def _take_records(recs, n, blob, names=None):

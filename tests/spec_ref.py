@@ -9,6 +9,9 @@ these functions judge both. Scores and hashes are int64 / uint64; every DP is th
   map_read      VMX-S1     index lookup under the occurrence cap, hits sorted by (r, q, s), clusters cut at reference gaps > 5000, ranked by
                            (size desc, first r asc), the first check_num emitted; default_mid_occ is the index's own cap
   ksw2_order_cigar         VMX-DP-G with ksw2's published tie order, cell by cell (small problems only)
+  local_guides / local_seed / local_raw    L1 / L2: the guide chains and the re-seeded local anchors, from the reference's text
+  local_dp                 L3 / L4 / `_scar`: the local chain DPs on rows in their input order, from the reference's text, with branch counters; the cost
+                           tables are handed in (the ones tests/golden/tables.json pins)
 """
 import re
 import numpy as np
@@ -612,3 +615,200 @@ def local_raw(contigs, read, paths, k, mode):
         rows += local_seed(contigs, read, g, k, mode)[0]
     rows.sort(key=(lambda a: a[0]) if mode == 'R' else (lambda a: a[0] + a[3]))
     return np.array(rows, dtype=np.int64).reshape(-1, 4)
+
+
+# ------------------------------------------------------------------------------------------------ L3 / L4 / `_scar`: the local chain DPs
+LOCAL_NOPRE = -9999999
+LOCAL_SWITCH_OPS = 100000        # the switch to the `_fast` twin: opcount > 100000 and opcount / prereadloc > 1000, tested where the candidate space advances
+LOCAL_SWITCH_RATIO = 1000
+
+
+def _small_or_equal(S, target, n, point):
+    """position of the last score <= target among the n entries of the score-sorted index `point`, -1 if none: the reference's own probe sequence"""
+    if target < S[point[0]]:
+        return -1
+    if target >= S[point[n - 1]]:
+        return n - 1
+    i, j, mid = 0, n, 0
+    while i < j:
+        mid = (i + j) // 2
+        v = S[point[mid]]
+        if target == v:
+            if mid < n - 1:
+                if S[point[mid + 1]] > target:
+                    return mid
+                i = mid + 1
+            else:
+                return mid
+        elif target < v:
+            if mid > 0 and target >= S[point[mid - 1]]:
+                return mid - 1
+            j = mid
+        else:
+            if mid < n - 1 and target < S[point[mid + 1]]:
+                return mid
+            i = mid + 1
+    return mid
+
+
+def local_gap_geometry(ai, aj):
+    """(readgap, refgap, bonus) of the step j -> i, rows (q, r, s, l); bonus <= 0 only where i ends inside j"""
+    readgap = ai[0] - aj[0] - aj[3]
+    if readgap < 0:
+        bonus = ai[0] + ai[3] - aj[0] - aj[3]
+        overlap = aj[0] + aj[3] - ai[0]
+        readgap = 0
+        if ai[2] == aj[2]:
+            refgap = ai[1] + overlap - (aj[1] + aj[3]) if ai[2] == 1 else aj[1] - (ai[1] + bonus)
+        else:
+            refgap = ai[1] + overlap - aj[1] + 1 if aj[2] == -1 else ai[1] + bonus - 1 - (aj[1] + aj[3])
+    else:
+        bonus = ai[3]
+        if ai[2] == aj[2]:
+            refgap = ai[1] - aj[1] - aj[3] if ai[2] == 1 else aj[1] - ai[1] - ai[3]
+        else:
+            refgap = ai[1] - aj[1] + 1 if aj[2] == -1 else ai[1] + ai[3] - 1 - aj[1] - aj[3]
+    return readgap, refgap, bonus
+
+
+def local_dp(rows, variant, mode, k, skipcost, maxdiff, maxgap, tables):
+    """The local chain DP on rows (q, r, s, l) in its input order (stable by q + l; `_scar`: by q). variant 0 LC-exact, 1 LC-mm, 2 `_scar`.
+    skipcost / maxgap: as the caller of the DP passes them for the mode. tables: dict of the cost tables extra, readgap_h, readgap_r, large_readgap (float32),
+    log2cache, log2int (float64) — the ones tests/golden/tables.json pins. Integers are Python integers; scores are IEEE doubles (Python floats are; S is
+    stored as numpy.float64) combined in the reference's order: ((S[j] + bonus) - gapcost_list) - readgapcost, (S[j] + bonus) - (skip + table).
+
+    Anchor i looks at the anchors whose read END lies before the read end at which the candidate space last advanced, best score first, and stops at the
+    first S[j] < max_scores - l_i (strict; opcount counts that candidate too). A step is co-linear when both anchors have one strand, refgap >= 0,
+    readgap <= maxgap and |readgap - refgap| <= maxdiff. An overlap whose bonus is <= 0 is passed over. The first candidate to reach a score keeps it (>).
+    New entries enter the score-sorted index above their equals. LC-exact and LC-mm hand the read to their `_fast` twin when, at an advance,
+    opcount > 100000 and opcount / prereadloc > 1000: the result then says so and holds nothing else.
+
+    Returns dict: S (float64), P (int64), score, chain (descending read order, overlaps trimmed), opcount, switch (the twin takes the read), tests (the
+    (opcount, prereadloc) every advance tested), kind (per row: 0 no predecessor, 1 co-linear step won, 2 non-co-linear step won), and counters."""
+    a = [tuple(int(v) for v in r) for r in np.asarray(rows, dtype=np.int64).reshape(-1, 4)]
+    n = len(a)
+    assert n > 0 and variant in (0, 1, 2)
+    scar, mm = variant == 2, variant == 1
+    log2int = tables['log2int']
+    gapcost_list = [0.0] * (maxdiff + 1)
+    for g in range(1, maxdiff + 1):
+        gapcost_list[g] = 0.01 * k * g + (0.5 if (g <= 10 or scar) else 2) * float(log2int[g])
+    rgc = tables['large_readgap'] if mm else (tables['readgap_r'] if mode == 'R' else tables['readgap_h'])
+    extra, log2cache = tables['extra'], tables['log2cache']
+    extra_size, l2c_size = len(extra) - 1, len(log2cache) - 1
+    skipcost = float(skipcost)
+    S = np.empty(n, np.float64); P = np.empty(n, np.int64); kind = np.zeros(n, np.int8)
+    S_arg = [0] * n
+    fixed = [0.0] * n; prepen = [0.0] * n
+    C = dict(colinear_wins=0, noncolinear_wins=0, cross_strand_wins=0, refunds=0, debts_carried=0, bonus_skips=0, longest_scan=0, below16=0, below3=0, insert_among_equals=0,
+             eq_break_evals=0, breaks=0, tie_tests=0, scans_past16=0, scans_past3=0, extra_saturated=0, l2c_saturated=0, gapcost_above10=0, overlaps=0, advances=0, held=0,
+             late_updates=0, kind_flips=0)
+    S[0] = float(a[0][3]); P[0] = LOCAL_NOPRE
+    g_max, g_idx = float(a[0][3]), 0
+    prereadloc = a[0][0] + a[0][3]
+    te, opcount = 1, 0
+    out = dict(switch=False, tests=[])
+    for i in range(1, n):
+        ai = a[i]
+        li = float(ai[3])
+        max_scores, pre = li, LOCAL_NOPRE
+        if prereadloc < ai[0] + ai[3]:
+            if not scar:
+                out['tests'].append((opcount, prereadloc))
+                if opcount > LOCAL_SWITCH_OPS and opcount / prereadloc > LOCAL_SWITCH_RATIO:
+                    out.update(switch=True, opcount=opcount, S=None, P=None, score=None, chain=None, kind=None, counters=C)
+                    return out
+            for kk in range(te, i):
+                loc = _small_or_equal(S, S[kk], kk, S_arg) + 1
+                C['insert_among_equals'] += loc > 0 and S[S_arg[loc - 1]] == S[kk]
+                C['below16'] += kk - loc >= 16
+                C['below3'] += kk - loc >= 3
+                S_arg[loc + 1:kk + 1] = S_arg[loc:kk]
+                S_arg[loc] = kk
+            te = i
+            prereadloc = ai[0] + ai[3]
+            C['advances'] += 1
+        else:
+            C['held'] += 1
+        scanned = updates = 0
+        win_kind = 0
+        for x in range(te - 1, -1, -1):
+            j = S_arg[x]
+            opcount += 1
+            scanned += 1
+            Sj = float(S[j])
+            lim = max_scores - li
+            if Sj < lim:
+                C['breaks'] += 1
+                break
+            C['eq_break_evals'] += Sj == lim
+            aj = a[j]
+            readgap, refgap, bonus = local_gap_geometry(ai, aj)
+            if ai[0] - aj[0] - aj[3] < 0:
+                C['overlaps'] += 1
+                if bonus <= 0:
+                    C['bonus_skips'] += 1
+                    continue
+            gapcost = abs(readgap - refgap)
+            col = ai[2] == aj[2] and refgap >= 0 and readgap <= maxgap and gapcost <= maxdiff
+            nf = npp = 0.0
+            if col:
+                test = Sj + bonus - gapcost_list[gapcost] - float(rgc[readgap])
+                if scar:
+                    refund = fixed[j] < 0 and fixed[j] + bonus >= 0
+                    if refund:
+                        test += prepen[j]
+                    if fixed[j] < 0 and fixed[j] + bonus < 0:
+                        nf, npp = fixed[j] + bonus, prepen[j]
+            elif scar:
+                test = Sj + bonus - skipcost
+                nf, npp = -skipcost + bonus, skipcost
+            elif not mm:
+                g = min(gapcost, extra_size)
+                pen = (min(50.0, skipcost) if ai[2] != aj[2] else skipcost) + float(extra[g])
+                test = Sj + bonus - pen
+            else:
+                pen = skipcost + float(log2cache[min(l2c_size, gapcost)])
+                test = Sj + bonus - pen
+            if test > max_scores:
+                updates += 1
+                C['kind_flips'] += win_kind != 0 and win_kind != (1 if col else 2)
+                max_scores, pre, win_kind = test, j, 1 if col else 2
+                win = dict(col=col, cross=ai[2] != aj[2], gapcost=gapcost, refund=col and scar and fixed[j] < 0 and fixed[j] + bonus >= 0, debt=col and scar and nf < 0)
+                if scar:
+                    fixed[i], prepen[i] = nf, npp
+            elif test == max_scores and pre != LOCAL_NOPRE:
+                C['tie_tests'] += 1
+        S[i] = max_scores; P[i] = pre; kind[i] = win_kind
+        C['longest_scan'] = max(C['longest_scan'], scanned)
+        C['scans_past16'] += scanned > 16
+        C['scans_past3'] += scanned > 3
+        C['late_updates'] += updates > 1
+        if pre != LOCAL_NOPRE:
+            C['colinear_wins'] += win['col']
+            C['noncolinear_wins'] += not win['col']
+            C['cross_strand_wins'] += (not win['col']) and win['cross']
+            C['refunds'] += win['refund']
+            C['debts_carried'] += win['debt']
+            C['gapcost_above10'] += win['col'] and win['gapcost'] > 10
+            C['extra_saturated'] += (not win['col']) and variant == 0 and win['gapcost'] >= extra_size
+            C['l2c_saturated'] += (not win['col']) and mm and win['gapcost'] >= l2c_size
+        if max_scores > g_max:
+            g_max, g_idx = max_scores, i
+    chain = []
+    take = g_idx
+    chain.append(a[take])
+    preitem = a[take]
+    C['trimmed'] = C['trimmed_to_1'] = 0
+    while P[take] != LOCAL_NOPRE:
+        take = int(P[take])
+        now = a[take]
+        if preitem[0] < now[0] + now[3]:
+            ov = now[0] + now[3] - preitem[0]
+            chain[-1] = (preitem[0] + ov, preitem[1] + ov if preitem[2] == 1 else preitem[1], preitem[2], preitem[3] - ov)
+            C['trimmed'] += 1
+            C['trimmed_to_1'] += preitem[3] - ov == 1
+        chain.append(now)
+        preitem = now
+    out.update(S=S, P=P, score=g_max, chain=np.array(chain, dtype=np.int64).reshape(-1, 4), opcount=opcount, kind=kind, counters={k_: int(v) for k_, v in C.items()})
+    return out

@@ -68,6 +68,18 @@ def test_oracle_equals_the_reference_fixture(cases, oracle):
     assert n == len(meta) > 700
 
 
+def test_long_row_sets_reach_gc_fast(cases, oracle):
+    """the bail-out set with a row of l = 32 768 (oracle only): GC-fast ran, did not raise, and the long row is in the primary path"""
+    n = 0
+    for c in cases:
+        if c.label.startswith('form/bailout/l32768'):
+            e = CC.expected_oracle(c, oracle)
+            assert e['fast_used'] and e['gmax'] >= 0 and e['score'] > 32768, (c.label, e['fast_used'], e['gmax'], e['score'])
+            assert any(32768 in [row[3] for row in p] for p in e['paths'][:1]), c.label
+            n += 1
+    assert n == 1
+
+
 def test_opcount_rule_of_the_oracle(cases, oracle):
     """the reference does not return opcount; its bail-out (:24914) shows it: isolated equal anchors never end a scan, so opcount is i (i - 1) / 2 at anchor i"""
     for c in cases:

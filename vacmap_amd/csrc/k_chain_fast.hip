@@ -115,7 +115,7 @@ struct vmx_fast_cost {
 template <int VARIANT>
 __device__ __forceinline__ bool vmx_fast_eval(const vmx_anchor& ai, const vmx_anchor& aj, double Sj, const vmx_fast_cost& C, double* test,
                                               double fpj = 0.0, double ppj = 0.0, double* nfp = nullptr, double* npp = nullptr) {
-    const int qi = ai.q, li = ai.l, si = ai.s, qj = aj.q, lj = aj.l, sj = aj.s; const long long ri = ai.r, rj = aj.r;
+    const int qi = ai.q, li = vmx_anchor_len(ai), si = ai.s, qj = aj.q, lj = vmx_anchor_len(aj), sj = aj.s; const long long ri = ai.r, rj = aj.r;
     long long readgap = (long long)qi - qj - lj, refgap, bonus;
     if (VARIANT == 4) {                                   // -mode asm: mammap_asm.py:20866-20895 (non_overlap_size form, no +-1)
         if (readgap < 0) {
@@ -196,15 +196,16 @@ __device__ int vmx_fast_dp(const vmx_fast_io& io, vmx_fast_cost C, const double*
     }
     __syncthreads();
     const vmx_anchor a0 = A[0];
+    const int l0 = vmx_anchor_len(a0);
     constexpr bool GC = VARIANT == 0 || VARIANT == 3 || VARIANT == 4;     // 4: GC-fast of the -mode asm fork (mammap_asm.py:20738-21037), no coverage terms
-    long long prereadloc = GC ? (long long)a0.q : (long long)a0.q + a0.l;
+    long long prereadloc = GC ? (long long)a0.q : (long long)a0.q + l0;
     C.gapcost = gapcost_list; C.skipcost = oskipcost; C.maxdiff = omaxdiff;
     int testspace_en_i = 1;
-    if ((int)a0.l >= io.cnt_n) return -5;
+    if (l0 >= io.cnt_n) return -5;
     const bool linked = VARIANT == 4 && lk && lk->n_pre > 0;
-    if (lane == 0) { io.SA[0] = 0; if (!linked) { io.S[0] = (double)a0.l; io.P[0] = VMX_NOPRE; } io.Si[0] = a0.l; io.CNT[a0.l] = 1; if (VARIANT == 3) { io.FP[0] = 0.0; io.PP[0] = 0.0; } }
+    if (lane == 0) { io.SA[0] = 0; if (!linked) { io.S[0] = (double)l0; io.P[0] = VMX_NOPRE; } io.Si[0] = l0; io.CNT[l0] = 1; if (VARIANT == 3) { io.FP[0] = 0.0; io.PP[0] = 0.0; } }
     __syncthreads();
-    double g_max_scores = (double)a0.l; int g_max_index = 0;
+    double g_max_scores = (double)l0; int g_max_index = 0;
     int max_score_i = 0;
     int err = 0;
     int pre_size = 1;
@@ -213,13 +214,14 @@ __device__ int vmx_fast_dp(const vmx_fast_io& io, vmx_fast_cost C, const double*
         __syncthreads();
         const int s0 = io.Si[0];
         if (s0 < 0 || s0 >= io.cnt_n) return -5;
-        if (lane == 0) { io.CNT[a0.l] = 0; io.CNT[s0] = 1; }
+        if (lane == 0) { io.CNT[l0] = 0; io.CNT[s0] = 1; }
         __syncthreads();
         pre_size = lk->n_pre; g_max_scores = lk->g_max_scores; g_max_index = lk->g_max_index; prereadloc = lk->prereadloc; max_score_i = s0;
     }
     for (int i = pre_size; i < n && !err; ++i) {
         const vmx_anchor ai = A[i];
-        const long long pos_i = GC ? (long long)ai.q : (long long)ai.q + ai.l;
+        const int li = vmx_anchor_len(ai);
+        const long long pos_i = GC ? (long long)ai.q : (long long)ai.q + li;
         if (prereadloc < pos_i) {
             for (int k = testspace_en_i; k < i; ++k) {                         // :25132-25146
                 const int sk = io.Si[k];
@@ -239,9 +241,9 @@ __device__ int vmx_fast_dp(const vmx_fast_io& io, vmx_fast_cost C, const double*
             }
             prereadloc = pos_i;
         }
-        double max_scores = (double)ai.l; int pre_index = VMX_NOPRE;
+        double max_scores = (double)li; int pre_index = VMX_NOPRE;
         double fp_i = 0.0, pp_i = 0.0;
-        const double f = (double)(ai.l + 1);
+        const double f = (double)(li + 1);
         const long long ti = io.T[i];
         int en_top = testspace_en_i;                      // end of the bucket of the highest level of the current window
         for (int top = max_score_i; top >= 0; top -= 64) {
@@ -372,9 +374,10 @@ __global__ void __launch_bounds__(64) k_chain_local_fast(const vmx_anchor* __res
             while (P[take] != VMX_NOPRE) {
                 take = P[take];
                 const vmx_anchor now = A[take];
-                if (pre.q < now.q + now.l) {
-                    const int ov = now.q + now.l - pre.q;
-                    vmx_anchor t = pre; t.q = pre.q + ov; t.l = (int16_t)(pre.l - ov); if (pre.s == 1) t.r = pre.r + ov;
+                const int nowl = vmx_anchor_len(now);
+                if (pre.q < now.q + nowl) {
+                    const int ov = now.q + nowl - pre.q;
+                    vmx_anchor t = pre; t.q = pre.q + ov; t.l = (int16_t)(vmx_anchor_len(pre) - ov); if (pre.s == 1) t.r = pre.r + ov;
                     O[w - 1] = t;
                 }
                 O[w++] = now;

@@ -181,21 +181,22 @@ __device__ __forceinline__ void vmx_chain_local_read(const vmx_anchor* __restric
             else {
                 vmx_anchor* O = out_chain + a0;
                 int w = 0; int take = g_max_index;
-                vmx_anchor pre; pre.q = AQ(take); pre.r = AR(take); pre.l = (int16_t)AL(take); pre.s = (int16_t)AS(take);
+                vmx_anchor pre = A[take];
                 O[w++] = pre;
                 while (P[take] != VMX_NOPRE) {
                     take = P[take];
-                    vmx_anchor now; now.q = AQ(take); now.r = AR(take); now.l = (int16_t)AL(take); now.s = (int16_t)AS(take);
+                    const vmx_anchor now = A[take];
+                    const int nowl = vmx_anchor_len(now);               // (lengths as unsigned 16-bit values: vmx_anchor_len)
                     if (asmv) {
                         vmx_anchor t = now;
-                        if (!(pre.q >= now.q + now.l)) { t.l = (int16_t)(pre.q - now.q); if (now.s != 1) t.r = now.r + now.l - pre.q + now.q; }
+                        if (!(pre.q >= now.q + nowl)) { t.l = (int16_t)(pre.q - now.q); if (now.s != 1) t.r = now.r + nowl - pre.q + now.q; }
                         O[w++] = t;
                         pre = now;
                         continue;
                     }
-                    if (pre.q < now.q + now.l) {
-                        int ov = now.q + now.l - pre.q;
-                        vmx_anchor t = pre; t.q = pre.q + ov; t.l = (int16_t)(pre.l - ov); if (pre.s == 1) t.r = pre.r + ov;
+                    if (pre.q < now.q + nowl) {
+                        int ov = now.q + nowl - pre.q;
+                        vmx_anchor t = pre; t.q = pre.q + ov; t.l = (int16_t)(vmx_anchor_len(pre) - ov); if (pre.s == 1) t.r = pre.r + ov;
                         O[w - 1] = t;
                     }
                     O[w++] = now;

@@ -21,6 +21,10 @@ struct vmx_anchor {
     int64_t r;     // global reference position
 };
 
+// The length is an UNSIGNED 16-bit field (0 ... 65535, what the stage entries accept) kept in an int16_t: every reader takes it through this, never as `a.l`
+// (a sign-extended 32768 ... 65535 is a negative length, and in k_chain_fast.hip a negative index into S_i_count).
+__host__ __device__ __forceinline__ int vmx_anchor_len(const vmx_anchor& a) { return (int)(uint16_t)a.l; }
+
 // hashed minimizer index slot (16 B): open addressing, empty key = ~0
 struct vmx_slot { uint64_t key; uint32_t start; uint32_t count; };
 

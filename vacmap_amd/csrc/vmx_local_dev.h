@@ -6,6 +6,11 @@
 #include "vmx_kernels.h"
 #include "vmx_local.h"
 
+// The 16-bit length field is exact for every row the two seeding kernels emit: a run of hits grows an anchor only while its length stays below 20
+// (`cl + bouns < 20`, :23240 — otherwise the anchor is flushed and the next one starts with the bonus, at most k), so l <= max(19, k), and the host admits
+// k <= 11 only (vmx_local_stage). Nothing is truncated here; local_cases.check_case asserts the bound on every raw row the stage returns. The banded form's third
+// caller (k_local_band.hip, the log's leftovers) takes the length from the low 32 bits of a log word: it is a length the same rule produced (`len` of `anchor`, logged by
+// logrec), so the same bound holds.
 __device__ __forceinline__ vmx_anchor vmx_mk_anchor(long long q, long long r, int s, long long l) {
     vmx_anchor a; a.q = (int32_t)q; a.r = r; a.s = (int16_t)s; a.l = (int16_t)l; return a;
 }

@@ -78,6 +78,14 @@ extern "C" int vmx_seed_stage(vm_ctx* c, const vm_index* mi, int check_num, int 
 int vmx_local_stage(vm_ctx* c, const vm_index_view& ix, const vm_params* prm, int64_t n, const uint8_t* d_ocodes, const int64_t* d_roff,
                     const std::vector<int64_t>& h_roff, const vmx_anchor* d_path_rows, const int32_t* d_path_len, const int32_t* d_npaths,
                     const int64_t* d_aoff, const std::vector<int64_t>& h_aoff, const double* d_gscore, vmx_local_bufs& L, bool fast = false);
+// The second half of vmx_local_stage, L3 - L5: the local chain DPs over the anchors in L (la_sorted / la_off / la_cnt / ng_total / status on the device, la_pool_rows,
+// h_la_cnt unless `fast`), with the routing of the product (row kernels or one wavefront per read, LDS buckets, device-built read list when `fast`). Also entered
+// by the stage entry vm_local_dp_batch on rows it is given. probe (that entry only; null in the product): what the host knows about the run and no kernel
+// stores — d_lc_status gets a copy of the per-read status between the LC launches and L5 (VM_READ_FASTPATH_DEV: the read went on to its `_fast` twin),
+// s_in_lds[r] (sized n by the caller) whether read r ran LDS-resident (its S never reached HBM).
+struct vmx_local_dp_probe { int32_t* d_lc_status = nullptr; std::vector<uint8_t> s_in_lds; };
+int vmx_local_dp(vm_ctx* c, const vm_params* prm, int64_t n, const int64_t* d_roff, const std::vector<int64_t>& h_roff, vmx_local_bufs& L, bool fast,
+                 vmx_local_dp_probe* probe = nullptr);
 // G1 selection (k_chain_select) over n reads, one launch per LDS size class of the reads' anchor counts (h_aoff), side by side
 int vmx_launch_chain_select(vm_ctx* c, int64_t n, const int64_t* h_aoff, vmx::DevBuf& d_list, const vmx_anchor* sorted, const int64_t* d_aoff, const int64_t* d_lens,
                             const double* S, const int32_t* P, const int32_t* SA, const int64_t* gmax, const int32_t* flip, int mode, char* scr, const int64_t* soff,

@@ -1,7 +1,9 @@
-// vmx_stage_local.hip — host orchestration of the local stage (L1-L4): vmx_local_stage() is shared by the stage entry
-// vm_local_chain_batch and by vm_align_batch. Kernels: k_local.hip.
+// vmx_stage_local.hip — host orchestration of the local stage (L1-L5): vmx_local_stage() is shared by the stage entry
+// vm_local_chain_batch and by vm_align_batch; its second half, the chain DPs (vmx_local_dp), also by vm_local_dp_batch. Kernels: k_local.hip, k_chain_rows.hip,
+// k_chain_local.hip, k_chain_fast.hip.
 #include "vmx_host.h"
 #include "vmx_local.h"
+#include "vmx_local_rows.h"
 #include "vmx_stage.h"
 #include <algorithm>
 #include <cstring>
@@ -31,6 +33,9 @@ __global__ void k_chain_local(const vmx_anchor* anchors, const int64_t* la_off, 
                               const int32_t* rlist, int nlist, int lds_cap, vmx_tables tab, const double* gapcost_list, double skip_exact,
                               double skip_mm, int maxdiff, int maxgap, int mode, double* S_pool, int32_t* P_pool, int32_t* SA_pool, double* out_score,
                               vmx_anchor* out_chain, int32_t* out_len, int32_t* out_variant, int32_t* status, double* FP_pool, double* PP_pool);
+
+// four reads per wavefront (k_chain_rows.hip); -mode asm keeps the one-wave kernel
+static inline bool vmx_local_rows_kernel(const vm_params* prm) { return vmx_chain_rows_on() && prm->mode != VM_MODE_ASM; }
 
 // Inputs on the device: oriented read codes + offsets; paths (rows at aoff[r], lengths at aoff[r]+p, n_paths[r]); gscore[r] (0 = unmapped).
 // h_roff / h_aoff are the host copies of the offsets. Leaves in L: la_off (device+host), chain rows / len / score / variant / status.
@@ -161,8 +166,7 @@ int vmx_local_stage(vm_ctx* c, const vm_index_view& ix, const vm_params* prm, in
     int64_t hit_cap_b = 1; while (hit_cap_b < Lmax / 2 + 8192) hit_cap_b <<= 1;        // >= the read's anchor slot (len / 2 + 4096) and its chunk log (~0.25 records per base)
     VMX_TRY(run_seed((int)n, band_on ? GB : G, band_on ? hit_cap_b : hit_cap, band_on, tpos_cap));
     (void)hipEventRecord(c->kev[1], c->stream); c->kev_set |= 1;
-    const bool rows_kernel = vmx_chain_rows_on() && prm->mode != VM_MODE_ASM;      // four reads per wavefront (k_chain_rows.hip); -mode asm keeps the one-wave kernel
-    if (fast && !rows_kernel) { set_error("vmx_local_stage: the fast form needs the row chain kernels"); return VM_ERR_ARG; }
+    if (fast && !vmx_local_rows_kernel(prm)) { set_error("vmx_local_stage: the fast form needs the row chain kernels"); return VM_ERR_ARG; }
     if (!fast) {
     // sizing sync #2: local anchor counts decide the LDS bucket of every read in the local chain DP
     L.h_la_cnt.resize((size_t)n);
@@ -222,7 +226,16 @@ int vmx_local_stage(vm_ctx* c, const vm_index_view& ix, const vm_params* prm, in
         }
     }
     } else L.h_la_cnt.clear();
-    // LC DP
+    return vmx_local_dp(c, prm, n, d_roff, h_roff, L, fast);
+}
+
+// LC DP (L3 - L5) over the local anchors that the seeding half (or vm_local_dp_batch) left in L: la_sorted / la_off / la_cnt / ng_total / status on the device,
+// L.la_pool_rows, and L.h_la_cnt on the host unless `fast`, where the read list is built on the device from la_cnt. probe (tests, may be null): see vmx_stage.h.
+int vmx_local_dp(vm_ctx* c, const vm_params* prm, int64_t n, const int64_t* d_roff, const std::vector<int64_t>& h_roff, vmx_local_bufs& L, bool fast, vmx_local_dp_probe* probe) {
+    const int k = prm->local_kmersize;
+    const int64_t la_tot = L.la_pool_rows;
+    const bool rows_kernel = vmx_local_rows_kernel(prm);
+    if (fast && !rows_kernel) { set_error("vmx_local_dp: the fast form needs the row chain kernels"); return VM_ERR_ARG; }
     const HostTables& T = host_tables();
     std::vector<double> gap(64, 0.0);
     for (int g = 1; g <= prm->local_maxdiff; ++g)
@@ -246,6 +259,7 @@ int vmx_local_stage(vm_ctx* c, const vm_index_view& ix, const vm_params* prm, in
         int bk = NB; for (int q = 0; q < NB; ++q) if (m <= caps[q] && caps[q] <= lds_max) { bk = q; break; }
         if (rows_kernel) bk = NB;                                         // k_chain_local_rows: one list, nothing in LDS
         lists[bk].push_back((int32_t)r);
+        if (probe) probe->s_in_lds[(size_t)r] = bk < NB;
     }
     std::vector<int32_t> rl; int64_t rl_off[NB + 2];
     for (int q = 0; q <= NB; ++q) {
@@ -305,6 +319,7 @@ int vmx_local_stage(vm_ctx* c, const vm_index_view& ix, const vm_params* prm, in
     }
     fk.join();
     vmx_chain_dbg_report(c->stream);
+    if (probe && probe->d_lc_status) VMX_HIP(hipMemcpyAsync(probe->d_lc_status, L.status.p, 4 * (size_t)n, hipMemcpyDeviceToDevice, c->stream));     // (before L5 rewrites the hand-offs)
     // L5: reads whose LC launch hit the opcount switch (:27380 / :28333) take the *_fast twin. One wave per read; all other reads
     // return at once.
     VMX_TRY(L.si.reserve(4 * (size_t)(la_tot + 1))); VMX_TRY(L.tg.reserve(8 * (size_t)(la_tot + 1))); VMX_TRY(L.cntp.reserve(4 * (size_t)(h_roff[n] + 50 * n + 64)));
@@ -372,10 +387,88 @@ int vm_local_chain_batch(vm_ctx* c, const vm_index* mi, const vm_params* prm, in
     int64_t oc = 0, orw = 0;
     for (int64_t r = 0; r < n; ++r) {
         out->chain_off[r] = oc; out->raw_off[r] = orw;
-        for (int x = 0; x < clen[r]; ++x) { const vmx_anchor& a = chain[L.h_la_off[r] + x]; int64_t* o = out->chain + 4 * oc++; o[0] = a.q; o[1] = a.r; o[2] = a.s; o[3] = a.l; }
-        for (int x = 0; x < L.h_la_cnt[r]; ++x) { const vmx_anchor& a = sorted[L.h_la_off[r] + x]; int64_t* o = out->raw + 4 * orw++; o[0] = a.q; o[1] = a.r; o[2] = a.s; o[3] = a.l; }
+        for (int x = 0; x < clen[r]; ++x) { const vmx_anchor& a = chain[L.h_la_off[r] + x]; int64_t* o = out->chain + 4 * oc++; o[0] = a.q; o[1] = a.r; o[2] = a.s; o[3] = vmx_anchor_len(a); }
+        for (int x = 0; x < L.h_la_cnt[r]; ++x) { const vmx_anchor& a = sorted[L.h_la_off[r] + x]; int64_t* o = out->raw + 4 * orw++; o[0] = a.q; o[1] = a.r; o[2] = a.s; o[3] = vmx_anchor_len(a); }
     }
     out->chain_off[n] = oc; out->raw_off[n] = orw;
+    return VM_OK;
+}
+
+void vm_local_dp_out_free(vm_local_dp_out* o) {
+    free(o->status); free(o->variant); free(o->fast_used); free(o->score); free(o->chain_off); free(o->chain); free(o->sp_valid); free(o->S); free(o->P);
+    memset(o, 0, sizeof(*o));
+}
+
+int vm_local_dp_batch(vm_ctx* c, const vm_params* prm, int64_t n, const int64_t* rows, const int64_t* row_off, const int32_t* n_guides_total,
+                      const int64_t* readlens, int flags, vm_local_dp_out* out) {
+    memset(out, 0, sizeof(*out));
+    if (!c) { set_error("no context"); return VM_ERR_NO_CTX; }
+    if (n < 0 || (flags & ~(VM_LOCAL_DP_WANT_SP | VM_LOCAL_DP_DEVICE_LIST))) { set_error("vm_local_dp_batch: bad read count or flag bits"); return VM_ERR_ARG; }
+    if (prm->mode == VM_MODE_ASM) { set_error("vm_local_dp_batch: -mode asm's local chain is not a stage of this entry"); return VM_ERR_UNSUPPORTED; }
+    if (prm->local_kmersize < 5 || prm->local_kmersize > 11) { set_error("local k-mer size must be in [5,11]"); return VM_ERR_UNSUPPORTED; }
+    if (prm->local_maxdiff > 62) { set_error("local_maxdiff > 62 unsupported"); return VM_ERR_UNSUPPORTED; }
+    static_assert(VMX_ROWS_ARG == VM_ERR_ARG && VMX_ROWS_UNSUPPORTED == VM_ERR_UNSUPPORTED, "vmx_local_rows.h restates the error codes");
+    if (const vmx_rows_verdict v = vmx_local_rows_check(rows, row_off, n, n_guides_total, readlens, prm->mode == VM_MODE_R); v.code != VMX_ROWS_OK) {
+        char msg[224];
+        if (v.code == VMX_ROWS_UNSUPPORTED) snprintf(msg, sizeof msg, "vm_local_dp_batch: anchor row %lld (read %lld) does not fit the device row: %s", (long long)v.row, (long long)v.read, v.what);
+        else snprintf(msg, sizeof msg, "vm_local_dp_batch: read %lld, row %lld: %s", (long long)v.read, (long long)v.row, v.what);
+        set_error(msg); return v.code;
+    }
+    const bool fast = (flags & VM_LOCAL_DP_DEVICE_LIST) != 0, want_sp = (flags & VM_LOCAL_DP_WANT_SP) != 0;
+    VMX_HIP(hipSetDevice(c->device));
+    vmx_fetch_scope fetch_scope(c);
+    const int64_t tot = row_off[n];
+    // the state the seeding half leaves: rows in the DP's order at la_off[r], their counts, the guide counts, status 0
+    vmx_local_bufs& L = *vmx_ctx_local_bufs(c);
+    std::vector<vmx_anchor> h_rows((size_t)tot + 1);
+    for (int64_t i = 0; i < tot; ++i) { vmx_anchor a; a.q = (int32_t)rows[4 * i]; a.r = rows[4 * i + 1]; a.s = (int16_t)rows[4 * i + 2]; a.l = (int16_t)(uint16_t)rows[4 * i + 3]; h_rows[(size_t)i] = a; }
+    memset(&h_rows[(size_t)tot], 0, sizeof(vmx_anchor));
+    std::vector<int64_t> h_roff((size_t)n + 1, 0);
+    std::vector<int32_t> h_cnt((size_t)n + 1, 0), h_ng(n_guides_total, n_guides_total + n);
+    for (int64_t r = 0; r < n; ++r) { h_roff[(size_t)r + 1] = h_roff[(size_t)r] + readlens[r]; h_cnt[(size_t)r] = (int32_t)(row_off[r + 1] - row_off[r]); }
+    h_ng.push_back(0);
+    L.la_pool_rows = tot;
+    L.h_la_off.assign(row_off, row_off + n + 1);
+    if (fast) L.h_la_cnt.clear(); else L.h_la_cnt.assign(h_cnt.begin(), h_cnt.begin() + n);
+    DevBuf& d_roff = vmx_ctx_entry_bufs(c)->a.off; DevBuf& d_lc = vmx_ctx_entry_bufs(c)->out;
+    VMX_TRY(upload(L.la_sorted, h_rows.data(), (size_t)tot + 1, c->stream)); VMX_TRY(upload(L.la_off, row_off, (size_t)n + 1, c->stream));
+    VMX_TRY(upload(L.la_cnt, h_cnt.data(), (size_t)n + 1, c->stream)); VMX_TRY(upload(L.ng_total, h_ng.data(), (size_t)n + 1, c->stream));
+    VMX_TRY(upload(d_roff, h_roff.data(), (size_t)n + 1, c->stream));
+    VMX_TRY(L.status.reserve(4 * (size_t)(n + 1))); VMX_HIP(hipMemsetAsync(L.status.p, 0, 4 * (size_t)(n + 1), c->stream));
+    VMX_TRY(d_lc.reserve(4 * (size_t)(n + 1))); VMX_HIP(hipMemsetAsync(d_lc.p, 0, 4 * (size_t)(n + 1), c->stream));
+    vmx_local_dp_probe probe; probe.d_lc_status = d_lc.as<int32_t>(); probe.s_in_lds.assign((size_t)n + 1, 0);
+    if (n) VMX_TRY(vmx_local_dp(c, prm, n, d_roff.as<int64_t>(), h_roff, L, fast, &probe));
+    // download
+    const size_t n1 = (size_t)std::max<int64_t>(n, 1), t1 = (size_t)std::max<int64_t>(tot, 1);
+    std::vector<int32_t> clen((size_t)n), lc((size_t)n), hP; std::vector<vmx_anchor> chain((size_t)tot);
+    out->status = (int32_t*)malloc(4 * n1); out->variant = (int32_t*)malloc(4 * n1); out->fast_used = (int32_t*)malloc(4 * n1); out->sp_valid = (int32_t*)malloc(4 * n1);
+    out->score = (double*)malloc(8 * n1); out->chain_off = (int64_t*)malloc(8 * (size_t)(n + 1));
+    if (n) {
+        VMX_TRY(download(out->status, L.status.p, (size_t)n, c->stream)); VMX_TRY(download(out->variant, L.variant.p, (size_t)n, c->stream));
+        VMX_TRY(download(out->score, L.score.p, (size_t)n, c->stream)); VMX_TRY(download(clen.data(), L.chain_len.p, (size_t)n, c->stream));
+        VMX_TRY(download(lc.data(), d_lc.p, (size_t)n, c->stream)); VMX_TRY(download(chain.data(), L.chain.p, (size_t)tot, c->stream));
+        if (want_sp) {
+            out->S = (double*)malloc(8 * t1); out->P = (int64_t*)malloc(8 * t1); hP.resize((size_t)tot);
+            VMX_TRY(download(out->S, L.S.p, (size_t)tot, c->stream)); VMX_TRY(download(hP.data(), L.P.p, (size_t)tot, c->stream));
+        }
+        VMX_HIP(vmx_stream_sync(c)); VMX_HIP(hipGetLastError());
+    }
+    if (want_sp && n) for (int64_t i = 0; i < tot; ++i) out->P[i] = hP[(size_t)i];
+    int64_t tc = 0;
+    for (int64_t r = 0; r < n; ++r) { if (clen[(size_t)r] < 0 || clen[(size_t)r] > h_cnt[(size_t)r]) { set_error("vm_local_dp_batch: a chain longer than its rows came back"); return VM_ERR_HIP; } tc += clen[(size_t)r]; }
+    out->chain = (int64_t*)malloc(32 * (size_t)std::max<int64_t>(tc, 1));
+    int64_t oc = 0;
+    for (int64_t r = 0; r < n; ++r) {
+        out->chain_off[r] = oc;
+        for (int x = 0; x < clen[(size_t)r]; ++x) { const vmx_anchor& a = chain[(size_t)(row_off[r] + x)]; int64_t* o = out->chain + 4 * oc++; o[0] = a.q; o[1] = a.r; o[2] = a.s; o[3] = vmx_anchor_len(a); }
+        const bool twin = lc[(size_t)r] == VM_READ_FASTPATH_DEV;
+        out->fast_used[r] = twin ? 1 : 0;
+        // S and P of a read that was chained: P always reaches HBM, S unless the one-wavefront form kept it in LDS (the twin works in HBM)
+        const bool ran = h_cnt[(size_t)r] > 0 && out->status[r] == 0;
+        out->sp_valid[r] = !want_sp || !ran ? 0 : ((twin || !probe.s_in_lds[(size_t)r]) ? 3 : 2);
+        if (h_cnt[(size_t)r] == 0) { out->variant[r] = prm->mode == VM_MODE_R ? 2 : (n_guides_total[r] > 1 ? 1 : 0); out->score[r] = 0.0; }      // nothing to chain: no kernel wrote the variant
+    }
+    out->chain_off[n] = oc;
     return VM_OK;
 }
 

@@ -55,6 +55,15 @@ class LocalOut(C.Structure):
                 ('raw', C.POINTER(C.c_int64))]
 
 
+class LocalDpOut(C.Structure):
+    _fields_ = [('status', C.POINTER(C.c_int32)), ('variant', C.POINTER(C.c_int32)), ('fast_used', C.POINTER(C.c_int32)), ('sp_valid', C.POINTER(C.c_int32)),
+                ('score', C.POINTER(C.c_double)), ('chain_off', C.POINTER(C.c_int64)), ('chain', C.POINTER(C.c_int64)), ('S', C.POINTER(C.c_double)),
+                ('P', C.POINTER(C.c_int64))]
+
+
+LOCAL_DP_WANT_SP, LOCAL_DP_DEVICE_LIST = 1, 2          # vm_local_dp_batch's flag bits
+
+
 class Record(C.Structure):
     _fields_ = [('read_idx', C.c_int32), ('contig', C.c_int32), ('strand', C.c_int32), ('mapq', C.c_int32),
                 ('q_st', C.c_int64), ('q_en', C.c_int64), ('r_st', C.c_int64), ('r_en', C.c_int64),
@@ -165,6 +174,8 @@ class VmxLib:
         L.vm_map.argtypes = [vp, vp, cp, i64, C.c_int, C.c_int, P(P(i64)), P(i64)]
         L.vm_local_chain_batch.argtypes = [vp, vp, P(Params), i64, cp, vp, vp, vp, vp, P(LocalOut)]
         L.vm_local_out_free.argtypes = [P(LocalOut)]
+        L.vm_local_dp_batch.argtypes = [vp, P(Params), i64, vp, vp, vp, vp, C.c_int, P(LocalDpOut)]
+        L.vm_local_dp_out_free.argtypes = [P(LocalDpOut)]
         L.vm_align_batch.argtypes = [vp, vp, P(Params), i64, cp, vp, P(P(Record)), P(i64), P(vp), vp, P(BatchStats)]
         L.vm_align_trace.argtypes = [vp, vp, P(Params), i64, cp, vp, C.c_int, P(P(i64)), P(P(i64))]
         L.vm_sam_emit.argtypes = [vp, P(SamOpts), i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, C.c_int, P(vp), P(P(i64)), P(i64), P(i64)]
@@ -1019,6 +1030,36 @@ def local_chain_batch(ctx, index, prm, seqs, paths_per_read):
     res = [{'status': int(out.status[r]), 'variant': int(out.variant[r]), 'score': float(out.score[r]), 'chain': ch[co[r]:co[r + 1]],
             'raw': rw[ro[r]:ro[r + 1]]} for r in range(n)]
     ctx.lib.L.vm_local_out_free(C.byref(out))
+    return res
+
+
+def local_dp_batch(ctx, prm, rows_list, n_guides_total, readlens, want_sp=False, device_list=False):
+    """vm_local_dp_batch: the local chain DPs on given rows. rows_list: per read an (m, 4) array (q, r, s, l) in the DP's input order (stable by q + l;
+    mode R: by q); n_guides_total, readlens: per read. Returns per read dict(status, variant, fast_used, score, chain, S, P) — S / P are None where
+    the entry does not define them (not asked for, the read not chained, S kept in LDS by the one-wavefront form)."""
+    n = len(rows_list)
+    off = np.zeros(n + 1, np.int64)
+    for i, a in enumerate(rows_list):
+        off[i + 1] = off[i] + len(a)
+    rows = np.ascontiguousarray(np.concatenate([np.asarray(a, dtype=np.int64).reshape(-1, 4) for a in rows_list]) if n else np.zeros((0, 4), np.int64))
+    ng = np.ascontiguousarray(n_guides_total, dtype=np.int32); rl = np.ascontiguousarray(readlens, dtype=np.int64)
+    assert len(ng) == n and len(rl) == n
+    out = LocalDpOut()
+    flags = (LOCAL_DP_WANT_SP if want_sp else 0) | (LOCAL_DP_DEVICE_LIST if device_list else 0)
+    try:
+        ctx.lib.check(ctx.lib.L.vm_local_dp_batch(ctx.h, C.byref(prm), n, rows.ctypes.data, off.ctypes.data, ng.ctypes.data, rl.ctypes.data, flags, C.byref(out)))
+        co = np.ctypeslib.as_array(out.chain_off, shape=(n + 1,)).copy()
+        ch = np.ctypeslib.as_array(out.chain, shape=(max(int(co[-1]), 1), 4))[:int(co[-1])].copy()
+        tot = int(off[-1])
+        S = np.ctypeslib.as_array(out.S, shape=(max(tot, 1),))[:tot].copy() if want_sp and n else None
+        Pp = np.ctypeslib.as_array(out.P, shape=(max(tot, 1),))[:tot].copy() if want_sp and n else None
+        res = []
+        for r in range(n):
+            v = int(out.sp_valid[r])
+            res.append({'status': int(out.status[r]), 'variant': int(out.variant[r]), 'fast_used': bool(out.fast_used[r]), 'score': float(out.score[r]),
+                        'chain': ch[co[r]:co[r + 1]], 'S': S[off[r]:off[r + 1]] if v & 1 else None, 'P': Pp[off[r]:off[r + 1]] if v & 2 else None})
+    finally:
+        ctx.lib.L.vm_local_dp_out_free(C.byref(out))
     return res
 
 
