@@ -395,6 +395,31 @@ int vm_sam_emit_device_comments(vm_ctx*, const vm_index*, const vm_sam_opts*, in
                                 const vm_record* recs, int64_t n_recs, const char* cigar_blob, const int32_t* status, char** text, int64_t** text_off,
                                 int64_t* n_lines, int64_t* n_skipped);
 int vm_sam_emit_device_times(vm_ctx*, double* seconds3);
+/* PAF text for the same records. THE RULE: a PAF line exists exactly where vm_sam_emit writes a record line for the same inputs and options; the reads
+ * skipped (status not 0, or the emission raises), reassign_mapq under markunbalancetra, the order inside a read (span descending, the later record first
+ * among equals), text_off[n + 1], n_lines and n_skipped are vm_sam_emit's. The line of a record, in that order:
+ *   QNAME qlen qs qe strand TNAME tlen r_st r_en nmatch alen MAPQ tp:A:P NM:i:nm [cg:Z:cg] [MD:Z:md cs:Z:cs]        (tab-separated, '\n' at the end)
+ * qlen: the read's length. qs, qe: on the read as sequenced, q_st / q_en for '+' and qlen - q_en / qlen - q_st for '-', printed as signed integers and
+ * not clamped. tlen: the contig's length in the index. r_st, r_en: as the record holds them. MAPQ and nm: the numbers the SAM line prints in its MAPQ
+ * column and in NM:i: (asm_mode's 60 / 1 and its NM rule included). alen: the sum of the lengths of the merged CIGAR's M = X I D operators. nmatch:
+ * alen - nm, signed (defined from the line's own NM: a PAF line raises exactly where the SAM line does, and no mode walks the sequences once more).
+ * cg: the merged CIGAR text without its leading maximal run of S / H operators and without its trailing one (interior S / H stay); when nothing is
+ * left the tab and the field are omitted; cigar2cg's '*' rule does not apply. md set: MD:Z: and cs:Z: with the SAM line's strings (empty where SAM
+ * prints them empty; shortcs as in SAM). No SEQ, QUAL, RG, SA or comment fields: hardclip, fakecigar, cigar2cg and rg_id change nothing.
+ * keep_unmapped: a read that emits no record line emits
+ *   QNAME qlen 0 0 * * 0 0 0 0 0 0
+ * at its place; it counts in n_lines, and n_skipped keeps its meaning.
+ * vm_paf_emit: vm_sam_emit's arguments without quals / qual_off and comments / com_off; host threads as vm_sam_emit uses them. */
+int vm_paf_emit(const vm_index*, const vm_sam_opts*, int64_t n_reads, const char* names, const int64_t* name_off, const char* seqs, const int64_t* seq_off,
+                const vm_record* recs, int64_t n_recs, const char* cigar_blob, const int32_t* status, int nthreads, char** text, int64_t** text_off,
+                int64_t* n_lines, int64_t* n_skipped);
+/* The same lines (THE RULE above) made on the GPU: vm_sam_emit_device's arguments without quals / qual_off. The records, their order, the merged CIGAR,
+ * NM, MD and cs come from the SAM emitter's kernels (k_sam_count, k_sam_order, k_sam_ops); the lines from k_paf_lines (k_paf.hip), which also finds alen
+ * and the cg range in the merged text. Returns vm_paf_emit's bytes, text_off, n_lines and n_skipped for the same inputs (text and text_off: vm_free).
+ * VM_ERR_UNSUPPORTED and VM_ERR_ARG as vm_sam_emit_device returns them. Three host waits per call; vm_sam_emit_device_times covers this entry too. */
+int vm_paf_emit_device(vm_ctx*, const vm_index*, const vm_sam_opts*, int64_t n_reads, const char* names, const int64_t* name_off, const char* seqs,
+                       const int64_t* seq_off, const vm_record* recs, int64_t n_recs, const char* cigar_blob, const int32_t* status, char** text,
+                       int64_t** text_off, int64_t* n_lines, int64_t* n_skipped);
 /* `mp.fastx_read(path, read_comment=)` (vacmap:445): FASTA / FASTQ, plain or gzip. vm_fastx_read returns up to max_reads records (stopping
  * early once max_bases bases are held) as blobs: names, UPPER-CASED sequences (vacmap:476), qualities (empty for FASTA), comments (header
  * text after the first blank, else tab). Returns the record count, 0 at the end of the input, or a negative vm_status. */

@@ -17,6 +17,7 @@
 // contig, as the host's T() / Q() / tslice do (a failed check is the host's Raise and sets the read's flag). Writes: the write pass repeats the
 // size pass's arithmetic on the same inputs, and its offsets are the exclusive scans of those sizes.
 #include "vmx_sam_dev.h"
+#include "k_sam_out.h"
 
 #define SAM_SAT 0x80000000LL            // operator counts saturate here; reaching it is VMX_SAM_E_COUNT
 
@@ -25,9 +26,6 @@ __device__ __forceinline__ long long sam_scan_i64(long long v, int lane) {      
     return v;
 }
 __device__ __forceinline__ long long sam_get_i64(long long v, int l) { return __shfl(v, l); }
-__device__ __forceinline__ unsigned long long sam_lt(int lane) { return (1ull << lane) - 1ull; }
-__device__ __forceinline__ int sam_top(unsigned long long m) { return 63 - __clzll((long long)m); }      // highest set bit (m != 0)
-__device__ __forceinline__ int sam_ndig(unsigned long long u) { int n = 1; while (u >= 10) { u /= 10; ++n; } return n; }
 __device__ __forceinline__ void sam_put_u(char* p, unsigned long long u, int nd) { for (int k = nd - 1; k >= 0; --k) { p[k] = (char)('0' + u % 10); u /= 10; } }
 __device__ __forceinline__ char sam_lo(char c) { return (c >= 'A' && c <= 'Z') ? (char)(c + 32) : c; }
 __device__ __forceinline__ char sam_comp(char c) {
@@ -306,22 +304,7 @@ __global__ void __launch_bounds__(64) k_sam_ops(vmx_sam_in A, vmx_sam_work K, in
 }
 
 // ------------------------------------------------------------------------------------------------ lines
-// a line under construction; every call is made by the whole wave with the same arguments
-template <bool W> struct SamOut {
-    char* p; int64_t pos; int lane;
-    __device__ __forceinline__ void ch(char c) { if (W && lane == 0) p[pos] = c; ++pos; }
-    __device__ __forceinline__ void bytes(const char* s, int64_t n) { if (W) for (int64_t x = lane; x < n; x += 64) p[pos + x] = s[x]; pos += n; }
-    __device__ __forceinline__ void num(int64_t v) {                    // put_int: sign included
-        const bool neg = v < 0;
-        const unsigned long long u = neg ? 0ull - (unsigned long long)v : (unsigned long long)v;
-        const int nd = sam_ndig(u);
-        if (W) {
-            if (neg && lane == 0) p[pos] = '-';
-            if (lane < nd) { unsigned long long t = u; for (int s = nd - 1 - lane; s > 0; --s) t /= 10; p[pos + (neg ? 1 : 0) + lane] = (char)('0' + t % 10); }
-        }
-        pos += nd + (neg ? 1 : 0);
-    }
-};
+// (SamOut, the line under construction: k_sam_out.h)
 
 template <bool W> __device__ __forceinline__ void sam_fake_cigar(SamOut<W>& O, const vm_record& y, int64_t qlen, char clip) {
     if (y.q_st > 0) { O.num(y.q_st); O.ch(clip); }

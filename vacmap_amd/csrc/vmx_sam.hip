@@ -8,6 +8,7 @@
 // CIGARs (--fakecigar), CG tag switch (:20962, Q4), P_alignmentstring (:5391) with comment copying (:20686). A read whose emission would
 // raise in the reference (an index past a sequence end) produces no line and is counted as skipped, like the worker's except (:24127-24134);
 // under vm_sam_opts.keep_unmapped it, a read whose status is not 0 and a read without records each produce one FLAG 4 line (unmapped_line).
+// PAF text for the same records (vm_paf_emit; the rule: vacmapx.h): stage_read() below is shared by the two formats, only the line assembly differs.
 // No device code in this file.
 #include "vmx_index_priv.h"
 #include <atomic>
@@ -248,51 +249,60 @@ static void unmapped_line(const vm_sam_opts* o, const char* name, int64_t name_l
     out.push_back('\n');
 }
 
-struct Scratch { std::vector<Rec> recs; std::vector<Ops> ops; std::vector<std::string> cig, md, cs, fake; std::vector<int64_t> nm, nops; std::string rcq, rcqual; };
+struct Scratch { std::vector<Rec> recs; std::vector<Ops> ops; std::vector<std::string> cig, md, cs, fake; std::vector<int64_t> nm, nops; std::string rcq, rcqual; bool need_rc = false; };
+
+// The per-record stage that the SAM and the PAF lines of a read share: the records in the emitted order with reassign_mapq applied, and per record
+// the merged CIGAR text, its operator count, NM, MD / cs and (SAM, --fakecigar) the approximate CIGAR. Throws Raise where the reference's emitter would.
+static void stage_read(const vm_index* mi, const std::string& bases, const vm_sam_opts* o, const char* query, int64_t qlen, const vm_record* rr, int64_t nr, const char* blob,
+                       bool want_fake, Scratch& S) {
+    S.recs.resize((size_t)nr);
+    for (int64_t i = 0; i < nr; ++i) {
+        Rec& r = S.recs[(size_t)i];
+        r.contig = rr[i].contig; r.strand = rr[i].strand == 1 ? '+' : '-'; r.mapq = rr[i].mapq; r.q_st = rr[i].q_st; r.q_en = rr[i].q_en; r.r_st = rr[i].r_st; r.r_en = rr[i].r_en;
+        r.cigar = blob + rr[i].cigar_off; r.cigar_len = rr[i].cigar_len;
+    }
+    if (o->markunbalancetra) reassign_mapq(S.recs);
+    // sort by query span ascending (stable), then reverse: longest first, later ones first among equals (:20855-20856)
+    std::stable_sort(S.recs.begin(), S.recs.end(), [](const Rec& a, const Rec& b) { return a.q_en - a.q_st < b.q_en - b.q_st; });
+    std::reverse(S.recs.begin(), S.recs.end());
+    bool need_rc = false; for (const Rec& r : S.recs) need_rc = need_rc || r.strand == '-';
+    S.need_rc = need_rc;
+    if (need_rc) revcomp_into(query, qlen, S.rcq);
+    const size_t n = S.recs.size();
+    S.ops.resize(n); S.cig.resize(n); S.md.resize(n); S.cs.resize(n); S.fake.resize(n); S.nm.resize(n); S.nops.resize(n);
+    const char clip = o->hardclip ? 'H' : 'S';
+    for (size_t i = 0; i < n; ++i) {
+        Rec& r = S.recs[i];
+        const char* qs = r.strand == '+' ? query : S.rcq.data();
+        const int64_t clen = mi->lens[(size_t)r.contig];
+        int64_t ta = r.r_st < 0 ? 0 : (r.r_st > clen ? clen : r.r_st), tb = r.r_en < 0 ? 0 : (r.r_en > clen ? clen : r.r_en);     // Python slice semantics of contig[a:b]
+        if (tb < ta) tb = ta;
+        const char* t = bases.data() + mi->offsets[(size_t)r.contig] + ta; const int64_t tl = tb - ta;
+        if (!o->md && o->asm_mode) {                           // asm: no walk over the sequences at all
+            merge_cigar(r.cigar, r.cigar_len, S.ops[i]); join_ops(S.ops[i], S.cig[i]); S.nops[i] = (int64_t)S.ops[i].op.size();
+            S.nm[i] = nm_asm_text(r.cigar, r.cigar_len);
+        } else if (!o->md) S.nm[i] = merge_cigar_nm(r.cigar, r.cigar_len, qs, qlen, t, tl, S.cig[i], &S.nops[i]);      // one pass: merged text + NM
+        else {
+            merge_cigar(r.cigar, r.cigar_len, S.ops[i]);
+            join_ops(S.ops[i], S.cig[i]);
+            S.nops[i] = (int64_t)S.ops[i].op.size();
+            int64_t qa = r.q_st < 0 ? 0 : (r.q_st > qlen ? qlen : r.q_st), qb = r.q_en < 0 ? 0 : (r.q_en > qlen ? qlen : r.q_en); if (qb < qa) qb = qa;
+            md_cs(S.ops[i], t, tl, qs + qa, qb - qa, o->shortcs != 0, S.md[i], S.cs[i]);
+            S.nm[i] = o->asm_mode ? nm_asm_text(r.cigar, r.cigar_len) : nm_from_cigar(S.ops[i], qs + qa, qb - qa, t, tl);
+        }
+        if (o->fakecigar && want_fake) fake_cigar(r, qlen, clip, S.fake[i]);
+    }
+}
 
 // SAM lines of one read appended to `out`; returns the number of lines, or -1 when the reference's emitter would raise
 static int emit_read(const vm_index* mi, const std::string& bases, const vm_sam_opts* o, const char* name, int64_t name_len, const char* query, int64_t qlen, const char* qual,
                      int64_t qual_len, const char* com, int64_t com_len, const vm_record* rr, int64_t nr, const char* blob, Scratch& S, std::string& out) {
     const size_t out0 = out.size();
     try {
-        S.recs.resize((size_t)nr);
-        for (int64_t i = 0; i < nr; ++i) {
-            Rec& r = S.recs[(size_t)i];
-            r.contig = rr[i].contig; r.strand = rr[i].strand == 1 ? '+' : '-'; r.mapq = rr[i].mapq; r.q_st = rr[i].q_st; r.q_en = rr[i].q_en; r.r_st = rr[i].r_st; r.r_en = rr[i].r_en;
-            r.cigar = blob + rr[i].cigar_off; r.cigar_len = rr[i].cigar_len;
-        }
-        if (o->markunbalancetra) reassign_mapq(S.recs);
-        // sort by query span ascending (stable), then reverse: longest first, later ones first among equals (:20855-20856)
-        std::stable_sort(S.recs.begin(), S.recs.end(), [](const Rec& a, const Rec& b) { return a.q_en - a.q_st < b.q_en - b.q_st; });
-        std::reverse(S.recs.begin(), S.recs.end());
-        bool need_rc = false; for (const Rec& r : S.recs) need_rc = need_rc || r.strand == '-';
-        if (need_rc) revcomp_into(query, qlen, S.rcq);
+        stage_read(mi, bases, o, query, qlen, rr, nr, blob, true, S);
         const bool has_qual = qual != nullptr && qual_len == qlen;
-        if (need_rc && has_qual) { S.rcqual.assign(qual, (size_t)qlen); std::reverse(S.rcqual.begin(), S.rcqual.end()); }
+        if (S.need_rc && has_qual) { S.rcqual.assign(qual, (size_t)qlen); std::reverse(S.rcqual.begin(), S.rcqual.end()); }
         const size_t n = S.recs.size();
-        S.ops.resize(n); S.cig.resize(n); S.md.resize(n); S.cs.resize(n); S.fake.resize(n); S.nm.resize(n); S.nops.resize(n);
-        const char clip = o->hardclip ? 'H' : 'S';
-        for (size_t i = 0; i < n; ++i) {
-            Rec& r = S.recs[i];
-            const char* qs = r.strand == '+' ? query : S.rcq.data();
-            const int64_t clen = mi->lens[(size_t)r.contig];
-            int64_t ta = r.r_st < 0 ? 0 : (r.r_st > clen ? clen : r.r_st), tb = r.r_en < 0 ? 0 : (r.r_en > clen ? clen : r.r_en);     // Python slice semantics of contig[a:b]
-            if (tb < ta) tb = ta;
-            const char* t = bases.data() + mi->offsets[(size_t)r.contig] + ta; const int64_t tl = tb - ta;
-            if (!o->md && o->asm_mode) {                           // asm: no walk over the sequences at all
-                merge_cigar(r.cigar, r.cigar_len, S.ops[i]); join_ops(S.ops[i], S.cig[i]); S.nops[i] = (int64_t)S.ops[i].op.size();
-                S.nm[i] = nm_asm_text(r.cigar, r.cigar_len);
-            } else if (!o->md) S.nm[i] = merge_cigar_nm(r.cigar, r.cigar_len, qs, qlen, t, tl, S.cig[i], &S.nops[i]);      // one pass: merged text + NM
-            else {
-                merge_cigar(r.cigar, r.cigar_len, S.ops[i]);
-                join_ops(S.ops[i], S.cig[i]);
-                S.nops[i] = (int64_t)S.ops[i].op.size();
-                int64_t qa = r.q_st < 0 ? 0 : (r.q_st > qlen ? qlen : r.q_st), qb = r.q_en < 0 ? 0 : (r.q_en > qlen ? qlen : r.q_en); if (qb < qa) qb = qa;
-                md_cs(S.ops[i], t, tl, qs + qa, qb - qa, o->shortcs != 0, S.md[i], S.cs[i]);
-                S.nm[i] = o->asm_mode ? nm_asm_text(r.cigar, r.cigar_len) : nm_from_cigar(S.ops[i], qs + qa, qb - qa, t, tl);
-            }
-            if (o->fakecigar) fake_cigar(r, qlen, clip, S.fake[i]);
-        }
         int lines = 0;
         const size_t primary = (o->asm_mode && n > 1 && S.recs[0].mapq == 1 && S.recs[1].mapq != 1) ? 1 : 0;     // mammap_asm.py:22847-22850
         auto mq_out = [&](int v) { return o->asm_mode ? (v != 0 ? 60 : 1) : v; };
@@ -337,21 +347,76 @@ static int emit_read(const vm_index* mi, const std::string& bases, const vm_sam_
     }
 }
 
+// ---- PAF (vacmapx.h states the rule at vm_paf_emit). alen and the cg range are read off the merged CIGAR text: alen = the lengths of its M = X I D
+// operators, cg = the text between its leading and its trailing maximal run of S / H operators ([*a, *b); empty when every operator is a clip).
+static void paf_cg_alen(const std::string& cig, size_t* a, size_t* b, int64_t* alen) {
+    size_t lead = 0, end = 0; bool body = false; int64_t num = 0, al = 0;
+    for (size_t i = 0; i < cig.size(); ++i) {
+        const char ch = cig[i];
+        if (ch >= '0' && ch <= '9') { num = num * 10 + (ch - '0'); continue; }
+        if (ch == 'S' || ch == 'H') { if (!body) lead = i + 1; }
+        else { body = true; end = i + 1; if (ch == 'M' || ch == '=' || ch == 'X' || ch == 'I' || ch == 'D') al += num; }
+        num = 0;
+    }
+    *a = body ? lead : 0; *b = body ? end : 0; *alen = al;
+}
+
+static void paf_unmapped_line(const char* name, int64_t name_len, int64_t qlen, std::string& out) {
+    out.append(name, (size_t)name_len); out.push_back('\t'); put_int(out, qlen);
+    out.append("\t0\t0\t*\t*\t0\t0\t0\t0\t0\t0\n");
+}
+
+// PAF lines of one read appended to `out`; returns the number of lines, or -1 where emit_read returns -1
+static int emit_read_paf(const vm_index* mi, const std::string& bases, const vm_sam_opts* o, const char* name, int64_t name_len, const char* query, int64_t qlen,
+                         const vm_record* rr, int64_t nr, const char* blob, Scratch& S, std::string& out) {
+    const size_t out0 = out.size();
+    try {
+        stage_read(mi, bases, o, query, qlen, rr, nr, blob, false, S);
+        const size_t n = S.recs.size();
+        for (size_t i = 0; i < n; ++i) {
+            const Rec& r = S.recs[i];
+            size_t ca, cb; int64_t alen;
+            paf_cg_alen(S.cig[i], &ca, &cb, &alen);
+            const bool fwd = r.strand == '+';
+            out.append(name, (size_t)name_len); out.push_back('\t');
+            put_int(out, qlen); out.push_back('\t');
+            put_int(out, fwd ? r.q_st : qlen - r.q_en); out.push_back('\t');
+            put_int(out, fwd ? r.q_en : qlen - r.q_st); out.push_back('\t');
+            out.push_back(r.strand); out.push_back('\t');
+            out.append(mi->names[(size_t)r.contig]); out.push_back('\t');
+            put_int(out, mi->lens[(size_t)r.contig]); out.push_back('\t');
+            put_int(out, r.r_st); out.push_back('\t');
+            put_int(out, r.r_en); out.push_back('\t');
+            put_int(out, alen - S.nm[i]); out.push_back('\t');
+            put_int(out, alen); out.push_back('\t');
+            put_int(out, o->asm_mode ? (r.mapq != 0 ? 60 : 1) : r.mapq);
+            out.append("\ttp:A:P\tNM:i:"); put_int(out, S.nm[i]);
+            if (cb > ca) { out.append("\tcg:Z:"); out.append(S.cig[i], ca, cb - ca); }
+            if (o->md) { out.append("\tMD:Z:"); out.append(S.md[i]); out.append("\tcs:Z:"); out.append(S.cs[i]); }
+            out.push_back('\n');
+        }
+        return (int)n;
+    } catch (const Raise&) {
+        out.resize(out0);
+        return -1;
+    }
+}
+
 }  // namespace
 
-extern "C" {
-
-int vm_sam_emit(const vm_index* mi, const vm_sam_opts* o, int64_t n_reads, const char* names, const int64_t* name_off, const char* seqs, const int64_t* seq_off,
+// vm_sam_emit (paf = false) and vm_paf_emit (paf = true; no quals, no comments): the same reads skipped, the same threading, the same text_off
+static int emit_text(const bool paf, const vm_index* mi, const vm_sam_opts* o, int64_t n_reads, const char* names, const int64_t* name_off, const char* seqs, const int64_t* seq_off,
                 const char* quals, const int64_t* qual_off, const char* comments, const int64_t* com_off, const vm_record* recs, int64_t n_recs, const char* cigar_blob,
                 const int32_t* status, int nthreads, char** text, int64_t** text_off, int64_t* n_lines, int64_t* n_skipped) {
+    const std::string who = paf ? "vm_paf_emit" : "vm_sam_emit";
     *text = nullptr; *text_off = nullptr; *n_lines = 0; *n_skipped = 0;
     try {
         const std::string& bases = host_bases(mi);
         // records are grouped by read_idx (ascending) as vm_align_batch returns them
         std::vector<int64_t> first((size_t)n_reads + 1, 0);
-        for (int64_t i = 0; i < n_recs; ++i) { if (recs[i].read_idx < 0 || recs[i].read_idx >= n_reads) { set_error("vm_sam_emit: record of an unknown read"); return VM_ERR_ARG; } first[(size_t)recs[i].read_idx + 1]++; }
+        for (int64_t i = 0; i < n_recs; ++i) { if (recs[i].read_idx < 0 || recs[i].read_idx >= n_reads) { set_error(who + ": record of an unknown read"); return VM_ERR_ARG; } first[(size_t)recs[i].read_idx + 1]++; }
         for (int64_t r = 0; r < n_reads; ++r) first[(size_t)r + 1] += first[(size_t)r];
-        for (int64_t i = 1; i < n_recs; ++i) if (recs[i].read_idx < recs[i - 1].read_idx) { set_error("vm_sam_emit: records must be ordered by read"); return VM_ERR_ARG; }
+        for (int64_t i = 1; i < n_recs; ++i) if (recs[i].read_idx < recs[i - 1].read_idx) { set_error(who + ": records must be ordered by read"); return VM_ERR_ARG; }
         if (nthreads < 1) nthreads = 1;
         if (nthreads > 64) nthreads = 64;
         const int64_t CH = 64;                                   // reads per work item
@@ -364,7 +429,7 @@ int vm_sam_emit(const vm_index* mi, const vm_sam_opts* o, int64_t n_reads, const
             while (true) {
                 const int64_t c = next.fetch_add(1); if (c >= nch) break;
                 std::string& out = part[(size_t)c];
-                { int64_t est = 0; for (int64_t r = c * CH; r < std::min(n_reads, (c + 1) * CH); ++r) est += 2 * (seq_off[r + 1] - seq_off[r]) + (seq_off[r + 1] - seq_off[r]) / 2 + 512; out.reserve((size_t)est); }
+                { int64_t est = 0; for (int64_t r = c * CH; r < std::min(n_reads, (c + 1) * CH); ++r) est += (paf ? 0 : 2 * (seq_off[r + 1] - seq_off[r])) + (seq_off[r + 1] - seq_off[r]) / 2 + 512; out.reserve((size_t)est); }
                 for (int64_t r = c * CH; r < std::min(n_reads, (c + 1) * CH); ++r) {
                     const size_t before = out.size();
                     const int64_t nr = first[(size_t)r + 1] - first[(size_t)r];
@@ -374,12 +439,15 @@ int vm_sam_emit(const vm_index* mi, const vm_sam_opts* o, int64_t n_reads, const
                     bool none = true;                            // the read emits no record line
                     if (status && status[r] != 0) skipped.fetch_add(1);
                     else if (nr > 0) {
-                        const int rc = emit_read(mi, bases, o, names + name_off[r], name_off[r + 1] - name_off[r], seqs + seq_off[r], seq_off[r + 1] - seq_off[r], qual, ql, com, cl,
-                                                 recs + first[(size_t)r], nr, cigar_blob, S, out);
+                        const int rc = paf ? emit_read_paf(mi, bases, o, names + name_off[r], name_off[r + 1] - name_off[r], seqs + seq_off[r], seq_off[r + 1] - seq_off[r],
+                                                           recs + first[(size_t)r], nr, cigar_blob, S, out)
+                                           : emit_read(mi, bases, o, names + name_off[r], name_off[r + 1] - name_off[r], seqs + seq_off[r], seq_off[r + 1] - seq_off[r], qual, ql, com, cl,
+                                                       recs + first[(size_t)r], nr, cigar_blob, S, out);
                         if (rc < 0) skipped.fetch_add(1); else { lines.fetch_add(rc); none = false; }
                     }
                     if (none && o->keep_unmapped) {
-                        unmapped_line(o, names + name_off[r], name_off[r + 1] - name_off[r], seqs + seq_off[r], seq_off[r + 1] - seq_off[r], qual, ql, com, cl, out);
+                        if (paf) paf_unmapped_line(names + name_off[r], name_off[r + 1] - name_off[r], seq_off[r + 1] - seq_off[r], out);
+                        else unmapped_line(o, names + name_off[r], name_off[r + 1] - name_off[r], seqs + seq_off[r], seq_off[r + 1] - seq_off[r], qual, ql, com, cl, out);
                         lines.fetch_add(1);
                     }
                     rlen[(size_t)r] = (int64_t)(out.size() - before);
@@ -404,8 +472,24 @@ int vm_sam_emit(const vm_index* mi, const vm_sam_opts* o, int64_t n_reads, const
         *n_lines = lines.load(); *n_skipped = skipped.load();
         return VM_OK;
     }
-    catch (const std::bad_alloc&) { set_error("vm_sam_emit: out of host memory"); return VM_ERR_OOM; }
-    catch (const std::exception& e) { set_error(std::string("vm_sam_emit: ") + e.what()); return VM_ERR_ARG; }
+    catch (const std::bad_alloc&) { set_error(who + ": out of host memory"); return VM_ERR_OOM; }
+    catch (const std::exception& e) { set_error(who + ": " + e.what()); return VM_ERR_ARG; }
+}
+
+extern "C" {
+
+int vm_sam_emit(const vm_index* mi, const vm_sam_opts* o, int64_t n_reads, const char* names, const int64_t* name_off, const char* seqs, const int64_t* seq_off,
+                const char* quals, const int64_t* qual_off, const char* comments, const int64_t* com_off, const vm_record* recs, int64_t n_recs, const char* cigar_blob,
+                const int32_t* status, int nthreads, char** text, int64_t** text_off, int64_t* n_lines, int64_t* n_skipped) {
+    return emit_text(false, mi, o, n_reads, names, name_off, seqs, seq_off, quals, qual_off, comments, com_off, recs, n_recs, cigar_blob, status, nthreads, text, text_off,
+                     n_lines, n_skipped);
+}
+
+int vm_paf_emit(const vm_index* mi, const vm_sam_opts* o, int64_t n_reads, const char* names, const int64_t* name_off, const char* seqs, const int64_t* seq_off,
+                const vm_record* recs, int64_t n_recs, const char* cigar_blob, const int32_t* status, int nthreads, char** text, int64_t** text_off, int64_t* n_lines,
+                int64_t* n_skipped) {
+    return emit_text(true, mi, o, n_reads, names, name_off, seqs, seq_off, nullptr, nullptr, nullptr, nullptr, recs, n_recs, cigar_blob, status, nthreads, text, text_off,
+                     n_lines, n_skipped);
 }
 
 // out = the entries idx[0..n) of a blob (offsets off) back to back, out_off[n + 1]; out must hold the sum of their lengths (the

@@ -47,12 +47,15 @@ __global__ void k_sam_ops(vmx_sam_in A, vmx_sam_work K, int write);
 __global__ void k_sam_lines(vmx_sam_in A, vmx_sam_work K, char* text, int write);
 __global__ void k_sam_unmapped(vmx_sam_in A, vmx_sam_work K, char* text, int write);
 __global__ void k_sam_text_off(vmx_sam_in A, vmx_sam_work K, int64_t* text_off);
+// k_paf.hip. pinfo: per emitted position (cg begin, cg end, alen), stored by the size pass and loaded by the write pass
+__global__ void k_paf_lines(vmx_sam_in A, vmx_sam_work K, int64_t* pinfo, char* text, int write);
 
 // grow-only buffers of a context's device emitter
 struct vmx_sam_bufs {
     vmx::DevBuf names, name_off, seqs, seq_off, quals, qual_off, comments, com_off, recs, cigars, status, rg;
     vmx::DevBuf cnt, first, keep, ord, mq, flag, rflag, ri, tsz, toff, scratch, lsz, loff, res, tmp;
     vmx::DevBuf text, text_off;
+    vmx::DevBuf pinfo;                                                              // PAF: three int64 per emitted position (k_paf_lines)
     vmx::DevBuf cnames, cname_off; uint64_t names_of = 0;                           // the contig-name blob and the serial of the index it was made for (vm_index.serial: never 0)
     std::string h_cnames; std::vector<int64_t> h_cname_off;
     double s_upload = 0, s_kernel = 0, s_download = 0;                              // wall seconds of the last call by phase
@@ -61,6 +64,7 @@ struct vmx_sam_totals { int64_t text_bytes, n_lines, n_skipped; };
 
 // The emitter on device pointers: `in` complete but for cnames / cname_off (taken from the context's blob for `mi`). The text lands in S->text
 // (tot->text_bytes bytes), the per-read offsets in S->text_off (n_reads + 1). Two host waits; the caller fetches what it wants and waits once more.
-int vmx_sam_emit_dev(vm_ctx* c, const struct vm_index* mi, vmx_sam_in in, vmx_sam_totals* tot);
+// paf: the lines are PAF lines (k_paf_lines in the place of k_sam_lines and k_sam_unmapped; `in` without qualities, comments and rg).
+int vmx_sam_emit_dev(vm_ctx* c, const struct vm_index* mi, vmx_sam_in in, vmx_sam_totals* tot, bool paf = false);
 vmx_sam_bufs* vmx_ctx_sam_bufs(vm_ctx* c);
 #endif

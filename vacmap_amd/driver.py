@@ -11,7 +11,8 @@ reader (vm_fastx_read) fills blobs, `vacmap_amd.pipeline` cuts windows of `--win
 batches, several batches are in flight, each worker thread aligns its batch on the GPU (vm_align_batch) and turns the records into SAM
 text with `-t` host threads (vm_sam_emit, the C++ twin of vacmap_amd/sam.py) while the other batches align; every window is written
 in input order. Like the reference's worker (:24116-24134) a read whose path or whose emission raises is skipped, and a read without
-records produces no line.
+records produces no line. `-o out.paf` writes PAF lines instead (vm_paf_emit / vm_paf_emit_device, vacmap_amd/paf.py: one line where a .sam run
+writes a record line, no header) on every text path a .sam takes.
 With N ranks, rank 0 builds the index and broadcasts it over RCCL (vacmap_amd/dist.py), batch i of a window goes to rank i mod N, and
 rank 0 gathers and writes the lines. `-mode asm` (assembly contigs; contig c -> rank c mod N): the contigs go through vm_align_batch with VM_MODE_ASM in
 groups, in input order, and their lines come from the native emitter in its asm form (vm_sam_opts.asm_mode = iterator_get_bam_dict_str,
@@ -627,8 +628,11 @@ def _parse_args(argv, comm, sw):
         _bam_tag_select(args.bam_tags)
     except ValueError as e:
         sys.exit(str(e))
-    if args.o != '-' and not (args.o.endswith('.sam') or args.o.endswith('.bam')):
-        sys.exit("Output path must end with .sam, .bam, .sorted.bam, or be '-' for stdout.")
+    if args.o != '-' and not (args.o.endswith('.sam') or args.o.endswith('.bam') or args.o.endswith('.paf')):
+        sys.exit("Output path must end with .sam, .paf, .bam, .sorted.bam, or be '-' for stdout.")
+    args.paf = args.o.endswith('.paf')                  # PAF lines (vm_paf_emit / vm_paf_emit_device) on every text path a .sam takes; no header
+    if args.paf and (args.copycomments or args.bam_tags):
+        sys.exit('%s cannot be written to %s: a PAF line carries no comment fields; write .sam or .bam, or drop the option' % ('--copycomments' if args.copycomments else '--bam-tags', args.o))
     if args.keep_unmapped and args.mode == 'asm':
         sys.exit('--keep-unmapped is for the read modes H, L, S and R: -mode asm takes whole contigs, which nobody wants as unmapped records')
     args.native_bam = args.bam_writer in ('native', 'native-sort') and args.o.endswith('.bam')
@@ -724,9 +728,9 @@ def _sharding(args, net):
     """stage 5: True for range mode (every rank parses its own byte range of each input and writes its own part of the SAM file), False for
     the batch scheme (every rank parses everything and keeps every N-th batch, rank 0 gathers the text)"""
     plain = all(_is_plain_fastx(pth) for grp in args.read for pth in grp)
-    range_mode = net.world > 1 and args.mode != 'asm' and args.shard != 'batch' and plain and args.o.endswith('.sam')
+    range_mode = net.world > 1 and args.mode != 'asm' and args.shard != 'batch' and plain and (args.o.endswith('.sam') or args.paf)
     if net.world > 1 and args.shard == 'range' and not range_mode:
-        sys.exit('--shard range needs uncompressed FASTA / FASTQ input and a .sam output path')
+        sys.exit('--shard range needs uncompressed FASTA / FASTQ input and a .sam or .paf output path')
     if range_mode:
         # every rank writes <out>.partNNN and rank 0 joins them: they must land in one directory. Ranks on several hosts only see each other's
         # parts on a shared file system — nothing here can check that, so `auto` falls back to the batch scheme (text gathered over gloo) and an
@@ -804,7 +808,7 @@ def _text_sink(path):
     """'-' / .sam: text; .bam / .sorted.bam: a `samtools view -b` / `samtools sort --write-index` pipe (output_functions.py:200-208)"""
     if path == '-':
         return sys.stdout.buffer, None
-    if path.endswith('.sam'):
+    if path.endswith('.sam') or path.endswith('.paf'):
         return open(path, 'w+b'), None
     if not shutil.which('samtools'):
         sys.exit('writing %s needs the samtools binary on PATH (the reference pipes SAM text into it too); write .sam instead' % path)
@@ -831,7 +835,7 @@ def _open_output(args, net, range_mode, index, rg, argv, device):
             else:
                 if not range_mode:
                     out.sink, out.proc = _text_sink(args.o)
-                for ln in head:
+                for ln in ([] if args.paf else head):            # (PAF has no header)
                     out.write(ln.encode() + b'\n')
         yield out
     except BaseException:
@@ -892,7 +896,7 @@ def _run_asm(args, net, lib, ctx, index, prm, opts, out, device, t_start):
     the GPU) and their SAM lines written in input order. A contig the reference would skip (raised) is logged and skipped.
     With N ranks every rank parses the input, contig c of it goes to rank c mod N (contigs are independent: no data-path collective), and
     rank 0 gathers each group's lines and writes them in input order. Returns the final stderr line as _finish takes it."""
-    from .lib import align_batch_raw, sam_emit, sam_emit_device, VmxError
+    from .lib import align_batch_raw, sam_emit, sam_emit_device, paf_emit, paf_emit_device, VmxError
     world, rank = net.world, net.rank
     on_device = [_device_emitter_wanted(args, rank)]
     with_c = args.copycomments or bool(args.bam_tags)
@@ -917,14 +921,19 @@ def _run_asm(args, net, lib, ctx, index, prm, opts, out, device, t_start):
             if on_device[0]:                                                                # --sam-emitter device: on the run's own context
                 try:
                     dev_c = with_c and args.sam_emitter == 'device-comments'
-                    text, toff, _, ns = sam_emit_device(ctx, index, opts, nb, no, sb, so, raw, quals=qb, qual_off=qo, comments=cb if dev_c else None,
-                                                        com_off=co if dev_c else None)
+                    if args.paf:
+                        text, toff, _, ns = paf_emit_device(ctx, index, opts, nb, no, sb, so, raw)
+                    else:
+                        text, toff, _, ns = sam_emit_device(ctx, index, opts, nb, no, sb, so, raw, quals=qb, qual_off=qo, comments=cb if dev_c else None,
+                                                            com_off=co if dev_c else None)
                 except VmxError as e:
                     if e.code != VM_ERR_UNSUPPORTED:
                         raise
                     on_device[0] = False
                     _device_emitter_given_up(str(e), rank)
-            if text is None:
+            if text is None and args.paf:
+                text, toff, _, ns = paf_emit(lib, index, opts, nb, no, sb, so, raw, nthreads=max(1, args.t))
+            elif text is None:
                 text, toff, _, ns = sam_emit(lib, index, opts, nb, no, sb, so, raw, quals=qb, qual_off=qo, comments=cb if with_c else None,
                                              com_off=co if with_c else None, nthreads=max(1, args.t))
             for x, g in enumerate(share):
@@ -969,7 +978,7 @@ def _run_asm(args, net, lib, ctx, index, prm, opts, out, device, t_start):
                         flush(group); group, gbases = [], 0
     if group:
         flush(group)
-    return lambda tail: 'vacmapx: %d contigs, %d SAM lines, %d contigs skipped, %.1f s%s\n' % (n_contigs, n_lines, n_skipped, max(time.time() - t_start, 0.001), tail)
+    return lambda tail: 'vacmapx: %d contigs, %d %s lines, %d contigs skipped, %.1f s%s\n' % (n_contigs, n_lines, 'PAF' if args.paf else 'SAM', n_skipped, max(time.time() - t_start, 0.001), tail)
 
 
 class Window:
@@ -1154,6 +1163,9 @@ class ReadStream:
         raw = self.V.align_batch_raw(self.pipe.ctxs[0], self.index, self.prm, sb, so)
         try:
             for ecx in self.emit_ctxs:
+                if self.args.paf:
+                    self.V.paf_emit_device(ecx, self.index, self.opts, nb, no, sb, so, raw)
+                    continue
                 self.V.sam_emit_device(ecx, self.index, self.opts, nb, no, sb, so, raw, quals=np.full(int(so[-1]), ord('I'), np.uint8) if has_q else None, qual_off=so if has_q else None)
         except self.V.VmxError as e:
             if e.code != VM_ERR_UNSUPPORTED:
@@ -1362,14 +1374,20 @@ class ReadStream:
             if self.emit_device:
                 try:
                     dev_c = self.emit_comments and cb is not None
-                    text, toff, nl, ns = self.V.sam_emit_device(self.emit_context(), self.index, self.opts, nb, no, sb, so, raw, quals=qb, qual_off=qo,
-                                                                comments=cb if dev_c else None, com_off=co if dev_c else None)
+                    if self.args.paf:
+                        text, toff, nl, ns = self.V.paf_emit_device(self.emit_context(), self.index, self.opts, nb, no, sb, so, raw)
+                    else:
+                        text, toff, nl, ns = self.V.sam_emit_device(self.emit_context(), self.index, self.opts, nb, no, sb, so, raw, quals=qb, qual_off=qo,
+                                                                    comments=cb if dev_c else None, com_off=co if dev_c else None)
                 except self.V.VmxError as e:
                     if e.code != VM_ERR_UNSUPPORTED:
                         raise
                     self.give_up_device(str(e))
             if text is None:
                 self.drop_emit_context()
+            if text is None and self.args.paf:
+                text, toff, nl, ns = self.V.paf_emit(self.lib, self.index, self.opts, nb, no, sb, so, raw, nthreads=self.emit_threads)
+            elif text is None:
                 text, toff, nl, ns = self.V.sam_emit(self.lib, self.index, self.opts, nb, no, sb, so, raw, quals=qb, qual_off=qo, comments=cb, com_off=co, nthreads=self.emit_threads)
             if self.args.debug and ns:                  # the reference's per-read failure log (--debug, mammap_clrnano.py:24120-24123)
                 nbb = nb.tobytes() if hasattr(nb, 'tobytes') else bytes(nb)
@@ -1495,7 +1513,7 @@ class ReadStream:
         """the final stderr lines (vacmap:535-541)"""
         tt, c = max(time.time() - self.t0, 0.001), self.counts
         return ('User time (h:m:s): %d:%d:%d %d / sec AVG. %d sequences processed.\n' % (tt // 3600, (tt % 3600) // 60, tt % 60, round(c['reads'] / tt), c['reads'])
-                + 'vacmapx: %d reads, %d SAM lines, %d reads skipped%s\n' % (c['reads'], c['lines'], c['skipped'], tail))
+                + 'vacmapx: %d reads, %d %s lines, %d reads skipped%s\n' % (c['reads'], c['lines'], 'PAF' if self.args.paf else 'SAM', c['skipped'], tail))
 
 
 def main(argv=None, comm=None):

@@ -182,6 +182,8 @@ class VmxLib:
         L.vm_sam_emit_device.argtypes = [vp, vp, P(SamOpts), i64, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, P(vp), P(P(i64)), P(i64), P(i64)]
         L.vm_sam_emit_device_comments.argtypes = [vp, vp, P(SamOpts), i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, P(vp), P(P(i64)), P(i64), P(i64)]
         L.vm_sam_emit_device_times.argtypes = [vp, P(dbl)]
+        L.vm_paf_emit.argtypes = [vp, P(SamOpts), i64, vp, vp, vp, vp, vp, i64, vp, vp, C.c_int, P(vp), P(P(i64)), P(i64), P(i64)]
+        L.vm_paf_emit_device.argtypes = [vp, vp, P(SamOpts), i64, vp, vp, vp, vp, vp, i64, vp, vp, P(vp), P(P(i64)), P(i64), P(i64)]
         L.vm_blob_gather.argtypes = [vp, vp, vp, i64, vp, vp]; L.vm_blob_gather.restype = i64
         L.vm_blob_write_parts.argtypes = [C.c_int, vp, vp, vp, vp, i64]; L.vm_blob_write_parts.restype = i64
         L.vm_pinned_alloc.argtypes = [i64, C.c_int]; L.vm_pinned_alloc.restype = vp
@@ -569,6 +571,38 @@ def sam_emit_device(ctx, index, opts, names, name_off, seqs, seq_off, raw, quals
     else:
         cm = _u8(comments) if comments is not None else None; co = np.ascontiguousarray(com_off, dtype=np.int64) if com_off is not None else None
         lib.check(lib.L.vm_sam_emit_device_comments(*head, cm.ctypes.data if cm is not None and len(cm) else None, co.ctypes.data if co is not None else None, *tail))
+    off = np.ctypeslib.as_array(toff, shape=(n + 1,)).copy()
+    lib.L.vm_free(toff)
+    buf = _OwnedText(lib, text, int(off[-1]))
+    return buf.array, off, nl.value, ns.value
+
+
+def paf_emit(lib, index, opts, names, name_off, seqs, seq_off, raw, nthreads=8):
+    """PAF lines of a batch (vm_paf_emit; the rule: include/vacmapx.h): sam_emit's return tuple. One line where sam_emit writes a record line."""
+    names = _u8(names); seqs = _u8(seqs)
+    name_off = np.ascontiguousarray(name_off, dtype=np.int64); seq_off = np.ascontiguousarray(seq_off, dtype=np.int64)
+    n = len(seq_off) - 1
+    text = C.c_void_p(); toff = C.POINTER(C.c_int64)(); nl = C.c_int64(); ns = C.c_int64()
+    lib.check(lib.L.vm_paf_emit(index.h, C.byref(opts), n, names.ctypes.data, name_off.ctypes.data, seqs.ctypes.data, seq_off.ctypes.data,
+                                C.cast(raw.recs, C.c_void_p), raw.nrec, raw.blob, raw.status.ctypes.data if len(raw.status) else None, int(nthreads),
+                                C.byref(text), C.byref(toff), C.byref(nl), C.byref(ns)))
+    off = np.ctypeslib.as_array(toff, shape=(n + 1,)).copy()
+    lib.L.vm_free(toff)
+    buf = _OwnedText(lib, text, int(off[-1]))
+    return buf.array, off, nl.value, ns.value
+
+
+def paf_emit_device(ctx, index, opts, names, name_off, seqs, seq_off, raw):
+    """PAF lines of a batch made on the GPU (vm_paf_emit_device, on the context's stream): paf_emit's return tuple, byte for byte; a reference
+    with letters other than ACGTN raises VmxError(VM_ERR_UNSUPPORTED)."""
+    lib = ctx.lib
+    names = _u8(names); seqs = _u8(seqs)
+    name_off = np.ascontiguousarray(name_off, dtype=np.int64); seq_off = np.ascontiguousarray(seq_off, dtype=np.int64)
+    n = len(seq_off) - 1
+    text = C.c_void_p(); toff = C.POINTER(C.c_int64)(); nl = C.c_int64(); ns = C.c_int64()
+    lib.check(lib.L.vm_paf_emit_device(ctx.h, index.h, C.byref(opts), n, names.ctypes.data, name_off.ctypes.data, seqs.ctypes.data, seq_off.ctypes.data,
+                                       C.cast(raw.recs, C.c_void_p), raw.nrec, raw.blob, raw.status.ctypes.data if len(raw.status) else None,
+                                       C.byref(text), C.byref(toff), C.byref(nl), C.byref(ns)))
     off = np.ctypeslib.as_array(toff, shape=(n + 1,)).copy()
     lib.L.vm_free(toff)
     buf = _OwnedText(lib, text, int(off[-1]))
