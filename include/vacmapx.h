@@ -420,6 +420,56 @@ int vm_paf_emit(const vm_index*, const vm_sam_opts*, int64_t n_reads, const char
 int vm_paf_emit_device(vm_ctx*, const vm_index*, const vm_sam_opts*, int64_t n_reads, const char* names, const int64_t* name_off, const char* seqs,
                        const int64_t* seq_off, const vm_record* recs, int64_t n_recs, const char* cigar_blob, const int32_t* status, char** text,
                        int64_t** text_off, int64_t* n_lines, int64_t* n_skipped);
+/* Per-window depth of coverage from the same records. An accumulator (vm_depth) is made for one index, a window size W >= 1 and a MAPQ threshold Q.
+ * THE RULE.
+ * Windows: contig c of length L_c has ceil(L_c / W) windows, window j covers [jW, min((j + 1)W, L_c)); the windows of all contigs are concatenated in
+ * index order and win_off[nseq + 1] delimits each contig's windows (a contig of length 0 has none).
+ * Which records count: a record contributes exactly when vm_sam_emit writes a record line for it for the same inputs and options (a read with a status
+ * other than 0, a read without records and a read whose emission raises contribute nothing) and the number that line prints in its MAPQ column (after
+ * reassign_mapq under markunbalancetra; asm_mode's 60 / 1) is >= Q.
+ * What a record contributes: its CIGAR is walked in the order the SAM line prints it, from the 0-based contig-local r_st. M = X D N advance the reference
+ * position, I S H P do not. Every reference position under an M, = or X counts 1; positions under D and N count 0 (samtools depth without -J). Merging
+ * adjacent operators changes nothing, so an implementation may walk the record's own text or the merged text. A position below 0 or at or beyond L_c
+ * counts nothing.
+ * Unaffected by: keep_unmapped lines count nothing; hardclip, fakecigar, cigar2cg, md, shortcs and rg_id change nothing.
+ * What accumulates: counts[w] = the number of (record, position) pairs counted inside window w, int64, summed over every call since creation. Sums of
+ * integers do not depend on order: every implementation, schedule, split of the reads into calls and number of ranks gives identical counts.
+ * Text (integers only, so every build prints the same bytes): VM_DEPTH_REGIONS is one line per window, empty ones included, contigs in index order,
+ *   TNAME \t start \t end \t mean \n
+ * VM_DEPTH_SUMMARY one line per contig,
+ *   TNAME \t length \t bases \t mean \n
+ * (bases = the sum of the contig's counts, mean taken over length) and a last line "total" over all contigs. mean of (count, len) has exactly two
+ * decimals: h = (200 * count + len) div (2 * len) hundredths (half up; h = 0 when len = 0), printed as h div 100, '.', and two digits of h mod 100.
+ * vm_depth_create: with a context the counts live in that context's HBM, without one in host memory. VM_ERR_ARG for window < 1, min_mapq outside
+ * 0 .. 255 and more than 2^28 windows in all.
+ * vm_depth_add: host code on a host accumulator (VM_ERR_ARG on a device one); vm_paf_emit's arguments up to nthreads and its refusals; it shares the
+ * host emitters' per-record stage, so the raises are theirs. Threads add with atomic integer adds.
+ * vm_depth_add_device: vm_paf_emit_device's arguments up to status, on the context the accumulator was made on (VM_ERR_ARG otherwise); k_sam_count,
+ * k_sam_order and k_sam_ops as they are, then k_depth_add (k_depth.hip). No line text; n_lines and n_skipped are vm_sam_emit's. Refusals: the device SAM
+ * entry's. Two host waits.
+ * vm_ctx_attach_depth (NULL detaches): while an accumulator made on the context is attached, every vm_sam_emit_device, vm_sam_emit_device_comments and
+ * vm_paf_emit_device call on the context also launches k_depth_add behind the write pass of k_sam_ops, on the same stream: no additional host wait, no
+ * additional upload, the same returned bytes, the counts of a stand-alone vm_depth_add_device on the same inputs. The index must be the accumulator's
+ * (VM_ERR_ARG). A call refused for its arguments or records adds nothing.
+ * vm_depth_merge: dst += src for any mix of host and device accumulators; VM_ERR_ARG unless contig lengths and window agree. vm_depth_add_counts:
+ * dst += a table that vm_depth_counts returned (another process's, say); VM_ERR_ARG unless n_windows is the accumulator's.
+ * vm_depth_counts: host copies of counts[n_windows] and win_off[nseq + 1] (both vm_free). vm_depth_text: which = VM_DEPTH_REGIONS / VM_DEPTH_SUMMARY
+ * (text: vm_free, n bytes, 0-terminated); a device accumulator makes the text on the device (k_depth_sums, k_depth_lines), a host one in host code. */
+typedef struct vm_depth vm_depth;
+enum { VM_DEPTH_REGIONS = 0, VM_DEPTH_SUMMARY = 1 };
+int vm_depth_create(vm_ctx* ctx_or_null, const vm_index*, int64_t window, int min_mapq, vm_depth** out);
+void vm_depth_free(vm_depth*);
+int vm_depth_add(vm_depth*, const vm_index*, const vm_sam_opts*, int64_t n_reads, const char* names, const int64_t* name_off, const char* seqs,
+                 const int64_t* seq_off, const vm_record* recs, int64_t n_recs, const char* cigar_blob, const int32_t* status, int nthreads, int64_t* n_lines,
+                 int64_t* n_skipped);
+int vm_depth_add_device(vm_depth*, vm_ctx*, const vm_index*, const vm_sam_opts*, int64_t n_reads, const char* names, const int64_t* name_off, const char* seqs,
+                        const int64_t* seq_off, const vm_record* recs, int64_t n_recs, const char* cigar_blob, const int32_t* status, int64_t* n_lines,
+                        int64_t* n_skipped);
+int vm_ctx_attach_depth(vm_ctx*, vm_depth* depth_or_null);
+int vm_depth_merge(vm_depth* dst, vm_depth* src);
+int vm_depth_add_counts(vm_depth* dst, const int64_t* counts, int64_t n_windows);
+int vm_depth_counts(vm_depth*, int64_t** counts, int64_t** win_off, int64_t* n_windows);
+int vm_depth_text(vm_depth*, int which, char** text, int64_t* n);
 /* `mp.fastx_read(path, read_comment=)` (vacmap:445): FASTA / FASTQ, plain or gzip. vm_fastx_read returns up to max_reads records (stopping
  * early once max_bases bases are held) as blobs: names, UPPER-CASED sequences (vacmap:476), qualities (empty for FASTA), comments (header
  * text after the first blank, else tab). Returns the record count, 0 at the end of the input, or a negative vm_status. */

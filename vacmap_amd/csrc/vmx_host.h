@@ -121,6 +121,7 @@ struct vm_ctx {
     struct vmx_local_bufs* lbufs = nullptr;
     struct vmx_batch_bufs* bbufs = nullptr;
     struct vmx_sam_bufs* sbufs = nullptr;        // vmx_sam_dev.h: the device SAM emitter's buffers
+    struct vm_depth* depth = nullptr;            // vmx_depth.h: the attached depth accumulator (vm_ctx_attach_depth; not owned)
 };
 
 // With several batches in flight a batch is made of ~170 small launches (a few to a few hundred microseconds each) around a handful of long VALU-bound

@@ -9,8 +9,10 @@
 // raise in the reference (an index past a sequence end) produces no line and is counted as skipped, like the worker's except (:24127-24134);
 // under vm_sam_opts.keep_unmapped it, a read whose status is not 0 and a read without records each produce one FLAG 4 line (unmapped_line).
 // PAF text for the same records (vm_paf_emit; the rule: vacmapx.h): stage_read() below is shared by the two formats, only the line assembly differs.
+// Depth of coverage for the same records (vm_depth_add; the rule: vacmapx.h): stage_read() again, then a walk over each counted record's merged CIGAR.
 // No device code in this file.
 #include "vmx_index_priv.h"
+#include "vmx_depth.h"
 #include <atomic>
 #include <cstdio>
 #include <cstring>
@@ -402,6 +404,39 @@ static int emit_read_paf(const vm_index* mi, const std::string& bases, const vm_
     }
 }
 
+// ---- depth of coverage (vacmapx.h states the rule at vm_depth_add): the records of one read added to the window table; returns the number of record
+// lines the read emits, or -1 where emit_read returns -1 (nothing added then: the stage runs before the first add)
+static void depth_add_run(int64_t* counts, int64_t W, int64_t s, int64_t e) {      // [s, e) inside the contig, counts = the contig's first window
+    int64_t w = s / W;
+    while (s < e) {
+        const int64_t stop = std::min(e, (w + 1) * W);
+        __atomic_fetch_add(&counts[w], stop - s, __ATOMIC_RELAXED);
+        s = stop; ++w;
+    }
+}
+static int depth_add_read(vm_depth* d, const vm_index* mi, const std::string& bases, const vm_sam_opts* o, const char* query, int64_t qlen, const vm_record* rr, int64_t nr,
+                          const char* blob, Scratch& S) {
+    try {
+        stage_read(mi, bases, o, query, qlen, rr, nr, blob, false, S);
+        for (size_t i = 0; i < S.recs.size(); ++i) {
+            const Rec& r = S.recs[i];
+            if ((o->asm_mode ? (r.mapq != 0 ? 60 : 1) : r.mapq) < d->min_mapq) continue;
+            const int64_t L = d->lens[(size_t)r.contig];
+            int64_t* counts = d->h_counts.data() + d->win_off[(size_t)r.contig];
+            const std::string& cig = S.cig[i];
+            int64_t pos = r.r_st, num = 0;
+            for (size_t k = 0; k < cig.size(); ++k) {
+                const char ch = cig[k];
+                if (ch >= '0' && ch <= '9') { num = num * 10 + (ch - '0'); continue; }
+                if (ch == 'M' || ch == '=' || ch == 'X') { const int64_t a = std::max<int64_t>(pos, 0), b = std::min(pos + num, L); if (a < b) depth_add_run(counts, d->window, a, b); }
+                if (ch == 'M' || ch == '=' || ch == 'X' || ch == 'D' || ch == 'N') pos += num;
+                num = 0;
+            }
+        }
+        return (int)S.recs.size();
+    } catch (const Raise&) { return -1; }
+}
+
 }  // namespace
 
 // vm_sam_emit (paf = false) and vm_paf_emit (paf = true; no quals, no comments): the same reads skipped, the same threading, the same text_off
@@ -490,6 +525,54 @@ int vm_paf_emit(const vm_index* mi, const vm_sam_opts* o, int64_t n_reads, const
                 int64_t* n_skipped) {
     return emit_text(true, mi, o, n_reads, names, name_off, seqs, seq_off, nullptr, nullptr, nullptr, nullptr, recs, n_recs, cigar_blob, status, nthreads, text, text_off,
                      n_lines, n_skipped);
+}
+
+// the reads' records added to a host accumulator: emit_text's validation, skips, threading and counters without any text
+int vm_depth_add(vm_depth* d, const vm_index* mi, const vm_sam_opts* o, int64_t n_reads, const char* names, const int64_t* name_off, const char* seqs, const int64_t* seq_off,
+                 const vm_record* recs, int64_t n_recs, const char* cigar_blob, const int32_t* status, int nthreads, int64_t* n_lines, int64_t* n_skipped) {
+    (void)names; (void)name_off;
+    if (n_lines) *n_lines = 0;
+    if (n_skipped) *n_skipped = 0;
+    if (!d || !mi || !o || !n_lines || !n_skipped || n_reads < 0 || n_recs < 0 || !seq_off || (n_recs && (!recs || !cigar_blob))) { set_error("vm_depth_add: bad arguments"); return VM_ERR_ARG; }
+    if (d->ctx) { set_error("vm_depth_add: the accumulator lives on a device (vm_depth_add_device adds to it)"); return VM_ERR_ARG; }
+    if (d->index_serial != mi->serial) { set_error("vm_depth_add: the accumulator was made for another index"); return VM_ERR_ARG; }
+    try {
+        const std::string& bases = host_bases(mi);
+        std::vector<int64_t> first((size_t)n_reads + 1, 0);
+        for (int64_t i = 0; i < n_recs; ++i) {
+            if (recs[i].read_idx < 0 || recs[i].read_idx >= n_reads) { set_error("vm_depth_add: record of an unknown read"); return VM_ERR_ARG; }
+            if (i && recs[i].read_idx < recs[i - 1].read_idx) { set_error("vm_depth_add: records must be ordered by read"); return VM_ERR_ARG; }
+            if (recs[i].contig < 0 || recs[i].contig >= (int64_t)mi->names.size() || recs[i].cigar_off < 0 || recs[i].cigar_len < 0) { set_error("vm_depth_add: record of an unknown contig or with a negative CIGAR range"); return VM_ERR_ARG; }
+            first[(size_t)recs[i].read_idx + 1]++;
+        }
+        for (int64_t r = 0; r < n_reads; ++r) first[(size_t)r + 1] += first[(size_t)r];
+        if (nthreads < 1) nthreads = 1;
+        if (nthreads > 64) nthreads = 64;
+        const int64_t CH = 64, nch = (n_reads + CH - 1) / CH;
+        std::atomic<int64_t> next(0), lines(0), skipped(0);
+        auto work = [&]() {
+            Scratch S;
+            while (true) {
+                const int64_t c = next.fetch_add(1); if (c >= nch) break;
+                for (int64_t r = c * CH; r < std::min(n_reads, (c + 1) * CH); ++r) {
+                    const int64_t nr = first[(size_t)r + 1] - first[(size_t)r];
+                    bool none = true;
+                    if (status && status[r] != 0) skipped.fetch_add(1);
+                    else if (nr > 0) {
+                        const int rc = depth_add_read(d, mi, bases, o, seqs + seq_off[r], seq_off[r + 1] - seq_off[r], recs + first[(size_t)r], nr, cigar_blob, S);
+                        if (rc < 0) skipped.fetch_add(1); else { lines.fetch_add(rc); none = false; }
+                    }
+                    if (none && o->keep_unmapped) lines.fetch_add(1);
+                }
+            }
+        };
+        if (nthreads == 1 || nch <= 1) work();
+        else { std::vector<std::thread> th; for (int t = 0; t < nthreads && t < nch; ++t) th.emplace_back(work); for (auto& t : th) t.join(); }
+        *n_lines = lines.load(); *n_skipped = skipped.load();
+        return VM_OK;
+    }
+    catch (const std::bad_alloc&) { set_error("vm_depth_add: out of host memory"); return VM_ERR_OOM; }
+    catch (const std::exception& e) { set_error(std::string("vm_depth_add: ") + e.what()); return VM_ERR_ARG; }
 }
 
 // out = the entries idx[0..n) of a blob (offsets off) back to back, out_off[n + 1]; out must hold the sum of their lengths (the

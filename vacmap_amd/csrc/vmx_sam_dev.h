@@ -65,6 +65,8 @@ struct vmx_sam_totals { int64_t text_bytes, n_lines, n_skipped; };
 // The emitter on device pointers: `in` complete but for cnames / cname_off (taken from the context's blob for `mi`). The text lands in S->text
 // (tot->text_bytes bytes), the per-read offsets in S->text_off (n_reads + 1). Two host waits; the caller fetches what it wants and waits once more.
 // paf: the lines are PAF lines (k_paf_lines in the place of k_sam_lines and k_sam_unmapped; `in` without qualities, comments and rg).
-int vmx_sam_emit_dev(vm_ctx* c, const struct vm_index* mi, vmx_sam_in in, vmx_sam_totals* tot, bool paf = false);
+// dep: a depth accumulator made on c (vmx_depth.h) that k_depth_add adds the call's records to, behind the write pass of k_sam_ops; lines = false: no
+// line kernel runs and no text is made (vm_depth_add_device: tot->text_bytes = 0, n_lines and n_skipped as ever).
+int vmx_sam_emit_dev(vm_ctx* c, const struct vm_index* mi, vmx_sam_in in, vmx_sam_totals* tot, bool paf = false, struct vm_depth* dep = nullptr, bool lines = true);
 vmx_sam_bufs* vmx_ctx_sam_bufs(vm_ctx* c);
 #endif

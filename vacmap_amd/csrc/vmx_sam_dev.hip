@@ -3,7 +3,9 @@
 // block). Three host waits per call: the operator pass's sizes, the lines' sizes, the text. Under vm_sam_opts.keep_unmapped the per-read pass
 // (k_sam_unmapped) runs beside k_sam_lines on both sides of wait 2 and adds no wait; it runs in a batch without records too.
 // vm_paf_emit_device is the same call with k_paf_lines (k_paf.hip) in the place of k_sam_lines and k_sam_unmapped: the same three waits.
-#include "vmx_sam_dev.h"
+// Depth of coverage (vmx_depth.h): while an accumulator is attached to the context, each of these calls launches k_depth_add behind the write pass of
+// k_sam_ops (no wait, no upload of its own); vm_depth_add_device is the call without line kernels and without text: two waits.
+#include "vmx_depth.h"
 #include "vmx_index_priv.h"
 
 using namespace vmx;
@@ -41,7 +43,7 @@ int contig_names(vm_ctx* c, vmx_sam_bufs* S, const vm_index* mi) {
 
 }  // namespace
 
-int vmx_sam_emit_dev(vm_ctx* c, const vm_index* mi, vmx_sam_in A, vmx_sam_totals* tot, bool paf) {
+int vmx_sam_emit_dev(vm_ctx* c, const vm_index* mi, vmx_sam_in A, vmx_sam_totals* tot, bool paf, vm_depth* dep, bool lines) {
     vmx_sam_bufs* S = vmx_ctx_sam_bufs(c);
     tot->text_bytes = 0; tot->n_lines = 0; tot->n_skipped = 0;
     const int64_t n = A.n_reads, m = A.n_recs, ns = vmx_sam_slots(A);    // reads, records, line slots
@@ -74,12 +76,13 @@ int vmx_sam_emit_dev(vm_ctx* c, const vm_index* mi, vmx_sam_in A, vmx_sam_totals
     VMX_TRY(vmx_scan64(c, S->tmp, K.tsz, K.toff, (size_t)m + 1));
     VMX_TRY(vmx_fetch(c, &h_tot, K.toff + m, 1)); VMX_TRY(vmx_fetch(c, h_res, K.res, 1));
     VMX_TRY(wait(c));                                                    // wait 1: the operator pass's sizes
-    if (h_res[0] & VMX_SAM_E_RECORD) { set_error(std::string(paf ? "vm_paf_emit_device" : "vm_sam_emit_device") + ": a record names no read or no contig, lies outside the CIGAR blob, or the records are not ordered by read"); return VM_ERR_ARG; }
-    if (h_res[0] & VMX_SAM_E_COUNT) { set_error(std::string(paf ? "vm_paf_emit_device" : "vm_sam_emit_device") + ": a CIGAR operator count of 2^31 or more"); return VM_ERR_ARG; }
+    if (h_res[0] & VMX_SAM_E_RECORD) { set_error(std::string(!lines ? "vm_depth_add_device" : paf ? "vm_paf_emit_device" : "vm_sam_emit_device") + ": a record names no read or no contig, lies outside the CIGAR blob, or the records are not ordered by read"); return VM_ERR_ARG; }
+    if (h_res[0] & VMX_SAM_E_COUNT) { set_error(std::string(!lines ? "vm_depth_add_device" : paf ? "vm_paf_emit_device" : "vm_sam_emit_device") + ": a CIGAR operator count of 2^31 or more"); return VM_ERR_ARG; }
     VMX_TRY(S->scratch.reserve((size_t)h_tot + 16));
     K.scratch = S->scratch.as<char>();
     if (m) hipLaunchKernelGGL(k_sam_ops, dim3((unsigned)m), dim3(64), 0, st, A, K, 1);
-    if (paf) { if (paf_grid) hipLaunchKernelGGL(k_paf_lines, dim3(paf_grid), dim3(64), 0, st, A, K, pinfo, (char*)nullptr, 0); }
+    if (!lines) {}
+    else if (paf) { if (paf_grid) hipLaunchKernelGGL(k_paf_lines, dim3(paf_grid), dim3(64), 0, st, A, K, pinfo, (char*)nullptr, 0); }
     else {
         if (m) hipLaunchKernelGGL(k_sam_lines, dim3((unsigned)m), dim3(64), 0, st, A, K, (char*)nullptr, 0);
         if (unm) hipLaunchKernelGGL(k_sam_unmapped, dim3((unsigned)n), dim3(64), 0, st, A, K, (char*)nullptr, 0);      // (rflag: the size pass of k_sam_ops, before wait 1)
@@ -90,7 +93,10 @@ int vmx_sam_emit_dev(vm_ctx* c, const vm_index* mi, vmx_sam_in A, vmx_sam_totals
     VMX_TRY(vmx_fetch(c, &h_tot, K.loff + ns, 1)); VMX_TRY(vmx_fetch(c, h_res, K.res, 3));
     VMX_TRY(wait(c));                                                    // wait 2: the lines' sizes
     VMX_TRY(S->text.reserve((size_t)h_tot + 16));
-    if (paf) { if (paf_grid) hipLaunchKernelGGL(k_paf_lines, dim3(paf_grid), dim3(64), 0, st, A, K, pinfo, S->text.as<char>(), 1); }
+    // depth: queued once nothing but the runtime can fail the call any more; it reads what k_sam_order and both passes of k_sam_ops stored
+    if (dep && m) hipLaunchKernelGGL(k_depth_add, dim3((unsigned)m), dim3(64), 0, st, A, K, dep->dev());
+    if (!lines) {}
+    else if (paf) { if (paf_grid) hipLaunchKernelGGL(k_paf_lines, dim3(paf_grid), dim3(64), 0, st, A, K, pinfo, S->text.as<char>(), 1); }
     else {
         if (m) hipLaunchKernelGGL(k_sam_lines, dim3((unsigned)m), dim3(64), 0, st, A, K, S->text.as<char>(), 1);
         if (unm) hipLaunchKernelGGL(k_sam_unmapped, dim3((unsigned)n), dim3(64), 0, st, A, K, S->text.as<char>(), 1);
@@ -100,9 +106,9 @@ int vmx_sam_emit_dev(vm_ctx* c, const vm_index* mi, vmx_sam_in A, vmx_sam_totals
     return 0;
 }
 
-// vm_sam_emit_device_comments (paf = false) and vm_paf_emit_device (paf = true: no qualities, no comments, no RG): validation, uploads, the passes,
-// the text's way back
-static int emit_device(const bool paf, vm_ctx* c, const vm_index* mi, const vm_sam_opts* o, int64_t n_reads, const char* names, const int64_t* name_off, const char* seqs,
+// vm_sam_emit_device_comments (kind 0), vm_paf_emit_device (kind 1: no qualities, no comments, no RG) and vm_depth_add_device (kind 2: as kind 1, adds
+// to dep, no lines and no text): validation, uploads, the passes, the text's way back. Kinds 0 and 1 add to the context's attached accumulator.
+static int emit_device(const int kind, vm_depth* dep, vm_ctx* c, const vm_index* mi, const vm_sam_opts* o, int64_t n_reads, const char* names, const int64_t* name_off, const char* seqs,
                        const int64_t* seq_off, const char* quals, const int64_t* qual_off, const char* comments, const int64_t* com_off, const vm_record* recs,
                        int64_t n_recs, const char* cigar_blob, const int32_t* status, char** text, int64_t** text_off, int64_t* n_lines, int64_t* n_skipped);
 
@@ -111,8 +117,22 @@ extern "C" {
 int vm_paf_emit_device(vm_ctx* c, const vm_index* mi, const vm_sam_opts* o, int64_t n_reads, const char* names, const int64_t* name_off, const char* seqs,
                        const int64_t* seq_off, const vm_record* recs, int64_t n_recs, const char* cigar_blob, const int32_t* status, char** text, int64_t** text_off,
                        int64_t* n_lines, int64_t* n_skipped) {
-    return emit_device(true, c, mi, o, n_reads, names, name_off, seqs, seq_off, nullptr, nullptr, nullptr, nullptr, recs, n_recs, cigar_blob, status, text, text_off, n_lines,
+    return emit_device(1, nullptr, c, mi, o, n_reads, names, name_off, seqs, seq_off, nullptr, nullptr, nullptr, nullptr, recs, n_recs, cigar_blob, status, text, text_off, n_lines,
                        n_skipped);
+}
+
+int vm_depth_add_device(vm_depth* d, vm_ctx* c, const vm_index* mi, const vm_sam_opts* o, int64_t n_reads, const char* names, const int64_t* name_off, const char* seqs,
+                        const int64_t* seq_off, const vm_record* recs, int64_t n_recs, const char* cigar_blob, const int32_t* status, int64_t* n_lines, int64_t* n_skipped) {
+    if (!d) { set_error("vm_depth_add_device: no accumulator"); return VM_ERR_ARG; }
+    return emit_device(2, d, c, mi, o, n_reads, names, name_off, seqs, seq_off, nullptr, nullptr, nullptr, nullptr, recs, n_recs, cigar_blob, status, nullptr, nullptr, n_lines,
+                       n_skipped);
+}
+
+int vm_ctx_attach_depth(vm_ctx* c, vm_depth* d) {
+    if (!c) { set_error("no context"); return VM_ERR_NO_CTX; }
+    if (d && d->ctx != c) { set_error("vm_ctx_attach_depth: the accumulator was not made on this context"); return VM_ERR_ARG; }
+    c->depth = d;
+    return VM_OK;
 }
 
 int vm_sam_emit_device(vm_ctx* c, const vm_index* mi, const vm_sam_opts* o, int64_t n_reads, const char* names, const int64_t* name_off, const char* seqs,
@@ -125,25 +145,32 @@ int vm_sam_emit_device(vm_ctx* c, const vm_index* mi, const vm_sam_opts* o, int6
 int vm_sam_emit_device_comments(vm_ctx* c, const vm_index* mi, const vm_sam_opts* o, int64_t n_reads, const char* names, const int64_t* name_off, const char* seqs,
                                 const int64_t* seq_off, const char* quals, const int64_t* qual_off, const char* comments, const int64_t* com_off, const vm_record* recs,
                                 int64_t n_recs, const char* cigar_blob, const int32_t* status, char** text, int64_t** text_off, int64_t* n_lines, int64_t* n_skipped) {
-    return emit_device(false, c, mi, o, n_reads, names, name_off, seqs, seq_off, quals, qual_off, comments, com_off, recs, n_recs, cigar_blob, status, text, text_off, n_lines,
+    return emit_device(0, nullptr, c, mi, o, n_reads, names, name_off, seqs, seq_off, quals, qual_off, comments, com_off, recs, n_recs, cigar_blob, status, text, text_off, n_lines,
                        n_skipped);
 }
 
 }  // extern "C"
 
-static int emit_device(const bool paf, vm_ctx* c, const vm_index* mi, const vm_sam_opts* o, int64_t n_reads, const char* names, const int64_t* name_off, const char* seqs,
+static int emit_device(const int kind, vm_depth* dep, vm_ctx* c, const vm_index* mi, const vm_sam_opts* o, int64_t n_reads, const char* names, const int64_t* name_off, const char* seqs,
                        const int64_t* seq_off, const char* quals, const int64_t* qual_off, const char* comments, const int64_t* com_off, const vm_record* recs,
                        int64_t n_recs, const char* cigar_blob, const int32_t* status, char** text, int64_t** text_off, int64_t* n_lines, int64_t* n_skipped) {
-    const std::string who = paf ? "vm_paf_emit_device" : "vm_sam_emit_device";
+    const bool paf = kind != 0, lines = kind != 2;
+    const std::string who = kind == 2 ? "vm_depth_add_device" : paf ? "vm_paf_emit_device" : "vm_sam_emit_device";
+    char* no_text = nullptr; int64_t* no_off = nullptr;
+    if (!lines) { text = &no_text; text_off = &no_off; }
     if (text) *text = nullptr;
     if (text_off) *text_off = nullptr;
     if (n_lines) *n_lines = 0;
     if (n_skipped) *n_skipped = 0;
     if (!c) { set_error("no context"); return VM_ERR_NO_CTX; }
+    if (lines) dep = c->depth;
     if (!mi || !o || !text || !text_off || !n_lines || !n_skipped || n_reads < 0 || n_recs < 0 || !name_off || !seq_off || (n_recs && (!recs || !cigar_blob))) { set_error(who + ": bad arguments"); return VM_ERR_ARG; }
     if (mi->has_host_seq && mi->n_other_letters > 0) {
         set_error(who + ": the reference holds " + std::to_string(mi->n_other_letters) + " letters other than ACGTN, which only the host emitter (" + (paf ? "vm_paf_emit" : "vm_sam_emit") + ") prints");
         return VM_ERR_UNSUPPORTED;
+    }
+    if (dep && (dep->ctx != c || dep->index_serial != mi->serial)) {
+        set_error(who + ": the depth accumulator was made " + (dep->ctx != c ? "on another context (or in host memory)" : "for another index")); return VM_ERR_ARG;
     }
     // recs as vm_sam_emit validates them, and what keeps the kernels inside the blobs
     int64_t cig_len = 0;
@@ -189,7 +216,8 @@ static int emit_device(const bool paf, vm_ctx* c, const vm_index* mi, const vm_s
     A.rg = (o->rg_id && !paf) ? S->rg.as<const char>() : nullptr; A.rg_len = (int32_t)rg_len;
     const double t1 = now_s();
     vmx_sam_totals tot;
-    VMX_TRY(vmx_sam_emit_dev(c, mi, A, &tot, paf));
+    VMX_TRY(vmx_sam_emit_dev(c, mi, A, &tot, paf, dep, lines));
+    if (!lines) { *n_lines = tot.n_lines; *n_skipped = tot.n_skipped; return VM_OK; }      // (the counts stay on the device; nothing to fetch)
     char* h_text = (char*)malloc((size_t)tot.text_bytes + 1); int64_t* h_off = (int64_t*)malloc(8 * ((size_t)n_reads + 1));
     if (!h_text || !h_off) { free(h_text); free(h_off); set_error("out of host memory"); return VM_ERR_OOM; }
     int rc = vmx_fetch(c, h_off, S->text_off.p, (size_t)n_reads + 1);

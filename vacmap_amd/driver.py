@@ -593,6 +593,13 @@ def build_parser():
                         'unmapped record (FLAG 4, MAPQ 0, the read and its qualities as given, RG and its comment fields) at its input position, so that '
                         'every input read occurs once; the reference, and the default, drop such reads. Every emitter and writer takes it; with '
                         '--bam-writer native-sort the unmapped records come last')
+    p.add_argument('--depth', metavar='PREFIX', default=None,
+                   help='per-window depth of coverage of the records the run writes, taken while their lines are made (on the GPU under --sam-emitter device): '
+                        'PREFIX.regions.bed (contig, start, end, mean depth per window, empty windows included) and PREFIX.summary.txt (contig, length, covered '
+                        'bases, mean; a last line `total`). M, = and X columns count, D and N do not (samtools depth without -J); means have two decimals. Every '
+                        'mode, emitter and -o kind takes it')
+    p.add_argument('--depth-window', type=int, default=500, help='--depth: the window size in bases (default 500; at most 2^28 windows in all)')
+    p.add_argument('--depth-mapq', type=int, default=0, help='--depth: only records whose MAPQ column is at least this count (default 0)')
     return p
 
 
@@ -635,6 +642,8 @@ def _parse_args(argv, comm, sw):
         sys.exit('%s cannot be written to %s: a PAF line carries no comment fields; write .sam or .bam, or drop the option' % ('--copycomments' if args.copycomments else '--bam-tags', args.o))
     if args.keep_unmapped and args.mode == 'asm':
         sys.exit('--keep-unmapped is for the read modes H, L, S and R: -mode asm takes whole contigs, which nobody wants as unmapped records')
+    if args.depth is not None and (not args.depth or args.depth_window < 1 or not 0 <= args.depth_mapq <= 255):
+        sys.exit('--depth needs a file prefix, --depth-window a size of at least 1 and --depth-mapq a threshold in 0 .. 255')
     args.native_bam = args.bam_writer in ('native', 'native-sort') and args.o.endswith('.bam')
     args.native_sort = args.bam_writer == 'native-sort' and args.o.endswith('sorted.bam')
     if args.native_bam and args.o.endswith('sorted.bam') and not args.native_sort:
@@ -863,6 +872,86 @@ def _blob(parts):
 VM_ERR_UNSUPPORTED = -7
 
 
+class DepthSink:
+    """--depth PREFIX: the run's depth-of-coverage accumulators (lib.Depth; the rule: include/vacmapx.h at vm_depth_add). Under the device emitter one
+    accumulator per emit context, attached when the context makes its first text of the stream (so the sizing run's warm-up calls do not count): the
+    emit calls themselves add, on the GPU. Under the host emitter one host accumulator that the emit threads add to (vm_depth_add: atomic adds). A
+    context that is given up hands its counts to the host accumulator first. finish() merges everything, sums the ranks on rank 0 and writes
+    PREFIX.regions.bed and PREFIX.summary.txt there. Without --depth nothing is made and every method returns at once."""
+
+    def __init__(self, args, lib, index):
+        self.on = args.depth is not None
+        self.args, self.lib, self.index = args, lib, index
+        self.host, self.dev, self.lock = None, {}, threading.Lock()
+
+    def _create(self, ctx=None):
+        from .lib import Depth
+        return Depth.create(self.index, self.args.depth_window, self.args.depth_mapq, ctx=ctx, lib=self.lib)
+
+    def attach(self, ctx):
+        """before a device emit call of the stream on ctx"""
+        if self.on and id(ctx) not in self.dev:
+            d = self._create(ctx)
+            ctx.attach_depth(d)
+            with self.lock:
+                self.dev[id(ctx)] = (ctx, d)
+
+    def add_host(self, opts, nb, no, sb, so, raw, nthreads):
+        """beside a host emit call"""
+        if not self.on:
+            return
+        with self.lock:
+            if self.host is None:
+                self.host = self._create()
+        self.host.add(self.index, opts, nb, no, sb, so, raw, nthreads=nthreads)
+
+    def release(self, ctx):
+        """before ctx is closed: its accumulator's counts move to the host accumulator"""
+        with self.lock:
+            e = self.dev.pop(id(ctx), None)
+            if e is not None and self.host is None:
+                self.host = self._create()
+        if e is not None:
+            ctx.attach_depth(None)
+            with self.lock:
+                self.host.merge(e[1])
+            e[1].close()
+
+    def close(self):
+        for ctx, d in self.dev.values():
+            if ctx.h:
+                ctx.attach_depth(None)
+            d.close()
+        self.dev = {}
+        if self.host is not None:
+            self.host.close(); self.host = None
+
+    def finish(self, net):
+        """after the last emit call: one accumulator (a device one when there is any), the other ranks' tables added on rank 0, the two files"""
+        if not self.on:
+            return
+        try:
+            accs = [d for _, d in self.dev.values()] + ([self.host] if self.host is not None else [])
+            if not accs:
+                accs = [self._create()]; self.host = accs[0]
+            dst = accs[0]
+            for d in accs[1:]:
+                dst.merge(d)
+            if net.world > 1:
+                from .dist import gather_lines
+                tables = gather_lines(dst.counts()[0], dst=0, group=net.text_group)
+                if net.rank == 0:
+                    for t in tables[1:]:
+                        dst.add_counts(t)
+            if net.rank == 0:
+                with open(self.args.depth + '.regions.bed', 'wb') as f:
+                    f.write(dst.regions())
+                with open(self.args.depth + '.summary.txt', 'wb') as f:
+                    f.write(dst.summary())
+        finally:
+            self.close()
+
+
 def _carries_comments(args, path):
     """a .bam input's comments are the tags --bam-tags selected and go to the emitter with or without --copycomments; FASTA / FASTQ comments need --copycomments"""
     return bool(args.bam_tags) if path.endswith('.bam') else args.copycomments
@@ -890,7 +979,7 @@ def _device_emitter_given_up(why, rank):
         sys.stderr.write('vacmapx: the host SAM emitter is used for the whole run (%s)\n' % why)
 
 
-def _run_asm(args, net, lib, ctx, index, prm, opts, out, device, t_start):
+def _run_asm(args, net, lib, ctx, index, prm, opts, out, device, t_start, depth):
     """-mode asm (src/vacmap/vacmap:245-255, :394-411; worker mammap_asm.py:23462-23511): every input sequence is an assembly contig. --eqx is
     forced and maxdivergence set to 1 by vm_params_default(VM_MODE_ASM); contigs are aligned in groups (the long ones of a group side by side on
     the GPU) and their SAM lines written in input order. A contig the reference would skip (raised) is logged and skipped.
@@ -921,6 +1010,7 @@ def _run_asm(args, net, lib, ctx, index, prm, opts, out, device, t_start):
             if on_device[0]:                                                                # --sam-emitter device: on the run's own context
                 try:
                     dev_c = with_c and args.sam_emitter == 'device-comments'
+                    depth.attach(ctx)
                     if args.paf:
                         text, toff, _, ns = paf_emit_device(ctx, index, opts, nb, no, sb, so, raw)
                     else:
@@ -931,6 +1021,9 @@ def _run_asm(args, net, lib, ctx, index, prm, opts, out, device, t_start):
                         raise
                     on_device[0] = False
                     _device_emitter_given_up(str(e), rank)
+                    depth.release(ctx)
+            if text is None:
+                depth.add_host(opts, nb, no, sb, so, raw, max(1, args.t))
             if text is None and args.paf:
                 text, toff, _, ns = paf_emit(lib, index, opts, nb, no, sb, so, raw, nthreads=max(1, args.t))
             elif text is None:
@@ -1009,9 +1102,10 @@ class ReadStream:
     error of any thread (errs) ends all of them. run() starts and joins the threads; leaving the `with` block releases the pinned pool and the
     pipeline's contexts."""
 
-    def __init__(self, args, sw, net, lib, ctx, index, prm, opts, out, range_mode, device, t_start):
+    def __init__(self, args, sw, net, lib, ctx, index, prm, opts, out, range_mode, device, t_start, depth):
         from . import lib as V, pipeline
         self.V = V                                          # (the module, imported late: see the note at the imports)
+        self.depth = depth                                  # --depth (DepthSink)
         self.args, self.sw, self.net, self.lib, self.index, self.prm, self.opts, self.out = args, sw, net, lib, index, prm, opts, out
         self.range_mode, self.device, self.rank, self.world = range_mode, device, net.rank, net.world
         self.ramp_on = sw['VMX_DRIVER_RAMP'] and not sw['VMX_NO_WARM']
@@ -1185,14 +1279,16 @@ class ReadStream:
         _device_emitter_given_up(why, self.rank)
         while True:
             try:
-                self.emit_free.get_nowait().close()
+                cx = self.emit_free.get_nowait()
             except queue.Empty:
                 break
+            self.depth.release(cx); cx.close()
         self.drop_emit_context()
 
     def drop_emit_context(self):
         cx = getattr(self.emit_local, 'cx', None)
         if cx is not None:
+            self.depth.release(cx)
             cx.close(); self.emit_local.cx = None
 
     def plan(self, wnd):
@@ -1374,6 +1470,7 @@ class ReadStream:
             if self.emit_device:
                 try:
                     dev_c = self.emit_comments and cb is not None
+                    self.depth.attach(self.emit_context())
                     if self.args.paf:
                         text, toff, nl, ns = self.V.paf_emit_device(self.emit_context(), self.index, self.opts, nb, no, sb, so, raw)
                     else:
@@ -1385,6 +1482,7 @@ class ReadStream:
                     self.give_up_device(str(e))
             if text is None:
                 self.drop_emit_context()
+                self.depth.add_host(self.opts, nb, no, sb, so, raw, self.emit_threads)
             if text is None and self.args.paf:
                 text, toff, nl, ns = self.V.paf_emit(self.lib, self.index, self.opts, nb, no, sb, so, raw, nthreads=self.emit_threads)
             elif text is None:
@@ -1533,12 +1631,14 @@ def main(argv=None, comm=None):
         with _context_and_index(args, net, device) as (ctx, index):
             prm, rg, opts = _alignment_options(args, lib)
             range_mode = _sharding(args, net)
-            with _open_output(args, net, range_mode, index, rg, argv, device) as out:
+            with _open_output(args, net, range_mode, index, rg, argv, device) as out, contextlib.closing(DepthSink(args, lib, index)) as depth:
                 if args.mode == 'asm':
-                    report = _run_asm(args, net, lib, ctx, index, prm, opts, out, device, t_start)
+                    report = _run_asm(args, net, lib, ctx, index, prm, opts, out, device, t_start, depth)
+                    depth.finish(net)
                 else:
-                    with contextlib.closing(ReadStream(args, sw, net, lib, ctx, index, prm, opts, out, range_mode, device, t_start)) as stream:
+                    with contextlib.closing(ReadStream(args, sw, net, lib, ctx, index, prm, opts, out, range_mode, device, t_start, depth)) as stream:
                         stream.run()
+                        depth.finish(net)                   # (before the emit contexts close: the device accumulators live in their memory)
                     if range_mode:
                         stream.collect_parts()
                     report = stream.report

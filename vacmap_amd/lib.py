@@ -5,6 +5,7 @@ raises, and without a GPU `Context()` raises VmxError(VM_ERR_NO_DEVICE).
 """
 import ctypes as C
 import os
+import weakref
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -184,6 +185,15 @@ class VmxLib:
         L.vm_sam_emit_device_times.argtypes = [vp, P(dbl)]
         L.vm_paf_emit.argtypes = [vp, P(SamOpts), i64, vp, vp, vp, vp, vp, i64, vp, vp, C.c_int, P(vp), P(P(i64)), P(i64), P(i64)]
         L.vm_paf_emit_device.argtypes = [vp, vp, P(SamOpts), i64, vp, vp, vp, vp, vp, i64, vp, vp, P(vp), P(P(i64)), P(i64), P(i64)]
+        L.vm_depth_create.argtypes = [vp, vp, i64, C.c_int, P(vp)]
+        L.vm_depth_free.argtypes = [vp]; L.vm_depth_free.restype = None
+        L.vm_depth_add.argtypes = [vp, vp, P(SamOpts), i64, vp, vp, vp, vp, vp, i64, vp, vp, C.c_int, P(i64), P(i64)]
+        L.vm_depth_add_device.argtypes = [vp, vp, vp, P(SamOpts), i64, vp, vp, vp, vp, vp, i64, vp, vp, P(i64), P(i64)]
+        L.vm_ctx_attach_depth.argtypes = [vp, vp]
+        L.vm_depth_merge.argtypes = [vp, vp]
+        L.vm_depth_add_counts.argtypes = [vp, vp, i64]
+        L.vm_depth_counts.argtypes = [vp, P(P(i64)), P(P(i64)), P(i64)]
+        L.vm_depth_text.argtypes = [vp, C.c_int, P(vp), P(i64)]
         L.vm_blob_gather.argtypes = [vp, vp, vp, i64, vp, vp]; L.vm_blob_gather.restype = i64
         L.vm_blob_write_parts.argtypes = [C.c_int, vp, vp, vp, vp, i64]; L.vm_blob_write_parts.restype = i64
         L.vm_pinned_alloc.argtypes = [i64, C.c_int]; L.vm_pinned_alloc.restype = vp
@@ -277,8 +287,17 @@ class Context:
         self.lib.check(self.lib.L.vm_ctx_mem_info(self.h, C.byref(f), C.byref(t)))
         return f.value, t.value
 
+    def attach_depth(self, depth):
+        """vm_ctx_attach_depth: while `depth` (a Depth made on this context; None detaches) is attached, every sam_emit_device and paf_emit_device
+        call on this context also adds its records to it, with no further wait or upload and the same returned bytes"""
+        self.lib.check(self.lib.L.vm_ctx_attach_depth(self.h, depth.h if depth is not None else None))
+
     def close(self):
         if self.h:
+            for ref in getattr(self, '_depths', []):      # (their counts live in this context's memory)
+                d = ref()
+                if d is not None:
+                    d.close()
             self.lib.L.vm_ctx_destroy(self.h)
             self.h = None
 
@@ -607,6 +626,94 @@ def paf_emit_device(ctx, index, opts, names, name_off, seqs, seq_off, raw):
     lib.L.vm_free(toff)
     buf = _OwnedText(lib, text, int(off[-1]))
     return buf.array, off, nl.value, ns.value
+
+
+class Depth:
+    """Per-window depth of coverage (vm_depth; the rule: include/vacmapx.h at vm_depth_add, in Python: vacmap_amd/depth.py). Made for one index, a
+    window size and a MAPQ threshold; with a context the counts live on its GPU (add_device, Context.attach_depth), without one in host memory (add)."""
+
+    REGIONS, SUMMARY = 0, 1
+
+    def __init__(self, lib, h, ctx, nseq):
+        self.lib, self.h, self.ctx, self.nseq = lib, h, ctx, nseq
+
+    @classmethod
+    def create(cls, index, window=500, min_mapq=0, ctx=None, lib=None):
+        lib = ctx.lib if ctx is not None else (lib or load())
+        h = C.c_void_p()
+        lib.check(lib.L.vm_depth_create(ctx.h if ctx is not None else None, index.h, int(window), int(min_mapq), C.byref(h)))
+        d = cls(lib, h, ctx, index.nseq)
+        if ctx is not None:
+            if not hasattr(ctx, '_depths'):
+                ctx._depths = []
+            ctx._depths.append(weakref.ref(d))
+        return d
+
+    @staticmethod
+    def _blobs(names, name_off, seqs, seq_off):
+        return _u8(names), np.ascontiguousarray(name_off, dtype=np.int64), _u8(seqs), np.ascontiguousarray(seq_off, dtype=np.int64)
+
+    def add(self, index, opts, names, name_off, seqs, seq_off, raw, nthreads=8):
+        """vm_depth_add (host accumulator): paf_emit's arguments; returns (n_lines, n_skipped) as sam_emit counts them"""
+        names, name_off, seqs, seq_off = self._blobs(names, name_off, seqs, seq_off)
+        nl = C.c_int64(); ns = C.c_int64()
+        self.lib.check(self.lib.L.vm_depth_add(self.h, index.h, C.byref(opts), len(seq_off) - 1, names.ctypes.data, name_off.ctypes.data, seqs.ctypes.data, seq_off.ctypes.data,
+                                               C.cast(raw.recs, C.c_void_p), raw.nrec, raw.blob, raw.status.ctypes.data if len(raw.status) else None, int(nthreads),
+                                               C.byref(nl), C.byref(ns)))
+        return nl.value, ns.value
+
+    def add_device(self, ctx, index, opts, names, name_off, seqs, seq_off, raw):
+        """vm_depth_add_device (an accumulator made on ctx): paf_emit_device's arguments; no text is made; returns (n_lines, n_skipped)"""
+        names, name_off, seqs, seq_off = self._blobs(names, name_off, seqs, seq_off)
+        nl = C.c_int64(); ns = C.c_int64()
+        self.lib.check(self.lib.L.vm_depth_add_device(self.h, ctx.h, index.h, C.byref(opts), len(seq_off) - 1, names.ctypes.data, name_off.ctypes.data, seqs.ctypes.data,
+                                                      seq_off.ctypes.data, C.cast(raw.recs, C.c_void_p), raw.nrec, raw.blob,
+                                                      raw.status.ctypes.data if len(raw.status) else None, C.byref(nl), C.byref(ns)))
+        return nl.value, ns.value
+
+    def merge(self, other):
+        """vm_depth_merge: self += other (any mix of host and device accumulators of one layout)"""
+        self.lib.check(self.lib.L.vm_depth_merge(self.h, other.h))
+
+    def add_counts(self, counts):
+        """vm_depth_add_counts: self += a table that counts() returned for an accumulator of the same layout (another rank's)"""
+        counts = np.ascontiguousarray(counts, dtype=np.int64)
+        self.lib.check(self.lib.L.vm_depth_add_counts(self.h, counts.ctypes.data, len(counts)))
+
+    def counts(self):
+        """(counts[n_windows], win_off[nseq + 1]) as int64 arrays"""
+        cp = C.POINTER(C.c_int64)(); wp = C.POINTER(C.c_int64)(); n = C.c_int64()
+        self.lib.check(self.lib.L.vm_depth_counts(self.h, C.byref(cp), C.byref(wp), C.byref(n)))
+        counts = np.ctypeslib.as_array(cp, shape=(max(n.value, 1),))[:n.value].copy()
+        win_off = np.ctypeslib.as_array(wp, shape=(self.nseq + 1,)).copy()
+        self.lib.L.vm_free(cp); self.lib.L.vm_free(wp)
+        return counts, win_off
+
+    def _text(self, which):
+        t = C.c_void_p(); n = C.c_int64()
+        self.lib.check(self.lib.L.vm_depth_text(self.h, which, C.byref(t), C.byref(n)))
+        out = C.string_at(t, n.value)
+        self.lib.L.vm_free(t)
+        return out
+
+    def regions(self):
+        """the regions text (bytes): one line per window, TNAME start end mean"""
+        return self._text(self.REGIONS)
+
+    def summary(self):
+        """the summary text (bytes): one line per contig, TNAME length bases mean, and `total`"""
+        return self._text(self.SUMMARY)
+
+    def close(self):
+        if self.h:
+            self.lib.L.vm_depth_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def sam_emit_device_times(ctx):
